@@ -54,7 +54,7 @@ def test_dense_media_count_nothing(cvr):
 
 @pytest.mark.gpu
 def test_bench_line_counts_sparse_words(tmp_path):
-    """bench.py on a sparse scene reports the words its counting launch found
+    """bench.py --full on a sparse scene reports the words its counting launch found
     (counts_per_launch.brick_words_loaded) and builds its algorithmic bytes from
     them, so the bytes are exact rather than one word per density evaluation."""
     import json
@@ -63,7 +63,7 @@ def test_bench_line_counts_sparse_words(tmp_path):
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--scene", "cloud", "--resolution", "256", "256",
-                        "--iterations", "2", "--steps", "2", "--warmup", "1", "--no-cpu-baseline",
+                        "--iterations", "2", "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline",
                         "--no-shard-emulation"], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])

@@ -43,7 +43,7 @@ def test_two_ranks_one_gpu_bench_step_equals_single_render(cvr, tmp_path, shard,
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     cmd = pre + [os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--backend", "gloo", "--same-device",
            "--resolution", str(W), str(H), "--iterations", str(iters), "--shard", shard,
-           "--number-of-tiles", str(tiles[0]), str(tiles[1]), "--no-cpu-baseline", "--dump-image", out]
+           "--number-of-tiles", str(tiles[0]), str(tiles[1]), "--full", "--no-cpu-baseline", "--dump-image", out]
     r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=600, env=env)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
     js = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]

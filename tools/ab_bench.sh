@@ -10,7 +10,7 @@ shift 2
 for r in $(seq "$rounds"); do
   for v in "$@"; do
     if [ "$v" = default ]; then lib=""; else lib="build/variants/$v/libcvr.so"; fi
-    CVR_LIB=$lib timeout -k 10 200 python3 bench.py --no-cpu-baseline $args > /tmp/abb_$$.json 2>/tmp/abb_$$.err \
+    CVR_LIB=$lib timeout -k 10 200 python3 bench.py --full --no-cpu-baseline $args > /tmp/abb_$$.json 2>/tmp/abb_$$.err \
       || { echo "== $v FAILED"; tail -20 /tmp/abb_$$.err; exit 1; }
     python3 - "$v" "$r" /tmp/abb_$$.json <<'PY'
 import json, sys

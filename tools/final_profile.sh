@@ -18,7 +18,7 @@ step() {  # name seconds cmd...
   echo "== $name rc=$rc $(( $(date +%s) - t0 ))s"
   [ $rc -eq 0 ] || { tail -20 "$OUT/$name.log"; exit $rc; }
 }
-B="python3 bench.py --no-cpu-baseline"
+B="python3 bench.py --full --no-cpu-baseline"
 PART=${1:-all}  # 1: tests, traces, traffic / VALU passes, bench lines; 2: SQ groups, kernel ids, pair
 if [ "$PART" != 2 ]; then
 step smoke 300 python3 -c "import __graft_entry__ as g; g.smoke()"
@@ -45,10 +45,10 @@ python3 tools/traffic.py "$OUT/pmcf_manix" "$OUT/pmcw_manix" k_wpool_1024x1024_2
 python3 tools/valu.py "$OUT/pmcv_manix" k_wpool_1024x1024_20it "k_wpool<false, 5, 2, false, false>" > /dev/null &&
   python3 tools/valu.py "$OUT/pmcv_hetvol" hetvol_k_wpool_1024x1024_20it "k_wpool<false, 5, 3, false, false>" > /dev/null &&
   python3 tools/valu.py "$OUT/pmcv_cloud" cloud_k_wpool_4096x4096_20it "k_wpool<false, 5, 1, false, false>" > /dev/null || exit 1
-step c2_bench 200 python3 bench.py --steps 20 --warmup 5
-step c1_bench 200 python3 bench.py --scene bucky --steps 20 --warmup 5
-step c3_bench 200 python3 bench.py --scene hetvol --steps 20 --warmup 5
-step c5_bench 400 python3 bench.py --scene cloud --steps 5 --warmup 1
+step c2_bench 200 python3 bench.py --full --steps 20 --warmup 5
+step c1_bench 200 python3 bench.py --full --scene bucky --steps 20 --warmup 5
+step c3_bench 200 python3 bench.py --full --scene hetvol --steps 20 --warmup 5
+step c5_bench 400 python3 bench.py --full --scene cloud --steps 5 --warmup 1
 step c4_bench 400 $B --shard tiles --resolution 2048 2048 --iterations 256 --steps 2 --warmup 1
 fi
 [ "$PART" = 1 ] && { echo "final profile part 1 done"; exit 0; }
@@ -62,6 +62,6 @@ step pmc5_b 300 rocprofv3 --pmc SQ_THREAD_CYCLES_VALU SQ_ACTIVE_INST_VMEM SQ_INS
 step pmc5_c 300 rocprofv3 --pmc TCC_HIT_sum TCC_MISS_sum TCP_TOTAL_CACHE_ACCESSES_sum TCP_TCC_READ_REQ_sum --kernel-trace -d "$OUT/pmc5_c" -o run --output-format csv -- $C5
 # every kernel id's C2 line (all on the wave pool by default)
 for k in streamingSK sortingSK streamingMK naiveSK naiveMK; do
-  step k_$k 300 python3 bench.py --kernel $k --steps 20 --warmup 5 --no-shard-emulation --no-cpu-baseline
+  step k_$k 300 python3 bench.py --full --kernel $k --steps 20 --warmup 5 --no-shard-emulation --no-cpu-baseline
 done
 echo "final profile done"

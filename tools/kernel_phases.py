@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Split a rocprofv3 kernel trace of one default `bench.py` run into its two
+"""Split a rocprofv3 kernel trace of one `bench.py --full` run into its two
 timed phases (tools/final_profile.sh):
   pipelined  warmup + steps launches with renders in flight: per-dispatch
              durations overlap, so the amortized time per launch is the span
