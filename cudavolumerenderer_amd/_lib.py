@@ -33,6 +33,8 @@ OPT_SCHEDULER, OPT_POOL, OPT_TIMING, OPT_CELLS, OPT_WAVES, OPT_ORDER, OPT_QUEUES
 OPT_BOUNDS, OPT_TAIL, OPT_BATCH, OPT_RNG_BINDING, OPT_MORTON = 13, 14, 15, 16, 17
 OPT_WORLD_TO_AABB, OPT_MK_COMPACTION, OPT_SUBQUEUES, OPT_DRAIN, OPT_INFLIGHT, OPT_FRAME_FLUSH = 18, 19, 20, 22, 23, 24
 OPT_UNIFORM_ALBEDO, OPT_WAVE_PAIR, OPT_SAMPLE_ORDER, OPT_EMPTY_MASK, OPT_COUNT_WORDS = 25, 26, 27, 28, 29
+OPT_MEDIUM_FORMAT = 30
+FORMAT_F32, FORMAT_F16 = 0, 1  # OPT_MEDIUM_FORMAT: storage precision of the voxel values in HBM
 
 
 class CvrError(RuntimeError):
@@ -66,6 +68,16 @@ class Stats(C.Structure):
                 ("truncated", C.c_uint64), ("kernel_ms", C.c_double), ("iterations", C.c_uint64),
                 ("track_ms", C.c_double), ("events_ms", C.c_double), ("fetches", C.c_uint64),
                 ("words", C.c_uint64)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class MediumInfo(C.Structure):
+    """cvr_medium_info: format and device bytes of a context's medium."""
+    _fields_ = [("format", C.c_int32), ("max_density_eff", C.c_float), ("density_bytes", C.c_uint64),
+                ("cells_bytes", C.c_uint64), ("albedo_bytes", C.c_uint64), ("bounds_bytes", C.c_uint64),
+                ("total_bytes", C.c_uint64)]
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
@@ -125,6 +137,8 @@ def load() -> C.CDLL:
         "cvr_set_block_shard": (I32, [P, U32, U32]),
         "cvr_set_block_order": (I32, [P, P, U32]),
         "cvr_share_medium": (I32, [P, P]),
+        "cvr_medium_info": (I32, [P, C.POINTER(MediumInfo)]),
+        "cvr_half_round": (I32, [FP, FP, C.c_size_t]),
         "cvr_trace_launch": (I32, [P, P, U64]),
         "cvr_image_to_host": (I32, [P, P, C.c_size_t, C.c_float, P]),
         "cvr_render_frame": (I32, [P, P, C.c_size_t, U32, C.POINTER(Stats)]),
@@ -190,6 +204,16 @@ def _check(code: int, ctx=None):
 
 
 # ------------------------------------------------------------------ helpers --
+def half_round(a) -> np.ndarray:
+    """f32 -> IEEE binary16 (nearest even, subnormals kept) -> f32, the rounding of OPT_MEDIUM_FORMAT
+    FORMAT_F16 (cvr_half_round; host only): a FORMAT_F16 render is bit-identical per path to a
+    FORMAT_F32 render of the half_round()ed arrays."""
+    src = np.ascontiguousarray(a, dtype=np.float32)
+    out = np.empty_like(src)
+    _check(load().cvr_half_round(_fp(src), _fp(out), src.size))
+    return out
+
+
 def default_camera(width: int, height: int):
     """Camera.h:25-71 + CudaVolPath.cpp:67-85 -> (inv_view[12], raster_to_view[2])."""
     lib = load()
@@ -425,6 +449,12 @@ class Context:
         """Render `src`'s medium without a copy (cvr_share_medium); keep `src` alive."""
         self._c(load().cvr_share_medium(self._h, src._h))
         self._medium_src = src
+
+    def medium_info(self) -> MediumInfo:
+        """Format, majorant in use and device bytes of the medium (a shared medium: the source's)."""
+        mi = MediumInfo()
+        self._c(load().cvr_medium_info(self._h, C.byref(mi)))
+        return mi
 
     def set_block_order(self, perm: Optional[np.ndarray]):
         """Block work order of the launch (cvr_set_block_order); None = natural."""

@@ -56,6 +56,53 @@ void camera_for_fov(float fov_x, uint32_t w, uint32_t h, float inv_view[12], flo
 }
 }  // namespace cvr
 
+namespace {
+// f32 -> binary16 -> f32, round to nearest even, subnormals kept (CVR_OPT_MEDIUM_FORMAT 1).
+float half_round1(float f) {
+  uint32_t u;
+  memcpy(&u, &f, 4);
+  const uint32_t sign = u & 0x80000000u, a = u & 0x7FFFFFFFu;
+  uint32_t r;
+  if (a >= 0x7F800000u) {
+    // inf stays inf; NaN keeps its top 10 payload bits and stays NaN (quiet bit set if they are all 0)
+    r = a == 0x7F800000u ? a : ((a & 0xFFFFE000u) | 0x00400000u);
+  } else if (a >= 0x477FF000u) {
+    r = 0x7F800000u;  // >= 65520: rounds to inf
+  } else if (a >= 0x38800000u) {
+    // normal half: keep 10 mantissa bits, nearest even on the 13 dropped (a carry moves to the next
+    // exponent, at most to 65504's successor, excluded above)
+    r = (a + 0x00000FFFu + ((a >> 13) & 1u)) & 0xFFFFE000u;
+  } else {
+    // below 2^-14: multiples of 2^-24.  Adding 2^-1 (ulp 2^-24 in [0.5, 1)) rounds to nearest even.
+    float t;
+    memcpy(&t, &a, 4);
+    const float k = (t + 0.5f) - 0.5f;
+    memcpy(&r, &k, 4);
+  }
+  r |= sign;
+  float o;
+  memcpy(&o, &r, 4);
+  return o;
+}
+// first finite value of v[0..n) (of every `stride`-th group's first `take` values) that rounds to +-inf
+bool half_overflows(const float* v, size_t n, size_t stride, size_t take, size_t* at) {
+  for (size_t i = 0; i < n; ++i)
+    for (size_t k = 0; k < take; ++k) {
+      const float f = v[i * stride + k];
+      if (std::fabs(f) >= 65520.0f && std::isfinite(f)) {
+        *at = i * stride + k;
+        return true;
+      }
+    }
+  return false;
+}
+// the format-1 majorant: max(max_density, f32(f16(max_density))), max_density itself if that overflows
+float half_majorant(float max_density) {
+  const float h = half_round1(max_density);
+  return (std::isfinite(h) && h > max_density) ? h : max_density;
+}
+}  // namespace
+
 struct cvr_ctx {
   int device = 0;
   int kernel = CVR_KERNEL_REGENERATION_SK;
@@ -76,6 +123,7 @@ struct cvr_ctx {
   uint32_t bound_shift = 2;     // log2 brick size, 0 = off
   bool bound_shift_set = false; // CVR_OPT_BOUNDS given (else sparse media use 8^3 bricks)
   size_t n_voxels = 0;
+  uint32_t grids_format = 0;  // format d_density / d_albedo were allocated for
   // sparse medium (cvr_set_medium_sparse)
   uint32_t* d_leaves = nullptr;
   float* d_leaf_density = nullptr;
@@ -88,6 +136,8 @@ struct cvr_ctx {
   size_t n_cell_leaves = 0;  // cell-leaf pool slots (incl. the zero slot)
   bool have_medium = false;
   cvr::MediumParams m{};
+  int medium_format = 0;     // CVR_OPT_MEDIUM_FORMAT (the next set-medium's; the medium's own is m.format)
+  struct cvr_medium_info minfo{};  // cvr_medium_info of the medium in use (own or shared)
 
   // launcher state (the reference's __constant__ symbols)
   float inv_view[12] = {1, 0, 0, 0, 0, -1, 0, 0, 0, 0, -1, 100};
@@ -814,31 +864,64 @@ int cvr_set_medium(cvr_ctx* c, const cvr_medium_desc* md) {
   // the kernels index cells and bricks with 24-bit multiplies
   if ((uint64_t)md->res[1] * md->res[2] >= (1ull << 24) || (uint64_t)md->res[0] * md->res[1] >= (1ull << 24))
     return set_err(&c->err, CVR_ERR_UNSUPPORTED, "dense grid with y*z or x*y >= 2^24: use cvr_set_medium_sparse");
+  const uint32_t fmt = (uint32_t)c->medium_format;
+  // bytes per density voxel / cell / albedo voxel
+  const size_t dB = fmt ? 2 : sizeof(float), cB = fmt ? 16 : 2 * sizeof(float4), aB = fmt ? 8 : sizeof(float4);
+  if (fmt) {
+    size_t at = 0;
+    const bool bad_d = half_overflows(md->density, n, 1, 1, &at);
+    const bool bad_a = !bad_d && half_overflows(md->albedo, n, 4, 3, &at);
+    if (bad_d || bad_a) {
+      c->have_medium = false;
+      return set_err(&c->err, CVR_ERR_INVALID, "medium format half: %s value %g at index %zu rounds to infinity",
+                     bad_d ? "density" : "albedo", (double)(bad_d ? md->density : md->albedo)[at], at);
+    }
+  }
+  const float max_density = fmt ? half_majorant(md->max_density) : md->max_density;
   int r = ensure_device(c);
   if (r) return r;
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   free_sparse(c);
-  if (n != c->n_voxels || !c->d_density) {
+  c->have_medium = false;
+  if (n != c->n_voxels || !c->d_density || c->grids_format != fmt) {  // (the grids' bytes depend on the format too)
     if (c->d_density) (void)hipFree(c->d_density);
     if (c->d_albedo) (void)hipFree(c->d_albedo);
     c->d_density = nullptr;
     c->d_albedo = nullptr;
-    HIP_TRY(c, hipMalloc(&c->d_density, n * sizeof(float)));
-    HIP_TRY(c, hipMalloc(&c->d_albedo, n * sizeof(float4)));
+    c->n_voxels = 0;
+    HIP_TRY(c, hipMalloc(&c->d_density, n * dB));
+    HIP_TRY(c, hipMalloc(&c->d_albedo, n * aB));
     c->n_voxels = n;
+    c->grids_format = fmt;
   }
-  HIP_TRY(c, hipMemcpy(c->d_density, md->density, n * sizeof(float), hipMemcpyHostToDevice));
-  HIP_TRY(c, hipMemcpy(c->d_albedo, md->albedo, n * sizeof(float4), hipMemcpyHostToDevice));
+  if (fmt) {
+    // fp32 staging -> rounded half grids (converted on the device); the staging is freed before
+    // the cells and bounds are built, and in any case before this call returns
+    float* stage = nullptr;
+    HIP_TRY(c, hipMalloc(&stage, n * sizeof(float4)));
+    hipError_t e = hipMemcpy(stage, md->density, n * sizeof(float), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = cvr::launch_to_half(stage, c->d_density, n, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e == hipSuccess) e = hipMemcpy(stage, md->albedo, n * sizeof(float4), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = cvr::launch_to_half(stage, c->d_albedo, 4 * n, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    (void)hipFree(stage);
+    if (e != hipSuccess) return set_err(&c->err, CVR_ERR_HIP, "half medium upload: %s", hipGetErrorString(e));
+  } else {
+    HIP_TRY(c, hipMemcpy(c->d_density, md->density, n * sizeof(float), hipMemcpyHostToDevice));
+    HIP_TRY(c, hipMemcpy(c->d_albedo, md->albedo, n * sizeof(float4), hipMemcpyHostToDevice));
+  }
   if (c->d_cells) (void)hipFree(c->d_cells);
   c->d_cells = nullptr;
   if (c->use_cells) {
-    HIP_TRY(c, hipMalloc(&c->d_cells, 2 * n * sizeof(float4)));
-    HIP_TRY(c, cvr::launch_build_cells(c->d_density, md->res[0], md->res[1], md->res[2], c->d_cells, c->stream));
+    HIP_TRY(c, hipMalloc(&c->d_cells, n * cB));
+    HIP_TRY(c, cvr::launch_build_cells(c->d_density, md->res[0], md->res[1], md->res[2], c->d_cells, c->stream, fmt));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
   }
   if (c->d_bounds) (void)hipFree(c->d_bounds);
   c->d_bounds = nullptr;
-  const float sigma = md->scale * md->max_density;
+  const float sigma = md->scale * max_density;
+  size_t bounds_bytes = 0;
   uint32_t bnx = 0, bny = 0, bsentinel = 0;
   if (c->bound_shift && sigma > 0.0f && std::isfinite(sigma) && md->scale > 0.0f) {
     const uint32_t B = 1u << c->bound_shift;
@@ -847,8 +930,9 @@ int cvr_set_medium(cvr_ctx* c, const cvr_medium_desc* md) {
     const size_t nb = (size_t)bnx * bny * ((md->res[2] + B - 1) / B);
     bsentinel = (uint32_t)nb;  // the no-bound entry past the last brick (k_build_bounds writes it)
     HIP_TRY(c, hipMalloc(&c->d_bounds, nb + 1));
+    bounds_bytes = nb + 1;
     HIP_TRY(c, cvr::launch_build_bounds(c->d_density, md->res[0], md->res[1], md->res[2], c->bound_shift,
-                                        md->max_density, c->d_bounds, c->stream));
+                                        max_density, c->d_bounds, c->stream, fmt));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
   }
   cvr::MediumParams& m = c->m;
@@ -862,17 +946,36 @@ int cvr_set_medium(cvr_ctx* c, const cvr_medium_desc* md) {
   m.cells = c->d_cells;
   m.density = c->d_density;
   m.albedo = c->d_albedo;
-  fill_medium_common(m, md->res, md->box_min, md->box_max, md->scale, md->max_density, md->g, md->roughness,
-                     md->eta);
+  fill_medium_common(m, md->res, md->box_min, md->box_max, md->scale, max_density, md->g, md->roughness, md->eta);
+  m.format = fmt;
   if (c->uniform_albedo) {
-    // every voxel's rgb bit-identical to the first (the XML smoke scene's constant albedo)
+    // every voxel's rgb bit-identical to the first (the XML smoke scene's constant albedo);
+    // format 1: the rounded rgb (voxels that differ may round to the same halves)
+    float first[3] = {md->albedo[0], md->albedo[1], md->albedo[2]};
+    if (fmt)
+      for (float& v : first) v = half_round1(v);
     bool same = true;
-    for (size_t i = 1; i < n && same; ++i) same = memcmp(md->albedo + 4 * i, md->albedo, 3 * sizeof(float)) == 0;
+    for (size_t i = 1; i < n && same; ++i) {
+      same = memcmp(md->albedo + 4 * i, md->albedo, 3 * sizeof(float)) == 0;
+      if (!same && fmt) {
+        float v[3];
+        for (int k = 0; k < 3; ++k) v[k] = half_round1(md->albedo[4 * i + k]);
+        same = memcmp(v, first, sizeof(v)) == 0;
+      }
+    }
     if (same) {
       m.albedo_uniform = 1u;
-      m.albedo_bg = cvr::V3{md->albedo[0], md->albedo[1], md->albedo[2]};
+      m.albedo_bg = cvr::V3{first[0], first[1], first[2]};
     }
   }
+  c->minfo = {};
+  c->minfo.format = (int32_t)fmt;
+  c->minfo.max_density_eff = max_density;
+  c->minfo.density_bytes = n * dB;
+  c->minfo.cells_bytes = c->d_cells ? n * cB : 0;
+  c->minfo.albedo_bytes = n * aB;
+  c->minfo.bounds_bytes = bounds_bytes;
+  c->minfo.total_bytes = c->minfo.density_bytes + c->minfo.cells_bytes + c->minfo.albedo_bytes + c->minfo.bounds_bytes;
   c->have_medium = true;
   return CVR_OK;
 }
@@ -914,6 +1017,23 @@ int cvr_set_medium_sparse(cvr_ctx* c, const cvr_sparse_medium_desc* sd) {
   const size_t ncl = coords.size() / 3;
   if (ncl > (1u << 24))
     return set_err(&c->err, CVR_ERR_UNSUPPORTED, "sparse medium needs %zu cell leaves (> 2^24)", ncl);
+  const uint32_t fmt = (uint32_t)c->medium_format;
+  const size_t dB = fmt ? 2 : sizeof(float), cB = fmt ? 16 : 2 * sizeof(float4), aB = fmt ? 8 : sizeof(float4);
+  if (fmt) {
+    const size_t nv = (size_t)sd->n_leaves * 512;
+    size_t at = 0;
+    const char* what = nullptr;
+    const float* arr = nullptr;
+    if (half_overflows(sd->leaf_density, nv, 1, 1, &at)) what = "leaf density", arr = sd->leaf_density;
+    else if (sd->leaf_albedo && half_overflows(sd->leaf_albedo, nv, 4, 3, &at)) what = "leaf albedo", arr = sd->leaf_albedo;
+    else if (half_overflows(sd->albedo_background, 1, 4, 3, &at)) what = "albedo_background", arr = sd->albedo_background;
+    if (what) {
+      c->have_medium = false;
+      return set_err(&c->err, CVR_ERR_INVALID, "medium format half: %s value %g at index %zu rounds to infinity", what,
+                     (double)arr[at], at);
+    }
+  }
+  const float max_density = fmt ? half_majorant(sd->max_density) : sd->max_density;
   int r = ensure_device(c);
   if (r) return r;
   HIP_TRY(c, hipStreamSynchronize(c->stream));
@@ -932,23 +1052,40 @@ int cvr_set_medium_sparse(cvr_ctx* c, const cvr_sparse_medium_desc* sd) {
   const size_t np = (size_t)sd->n_leaves * 512;
   HIP_TRY(c, hipMalloc(&c->d_leaves, nleaf * sizeof(uint32_t)));
   HIP_TRY(c, hipMemcpy(c->d_leaves, sd->leaf_table, nleaf * sizeof(uint32_t), hipMemcpyHostToDevice));
-  HIP_TRY(c, hipMalloc(&c->d_leaf_density, (np ? np : 1) * sizeof(float)));
-  if (np) HIP_TRY(c, hipMemcpy(c->d_leaf_density, sd->leaf_density, np * sizeof(float), hipMemcpyHostToDevice));
-  if (sd->leaf_albedo && np) {
-    HIP_TRY(c, hipMalloc(&c->d_leaf_albedo, np * sizeof(float4)));
-    HIP_TRY(c, hipMemcpy(c->d_leaf_albedo, sd->leaf_albedo, np * sizeof(float4), hipMemcpyHostToDevice));
+  HIP_TRY(c, hipMalloc(&c->d_leaf_density, (np ? np : 1) * dB));
+  if (sd->leaf_albedo && np) HIP_TRY(c, hipMalloc(&c->d_leaf_albedo, np * aB));
+  if (fmt && np) {
+    // fp32 staging -> rounded half pools (converted on the device), freed before the cells are built
+    float* stage = nullptr;
+    HIP_TRY(c, hipMalloc(&stage, np * (c->d_leaf_albedo ? sizeof(float4) : sizeof(float))));
+    hipError_t e = hipMemcpy(stage, sd->leaf_density, np * sizeof(float), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = cvr::launch_to_half(stage, c->d_leaf_density, np, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e == hipSuccess && c->d_leaf_albedo) {
+      e = hipMemcpy(stage, sd->leaf_albedo, np * sizeof(float4), hipMemcpyHostToDevice);
+      if (e == hipSuccess) e = cvr::launch_to_half(stage, c->d_leaf_albedo, 4 * np, c->stream);
+      if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    }
+    (void)hipFree(stage);
+    if (e != hipSuccess) return set_err(&c->err, CVR_ERR_HIP, "half medium upload: %s", hipGetErrorString(e));
+  } else if (np) {
+    HIP_TRY(c, hipMemcpy(c->d_leaf_density, sd->leaf_density, np * sizeof(float), hipMemcpyHostToDevice));
+    if (c->d_leaf_albedo)
+      HIP_TRY(c, hipMemcpy(c->d_leaf_albedo, sd->leaf_albedo, np * sizeof(float4), hipMemcpyHostToDevice));
   }
   cvr::MediumParams& m = c->m;
   m = cvr::MediumParams{};
-  fill_medium_common(m, res, sd->box_min, sd->box_max, sd->scale, sd->max_density, sd->g, sd->roughness, sd->eta);
+  fill_medium_common(m, res, sd->box_min, sd->box_max, sd->scale, max_density, sd->g, sd->roughness, sd->eta);
+  m.format = fmt;
   m.leaves = c->d_leaves;
   m.leaf_density = c->d_leaf_density;
   m.leaf_albedo = c->d_leaf_albedo;
   m.lnx = lnx;
   m.lny = lny;
   m.albedo_bg = cvr::V3{sd->albedo_background[0], sd->albedo_background[1], sd->albedo_background[2]};
+  if (fmt) m.albedo_bg = cvr::V3{half_round1(m.albedo_bg.x), half_round1(m.albedo_bg.y), half_round1(m.albedo_bg.z)};
   // bricks of 2^bshift <= 8 cells (within one leaf); bounds off -> q = 255
-  const float sigma = sd->scale * sd->max_density;
+  const float sigma = sd->scale * max_density;
   const int unbounded = !(c->bound_shift && sigma > 0.0f && std::isfinite(sigma) && sd->scale > 0.0f);
   // Default 8^3 cells per brick: one brick word per leaf's cells (C5: 33.6 MB
   // of words instead of 268 MB at 4^3, so they stay in L2 / Infinity Cache;
@@ -964,14 +1101,14 @@ int cvr_set_medium_sparse(cvr_ctx* c, const cvr_sparse_medium_desc* sd) {
     return set_err(&c->err, CVR_ERR_UNSUPPORTED, "sparse grid has too many bricks (%zu)", nb);
   m.bsentinel = (uint32_t)nb;  // the no-bound word past the last brick (k_build_sparse_bounds writes it)
   HIP_TRY(c, hipMalloc(&c->d_sbounds, (nb + 1) * sizeof(uint32_t)));
-  if (c->use_cells) HIP_TRY(c, hipMalloc(&c->d_cells, ncl * 1024 * sizeof(float4)));
+  if (c->use_cells) HIP_TRY(c, hipMalloc(&c->d_cells, ncl * 512 * cB));
   uint32_t *d_coords = nullptr, *d_slot = nullptr;
   hipError_t e = hipMalloc(&d_coords, coords.size() * sizeof(uint32_t));
   if (e == hipSuccess) e = hipMalloc(&d_slot, nleaf * sizeof(uint32_t));
   if (e == hipSuccess) e = hipMemcpy(d_coords, coords.data(), coords.size() * sizeof(uint32_t), hipMemcpyHostToDevice);
   if (e == hipSuccess) e = hipMemcpy(d_slot, cell_slot.data(), nleaf * sizeof(uint32_t), hipMemcpyHostToDevice);
   if (e == hipSuccess)
-    e = cvr::launch_build_sparse(m, d_coords, c->use_cells ? ncl : 0, d_slot, bnz, sd->max_density, unbounded,
+    e = cvr::launch_build_sparse(m, d_coords, c->use_cells ? ncl : 0, d_slot, bnz, max_density, unbounded,
                                  c->d_cells, c->d_sbounds, c->stream);
   // Empty-region mask (MediumParams::emask): the smallest super-brick of 2^es
   // cells per axis whose grid, each axis padded to a power of two, fits 32
@@ -1013,6 +1150,14 @@ int cvr_set_medium_sparse(cvr_ctx* c, const cvr_sparse_medium_desc* sd) {
   m.cells = c->d_cells;
   m.sbounds = c->d_sbounds;
   c->n_cell_leaves = ncl;
+  c->minfo = {};
+  c->minfo.format = (int32_t)fmt;
+  c->minfo.max_density_eff = max_density;
+  c->minfo.density_bytes = (np ? np : 1) * dB;
+  c->minfo.cells_bytes = c->d_cells ? ncl * 512 * cB : 0;
+  c->minfo.albedo_bytes = c->d_leaf_albedo ? np * aB : 0;
+  c->minfo.bounds_bytes = (nb + 1 + nleaf + (c->d_emask ? cvr::kEmaskWords : 0)) * sizeof(uint32_t);
+  c->minfo.total_bytes = c->minfo.density_bytes + c->minfo.cells_bytes + c->minfo.albedo_bytes + c->minfo.bounds_bytes;
   c->have_medium = true;
   return CVR_OK;
 }
@@ -1038,9 +1183,26 @@ int cvr_share_medium(cvr_ctx* c, const cvr_ctx* src) {
   c->n_voxels = 0;
   free_sparse(c);
   c->m = src->m;
+  c->minfo = src->minfo;
   c->n_cell_leaves = src->n_cell_leaves;
   c->have_medium = true;
   c->inited = false;
+  return CVR_OK;
+}
+
+int cvr_medium_info(const cvr_ctx* c, struct cvr_medium_info* out) {
+  if (!c || !out) return set_err(nullptr, CVR_ERR_INVALID, "NULL argument");
+  if (!c->have_medium) {
+    cvr::set_last_error("no medium");
+    return CVR_ERR_STATE;
+  }
+  *out = c->minfo;
+  return CVR_OK;
+}
+
+int cvr_half_round(const float* in, float* out, size_t n) {
+  if (n && (!in || !out)) return set_err(nullptr, CVR_ERR_INVALID, "NULL argument");
+  for (size_t i = 0; i < n; ++i) out[i] = half_round1(in[i]);
   return CVR_OK;
 }
 
@@ -1260,6 +1422,12 @@ int cvr_set_option(cvr_ctx* c, int opt, int64_t v) {
       // takes effect at the next cvr_set_medium
       c->use_cells = v != 0;
       return CVR_OK;
+    case CVR_OPT_MEDIUM_FORMAT:
+      // takes effect at the next cvr_set_medium / cvr_set_medium_sparse
+      if (v != CVR_FORMAT_F32 && v != CVR_FORMAT_F16)
+        return set_err(&c->err, CVR_ERR_INVALID, "medium format must be 0 (fp32) or 1 (half)");
+      c->medium_format = (int)v;
+      return CVR_OK;
     case CVR_OPT_SAMPLE_ORDER:
       if (v < -1 || v > 1) return set_err(&c->err, CVR_ERR_INVALID, "sample order must be -1, 0 or 1");
       c->sample_order = (int)v;
@@ -1369,6 +1537,18 @@ int cvr_launch_render(cvr_ctx* c) {
   if (r) return r;
   if (!c->d_out) return set_err(&c->err, CVR_ERR_STATE, "no output buffer");
   if ((r = do_init(c))) return r;
+  if (c->m.format != 0u) {
+    // the half storage format: the wave-pool scheduler's 5-wave instances only
+    const bool sparse = c->m.leaves != nullptr;
+    const char* why = c->rng_binding                       ? "CVR_OPT_RNG_BINDING 1"
+                      : scheduler_for(c) != 3              ? "a scheduler other than the wave pool (CVR_OPT_SCHEDULER 3)"
+                      : wpool_waves_for(c, sparse) != 5    ? "CVR_OPT_WAVES other than 5"
+                      : c->mk_compaction                   ? "CVR_OPT_MK_COMPACTION 1"
+                      : c->count_words                     ? "CVR_OPT_COUNT_WORDS 1"
+                      : c->wave_pair                       ? "CVR_OPT_WAVE_PAIR 1"
+                                                           : nullptr;
+    if (why) return set_err(&c->err, CVR_ERR_UNSUPPORTED, "the half medium format does not run with %s", why);
+  }
   uint64_t first, count;
   compute_range(c, &first, &count);
   cvr::LaunchParams L{};

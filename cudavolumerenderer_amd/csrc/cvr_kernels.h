@@ -104,7 +104,7 @@ hipError_t launch_image_to_host(const float* src, float* dst, size_t n, float sc
 hipError_t launch_blocks_to_host(const float* src, float* dst, uint32_t w, uint32_t h, uint32_t rank, uint32_t world,
                                  float scale, hipStream_t s);
 hipError_t launch_build_bounds(const float* density, uint32_t rx, uint32_t ry, uint32_t rz, uint32_t bshift,
-                               float max_density, uint8_t* bounds, hipStream_t s);
+                               float max_density, uint8_t* bounds, hipStream_t s, uint32_t format = 0);
 // Sparse medium: cell-leaf pool (`coords`: 3 u32 leaf coordinates per slot,
 // slot 0 the zero leaf) and brick words (`cell_slot`: per leaf, its slot or 0).
 // `m` carries the leaf table/pools and the brick geometry (bshift <= 3).
@@ -112,7 +112,10 @@ hipError_t launch_build_sparse(const MediumParams& m, const uint32_t* coords, si
                                const uint32_t* cell_slot, uint32_t bnz, float max_density, int unbounded,
                                float4* cells, uint32_t* sbounds, hipStream_t s);
 hipError_t launch_build_cells(const float* density, uint32_t rx, uint32_t ry, uint32_t rz, float4* cells,
-                              hipStream_t s);
+                              hipStream_t s, uint32_t format = 0);
+// The half storage format (MediumParams::format 1; `format` above: `density` holds halves and
+// the cells are written as 8 halves): n fp32 values -> n binary16, round to nearest even.
+hipError_t launch_to_half(const float* src, void* dst, size_t n, hipStream_t s);
 hipError_t launch_tile_to_image(const float4* tile, uint32_t tw, uint32_t th, float4* image, uint32_t iw,
                                 uint32_t ox, uint32_t oy, float scale, hipStream_t s);
 

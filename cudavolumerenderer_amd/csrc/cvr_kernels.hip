@@ -730,16 +730,49 @@ hipError_t launch_blocks_to_host(const float* src, float* dst, uint32_t w, uint3
 
 // ----------------------------------------------------------- cell table ---
 // Corner-replicated density cells (see MediumParams::cells).
+// The half storage format (MediumParams::format 1): fp32 staging -> binary16, round to
+// nearest even, subnormals kept (v_cvt_f16_f32 in the kernels' default modes); what
+// cvr_half_round computes on the host.
+__global__ __launch_bounds__(256) void k_to_half(const float* __restrict__ src, _Float16* __restrict__ dst, size_t n) {
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256)
+    dst[i] = (_Float16)src[i];
+}
+
+// One density cell in the half format: the fp32 cell's 8 corners in its order, 16 bytes.
+// The corners are half values already, so the conversions are exact.
+__device__ void store_half_cell(float4* cells, size_t i, float4 lo, float4 hi) {
+  cvr_h8 h;
+  h[0] = (_Float16)lo.x;
+  h[1] = (_Float16)lo.y;
+  h[2] = (_Float16)lo.z;
+  h[3] = (_Float16)lo.w;
+  h[4] = (_Float16)hi.x;
+  h[5] = (_Float16)hi.y;
+  h[6] = (_Float16)hi.z;
+  h[7] = (_Float16)hi.w;
+  reinterpret_cast<cvr_h8*>(cells)[i] = h;
+}
+
+// `format` 1: D holds halves (the rounded grid) and the cells are written as 8 halves.
 __global__ __launch_bounds__(256) void k_build_cells(const float* __restrict__ D, uint32_t rx, uint32_t ry,
-                                                     uint32_t rz, float4* __restrict__ cells) {
+                                                     uint32_t rz, float4* __restrict__ cells, uint32_t format) {
   const size_t n = (size_t)rx * ry * rz;
   for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
     const uint32_t x = (uint32_t)(i % rx), y = (uint32_t)((i / rx) % ry), z = (uint32_t)(i / ((size_t)rx * ry));
     const uint32_t xb = min(x + 1, rx - 1), yb = min(y + 1, ry - 1), zb = min(z + 1, rz - 1);
-    auto at = [&](uint32_t a, uint32_t b, uint32_t c) { return D[((size_t)c * ry + b) * rx + a]; };
+    auto at = [&](uint32_t a, uint32_t b, uint32_t c) {
+      const size_t j = ((size_t)c * ry + b) * rx + a;
+      return format ? (float)reinterpret_cast<const _Float16*>(D)[j] : D[j];
+    };
     // trilerp_cell layout: (d000, d100, d001, d101), (d010, d110, d011, d111), d{z}{y}{x}
-    cells[2 * i] = make_float4(at(x, y, z), at(x, y, zb), at(xb, y, z), at(xb, y, zb));
-    cells[2 * i + 1] = make_float4(at(x, yb, z), at(x, yb, zb), at(xb, yb, z), at(xb, yb, zb));
+    const float4 lo = make_float4(at(x, y, z), at(x, y, zb), at(xb, y, z), at(xb, y, zb));
+    const float4 hi = make_float4(at(x, yb, z), at(x, yb, zb), at(xb, yb, z), at(xb, yb, zb));
+    if (format) {
+      store_half_cell(cells, i, lo, hi);
+    } else {
+      cells[2 * i] = lo;
+      cells[2 * i + 1] = hi;
+    }
   }
 }
 
@@ -765,7 +798,8 @@ __device__ uint32_t bound_code(float mx, float max_density, bool nan) {
 
 __global__ __launch_bounds__(256) void k_build_bounds(const float* __restrict__ D, uint32_t rx, uint32_t ry,
                                                       uint32_t rz, uint32_t bshift, uint32_t bnx, uint32_t bny,
-                                                      uint32_t bnz, float max_density, uint8_t* __restrict__ q) {
+                                                      uint32_t bnz, float max_density, uint8_t* __restrict__ q,
+                                                      uint32_t format) {
   const size_t nb = (size_t)bnx * bny * bnz;
   const uint32_t B = 1u << bshift;
   for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < nb; i += (size_t)gridDim.x * 256) {
@@ -777,7 +811,8 @@ __global__ __launch_bounds__(256) void k_build_bounds(const float* __restrict__ 
     for (uint32_t z = z0; z <= z1; ++z)
       for (uint32_t y = y0; y <= y1; ++y)
         for (uint32_t x = x0; x <= x1; ++x) {
-          const float v = D[((size_t)z * ry + y) * rx + x];
+          const size_t j = ((size_t)z * ry + y) * rx + x;
+          const float v = format ? (float)reinterpret_cast<const _Float16*>(D)[j] : D[j];  // format 1: the rounded grid
           nan |= !(v == v) || v == __builtin_inff();
           mx = fmaxf(mx, v);
         }
@@ -798,16 +833,20 @@ __global__ __launch_bounds__(256) void k_build_sparse_cells(MediumParams m, cons
     const uint32_t local = (uint32_t)(i & 511u);
     const uint32_t x = coords[3 * slot] * 8u + (local & 7u), y = coords[3 * slot + 1] * 8u + ((local >> 3) & 7u),
                    z = coords[3 * slot + 2] * 8u + (local >> 6);
-    if (slot == 0 || x >= m.rx || y >= m.ry || z >= m.rz) {
-      cells[2 * i] = make_float4(0.f, 0.f, 0.f, 0.f);
-      cells[2 * i + 1] = make_float4(0.f, 0.f, 0.f, 0.f);
-      continue;
+    float4 lo = make_float4(0.f, 0.f, 0.f, 0.f), hi = lo;
+    if (!(slot == 0 || x >= m.rx || y >= m.ry || z >= m.rz)) {
+      const uint32_t xb = min(x + 1, m.rx - 1), yb = min(y + 1, m.ry - 1), zb = min(z + 1, m.rz - 1);
+      lo = make_float4(texel_density(m, x, y, z), texel_density(m, x, y, zb), texel_density(m, xb, y, z),
+                       texel_density(m, xb, y, zb));
+      hi = make_float4(texel_density(m, x, yb, z), texel_density(m, x, yb, zb), texel_density(m, xb, yb, z),
+                       texel_density(m, xb, yb, zb));
     }
-    const uint32_t xb = min(x + 1, m.rx - 1), yb = min(y + 1, m.ry - 1), zb = min(z + 1, m.rz - 1);
-    cells[2 * i] = make_float4(texel_density(m, x, y, z), texel_density(m, x, y, zb), texel_density(m, xb, y, z),
-                               texel_density(m, xb, y, zb));
-    cells[2 * i + 1] = make_float4(texel_density(m, x, yb, z), texel_density(m, x, yb, zb),
-                                   texel_density(m, xb, yb, z), texel_density(m, xb, yb, zb));
+    if (m.format) {  // 512 x 16 bytes per slot
+      store_half_cell(cells, i, lo, hi);
+    } else {
+      cells[2 * i] = lo;
+      cells[2 * i + 1] = hi;
+    }
   }
 }
 
@@ -929,17 +968,24 @@ hipError_t launch_tile_to_image(const float4* tile, uint32_t tw, uint32_t th, fl
 }
 
 hipError_t launch_build_bounds(const float* density, uint32_t rx, uint32_t ry, uint32_t rz, uint32_t bshift,
-                               float max_density, uint8_t* bounds, hipStream_t s) {
+                               float max_density, uint8_t* bounds, hipStream_t s, uint32_t format) {
   const uint32_t B = 1u << bshift;
   const uint32_t bnx = (rx + B - 1) / B, bny = (ry + B - 1) / B, bnz = (rz + B - 1) / B;
   hipLaunchKernelGGL(k_build_bounds, dim3(1024), dim3(256), 0, s, density, rx, ry, rz, bshift, bnx, bny, bnz,
-                     max_density, bounds);
+                     max_density, bounds, format);
   return hipGetLastError();
 }
 
 hipError_t launch_build_cells(const float* density, uint32_t rx, uint32_t ry, uint32_t rz, float4* cells,
-                              hipStream_t s) {
-  hipLaunchKernelGGL(k_build_cells, dim3(4096), dim3(256), 0, s, density, rx, ry, rz, cells);
+                              hipStream_t s, uint32_t format) {
+  hipLaunchKernelGGL(k_build_cells, dim3(4096), dim3(256), 0, s, density, rx, ry, rz, cells, format);
+  return hipGetLastError();
+}
+
+hipError_t launch_to_half(const float* src, void* dst, size_t n, hipStream_t s) {
+  if (n == 0) return hipSuccess;
+  const uint32_t grid = (uint32_t)std::min<size_t>((n + 255) / 256, 8192);
+  hipLaunchKernelGGL(k_to_half, dim3(grid), dim3(256), 0, s, src, reinterpret_cast<_Float16*>(dst), n);
   return hipGetLastError();
 }
 

@@ -35,6 +35,7 @@ struct Options {
   std::string scene_file, scene_type = "Auto", algorithm = "cudaVolPath", kernel = "regenerationSK";
   std::string output, synthetic, rng_binding = "path", world_to_aabb = "reference", mk_compaction = "fixed";
   std::string devices;  // --devices: a count or a comma list of device ids
+  std::string medium_format = "float";  // --medium-format
   bool pfm = false;
   std::vector<float> default_albedo;
   bool interactive = true, unified = false;
@@ -67,6 +68,9 @@ void usage() {
       "                                     thread each; ids may repeat): tile k -> device k mod N\n"
       "                                     with --number-of-tiles, else 8x8-block shards of the image;\n"
       "                                     one value is a count (pick one device with --device)\n"
+      "  --medium-format float|half (=float)  storage precision of density, density cells and albedo on\n"
+      "                                     the device: half rounds every voxel to IEEE binary16 and halves\n"
+      "                                     their bytes (wave-pool scheduler; see CVR_OPT_MEDIUM_FORMAT)\n"
       "  --pfm                              also write the float image as <output>.pfm\n"
       "  --rng-binding path|thread (=path)  regenerationSK: thread = the reference's Rng(seed + tid)\n"
       "                                     per persistent thread (non-deterministic, SURVEY Q2)\n"
@@ -113,6 +117,7 @@ int parse(int argc, char** argv, Options& o) {
     else if (a == "--synthetic") o.synthetic = need("synthetic");
     else if (a == "--device") o.device = (unsigned)strtoul(need("device").c_str(), nullptr, 10);
     else if (a == "--devices") o.devices = need("devices");
+    else if (a == "--medium-format") o.medium_format = need("medium-format");
     else if (a == "--pfm") o.pfm = true;
     else if (a == "--rng-binding") o.rng_binding = need("rng-binding");
     else if (a == "--seed") o.seed = (unsigned)strtoul(need("seed").c_str(), nullptr, 10);
@@ -274,6 +279,10 @@ int main(int argc, char** argv) {
     fprintf(stderr, "[ConfigParser] Error: --mk-compaction must be fixed or reference\n");
     return 2;
   }
+  if (o.medium_format != "float" && o.medium_format != "half") {
+    fprintf(stderr, "[ConfigParser] Error: --medium-format must be float or half\n");
+    return 2;
+  }
   // One context: its options, the medium (its own upload, or `share`'s device copy when
   // another context on the same device already holds it), the camera.
   auto make_ctx = [&](int device, cvr_ctx* share) -> cvr_ctx* {
@@ -286,6 +295,7 @@ int main(int argc, char** argv) {
     if (!rc && o.rng_binding == "thread") rc = cvr_set_option(ctx, CVR_OPT_RNG_BINDING, 1);
     if (!rc && o.world_to_aabb == "fixed") rc = cvr_set_option(ctx, CVR_OPT_WORLD_TO_AABB, 1);
     if (!rc && o.mk_compaction == "reference") rc = cvr_set_option(ctx, CVR_OPT_MK_COMPACTION, 1);
+    if (!rc && o.medium_format == "half") rc = cvr_set_option(ctx, CVR_OPT_MEDIUM_FORMAT, CVR_FORMAT_F16);
     if (!rc && share) {
       rc = cvr_share_medium(ctx, share);
     } else if (!rc) {
@@ -401,6 +411,12 @@ int main(int argc, char** argv) {
     printf("rendering time      : %.2f sec \n", sec);
     printf("total traced rays %llu (woodcock steps %llu)\n", (unsigned long long)st.segments,
            (unsigned long long)st.steps);
+    struct cvr_medium_info mi;
+    if (cvr_medium_info(ctxs[0], &mi) == CVR_OK)
+      printf("medium on device    : %s, %llu bytes (density %llu, cells %llu, albedo %llu, bounds %llu)\n",
+             mi.format == CVR_FORMAT_F16 ? "half" : "float", (unsigned long long)mi.total_bytes,
+             (unsigned long long)mi.density_bytes, (unsigned long long)mi.cells_bytes,
+             (unsigned long long)mi.albedo_bytes, (unsigned long long)mi.bounds_bytes);
     if (t > 0) {
       times.push_back(sec);
       mean += sec;

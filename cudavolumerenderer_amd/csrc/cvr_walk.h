@@ -183,7 +183,22 @@ struct MediumParams {
   // unbounded, whose words are not 0).
   const uint32_t* emask;
   uint32_t eshift, eshy, eshz;
+  // Storage format of the voxel values (CVR_OPT_MEDIUM_FORMAT): 0 fp32 as declared
+  // above; 1 IEEE binary16: `density` / `leaf_density` point to one half per voxel,
+  // `albedo` / `leaf_albedo` to four halves (r, g, b, 1) per voxel, and a density cell
+  // is its 8 corners as 8 consecutive halves in the fp32 cell's order (16 bytes, the
+  // cell-leaf pool 512 x 16 bytes per slot).  A half converts to fp32 exactly and every
+  // operation after the load is the fp32 one, so the walk is that of the fp32 medium
+  // holding the rounded values.  Bounds, brick words and the mask are the same bytes
+  // in both formats.  Fills the struct's tail padding: the other fields keep their
+  // kernel-argument offsets and the struct its size.
+  uint32_t format;
 };
+// Half-format loads: plain conversions (v_cvt_f32_f16 and its high-half forms).
+typedef _Float16 cvr_h4 __attribute__((ext_vector_type(4)));
+typedef _Float16 cvr_h8 __attribute__((ext_vector_type(8)));
+// float4 units per density cell, as a shift: 2 float4 (fp32), 1 float4's bytes (half)
+CVR_DEV uint32_t cell_shift(const MediumParams& m) { return m.format ? 0u : 1u; }
 // Words of the empty-region mask (a power of two): 64 (2048 super-bricks, C5's
 // cloud at 128^3 cells each), staged once per workgroup of the sparse instances,
 // whose workgroups hold four wave-private pools (cvr_wpool.hip, kWpgSparse).  A
@@ -416,18 +431,31 @@ CVR_DEV uint32_t leaf_local(uint32_t x, uint32_t y, uint32_t z) {
 CVR_DEV float texel_density(const MediumParams& m, uint32_t x, uint32_t y, uint32_t z) {
   if (m.leaves) {
     const uint32_t slot = m.leaves[(__umul24(z >> 3, m.lny) + (y >> 3)) * m.lnx + (x >> 3)];
+    if (m.format)
+      return slot == 0xFFFFFFFFu
+                 ? 0.0f
+                 : (float)reinterpret_cast<const _Float16*>(m.leaf_density)[((size_t)slot << 9) | leaf_local(x, y, z)];
     return slot == 0xFFFFFFFFu ? 0.0f : m.leaf_density[((size_t)slot << 9) | leaf_local(x, y, z)];
   }
+  if (m.format) return (float)reinterpret_cast<const _Float16*>(m.density)[(z * m.ry + y) * m.rx + x];
   return m.density[(z * m.ry + y) * m.rx + x];
+}
+CVR_DEV float4 half4_texel(const float4* base, size_t i) {
+  const cvr_h4 h = reinterpret_cast<const cvr_h4*>(base)[i];
+  return make_float4((float)h.x, (float)h.y, (float)h.z, (float)h.w);
 }
 CVR_DEV float4 texel_albedo(const MediumParams& m, uint32_t x, uint32_t y, uint32_t z) {
   if (m.leaves) {
     const uint32_t slot = m.leaf_albedo ? m.leaves[(__umul24(z >> 3, m.lny) + (y >> 3)) * m.lnx + (x >> 3)]
                                         : 0xFFFFFFFFu;
+    if (m.format)
+      return slot == 0xFFFFFFFFu ? make_float4(m.albedo_bg.x, m.albedo_bg.y, m.albedo_bg.z, 1.0f)
+                                 : half4_texel(m.leaf_albedo, ((size_t)slot << 9) | leaf_local(x, y, z));
     return slot == 0xFFFFFFFFu ? make_float4(m.albedo_bg.x, m.albedo_bg.y, m.albedo_bg.z, 1.0f)
                                : m.leaf_albedo[((size_t)slot << 9) | leaf_local(x, y, z)];
   }
   if (m.albedo_uniform) return make_float4(m.albedo_bg.x, m.albedo_bg.y, m.albedo_bg.z, 1.0f);
+  if (m.format) return half4_texel(m.albedo, (z * m.ry + y) * m.rx + x);
   return m.albedo[(z * m.ry + y) * m.rx + x];
 }
 
@@ -522,7 +550,7 @@ struct WoodcockPoint {
   float cx, cy, cz;     // grid coordinate (DeviceVolume::volumeToGrid)
   bool in;              // lower corner inside the grid (cell path), else the 8-tap gather
   float qb;             // brick bound (bound_value; 1.9375: no bound)
-  const float4* cp;     // the cell's two float4 (valid when in && m.cells)
+  const float4* cp;     // the cell's two float4, or its 8 halves (valid when in && m.cells)
 };
 CVR_DEV void woodcock_coords(const MediumParams& m, V3 o, V3 d, float t, WoodcockPoint& P) {
   P.c = sub3(mk3(det_fmaf(t, d.x, o.x), det_fmaf(t, d.y, o.y), det_fmaf(t, d.z, o.z)), m.shift);
@@ -539,6 +567,11 @@ CVR_DEV void woodcock_coords(const MediumParams& m, V3 o, V3 d, float t, Woodcoc
   P.in = ((int)(det_f2u(P.cx) < det_f2u(m.fres_x)) & (int)(det_f2u(P.cy) < det_f2u(m.fres_y)) &
           (int)(det_f2u(P.cz) < det_f2u(m.fres_z))) != 0;
 }
+// A dense medium's cell (x1, y1, z1): 32 bytes per cell, 16 in the half format.
+CVR_DEV const float4* dense_cell(const MediumParams& m, uint32_t x1, uint32_t y1, uint32_t z1) {
+  if (m.format) return m.cells + (__umul24(z1, m.rxy) + __umul24(y1, m.rx) + x1);
+  return m.cells + 2 * (__umul24(z1, m.rxy) + __umul24(y1, m.rx) + x1);
+}
 CVR_DEV WoodcockPoint woodcock_point(const MediumParams& m, V3 o, V3 d, float t) {
   WoodcockPoint P;
   woodcock_coords(m, o, d, t, P);
@@ -553,12 +586,12 @@ CVR_DEV WoodcockPoint woodcock_point(const MediumParams& m, V3 o, V3 d, float t)
   if (m.sbounds) {  // sparse: bound and cell-leaf slot in one word
     const uint32_t sw = m.sbounds[bi];
     P.qb = bound_value(sw >> 24);
-    P.cp = m.cells + ((((size_t)(sw & 0xFFFFFFu)) << 9 | leaf_local(x1, y1, z1)) << 1);
+    P.cp = m.cells + ((((size_t)(sw & 0xFFFFFFu)) << 9 | leaf_local(x1, y1, z1)) << cell_shift(m));
   } else {
     uint32_t q = 255u;
     if (m.bounds) q = m.bounds[bi];
     P.qb = bound_value(q);
-    P.cp = m.cells + 2 * (__umul24(z1, m.rxy) + __umul24(y1, m.rx) + x1);
+    P.cp = dense_cell(m, x1, y1, z1);
   }
   return P;
 }
@@ -583,14 +616,22 @@ CVR_DEV WoodcockPoint woodcock_point_em(const MediumParams& m, V3 o, V3 d, float
   if (load) sw = m.sbounds[__umul24(z1 >> m.bshift, m.bnxy) + __umul24(y1 >> m.bshift, m.bnx) + (x1 >> m.bshift)];
   if (n_words) *n_words += load ? 1u : 0u;
   P.qb = bound_value(sw >> 24);
-  P.cp = m.cells + ((((size_t)(sw & 0xFFFFFFu)) << 9 | leaf_local(x1, y1, z1)) << 1);
+  P.cp = m.cells + ((((size_t)(sw & 0xFFFFFFu)) << 9 | leaf_local(x1, y1, z1)) << cell_shift(m));
   return P;
 }
 
 // The exact density at the point (cell trilinear or the 8-tap gather).
 CVR_DEV float woodcock_density(const MediumParams& m, const WoodcockPoint& P) {
   if (P.in && m.cells) {
-    const float4 lo = P.cp[0], hi = P.cp[1];
+    float4 lo, hi;
+    if (m.format) {  // one 16-byte load, converted
+      const cvr_h8 h = *reinterpret_cast<const cvr_h8*>(P.cp);
+      lo = make_float4((float)h[0], (float)h[1], (float)h[2], (float)h[3]);
+      hi = make_float4((float)h[4], (float)h[5], (float)h[6], (float)h[7]);
+    } else {
+      lo = P.cp[0];
+      hi = P.cp[1];
+    }
     // cx - floorf(cx) (Volume.h:56-58): exact for 0 <= cx, which is what v_fract_f32 returns
     return trilerp_cell(lo, hi, __builtin_amdgcn_fractf(P.cx), __builtin_amdgcn_fractf(P.cy),
                         __builtin_amdgcn_fractf(P.cz));

@@ -632,6 +632,10 @@ constexpr int kMedMK = 4;
 // (the empty-region mask skips the rest), so that the launch's algorithmic bytes are
 // exact; the benchmarked instances carry no counter.
 constexpr int kMedCount = 8;
+// kMedHalf (or-ed into kMed): the instance reads the half storage format
+// (MediumParams::format 1) as a compile-time constant, the instances without it format
+// 0, as albedo_uniform is pinned; the generic kMedDense instances read it at run time.
+constexpr int kMedHalf = 16;
 template <bool kScatterEps, int kWaves, int kMedMk, bool kRecord, bool kFlush>
 __global__ __launch_bounds__(64 * wpg_of(kMedMk, kWaves), kWaves) void k_wpool(MediumParams mk, LaunchParams Lk) {
   constexpr bool kMK = (kMedMk & kMedMK) != 0;
@@ -670,6 +674,7 @@ __global__ __launch_bounds__(64 * wpg_of(kMedMk, kWaves), kWaves) void k_wpool(M
       __builtin_assume(m.cells != nullptr);
       __builtin_assume(m.bounds != nullptr);
       m.albedo_uniform = kMed == kMedDenseFullUniform ? 1u : 0u;
+      m.format = (kMedMk & kMedHalf) ? 1u : 0u;
     }
   } else {
     // and sparse instances see the dense pointers as constant null (a sparse medium
@@ -680,7 +685,9 @@ __global__ __launch_bounds__(64 * wpg_of(kMedMk, kWaves), kWaves) void k_wpool(M
     __builtin_assume(m.leaves != nullptr);
     __builtin_assume(m.sbounds != nullptr);
     m.albedo_uniform = 0u;
+    m.format = (kMedMk & kMedHalf) ? 1u : 0u;
   }
+  static_assert(!(kMedMk & kMedHalf) || kMed != kMedDense, "the generic dense instance reads the format at run time");
 #if CVR_WPOOL_TAILSTAMP
   const unsigned long long ts_start = __builtin_amdgcn_s_memrealtime();
   unsigned long long ts_ex = 0, ts_ev = 0, ts_a = 0;
@@ -812,7 +819,7 @@ __global__ __launch_bounds__(64 * wpg_of(kMedMk, kWaves), kWaves) void k_wpool(M
             WoodcockPoint P;
             woodcock_coords(m, o, d, t, P);
             const uint32_t x1 = (uint32_t)P.cx, y1 = (uint32_t)P.cy, z1 = (uint32_t)P.cz;
-            P.cp = m.cells + 2 * (__umul24(z1, m.rxy) + __umul24(y1, m.rx) + x1);
+            P.cp = dense_cell(m, x1, y1, z1);
             const float xt = det_fmaf((float)(rng.v4 + rng.d), 2.3283064e-10f, 1.1641532e-10f);  // its test draw
             const float rho = m.scale * woodcock_density(m, P);
             fst = !(rho * m.inv_sigma < xt) ? 2 : 0;
@@ -1381,6 +1388,7 @@ __global__ __launch_bounds__(128, kWaves) void k_wpair(MediumParams mk, LaunchPa
   __builtin_assume(m.cells != nullptr);
   __builtin_assume(m.bounds != nullptr);
   m.albedo_uniform = kMed == kMedDenseFullUniform ? 1u : 0u;
+  m.format = 0u;  // (launch_wpool keeps half-format media off the paired instances)
   static_assert(sizeof(PairPool<kN>) + sizeof(LaunchParams) <= (size_t)PairSize<kWaves>::kBudget,
                 "paired pool exceeds the LDS budget of kWaves waves per SIMD");
   __shared__ PairPool<kN> S;
@@ -1834,8 +1842,18 @@ __global__ __launch_bounds__(128, kWaves) void k_wpair(MediumParams mk, LaunchPa
 // Instances: 5 waves per SIMD (the default budget) for every medium layout, with and
 // without the in-launch output; the other budgets for the generic layouts.
 template <bool E>
-static const void* wpool_fn(int waves, bool sparse, bool full, bool flush = false, bool uniform = false) {
+static const void* wpool_fn(int waves, bool sparse, bool full, bool flush = false, bool uniform = false,
+                            bool half = false) {
 #define CVR_WP(W, M, F) reinterpret_cast<const void*>(&k_wpool<E, W, M, false, F>)
+  if (half) {
+    // the half storage format: 5 waves per SIMD; the generic dense instance reads the format at run time
+    if (waves != 5) return nullptr;
+    if (sparse) return flush ? CVR_WP(5, kMedSparse | kMedHalf, true) : CVR_WP(5, kMedSparse | kMedHalf, false);
+    if (full && uniform)
+      return flush ? CVR_WP(5, kMedDenseFullUniform | kMedHalf, true) : CVR_WP(5, kMedDenseFullUniform | kMedHalf, false);
+    if (full) return flush ? CVR_WP(5, kMedDenseFull | kMedHalf, true) : CVR_WP(5, kMedDenseFull | kMedHalf, false);
+    return flush ? CVR_WP(5, kMedDense, true) : CVR_WP(5, kMedDense, false);
+  }
   if (waves == 5) {
     if (sparse) return flush ? CVR_WP(5, kMedSparse, true) : CVR_WP(5, kMedSparse, false);
     if (full && uniform) return flush ? CVR_WP(5, kMedDenseFullUniform, true) : CVR_WP(5, kMedDenseFullUniform, false);
@@ -1852,7 +1870,11 @@ static const void* wpool_fn(int waves, bool sparse, bool full, bool flush = fals
 // Record instances (cvr_trace_launch; debug only, so the production kernels
 // carry none of the record code): the default register budgets, generic layouts.
 template <bool E>
-static const void* wpool_record_fn(int waves, bool sparse) {
+static const void* wpool_record_fn(int waves, bool sparse, bool half) {
+  if (half)
+    return waves != 5 ? nullptr
+           : sparse   ? reinterpret_cast<const void*>(&k_wpool<E, 5, kMedSparse | kMedHalf, true, false>)
+                      : reinterpret_cast<const void*>(&k_wpool<E, 5, kMedDense, true, false>);
   if (sparse) return waves == 5   ? reinterpret_cast<const void*>(&k_wpool<E, 5, kMedSparse, true, false>)
                     : waves == 4 ? reinterpret_cast<const void*>(&k_wpool<E, 4, kMedSparse, true, false>)
                                  : nullptr;
@@ -1860,8 +1882,14 @@ static const void* wpool_record_fn(int waves, bool sparse) {
 }
 
 // naiveMK instances (kMedMK): 5 waves per SIMD, every medium layout, scatter -eps.
-static const void* wpool_mk_fn(bool sparse, bool full, bool uniform) {
+static const void* wpool_mk_fn(bool sparse, bool full, bool uniform, bool half) {
 #define CVR_WPMK(M) reinterpret_cast<const void*>(&k_wpool<true, 5, (M) | kMedMK, false, false>)
+  if (half) {
+    if (sparse) return CVR_WPMK(kMedSparse | kMedHalf);
+    if (full && uniform) return CVR_WPMK(kMedDenseFullUniform | kMedHalf);
+    if (full) return CVR_WPMK(kMedDenseFull | kMedHalf);
+    return CVR_WPMK(kMedDense);
+  }
   if (sparse) return CVR_WPMK(kMedSparse);
   if (full && uniform) return CVR_WPMK(kMedDenseFullUniform);
   if (full) return CVR_WPMK(kMedDenseFull);
@@ -1876,6 +1904,9 @@ hipError_t launch_wpool(const MediumParams& m, const LaunchParams& L, bool scatt
   const bool flush = L.frame_done != nullptr;
   const bool full = !sparse && m.cells != nullptr && m.bounds != nullptr;
   const bool uniform = m.albedo_uniform != 0u;
+  const bool half = m.format != 0u;
+  // the half format has no paired, counting or other-budget instances (cvr_launch_render refuses them first)
+  if (half && (pair || count_words || waves != 5)) return hipErrorInvalidValue;
   if (L.rec && flush) return hipErrorInvalidValue;
   if (naive_mk) {
     if (waves != 5 || flush || L.rec) return hipErrorInvalidValue;
@@ -1883,7 +1914,7 @@ hipError_t launch_wpool(const MediumParams& m, const LaunchParams& L, bool scatt
     MediumParams mm = m;
     LaunchParams ll = L;
     void* args[] = {&mm, &ll};
-    return hipLaunchKernel(wpool_mk_fn(sparse, full, uniform), dim3(grid / wpool_wpg(waves, sparse)),
+    return hipLaunchKernel(wpool_mk_fn(sparse, full, uniform, half), dim3(grid / wpool_wpg(waves, sparse)),
                            dim3(64 * wpool_wpg(waves, sparse)), args, 0, s);
   }
 #if CVR_WPOOL_PAIR
@@ -1901,9 +1932,10 @@ hipError_t launch_wpool(const MediumParams& m, const LaunchParams& L, bool scatt
 #else
   if (pair) return hipErrorInvalidValue;  // (cvr_set_option refuses it first)
 #endif
-  const void* fn = L.rec ? (scatter_eps ? wpool_record_fn<true>(waves, sparse) : wpool_record_fn<false>(waves, sparse))
-                         : (scatter_eps ? wpool_fn<true>(waves, sparse, full, flush, uniform)
-                                        : wpool_fn<false>(waves, sparse, full, flush, uniform));
+  const void* fn = L.rec ? (scatter_eps ? wpool_record_fn<true>(waves, sparse, half)
+                                        : wpool_record_fn<false>(waves, sparse, half))
+                         : (scatter_eps ? wpool_fn<true>(waves, sparse, full, flush, uniform, half)
+                                        : wpool_fn<false>(waves, sparse, full, flush, uniform, half));
   // the counting instances (CVR_OPT_COUNT_WORDS): sparse media, 5 waves per SIMD, no records
   // or in-launch output (other launches count nothing: cvr_stats.words stays 0)
   if (count_words && sparse && waves == 5 && !L.rec && !flush)

@@ -24,7 +24,8 @@
 extern "C" {
 #endif
 
-#define CVR_ABI_VERSION 4  /* 3: cvr_render_frame takes the host buffer size; 4: cvr_stats.words */
+#define CVR_ABI_VERSION 5  /* 3: cvr_render_frame takes the host buffer size; 4: cvr_stats.words;
+                              5: CVR_OPT_MEDIUM_FORMAT, cvr_half_round, cvr_medium_info */
 
 enum {
   CVR_OK = 0,
@@ -170,6 +171,33 @@ typedef enum {
                                  into cvr_stats.words (the benchmark's exact algorithmic bytes; one
                                  more VGPR in the track loop, so not the benchmarked kernel); 0
                                  (default) counts nothing.  Results are unchanged. */
+  CVR_OPT_MEDIUM_FORMAT = 30,  /* storage precision of the voxel values in HBM, taken at the next cvr_set_medium /
+                                 cvr_set_medium_sparse (as CVR_OPT_CELLS): 0 (default, CVR_FORMAT_F32) fp32;
+                                 1 (CVR_FORMAT_F16) IEEE binary16: half the bytes of the density, the density
+                                 cells and the albedo (cvr_medium_info).  Other values: CVR_ERR_INVALID.
+                                 Format 1 contract:
+                                 - every density voxel and the r, g, b of every albedo voxel (and the sparse
+                                   albedo_background) is rounded to binary16, round to nearest even, before
+                                   anything is built from it; fp16 subnormals are kept, not flushed;
+                                 - the majorant used is max_density_eff = max(max_density,
+                                   f32(f16(max_density))) (max_density itself if that rounds to inf): rounding
+                                   is monotonic, so a valid majorant stays valid;
+                                 - a half converts to fp32 exactly and all arithmetic after the load is fp32,
+                                   so the render is bit-identical per path to a format-0 render of the rounded
+                                   medium (cvr_half_round) with max_density_eff: the same image id, flags, T
+                                   bits, segment count and counters; pixels equal up to fp32 summation order;
+                                 - a finite value that rounds to +-inf (|v| >= 65520) fails the set-medium call
+                                   with CVR_ERR_INVALID, the message names the first one, and the context is
+                                   left without a medium; NaN, inf and negative values pass through rounded,
+                                   as format 0 passes them;
+                                 - the fp32 arrays are staged on the device, converted there and the staging
+                                   freed before the call returns: the resident medium is halved, the peak
+                                   during the upload is not (fp32 staging + the half grid).
+                                 Runs on the wave-pool scheduler at 5 waves per SIMD (every kernel id,
+                                 cvr_render_frame's in-launch output, cvr_trace_launch, CVR_OPT_CELLS 0 too) and
+                                 in cvr_trace_paths; with another CVR_OPT_SCHEDULER or CVR_OPT_WAVES value,
+                                 CVR_OPT_RNG_BINDING 1, CVR_OPT_COUNT_WORDS 1, CVR_OPT_MK_COMPACTION 1 or
+                                 CVR_OPT_WAVE_PAIR 1 a launch on a format-1 medium returns CVR_ERR_UNSUPPORTED. */
   /* 21: unused (a drain-time path migration between waves, measured slower: DESIGN.md §6) */
   CVR_OPT_DRAIN = 22,          /* wave-pool scheduler, once the queues are empty: an event batch runs as
                                  soon as the waiting segments x d >= the tracking ones (d = 0: only when
@@ -182,6 +210,7 @@ typedef enum {
                                  launch with CVR_ERR_STATE.  Runs the reference's per-bounce kernel
                                  sequence (one launch and host sync per bounce). */
 } cvr_option;
+enum { CVR_FORMAT_F32 = 0, CVR_FORMAT_F16 = 1 }; /* CVR_OPT_MEDIUM_FORMAT */
 
 /* HeterogeneousMedium + GGX boundary (Medium.h:110-190, Bsdf.h:17-30). */
 typedef struct cvr_medium_desc {
@@ -241,6 +270,18 @@ typedef struct cvr_stats {
                           rest); counted only by launches with CVR_OPT_COUNT_WORDS 1, else 0 */
 } cvr_stats;
 
+/* The medium a context renders: device bytes by part.  The function cvr_medium_info fills it, so
+ * the type has no typedef: write `struct cvr_medium_info`. */
+struct cvr_medium_info {
+  int32_t format;          /* CVR_FORMAT_F32 / CVR_FORMAT_F16 */
+  float max_density_eff;   /* the majorant in use (format 0: max_density as given) */
+  uint64_t density_bytes;  /* density grid, or the leaf density pool */
+  uint64_t cells_bytes;    /* density cells, or the cell-leaf pool (0 with CVR_OPT_CELLS 0) */
+  uint64_t albedo_bytes;   /* albedo grid, or the leaf albedo pool (0: background only) */
+  uint64_t bounds_bytes;   /* brick bounds; sparse: brick words + leaf table + empty-region mask */
+  uint64_t total_bytes;    /* the four above */
+};
+
 typedef struct cvr_path_record {
   uint32_t image_id;
   uint32_t flags; /* bit0 escaped, bit1 truncated */
@@ -269,6 +310,14 @@ int cvr_set_medium_sparse(cvr_ctx* ctx, const cvr_sparse_medium_desc* medium);
  * `ctx` first, or give it a medium of its own, before `src` changes or frees
  * its medium).  For several contexts with renders in flight on one GPU. */
 int cvr_share_medium(cvr_ctx* ctx, const cvr_ctx* src);
+/* Format and device bytes of the context's medium, either format.  A context that
+ * shares a medium (cvr_share_medium) reports the source's, and renders in that
+ * format whatever its own CVR_OPT_MEDIUM_FORMAT says.  CVR_ERR_STATE: no medium. */
+int cvr_medium_info(const cvr_ctx* ctx, struct cvr_medium_info* out);
+/* Host only (no GPU): out[i] = f32(f16(in[i])), exactly the rounding of CVR_OPT_MEDIUM_FORMAT 1
+ * (nearest even, subnormals kept, |v| >= 65520 -> +-inf, NaN stays NaN), so that a caller
+ * can build the fp32 medium a format-1 render is bit-identical to.  in == out is allowed. */
+int cvr_half_round(const float* in, float* out, size_t n);
 /* copyInvViewMatrix (12 floats), copyRasterToView, copyPixelIndexRange */
 int cvr_set_camera(cvr_ctx* ctx, const float inv_view[12], const float raster_to_view[2],
                    const float full_res[2]);

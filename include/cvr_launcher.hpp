@@ -151,6 +151,11 @@ class HipVolPTKernelLauncher {
     check(cvr_set_offset(ctx(), static_cast<uint32_t>(offset.x), static_cast<uint32_t>(offset.y)));
   }
 
+  /* Extension (no counterpart in the reference): storage precision of the
+   * voxel values on the device, CVR_FORMAT_F32 (default) or CVR_FORMAT_F16
+   * (CVR_OPT_MEDIUM_FORMAT); takes effect at the next setScene. */
+  void setMediumFormat(int format) { check(cvr_set_option(ctx(), CVR_OPT_MEDIUM_FORMAT, format)); }
+
   /* VolPTKernelLauncher::setScene (RenderKernelLauncher.h:67-69): uploads
    * the host volumes into HBM. */
   void setScene(const DeviceScene& scene) {
