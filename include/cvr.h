@@ -265,9 +265,19 @@ typedef struct cvr_stats {
   uint64_t iterations; /* wavefront: events/track kernel pairs of the last launch */
   double track_ms;     /* wavefront: summed device time of the tracking kernels (CVR_OPT_TIMING) */
   double events_ms;    /* wavefront: summed device time of the event kernels (CVR_OPT_TIMING) */
-  uint64_t fetches;    /* density cells fetched (evaluations not settled by a brick bound) */
-  uint64_t words;      /* sparse media: brick words loaded (the empty-region mask skips the
-                          rest); counted only by launches with CVR_OPT_COUNT_WORDS 1, else 0 */
+  uint64_t fetches;    /* density evaluations that read their density (a 32-byte cell, or the 8-tap
+                          gather off the cell grid or with CVR_OPT_CELLS 0): exactly those whose brick
+                          bound does not settle the test, !(bound_value(code) < test draw), where a point
+                          with 0 <= c < res on every axis of its grid coordinate reads its brick's code
+                          and any other point reads 255 (no bound); bounds off: equal to `density`.
+                          Independent of scheduler, kernel instance and the empty-region mask. */
+  uint64_t words;      /* sparse media: brick words loaded; counted only by launches with
+                          CVR_OPT_COUNT_WORDS 1, else 0.  A word is loaded for each of the two tentative
+                          points of a lookahead pair that lies on the cell grid in a super-brick whose
+                          mask bit is set (mask off or bounds off: on the cell grid), dropped points
+                          included.  So W_lo <= words <= W_lo + 2 S + fetches, W_lo the evaluated points
+                          of that kind and S the segments that ran Woodcock tracking (each ends past
+                          max_t at most once, dropping at most two points; each fetch drops at most one). */
 } cvr_stats;
 
 /* The medium a context renders: device bytes by part.  The function cvr_medium_info fills it, so

@@ -263,6 +263,22 @@ static int aabb_intersect(const oracle_medium* m, f3 o, f3 d, isect_t* is) {
  * precedence (Q4, the default).  fix_q4: the intended (p - start)/range, as
  * the kernels compute it with CVR_OPT_WORLD_TO_AABB 1: c = p - start, then the
  * grid coordinate c * ((res - 1)/range), one rounding per step. */
+/* Evaluation log (oracle_trace_evals): one row per density evaluation of the
+ * calling thread's walk, in walk order.  NULL outside that call, so every other
+ * entry point pays one pointer test per evaluation. */
+typedef struct {
+  uint32_t path_id;
+  float cx, cy, cz; /* the grid coordinate tri_setup_g computes (c * g) */
+  float xi_test;    /* the test draw */
+  float test_value; /* fl(fl(scale * rho) * inv) */
+} oracle_eval;
+typedef struct {
+  oracle_eval* rows;
+  uint64_t cap, n; /* n counts every evaluation; rows beyond cap are not written */
+  uint32_t path_id;
+} eval_log_t;
+static __thread eval_log_t* tl_eval_log = NULL;
+
 static float woodcock(const oracle_medium* m, f3 o, f3 d, float max_t, xorwow_t* rng,
                       uint32_t* n_steps, uint32_t* n_density, int fix_q4) {
   f3 bmin = mk3(m->box_min[0], m->box_min[1], m->box_min[2]);
@@ -285,7 +301,22 @@ static float woodcock(const oracle_medium* m, f3 o, f3 d, float max_t, xorwow_t*
     f3 c = sub3(p, shift);
     float rho = m->scale * density_lookup_g(m, c, g);
     ++*n_density;
-    if (!(rho * inv < rng_float(rng))) break;
+    const float xt = rng_float(rng);
+    const float tv = rho * inv;
+    if (tl_eval_log) {
+      eval_log_t* lg = tl_eval_log;
+      if (lg->n < lg->cap) {
+        oracle_eval* e = &lg->rows[lg->n];
+        e->path_id = lg->path_id;
+        e->cx = c.x * g[0];
+        e->cy = c.y * g[1];
+        e->cz = c.z * g[2];
+        e->xi_test = xt;
+        e->test_value = tv;
+      }
+      ++lg->n;
+    }
+    if (!(tv < xt)) break;
   }
   return t;
 }
@@ -744,6 +775,25 @@ EXPORT void oracle_trace_path(const oracle_medium* m, const oracle_launch* L, ui
 EXPORT void oracle_trace_paths(const oracle_medium* m, const oracle_launch* L, uint32_t first,
                                uint32_t count, oracle_path* out) {
   for (uint32_t i = 0; i < count; ++i) oracle_trace_path(m, L, first + i, &out[i]);
+}
+
+/* oracle_trace_paths plus the evaluation log: `evals` receives the first `cap`
+ * density evaluations of path ids [first, first+count) in walk order (every
+ * kernel id: the log is written by woodcock()); returns how many there were, so
+ * a call with cap 0 sizes the buffer.  Single-threaded. */
+EXPORT uint64_t oracle_trace_evals(const oracle_medium* m, const oracle_launch* L, uint32_t first,
+                                   uint32_t count, oracle_path* out, oracle_eval* evals, uint64_t cap) {
+  eval_log_t lg;
+  lg.rows = evals;
+  lg.cap = evals ? cap : 0;
+  lg.n = 0;
+  tl_eval_log = &lg;
+  for (uint32_t i = 0; i < count; ++i) {
+    lg.path_id = first + i;
+    oracle_trace_path(m, L, first + i, &out[i]);
+  }
+  tl_eval_log = NULL;
+  return lg.n;
 }
 
 /* ---------------------------------------------------- tile render ------ */

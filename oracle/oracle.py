@@ -18,6 +18,10 @@ LIB_PATH = os.path.join(_HERE, "liboracle.so")
 PATH_DTYPE = np.dtype([("image_id", "<u4"), ("flags", "<u4"), ("T", "<f4", (3,)),
                        ("n_segments", "<u4"), ("n_steps", "<u4"), ("n_density", "<u4"),
                        ("n_albedo", "<u4")])
+# one density evaluation (oracle_eval): the grid coordinate of the point (tri_setup_g's c * g), the
+# test draw and the test value fl(fl(scale * rho) * inv) it is compared with
+EVAL_DTYPE = np.dtype([("path_id", "<u4"), ("cx", "<f4"), ("cy", "<f4"), ("cz", "<f4"), ("xi_test", "<f4"),
+                       ("test_value", "<f4")])
 
 
 class OracleMedium(C.Structure):
@@ -63,6 +67,9 @@ def load():
     P = C.c_void_p
     lib.oracle_trace_paths.argtypes = [C.POINTER(OracleMedium), C.POINTER(OracleLaunch), C.c_uint32,
                                        C.c_uint32, P]
+    lib.oracle_trace_evals.argtypes = [C.POINTER(OracleMedium), C.POINTER(OracleLaunch), C.c_uint32,
+                                       C.c_uint32, P, P, C.c_uint64]
+    lib.oracle_trace_evals.restype = C.c_uint64
     lib.oracle_render.argtypes = [C.POINTER(OracleMedium), C.POINTER(OracleLaunch), C.c_uint64,
                                   C.c_uint64, C.c_uint64, C.POINTER(C.c_float), C.c_int,
                                   C.POINTER(OracleStats)]
@@ -173,6 +180,16 @@ class Oracle:
         out = np.zeros(count, PATH_DTYPE)
         self.lib.oracle_trace_paths(C.byref(self.m), C.byref(L), first, count, _p(out))
         return out
+
+    def trace_evals(self, L: OracleLaunch, first: int, count: int):
+        """(records, evals): trace_paths' records and one EVAL_DTYPE row per density
+        evaluation of those paths, in walk order (oracle_trace_evals; single-threaded)."""
+        out = np.zeros(count, PATH_DTYPE)
+        n = self.lib.oracle_trace_evals(C.byref(self.m), C.byref(L), first, count, _p(out), None, 0)
+        evals = np.zeros(n, EVAL_DTYPE)
+        got = self.lib.oracle_trace_evals(C.byref(self.m), C.byref(L), first, count, _p(out), _p(evals), n)
+        assert got == n
+        return out, evals
 
     def render(self, L: OracleLaunch, first: int, count: int, stride: int = 1, nthreads: int = 1,
                out: np.ndarray | None = None):

@@ -13,97 +13,20 @@ Scenes are the smallest that take every path of the code: a dense 19x13x11 grid
 (no multiple of the 4^3 brick, ~40 % zeros, planted fp16 subnormal / flush-to-
 zero / tie values), the same with a uniform albedo, and a sparse 20x12x28 index
 box with about half of its 8^3 leaves absent."""
-import ctypes as C
-
 import numpy as np
 import pytest
 
+from media import SCALE, dense_arrays, sparse_arrays, sparse_desc
 from parity_util import (COUNTERS, NTHREADS, assert_counters_equal, assert_pixels_close, gpu_range_render,
                          oracle_image)
 
 pytestmark = pytest.mark.gpu
 
-SCALE = 100.0
 TILE = (16, 16)
 ITERS = 4  # 1024 paths
 
 
 # ------------------------------------------------------------------ scenes --
-def dense_arrays(md_case="max", uniform=False, seed=7):
-    """Scene 1 (and 2 with uniform): (density, albedo, max_density), unrounded."""
-    rng = np.random.default_rng(seed)
-    nz, ny, nx = 11, 13, 19
-    d = rng.random((nz, ny, nx), dtype=np.float32)
-    d[rng.random(d.shape) < 0.4] = 0.0
-    d[5, 6, 9] = 1e-6              # an fp16 subnormal
-    d[5, 6, 10] = 1e-8             # rounds to 0
-    d[4, 6, 9] = 0.5 + 2.0 ** -12  # a tie (to even: 0.5)
-    a = np.ones((nz, ny, nx, 4), np.float32)
-    if uniform:
-        a[..., :3] = np.float32(0.9)
-    else:
-        a[..., :3] = 0.2 + 0.8 * rng.random((nz, ny, nx, 3), dtype=np.float32)
-    if md_case == "max":
-        md = float(d.max())
-    elif md_case == "up":      # f16(0.3) = 0.30004883 > 0.3
-        d *= np.float32(0.29)
-        md = float(np.float32(0.3))
-    else:                      # f16(0.9) = 0.89990234 < 0.9
-        d *= np.float32(0.89)
-        md = float(np.float32(0.9))
-    return d, a, md
-
-
-def sparse_arrays(with_albedo=True, seed=11):
-    """Scene 3: index box 20x12x28 -> 3x2x4 leaves, about half absent, the z = 3 slab and
-    most of z = 2 empty, so that whole super-bricks (here: leaves) hold no cell leaf."""
-    rng = np.random.default_rng(seed)
-    res = (20, 12, 28)
-    lx, ly, lz = 3, 2, 4
-    present = np.zeros((lz, ly, lx), bool)
-    present[0] = [[1, 0, 1], [1, 1, 0]]
-    present[1] = [[0, 1, 1], [1, 0, 1]]
-    present[2] = [[0, 0, 0], [0, 0, 1]]
-    table = np.full((lz, ly, lx), 0xFFFFFFFF, np.uint32)
-    table[present] = np.arange(present.sum(), dtype=np.uint32)
-    n = int(present.sum())
-    dens = rng.random((n, 512), dtype=np.float32)
-    dens[rng.random(dens.shape) < 0.4] = 0.0
-    dens[0, 73] = 1e-6
-    dens[0, 74] = 1e-8
-    dens[1, 200] = 0.5 + 2.0 ** -12
-    alb = None
-    if with_albedo:
-        alb = np.ones((n, 512, 4), np.float32)
-        alb[..., :3] = 0.2 + 0.8 * rng.random((n, 512, 3), dtype=np.float32)
-    bg = (0.7, 0.55, 0.33, 1.0)
-    return res, table, dens, alb, bg, float(dens.max())
-
-
-def sparse_desc(cvr, res, table, dens, alb, bg, md):
-    from cudavolumerenderer_amd._lib import SparseMediumDesc
-    table = np.ascontiguousarray(table, np.uint32)
-    dens = np.ascontiguousarray(dens, np.float32)
-    alb = None if alb is None else np.ascontiguousarray(alb, np.float32)
-    s = SparseMediumDesc()
-    s.res[:] = res
-    s.leaf_dims[:] = table.shape[::-1]
-    s.leaf_table = table.ctypes.data_as(C.POINTER(C.c_uint32))
-    s.n_leaves = dens.shape[0]
-    s.leaf_density = dens.ctypes.data_as(C.POINTER(C.c_float))
-    if alb is not None:
-        s.leaf_albedo = alb.ctypes.data_as(C.POINTER(C.c_float))
-    s.albedo_background[:] = bg
-    s.box_min[:] = (-0.5,) * 3
-    s.box_max[:] = (0.5,) * 3
-    s.scale = SCALE
-    s.max_density = md
-    s.g = 0.0
-    s.roughness[:] = (0.1, 0.1)
-    s.eta = np.float32(np.float32(1.05) / np.float32(1.01))
-    return s, (table, dens, alb)
-
-
 def md_eff(cvr, md):
     h = float(cvr.half_round(np.array([md], np.float32))[0])
     return max(float(np.float32(md)), h)
