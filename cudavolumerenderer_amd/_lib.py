@@ -34,6 +34,7 @@ OPT_BOUNDS, OPT_TAIL, OPT_BATCH, OPT_RNG_BINDING, OPT_MORTON = 13, 14, 15, 16, 1
 OPT_WORLD_TO_AABB, OPT_MK_COMPACTION, OPT_SUBQUEUES, OPT_DRAIN, OPT_INFLIGHT, OPT_FRAME_FLUSH = 18, 19, 20, 22, 23, 24
 OPT_UNIFORM_ALBEDO, OPT_WAVE_PAIR, OPT_SAMPLE_ORDER, OPT_EMPTY_MASK, OPT_COUNT_WORDS = 25, 26, 27, 28, 29
 OPT_MEDIUM_FORMAT = 30
+OPT_MOMENTS = 31  # per-pixel second moments behind the tile (Context.copy_moments)
 FORMAT_F32, FORMAT_F16 = 0, 1  # OPT_MEDIUM_FORMAT: storage precision of the voxel values in HBM
 
 
@@ -104,6 +105,25 @@ LOAD_DEFAULT_ALBEDO = 1
 
 class RenderDesc(C.Structure):
     _fields_ = [("resolution", C.c_uint32 * 2), ("n_tiles", C.c_uint32 * 2), ("iterations", C.c_uint32)]
+
+
+class AdaptiveDesc(C.Structure):
+    """cvr_adaptive_desc: the sampling plan of a noise-targeted render."""
+    _fields_ = [("min_iterations", C.c_uint32), ("max_iterations", C.c_uint32), ("pass_iterations", C.c_uint32),
+                ("target", C.c_float), ("floor", C.c_float)]
+
+    def __init__(self, min_iterations=8, max_iterations=32, pass_iterations=4, target=0.05, floor=0.01):
+        super().__init__(min_iterations, max_iterations, pass_iterations, target, floor)
+
+
+class AdaptiveResult(C.Structure):
+    """cvr_adaptive_result: the session's state after a pass."""
+    _fields_ = [("passes", C.c_uint32), ("blocks", C.c_uint32), ("blocks_active", C.c_uint32),
+                ("paths", C.c_uint64), ("max_error", C.c_double), ("mean_error", C.c_double),
+                ("done", C.c_int32)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
 
 
 _lib = None
@@ -179,6 +199,15 @@ def load() -> C.CDLL:
         "cvr_write_hdr": (I32, [C.c_char_p, FP, U32, U32]),
         "cvr_kernel_from_name": (I32, [C.c_char_p]),
         "cvr_kernel_name": (C.c_char_p, [I32]),
+        "cvr_copy_moments": (I32, [P, FP, FP]),
+        "cvr_block_error": (I32, [FP, FP, U32, U32, F, C.POINTER(C.c_double)]),
+        "cvr_adaptive_begin": (I32, [P, C.POINTER(AdaptiveDesc)]),
+        "cvr_adaptive_pass": (I32, [P, C.POINTER(AdaptiveResult)]),
+        "cvr_adaptive_maps": (I32, [P, C.POINTER(C.c_double), C.POINTER(U32)]),
+        "cvr_adaptive_image": (I32, [P, P, C.c_size_t]),
+        "cvr_adaptive_end": (I32, [P]),
+        "cvr_render_adaptive": (I32, [P, C.POINTER(AdaptiveDesc), P, C.c_size_t, C.POINTER(AdaptiveResult),
+                                      C.POINTER(Stats)]),
     }
     # an older experiment build (tools' --lib, A/B against a previous commit) may lack newer entry
     # points; the in-tree library must export every one (tests/test_host_abi.py)
@@ -212,6 +241,19 @@ def half_round(a) -> np.ndarray:
     out = np.empty_like(src)
     _check(load().cvr_half_round(_fp(src), _fp(out), src.size))
     return out
+
+
+def block_error(sum_rgba, m2_rgba, n_samples: int, floor: float) -> float:
+    """The adaptive render's noise metric (cvr_block_error; host only): the mean over the given
+    pixels (an 8x8 block) of the relative standard error of the pixel's mean, from the raw sums
+    `sum_rgba` (framebuffer) and `m2_rgba` (moments), (..., 4) floats each, n_samples per pixel."""
+    a = np.ascontiguousarray(sum_rgba, dtype=np.float32).reshape(-1, 4)
+    b = np.ascontiguousarray(m2_rgba, dtype=np.float32).reshape(-1, 4)
+    if a.shape != b.shape:
+        raise CvrError(-1, "block_error: sum and m2 differ in shape")
+    out = C.c_double()
+    _check(load().cvr_block_error(_fp(a), _fp(b), a.shape[0], n_samples, floor, C.byref(out)))
+    return out.value
 
 
 def default_camera(width: int, height: int):
@@ -520,6 +562,38 @@ class Context:
         self._c(load().cvr_copy_output(self._h, _fp(out), scale))
         return out
 
+    def copy_moments(self):
+        """(sum, m2): the raw framebuffer sums and the second moments (sum T^2 per channel, w: the
+        pixel's escape count) of an OPT_MOMENTS 1 context, (h, w, 4) each (cvr_copy_moments)."""
+        w, h = self.resolution
+        s1 = np.zeros((h, w, 4), np.float32)
+        s2 = np.zeros((h, w, 4), np.float32)
+        self._c(load().cvr_copy_moments(self._h, _fp(s1), _fp(s2)))
+        return s1, s2
+
+    def adaptive(self, desc: AdaptiveDesc) -> "AdaptiveSession":
+        """A noise-targeted render of the set tile as a context manager (cvr_adaptive_begin ..
+        cvr_adaptive_end): `with ctx.adaptive(desc) as a: while not a.step().done: ...; img = a.image()`."""
+        return AdaptiveSession(self, desc)
+
+    def render_adaptive(self, desc: AdaptiveDesc, host_ptr=None):
+        """cvr_render_adaptive: passes until every 8x8 block meets desc.target or has
+        desc.max_iterations samples.  Returns (image, AdaptiveResult, block error map, block
+        samples map); the maps are (tile_h / 8, tile_w / 8), the summed counters are left in
+        self.adaptive_stats.  host_ptr: a PinnedImage to store into (the image returned is then
+        its array)."""
+        w, h = self.resolution
+        res, st = AdaptiveResult(), Stats()
+        if isinstance(host_ptr, PinnedImage):
+            img, ptr, n = host_ptr.array, host_ptr.ptr, host_ptr.floats
+        else:
+            img = np.zeros((h, w, 4), np.float32)
+            ptr, n = C.c_void_p(img.ctypes.data), img.size
+        self._c(load().cvr_render_adaptive(self._h, C.byref(desc), ptr, n, C.byref(res), C.byref(st)))
+        self.adaptive_stats = st
+        err, smp = _adaptive_maps(self)
+        return img, res, err, smp
+
     def trace_paths(self, first: int, count: int) -> np.ndarray:
         out = np.zeros(count, PATH_RECORD_DTYPE)
         self._c(load().cvr_trace_paths(self._h, first, count,
@@ -625,6 +699,61 @@ class Context:
 
     def __exit__(self, *a):
         self.close()
+
+
+def _adaptive_maps(ctx: Context):
+    """(block error map f64, block samples map u32), (tile_h / 8, tile_w / 8) (cvr_adaptive_maps)."""
+    w, h = ctx.resolution
+    err = np.zeros((h // 8, w // 8), np.float64)
+    smp = np.zeros((h // 8, w // 8), np.uint32)
+    ctx._c(load().cvr_adaptive_maps(ctx._h, err.ctypes.data_as(C.POINTER(C.c_double)),
+                                    smp.ctypes.data_as(C.POINTER(C.c_uint32))))
+    return err, smp
+
+
+class AdaptiveSession:
+    """An open adaptive render of a Context (Context.adaptive): step() runs one pass, maps() gives
+    every block's last error and sample count, image() the image normalised per block."""
+
+    def __init__(self, ctx: Context, desc: AdaptiveDesc):
+        self.ctx = ctx
+        self.desc = desc
+        self.open = False
+        self.result = None
+        self.stats = Stats()  # summed counters of the passes so far
+
+    def __enter__(self):
+        self.ctx._c(load().cvr_adaptive_begin(self.ctx._h, C.byref(self.desc)))
+        self.open = True
+        return self
+
+    def __exit__(self, *exc):
+        if self.open:
+            self.open = False
+            self.ctx._c(load().cvr_adaptive_end(self.ctx._h))
+        return False
+
+    def step(self) -> AdaptiveResult:
+        res = AdaptiveResult()
+        self.ctx._c(load().cvr_adaptive_pass(self.ctx._h, C.byref(res)))
+        s = self.ctx.stats()  # the pass's launch
+        for k in ("paths", "segments", "steps", "density", "albedo", "escaped", "truncated", "fetches"):
+            setattr(self.stats, k, getattr(self.stats, k) + getattr(s, k))
+        self.stats.kernel_ms += s.kernel_ms
+        self.result = res
+        return res
+
+    def maps(self):
+        return _adaptive_maps(self.ctx)
+
+    def image(self, host_ptr=None) -> np.ndarray:
+        w, h = self.ctx.resolution
+        if isinstance(host_ptr, PinnedImage):
+            self.ctx._c(load().cvr_adaptive_image(self.ctx._h, host_ptr.ptr, host_ptr.floats))
+            return host_ptr.array
+        img = np.zeros((h, w, 4), np.float32)
+        self.ctx._c(load().cvr_adaptive_image(self.ctx._h, C.c_void_p(img.ctypes.data), img.size))
+        return img
 
 
 class PinnedImage:

@@ -237,7 +237,39 @@ struct cvr_ctx {
   bool flush_hdr_valid = false;  // d_flush holds flush_hdr
   unsigned int* frame_done_active = nullptr;
   uint32_t flush_last_blocks = 0, flush_fallbacks = 0;
+
+  // CVR_OPT_MOMENTS: the owned framebuffer holds a second float4 per pixel behind the tile
+  int moments = 0;
+  // The active block list (cvr_adaptive_*): while active_on, a launch renders exactly the tile
+  // blocks of `active` (ascending ids), n_blocks = its length; d_active holds them in the
+  // launch's order (each XCD band in 2-D Morton order), h_active the same on the host.
+  bool active_on = false;
+  std::vector<uint32_t> active, h_active;
+  uint32_t* d_active = nullptr;  // tile_px / 64 entries
+  // the adaptive session
+  struct Adaptive {
+    bool on = false;        // between cvr_adaptive_begin and cvr_adaptive_end
+    bool internal = false;  // the session's own launch is running through the public entry points
+    cvr_adaptive_desc d{};
+    uint32_t n_blocks = 0, passes = 0;
+    int done = 0;
+    uint64_t paths = 0;
+    std::vector<uint32_t> samples;  // per tile block
+    std::vector<double> err;        // per tile block, at its last check
+    std::vector<double> h_err;      // the last pass's errors, in h_active order
+    double* d_err = nullptr;        // tile_px / 64 doubles
+    uint32_t* d_counts = nullptr;   // tile_px / 64 sample counts (cvr_adaptive_image)
+    int saved_moments = 0;
+    uint32_t saved_iterations = 1;
+    cvr_stats acc{};
+  } ad;
 };
+// Calls that are out of order inside an adaptive session (the session's own launches pass).
+#define CVR_NOT_IN_SESSION(c, what)                                                                       \
+  do {                                                                                                    \
+    if ((c)->ad.on && !(c)->ad.internal)                                                                  \
+      return set_err(&(c)->err, CVR_ERR_STATE, "%s inside an adaptive session (cvr_adaptive_end first)", what); \
+  } while (0)
 
 using cvr::kWorkDebug;
 using cvr::kWorkQueues;
@@ -306,6 +338,22 @@ bool mk_on_wpool(const cvr_ctx* c) {
          wpool_waves_for(c, c->m.leaves != nullptr) == 5;
 }
 
+// CVR_OPT_MOMENTS: what the context's configuration has that the moments instances (wave pool,
+// 5 waves per SIMD, generic dense / fp32 sparse layout) do not run with, or null.
+const char* moments_refusal(const cvr_ctx* c) {
+  const bool sparse = c->m.leaves != nullptr;
+  return c->external_out                       ? "a caller's output buffer (cvr_set_output)"
+         : c->kernel == CVR_KERNEL_NAIVE_MK    ? "kernel id naiveMK"
+         : c->rng_binding                      ? "CVR_OPT_RNG_BINDING 1"
+         : scheduler_for(c) != 3               ? "a scheduler other than the wave pool (CVR_OPT_SCHEDULER 3)"
+         : wpool_waves_for(c, sparse) != 5     ? "CVR_OPT_WAVES other than 5"
+         : c->mk_compaction                    ? "CVR_OPT_MK_COMPACTION 1"
+         : c->count_words                      ? "CVR_OPT_COUNT_WORDS 1"
+         : c->wave_pair                        ? "CVR_OPT_WAVE_PAIR 1"
+         : (sparse && c->m.format != 0u)       ? "a sparse half medium"
+                                               : nullptr;
+}
+
 // Wave-pool grid of a launch of n_paths (one wave per workgroup): CVR_OPT_GRID,
 // else the occupancy grid, of which a small launch takes a part.  A launch of
 // fewer than 64 paths per wave (C1: 262 K paths) ends mostly in ramp-up and
@@ -339,14 +387,17 @@ int ensure_output(cvr_ctx* c) {
   if (c->external_out) return CVR_OK;
   const size_t px = (size_t)c->tile_w * c->tile_h;
   if (px == 0) return set_err(&c->err, CVR_ERR_STATE, "resolution not set");
-  if (c->out_owned_px < px) {
+  // CVR_OPT_MOMENTS: a second float4 per pixel behind the tile (out_owned_px: float4 allocated)
+  const size_t need = c->moments ? 2 * px : px;
+  if (c->out_owned_px < need) {
     // the old framebuffer may still be written by a launch in flight
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     if (c->d_out_owned) (void)hipFree(c->d_out_owned);
     c->d_out_owned = nullptr;
-    HIP_TRY(c, hipMalloc(&c->d_out_owned, px * sizeof(float4)));
-    HIP_TRY(c, hipMemsetAsync(c->d_out_owned, 0, px * sizeof(float4), c->stream));
-    c->out_owned_px = px;
+    c->out_owned_px = 0;
+    HIP_TRY(c, hipMalloc(&c->d_out_owned, need * sizeof(float4)));
+    HIP_TRY(c, hipMemsetAsync(c->d_out_owned, 0, need * sizeof(float4), c->stream));
+    c->out_owned_px = need;
   }
   c->d_out = c->d_out_owned;
   return CVR_OK;
@@ -414,7 +465,12 @@ void fill_launch(const cvr_ctx* c, cvr::LaunchParams& L, uint64_t first, uint64_
     L.samples = (uint32_t)(count / P);
     L.blocks_x = c->tile_w / 8;
     L.n_blocks = (uint32_t)(P / 64);
-    if (shard_world > 1 && block_order) {  // blocks shard_rank, shard_rank + world, ...
+    if (c->active_on) {
+      // the active block list: the launch's blocks are exactly the listed tile blocks, which reach
+      // the kernel as block_perm (cvr_launch_render, ensure_active_order); blk_off 0, blk_stride 1
+      L.n_blocks = (uint32_t)c->active.size();
+      L.path_count = L.n_blocks * 64u * L.samples;
+    } else if (shard_world > 1 && block_order) {  // blocks shard_rank, shard_rank + world, ...
       L.blk_off = c->shard_rank;
       L.blk_stride = c->shard_world;
       L.n_blocks = L.n_blocks > c->shard_rank ? (L.n_blocks - c->shard_rank + c->shard_world - 1) / c->shard_world : 0;
@@ -442,7 +498,9 @@ void fill_launch(const cvr_ctx* c, cvr::LaunchParams& L, uint64_t first, uint64_
     L.sub = 1;
   }
   L.div_queues = make_fastdiv(L.n_queues);
-  L.block_perm = (L.order == 1 && c->d_block_perm && c->block_perm_n == L.n_blocks) ? c->d_block_perm : nullptr;
+  // (a user table is ignored while a block list is active: the list itself travels as block_perm)
+  L.block_perm = (L.order == 1 && !c->active_on && c->d_block_perm && c->block_perm_n == L.n_blocks) ? c->d_block_perm
+                                                                                                       : nullptr;
   L.div_tile_px = make_fastdiv(L.tile_px);
   L.div_tile_w = make_fastdiv(L.tile_w);
   L.div_block = make_fastdiv(64u * L.samples);
@@ -796,6 +854,9 @@ int cvr_destroy(cvr_ctx* c) {
   if (c->d_smk) (void)hipFree(c->d_smk);
   if (c->d_block_perm) (void)hipFree(c->d_block_perm);
   if (c->d_zperm) (void)hipFree(c->d_zperm);
+  if (c->d_active) (void)hipFree(c->d_active);
+  if (c->ad.d_err) (void)hipFree(c->ad.d_err);
+  if (c->ad.d_counts) (void)hipFree(c->ad.d_counts);
   if (c->ev_start) (void)hipEventDestroy(c->ev_start);
   if (c->ev_stop) (void)hipEventDestroy(c->ev_stop);
   if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
@@ -856,6 +917,7 @@ static void fill_medium_common(cvr::MediumParams& m, const uint32_t res[3], cons
 
 int cvr_set_medium(cvr_ctx* c, const cvr_medium_desc* md) {
   if (!c || !md) return set_err(c ? &c->err : nullptr, CVR_ERR_INVALID, "NULL argument");
+  CVR_NOT_IN_SESSION(c, "cvr_set_medium");
   if (!md->density || !md->albedo) return set_err(&c->err, CVR_ERR_INVALID, "density/albedo is NULL");
   if (md->res[0] == 0 || md->res[1] == 0 || md->res[2] == 0)
     return set_err(&c->err, CVR_ERR_INVALID, "empty grid");
@@ -982,6 +1044,7 @@ int cvr_set_medium(cvr_ctx* c, const cvr_medium_desc* md) {
 
 int cvr_set_medium_sparse(cvr_ctx* c, const cvr_sparse_medium_desc* sd) {
   if (!c || !sd) return set_err(c ? &c->err : nullptr, CVR_ERR_INVALID, "NULL argument");
+  CVR_NOT_IN_SESSION(c, "cvr_set_medium_sparse");
   const uint32_t* res = sd->res;
   if (res[0] == 0 || res[1] == 0 || res[2] == 0) return set_err(&c->err, CVR_ERR_INVALID, "empty grid");
   for (int k = 0; k < 3; ++k)
@@ -1164,6 +1227,7 @@ int cvr_set_medium_sparse(cvr_ctx* c, const cvr_sparse_medium_desc* sd) {
 
 int cvr_share_medium(cvr_ctx* c, const cvr_ctx* src) {
   if (!c || !src) return set_err(c ? &c->err : nullptr, CVR_ERR_INVALID, "NULL argument");
+  CVR_NOT_IN_SESSION(c, "cvr_share_medium");
   if (c == src) return CVR_OK;
   if (!src->have_medium) return set_err(&c->err, CVR_ERR_STATE, "source context has no medium");
   if (src->device != c->device)
@@ -1208,6 +1272,7 @@ int cvr_half_round(const float* in, float* out, size_t n) {
 
 int cvr_set_camera(cvr_ctx* c, const float inv_view[12], const float r2v[2], const float full_res[2]) {
   if (!c || !inv_view || !r2v || !full_res) return set_err(c ? &c->err : nullptr, CVR_ERR_INVALID, "NULL argument");
+  CVR_NOT_IN_SESSION(c, "cvr_set_camera");
   memcpy(c->inv_view, inv_view, sizeof(c->inv_view));
   c->r2v[0] = r2v[0];
   c->r2v[1] = r2v[1];
@@ -1219,6 +1284,7 @@ int cvr_set_camera(cvr_ctx* c, const float inv_view[12], const float r2v[2], con
 
 int cvr_set_resolution(cvr_ctx* c, uint32_t w, uint32_t h) {
   if (!c) return set_err(nullptr, CVR_ERR_INVALID, "NULL ctx");
+  CVR_NOT_IN_SESSION(c, "cvr_set_resolution");
   if (w == 0 || h == 0) return set_err(&c->err, CVR_ERR_INVALID, "zero tile resolution");
   if ((uint64_t)w * h > (1ull << 24))
     return set_err(&c->err, CVR_ERR_INVALID, "tile of %ux%u exceeds 2^24 pixels (float pixel indexing)", w, h);
@@ -1240,6 +1306,7 @@ int cvr_get_resolution(const cvr_ctx* c, uint32_t* w, uint32_t* h) {
 
 int cvr_set_offset(cvr_ctx* c, uint32_t x, uint32_t y) {
   if (!c) return set_err(nullptr, CVR_ERR_INVALID, "NULL ctx");
+  CVR_NOT_IN_SESSION(c, "cvr_set_offset");
   c->off[0] = x;
   c->off[1] = y;
   return CVR_OK;
@@ -1247,6 +1314,7 @@ int cvr_set_offset(cvr_ctx* c, uint32_t x, uint32_t y) {
 
 int cvr_set_iterations(cvr_ctx* c, uint32_t it) {
   if (!c) return set_err(nullptr, CVR_ERR_INVALID, "NULL ctx");
+  CVR_NOT_IN_SESSION(c, "cvr_set_iterations");
   const uint64_t np = (uint64_t)c->tile_w * c->tile_h * it;
   if (np > 0xFFFFFFFFull)
     return set_err(&c->err, CVR_ERR_INVALID, "n_paths = %llu exceeds the reference's uint32 path ids",
@@ -1258,6 +1326,7 @@ int cvr_set_iterations(cvr_ctx* c, uint32_t it) {
 
 int cvr_set_path_range(cvr_ctx* c, uint64_t first, uint64_t count) {
   if (!c) return set_err(nullptr, CVR_ERR_INVALID, "NULL ctx");
+  CVR_NOT_IN_SESSION(c, "cvr_set_path_range");
   c->range_first = first;
   c->range_count = count;
   return CVR_OK;
@@ -1265,6 +1334,7 @@ int cvr_set_path_range(cvr_ctx* c, uint64_t first, uint64_t count) {
 
 int cvr_set_block_shard(cvr_ctx* c, uint32_t rank, uint32_t world) {
   if (!c) return set_err(nullptr, CVR_ERR_INVALID, "NULL ctx");
+  CVR_NOT_IN_SESSION(c, "cvr_set_block_shard");
   if (world == 0 || rank >= world) return set_err(&c->err, CVR_ERR_INVALID, "bad shard %u of %u", rank, world);
   c->shard_rank = rank;
   c->shard_world = world;
@@ -1306,6 +1376,7 @@ int cvr_launch_blocks(const cvr_ctx* c, uint32_t* n_blocks, uint32_t* n_queues, 
 
 int cvr_set_seed(cvr_ctx* c, uint32_t seed) {
   if (!c) return set_err(nullptr, CVR_ERR_INVALID, "NULL ctx");
+  CVR_NOT_IN_SESSION(c, "cvr_set_seed");
   c->seed = seed;
   return CVR_OK;
 }
@@ -1318,7 +1389,12 @@ int cvr_get_seed(const cvr_ctx* c, uint32_t* seed) {
 
 int cvr_set_output(cvr_ctx* c, void* p) {
   if (!c) return set_err(nullptr, CVR_ERR_INVALID, "NULL ctx");
+  CVR_NOT_IN_SESSION(c, "cvr_set_output");
   if (p) {
+    if (c->moments)
+      return set_err(&c->err, CVR_ERR_UNSUPPORTED,
+                     "a caller's output buffer does not run with second moments (CVR_OPT_MOMENTS 1): the moments lie "
+                     "behind the tile in the context's own allocation");
     c->d_out = static_cast<float4*>(p);
     c->external_out = true;
     return CVR_OK;
@@ -1333,6 +1409,7 @@ void* cvr_output_ptr(cvr_ctx* c) { return c ? c->d_out : nullptr; }
 
 int cvr_set_stream(cvr_ctx* c, void* s) {
   if (!c) return set_err(nullptr, CVR_ERR_INVALID, "NULL ctx");
+  CVR_NOT_IN_SESSION(c, "cvr_set_stream");
   c->stream = static_cast<hipStream_t>(s);  // NULL = the device's null stream
   return CVR_OK;
 }
@@ -1341,6 +1418,7 @@ void* cvr_own_stream(cvr_ctx* c) { return c ? (void*)c->own_stream : nullptr; }
 
 int cvr_set_option(cvr_ctx* c, int opt, int64_t v) {
   if (!c) return set_err(nullptr, CVR_ERR_INVALID, "NULL ctx");
+  CVR_NOT_IN_SESSION(c, "cvr_set_option");
   switch (opt) {
     case CVR_OPT_MAX_SEGMENTS:
       if (v < 0) return set_err(&c->err, CVR_ERR_INVALID, "max_segments < 0");
@@ -1428,6 +1506,27 @@ int cvr_set_option(cvr_ctx* c, int opt, int64_t v) {
         return set_err(&c->err, CVR_ERR_INVALID, "medium format must be 0 (fp32) or 1 (half)");
       c->medium_format = (int)v;
       return CVR_OK;
+    case CVR_OPT_MOMENTS:
+      if (v != 0 && v != 1) return set_err(&c->err, CVR_ERR_INVALID, "moments must be 0 or 1");
+      if (v == 1 && c->external_out)
+        return set_err(&c->err, CVR_ERR_UNSUPPORTED,
+                       "second moments (CVR_OPT_MOMENTS 1) do not run with a caller's output buffer (cvr_set_output)");
+      if (v == 1 && !c->moments) {
+        c->moments = 1;
+        if (c->tile_w && c->tile_h) {
+          // the moments half behind the tile (a grown allocation starts cleared, a reused one is cleared here)
+          const size_t px = (size_t)c->tile_w * c->tile_h;
+          const bool grown = c->out_owned_px < 2 * px;
+          int r = ensure_output(c);
+          if (r) {
+            c->moments = 0;
+            return r;
+          }
+          if (!grown) HIP_TRY(c, hipMemsetAsync(c->d_out + px, 0, px * sizeof(float4), c->stream));
+        }
+      }
+      if (v == 0) c->moments = 0;
+      return CVR_OK;
     case CVR_OPT_SAMPLE_ORDER:
       if (v < -1 || v > 1) return set_err(&c->err, CVR_ERR_INVALID, "sample order must be -1, 0 or 1");
       c->sample_order = (int)v;
@@ -1502,24 +1601,34 @@ static uint32_t spread_bits16(uint32_t v) {  // bit i -> bit 2i
 // block row.  C5 (4096^2, sparse cloud): 149.3 vs 155.3 ms row-major; C2
 // unchanged (tools/block_order.py).  Computed on the host once per block
 // layout, kept on the device.
+// The table for the given tile blocks: the launch's b-th block (b in [0, L.n_blocks), split
+// into the launch's XCD bands) is tile block tile_of[b]; perm[b] = the index of the block
+// that takes b's turn.
+static void morton_bands(const cvr::LaunchParams& L, const std::vector<uint32_t>& tile_of, std::vector<uint32_t>& perm) {
+  const uint32_t nb = L.n_blocks;
+  perm.resize(nb);
+  std::vector<std::pair<uint32_t, uint32_t>> code(nb);
+  for (uint32_t q = 0; q < L.n_queues / L.sub; ++q) {  // Morton order within each XCD band
+    const uint32_t a = band_begin(L, q), e = band_begin(L, q + 1);
+    for (uint32_t b = a; b < e; ++b) {
+      const uint32_t tb = tile_of[b];
+      const uint32_t bx = tb % L.blocks_x, by = tb / L.blocks_x;
+      code[b] = {spread_bits16(bx) | (spread_bits16(by) << 1), b};
+    }
+    std::sort(code.begin() + a, code.begin() + e);
+    for (uint32_t b = a; b < e; ++b) perm[b] = code[b].second;
+  }
+}
+
 static int ensure_zorder(cvr_ctx* c, cvr::LaunchParams& L) {
   if (L.order != 1 || L.block_perm || c->order != 2 || L.n_blocks == 0) return CVR_OK;
   const uint64_t key[5] = {L.n_blocks, (uint64_t)L.n_queues / L.sub, L.blk_off, L.blk_stride, L.blocks_x};
   if (!c->d_zperm || memcmp(key, c->zkey, sizeof(key)) != 0) {
     const uint32_t nb = L.n_blocks;
     std::vector<uint32_t>& perm = c->h_zperm;
-    perm.resize(nb);
-    std::vector<std::pair<uint32_t, uint32_t>> code(nb);
-    for (uint32_t q = 0; q < L.n_queues / L.sub; ++q) {  // Morton order within each XCD band
-      const uint32_t a = band_begin(L, q), e = band_begin(L, q + 1);
-      for (uint32_t b = a; b < e; ++b) {
-        const uint32_t tb = L.blk_off + b * L.blk_stride;
-        const uint32_t bx = tb % L.blocks_x, by = tb / L.blocks_x;
-        code[b] = {spread_bits16(bx) | (spread_bits16(by) << 1), b};
-      }
-      std::sort(code.begin() + a, code.begin() + e);
-      for (uint32_t b = a; b < e; ++b) perm[b] = code[b].second;
-    }
+    std::vector<uint32_t> tiles(nb);  // the blocks of the shard / band
+    for (uint32_t b = 0; b < nb; ++b) tiles[b] = L.blk_off + b * L.blk_stride;
+    morton_bands(L, tiles, perm);
     HIP_TRY(c, hipStreamSynchronize(c->stream));  // the previous table may still be in use
     if (c->d_zperm) (void)hipFree(c->d_zperm);
     c->d_zperm = nullptr;
@@ -1531,8 +1640,34 @@ static int ensure_zorder(cvr_ctx* c, cvr::LaunchParams& L) {
   return CVR_OK;
 }
 
+// The active block list as the launch's block table: unit_to_path takes the launch's b-th
+// block as tile block block_perm[b] (blk_off 0, blk_stride 1) and needs no permutation of
+// all blocks there, so a table that lists exactly the active tile blocks renders only
+// them, with the path ids (and so the RNG streams) of the full launch.  Order 2 puts each
+// XCD band of the list in 2-D Morton order (morton_bands), order 1 keeps it ascending.
+static int ensure_active_order(cvr_ctx* c, cvr::LaunchParams& L) {
+  if (!c->active_on) return CVR_OK;
+  if (L.order != 1 || L.n_blocks != c->active.size() || L.blk_off != 0 || L.blk_stride != 1)
+    return set_err(&c->err, CVR_ERR_STATE, "an active block list needs the pixel-block work order of whole samples");
+  const uint32_t tile_blocks = L.blocks_x * (c->tile_h / 8u);
+  for (uint32_t b : c->active)
+    if (b >= tile_blocks) return set_err(&c->err, CVR_ERR_STATE, "active block %u outside the tile's %u", b, tile_blocks);
+  c->h_active = c->active;
+  if (c->order == 2 && L.n_blocks) {
+    std::vector<uint32_t> perm;
+    morton_bands(L, c->active, perm);
+    for (uint32_t b = 0; b < L.n_blocks; ++b) c->h_active[b] = c->active[perm[b]];
+  }
+  if (!c->d_active || L.n_blocks == 0) return set_err(&c->err, CVR_ERR_STATE, "empty active block list");
+  HIP_TRY(c, hipStreamSynchronize(c->stream));  // the previous table may still be in use
+  HIP_TRY(c, hipMemcpy(c->d_active, c->h_active.data(), (size_t)L.n_blocks * sizeof(uint32_t), hipMemcpyHostToDevice));
+  L.block_perm = c->d_active;
+  return CVR_OK;
+}
+
 int cvr_launch_render(cvr_ctx* c) {
   if (!c) return set_err(nullptr, CVR_ERR_INVALID, "NULL ctx");
+  CVR_NOT_IN_SESSION(c, "cvr_launch_render");
   int r = check_ready(c);
   if (r) return r;
   if (!c->d_out) return set_err(&c->err, CVR_ERR_STATE, "no output buffer");
@@ -1549,10 +1684,20 @@ int cvr_launch_render(cvr_ctx* c) {
                                                            : nullptr;
     if (why) return set_err(&c->err, CVR_ERR_UNSUPPORTED, "the half medium format does not run with %s", why);
   }
+  if (c->moments) {
+    // second moments: the wave pool's two moments instances only, into the context's own buffer
+    const char* why = moments_refusal(c);
+    if (!why && c->d_rec_active) why = "cvr_trace_launch";
+    if (!why && c->frame_done_active) why = "cvr_render_frame's in-launch output";
+    if (why) return set_err(&c->err, CVR_ERR_UNSUPPORTED, "second moments (CVR_OPT_MOMENTS 1) do not run with %s", why);
+    if (c->out_owned_px < 2 * (size_t)c->tile_w * c->tile_h || c->d_out != c->d_out_owned)
+      return set_err(&c->err, CVR_ERR_STATE, "the framebuffer holds no moments (cvr_set_resolution)");
+  }
   uint64_t first, count;
   compute_range(c, &first, &count);
   cvr::LaunchParams L{};
   fill_launch(c, L, first, count);
+  if ((r = ensure_active_order(c, L))) return r;
   if ((r = ensure_zorder(c, L))) return r;
   const bool eps = scatter_eps_for(c);
   if (!c->chunk && scheduler_for(c) == 3) {
@@ -1652,7 +1797,7 @@ int cvr_launch_render(cvr_ctx* c) {
       L.frame_done = c->frame_done_active;
     }
     HIP_TRY(c, cvr::launch_wpool(launch_medium(c), L, eps, waves, grid, c->stream, c->wave_pair != 0,
-                                 c->kernel == CVR_KERNEL_NAIVE_MK, c->count_words != 0));
+                                 c->kernel == CVR_KERNEL_NAIVE_MK, c->count_words != 0, c->moments != 0));
   } else if (L.path_count > 0) {
     if ((r = wf_render(c, L, eps))) return r;
   }
@@ -1680,6 +1825,7 @@ static uint32_t seed_after_resets(const cvr_ctx* c, uint32_t seed, uint32_t rese
 
 int cvr_reset(cvr_ctx* c) {
   if (!c) return set_err(nullptr, CVR_ERR_INVALID, "NULL ctx");
+  CVR_NOT_IN_SESSION(c, "cvr_reset");
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   // Queue heads are re-zeroed per launch; only the seed carries over.
   c->seed = seed_after_resets(c, c->seed, 1);
@@ -1688,8 +1834,34 @@ int cvr_reset(cvr_ctx* c) {
 
 int cvr_clear_output(cvr_ctx* c) {
   if (!c) return set_err(nullptr, CVR_ERR_INVALID, "NULL ctx");
+  CVR_NOT_IN_SESSION(c, "cvr_clear_output");
   if (!c->d_out) return set_err(&c->err, CVR_ERR_STATE, "no output buffer");
-  HIP_TRY(c, hipMemsetAsync(c->d_out, 0, (size_t)c->tile_w * c->tile_h * sizeof(float4), c->stream));
+  // (CVR_OPT_MOMENTS: both halves, the moments lie directly behind the tile)
+  const size_t halves = (c->moments && c->d_out == c->d_out_owned) ? 2 : 1;
+  HIP_TRY(c, hipMemsetAsync(c->d_out, 0, halves * c->tile_w * c->tile_h * sizeof(float4), c->stream));
+  return CVR_OK;
+}
+
+int cvr_copy_moments(cvr_ctx* c, float* host_sum, float* host_m2) {
+  if (!c) return set_err(nullptr, CVR_ERR_INVALID, "NULL ctx");
+  if (!c->moments) return set_err(&c->err, CVR_ERR_STATE, "second moments are off (CVR_OPT_MOMENTS)");
+  const size_t px = (size_t)c->tile_w * c->tile_h;
+  if (!c->d_out || c->d_out != c->d_out_owned || c->out_owned_px < 2 * px || px == 0)
+    return set_err(&c->err, CVR_ERR_STATE, "the framebuffer holds no moments (cvr_set_resolution)");
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  if (host_sum) HIP_TRY(c, hipMemcpy(host_sum, c->d_out, px * sizeof(float4), hipMemcpyDeviceToHost));
+  if (host_m2) HIP_TRY(c, hipMemcpy(host_m2, c->d_out + px, px * sizeof(float4), hipMemcpyDeviceToHost));
+  return CVR_OK;
+}
+
+int cvr_block_error(const float* sum_rgba, const float* m2_rgba, uint32_t n_pixels, uint32_t n_samples, float floor,
+                    double* out) {
+  if (!sum_rgba || !m2_rgba || !out) return set_err(nullptr, CVR_ERR_INVALID, "NULL argument");
+  if (n_samples < 2) return set_err(nullptr, CVR_ERR_INVALID, "the error metric needs at least 2 samples");
+  if (n_pixels == 0) return set_err(nullptr, CVR_ERR_INVALID, "no pixels");
+  double acc = 0.0;
+  for (size_t i = 0; i < n_pixels; ++i) acc += cvr::pixel_error(sum_rgba + 4 * i, m2_rgba + 4 * i, n_samples, floor);
+  *out = acc / (double)n_pixels;
   return CVR_OK;
 }
 
@@ -1776,6 +1948,9 @@ int cvr_copy_output(cvr_ctx* c, float* host, float scale) {
 
 int cvr_trace_launch(cvr_ctx* c, cvr_path_record* out, uint64_t n_out) {
   if (!c || !out) return set_err(c ? &c->err : nullptr, CVR_ERR_INVALID, "NULL argument");
+  CVR_NOT_IN_SESSION(c, "cvr_trace_launch");
+  if (c->moments && !c->ad.internal)
+    return set_err(&c->err, CVR_ERR_UNSUPPORTED, "second moments (CVR_OPT_MOMENTS 1) do not run with cvr_trace_launch");
   int r = check_ready(c);
   if (r) return r;
   if ((r = do_init(c))) return r;
@@ -1829,6 +2004,7 @@ int cvr_trace_launch(cvr_ctx* c, cvr_path_record* out, uint64_t n_out) {
 
 int cvr_trace_paths(cvr_ctx* c, uint32_t first, uint32_t count, cvr_path_record* out) {
   if (!c || !out) return set_err(c ? &c->err : nullptr, CVR_ERR_INVALID, "NULL argument");
+  CVR_NOT_IN_SESSION(c, "cvr_trace_paths");
   int r = check_ready(c);
   if (r) return r;
   if (count == 0) return CVR_OK;
@@ -1853,6 +2029,10 @@ int cvr_render_image(cvr_ctx* c, const cvr_render_desc* d, void* device_image, f
 int cvr_render_tiles(cvr_ctx* c, const cvr_render_desc* d, uint32_t first_tile, uint32_t tile_stride,
                      void* device_image, float* host_image, cvr_stats* stats) {
   if (!c || !d) return set_err(c ? &c->err : nullptr, CVR_ERR_INVALID, "NULL argument");
+  CVR_NOT_IN_SESSION(c, "cvr_render_image / cvr_render_tiles");
+  if (c->moments && !c->ad.internal)
+    return set_err(&c->err, CVR_ERR_UNSUPPORTED,
+                   "second moments (CVR_OPT_MOMENTS 1) do not run with cvr_render_image / cvr_render_tiles");
   if (tile_stride == 0) return set_err(&c->err, CVR_ERR_INVALID, "tile stride 0");
   uint32_t tile_dim[2];
   int r = cvr_tiling(d->resolution[0], d->resolution[1], d->n_tiles[0], d->n_tiles[1], tile_dim);
@@ -1941,6 +2121,10 @@ done:
 int cvr_render_share_to_host(cvr_ctx* c, const cvr_render_desc* d, uint32_t first_tile, uint32_t tile_stride,
                              float* host_image, size_t host_floats, cvr_stats* stats) {
   if (!c || !d || !host_image) return set_err(c ? &c->err : nullptr, CVR_ERR_INVALID, "NULL argument");
+  CVR_NOT_IN_SESSION(c, "cvr_render_share_to_host");
+  if (c->moments && !c->ad.internal)
+    return set_err(&c->err, CVR_ERR_UNSUPPORTED,
+                   "second moments (CVR_OPT_MOMENTS 1) do not run with cvr_render_share_to_host");
   if (tile_stride == 0) return set_err(&c->err, CVR_ERR_INVALID, "tile stride 0");
   const uint32_t W = d->resolution[0], H = d->resolution[1];
   if (host_floats < (size_t)W * H * 4u)
@@ -2133,6 +2317,9 @@ int cvr_frame_flush_info(const cvr_ctx* c, uint32_t* blocks, uint32_t* fallbacks
 
 int cvr_render_frame(cvr_ctx* c, float* host_image, size_t host_floats, uint32_t parts, cvr_stats* stats) {
   if (!c || !host_image) return set_err(c ? &c->err : nullptr, CVR_ERR_INVALID, "NULL argument");
+  CVR_NOT_IN_SESSION(c, "cvr_render_frame");
+  if (c->moments && !c->ad.internal)
+    return set_err(&c->err, CVR_ERR_UNSUPPORTED, "second moments (CVR_OPT_MOMENTS 1) do not run with cvr_render_frame");
   int r = check_ready(c);
   if (r) return r;
   if (host_floats < (size_t)c->tile_w * c->tile_h * 4u)
@@ -2256,6 +2443,220 @@ int cvr_render_frame(cvr_ctx* c, float* host_image, size_t host_floats, uint32_t
   acc.kernel_ms = ms;
   c->last = acc;
   *stats = acc;
+  return CVR_OK;
+}
+
+// ---------------------------------------------------- adaptive sampling ----
+// A noise-targeted render (cvr.h): passes over the still-active 8x8 blocks, each pass one
+// launch whose block list is the active blocks (ensure_active_order) and whose path range
+// is the next whole samples of the max_iterations launch, then k_block_error on the
+// moments and one small read-back, from which the host drops the converged blocks.
+static void adaptive_result(const cvr_ctx* c, cvr_adaptive_result* out) {
+  if (!out) return;
+  const cvr_ctx::Adaptive& a = c->ad;
+  cvr_adaptive_result r{};
+  r.passes = a.passes;
+  r.blocks = a.n_blocks;
+  r.blocks_active = (uint32_t)c->active.size();
+  r.paths = a.paths;
+  double mx = 0.0, sum = 0.0;
+  for (double e : a.err) {
+    mx = std::max(mx, e);
+    sum += e;
+  }
+  r.max_error = mx;
+  r.mean_error = a.n_blocks ? sum / a.n_blocks : 0.0;
+  r.done = a.done;
+  *out = r;
+}
+
+int cvr_adaptive_begin(cvr_ctx* c, const cvr_adaptive_desc* d) {
+  if (!c || !d) return set_err(c ? &c->err : nullptr, CVR_ERR_INVALID, "NULL argument");
+  if (c->ad.on) return set_err(&c->err, CVR_ERR_STATE, "an adaptive session is already open (cvr_adaptive_end)");
+  int r = check_ready(c);
+  if (r) return r;
+  if (d->pass_iterations == 0 || d->min_iterations < 2 || d->max_iterations < d->min_iterations ||
+      d->min_iterations % d->pass_iterations || d->max_iterations % d->pass_iterations)
+    return set_err(&c->err, CVR_ERR_INVALID,
+                   "adaptive descriptor: min %u (>= 2) and max %u (>= min) must be multiples of pass %u (>= 1)",
+                   d->min_iterations, d->max_iterations, d->pass_iterations);
+  if (!(d->floor >= 0.0f) || !std::isfinite(d->floor) || d->target != d->target)
+    return set_err(&c->err, CVR_ERR_INVALID, "adaptive descriptor: floor must be finite and >= 0, target not NaN");
+  const uint64_t P = (uint64_t)c->tile_w * c->tile_h;
+  if (P * d->max_iterations > 0xFFFFFFFFull)
+    return set_err(&c->err, CVR_ERR_INVALID, "n_paths = %llu exceeds the reference's uint32 path ids",
+                   (unsigned long long)(P * d->max_iterations));
+  uint64_t rf = 0, rc = 0;
+  compute_range(c, &rf, &rc);
+  const char* why = (c->tile_w % 8 || c->tile_h % 8)       ? "tile sides that are not multiples of 8"
+                    : c->shard_world != 1                   ? "a block shard (cvr_set_block_shard)"
+                    : (rf != 0 || rc != c->n_paths)         ? "a path range (cvr_set_path_range)"
+                    : c->order == 0                         ? "CVR_OPT_ORDER 0 (no pixel-block work order)"
+                                                            : moments_refusal(c);
+  if (why) return set_err(&c->err, CVR_ERR_UNSUPPORTED, "an adaptive render does not run with %s", why);
+  if ((r = ensure_device(c)) || (r = do_init(c)) || (r = ensure_output(c))) return r;
+  cvr_ctx::Adaptive& a = c->ad;
+  const uint32_t nb = (uint32_t)(P / 64);
+  if (a.n_blocks != nb || !c->d_active) {  // the per-block device tables
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (c->d_active) (void)hipFree(c->d_active);
+    if (a.d_err) (void)hipFree(a.d_err);
+    if (a.d_counts) (void)hipFree(a.d_counts);
+    c->d_active = nullptr;
+    a.d_err = nullptr;
+    a.d_counts = nullptr;
+    a.n_blocks = 0;
+    HIP_TRY(c, hipMalloc(&c->d_active, (size_t)nb * sizeof(uint32_t)));
+    HIP_TRY(c, hipMalloc(&a.d_err, (size_t)nb * sizeof(double)));
+    HIP_TRY(c, hipMalloc(&a.d_counts, (size_t)nb * sizeof(uint32_t)));
+    a.n_blocks = nb;
+  }
+  a.saved_moments = c->moments;
+  if (!c->moments && (r = cvr_set_option(c, CVR_OPT_MOMENTS, 1))) return r;
+  HIP_TRY(c, hipMemsetAsync(c->d_out, 0, 2 * (size_t)P * sizeof(float4), c->stream));
+  a.saved_iterations = c->iterations;
+  c->iterations = d->max_iterations;
+  c->n_paths = P * d->max_iterations;
+  a.d = *d;
+  a.passes = 0;
+  a.done = 0;
+  a.paths = 0;
+  a.samples.assign(nb, 0u);
+  a.err.assign(nb, HUGE_VAL);
+  a.acc = cvr_stats{};
+  c->active.resize(nb);
+  for (uint32_t b = 0; b < nb; ++b) c->active[b] = b;
+  c->active_on = true;
+  a.on = true;
+  return CVR_OK;
+}
+
+int cvr_adaptive_pass(cvr_ctx* c, cvr_adaptive_result* result) {
+  if (!c) return set_err(nullptr, CVR_ERR_INVALID, "NULL ctx");
+  cvr_ctx::Adaptive& a = c->ad;
+  if (!a.on) return set_err(&c->err, CVR_ERR_STATE, "no adaptive session (cvr_adaptive_begin)");
+  if (a.done) return set_err(&c->err, CVR_ERR_STATE, "the adaptive render is done: no block is active");
+  const uint64_t P = (uint64_t)c->tile_w * c->tile_h;
+  // the active blocks advance in step: all of them hold the same sample count
+  const uint32_t s0 = a.passes == 0 ? 0u : a.samples[c->active[0]];
+  const uint32_t add = a.passes == 0 ? a.d.min_iterations : a.d.pass_iterations, N = s0 + add;
+  const uint32_t n = (uint32_t)c->active.size();
+  c->range_first = s0 * P;  // whole samples [s0, s0 + add) of the max_iterations launch: its path ids
+  c->range_count = add * P;
+  a.internal = true;
+  int r = cvr_launch_render(c);
+  a.internal = false;
+  c->range_first = 0;
+  c->range_count = UINT64_MAX;
+  if (r) return r;
+  // the active blocks' errors, in the launch's block order (d_active / h_active)
+  HIP_TRY(c, cvr::launch_block_error(c->d_out, (uint32_t)P, c->tile_w, c->d_active, n, N, a.d.floor, a.d_err, c->stream));
+  a.h_err.resize(n);
+  HIP_TRY(c, hipMemcpyAsync(a.h_err.data(), a.d_err, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  cvr_stats s{};
+  if ((r = cvr_get_stats(c, &s))) return r;  // synchronises: the errors are on the host
+  a.acc.paths += s.paths;
+  a.acc.segments += s.segments;
+  a.acc.steps += s.steps;
+  a.acc.density += s.density;
+  a.acc.albedo += s.albedo;
+  a.acc.escaped += s.escaped;
+  a.acc.truncated += s.truncated;
+  a.acc.fetches += s.fetches;
+  a.acc.kernel_ms += s.kernel_ms;
+  std::vector<uint32_t> next;
+  for (uint32_t i = 0; i < n; ++i) {
+    const uint32_t b = c->h_active[i];
+    const double e = a.h_err[i];
+    a.samples[b] = N;
+    a.err[b] = e;
+    if (!(e <= (double)a.d.target) && N < a.d.max_iterations) next.push_back(b);
+  }
+  std::sort(next.begin(), next.end());
+  c->active.swap(next);
+  a.passes += 1;
+  a.paths += (uint64_t)n * 64u * add;
+  a.done = c->active.empty() ? 1 : 0;
+  adaptive_result(c, result);
+  return CVR_OK;
+}
+
+int cvr_adaptive_maps(cvr_ctx* c, double* block_error, uint32_t* block_samples) {
+  if (!c) return set_err(nullptr, CVR_ERR_INVALID, "NULL ctx");
+  // (the maps of the last session stay readable after its cvr_adaptive_end, at that tile size)
+  if (c->ad.err.empty() || c->ad.err.size() != (size_t)(c->tile_w / 8u) * (c->tile_h / 8u))
+    return set_err(&c->err, CVR_ERR_STATE, "no adaptive session (cvr_adaptive_begin)");
+  if (block_error) memcpy(block_error, c->ad.err.data(), c->ad.err.size() * sizeof(double));
+  if (block_samples) memcpy(block_samples, c->ad.samples.data(), c->ad.samples.size() * sizeof(uint32_t));
+  return CVR_OK;
+}
+
+int cvr_adaptive_image(cvr_ctx* c, float* host, size_t host_floats) {
+  if (!c || !host) return set_err(c ? &c->err : nullptr, CVR_ERR_INVALID, "NULL argument");
+  cvr_ctx::Adaptive& a = c->ad;
+  if (!a.on) return set_err(&c->err, CVR_ERR_STATE, "no adaptive session (cvr_adaptive_begin)");
+  const size_t px = (size_t)c->tile_w * c->tile_h;
+  if (host_floats < px * 4u)
+    return set_err(&c->err, CVR_ERR_INVALID, "host image holds %zu floats, the %ux%u tile needs %zu", host_floats,
+                   c->tile_w, c->tile_h, px * 4u);
+  HIP_TRY(c, hipMemcpyAsync(a.d_counts, a.samples.data(), (size_t)a.n_blocks * sizeof(uint32_t), hipMemcpyHostToDevice,
+                            c->stream));
+  void* dhost = nullptr;  // pinned or registered memory: the kernel stores the image itself
+  if (((uintptr_t)host & 15u) || hipHostGetDevicePointer(&dhost, host, 0) != hipSuccess) {
+    (void)hipGetLastError();  // pageable memory: not an error, the staging copy below
+    dhost = nullptr;
+  }
+  if (dhost) {
+    HIP_TRY(c, cvr::launch_tile_to_image_counts(c->d_out, c->tile_w, c->tile_h, a.d_counts, static_cast<float4*>(dhost),
+                                                c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return CVR_OK;
+  }
+  float4* stage = nullptr;
+  HIP_TRY(c, hipMalloc(&stage, px * sizeof(float4)));
+  hipError_t e = cvr::launch_tile_to_image_counts(c->d_out, c->tile_w, c->tile_h, a.d_counts, stage, c->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+  if (e == hipSuccess) e = hipMemcpy(host, stage, px * sizeof(float4), hipMemcpyDeviceToHost);
+  (void)hipFree(stage);
+  if (e != hipSuccess) return set_err(&c->err, CVR_ERR_HIP, "adaptive image: %s", hipGetErrorString(e));
+  return CVR_OK;
+}
+
+int cvr_adaptive_end(cvr_ctx* c) {
+  if (!c) return set_err(nullptr, CVR_ERR_INVALID, "NULL ctx");
+  cvr_ctx::Adaptive& a = c->ad;
+  if (!a.on) return set_err(&c->err, CVR_ERR_STATE, "no adaptive session (cvr_adaptive_begin)");
+  const hipError_t e = hipStreamSynchronize(c->stream);
+  // reset() after a launch of max_iterations (n_paths is that launch's): wherever the blocks stopped
+  c->seed = seed_after_resets(c, c->seed, 1);
+  c->iterations = a.saved_iterations;
+  c->n_paths = (uint64_t)c->tile_w * c->tile_h * c->iterations;
+  c->moments = a.saved_moments;
+  c->active_on = false;
+  c->active.clear();
+  a.on = false;
+  if (e != hipSuccess) return set_err(&c->err, CVR_ERR_HIP, "hipStreamSynchronize failed: %s", hipGetErrorString(e));
+  return CVR_OK;
+}
+
+int cvr_render_adaptive(cvr_ctx* c, const cvr_adaptive_desc* d, float* host, size_t host_floats,
+                        cvr_adaptive_result* result, cvr_stats* stats) {
+  if (!c || !d || !host) return set_err(c ? &c->err : nullptr, CVR_ERR_INVALID, "NULL argument");
+  if (host_floats < (size_t)c->tile_w * c->tile_h * 4u)
+    return set_err(&c->err, CVR_ERR_INVALID, "host image holds %zu floats, the %ux%u tile needs %zu", host_floats,
+                   c->tile_w, c->tile_h, (size_t)c->tile_w * c->tile_h * 4u);
+  int r = cvr_adaptive_begin(c, d);
+  if (r) return r;
+  cvr_adaptive_result res{};
+  while (!r && !c->ad.done) r = cvr_adaptive_pass(c, &res);
+  if (!r) r = cvr_adaptive_image(c, host, host_floats);
+  const cvr_stats acc = c->ad.acc;
+  const std::string msg = c->err;
+  const int r2 = cvr_adaptive_end(c);
+  if (r) return set_err(&c->err, r, "%s", msg.c_str());
+  if (r2) return r2;
+  if (result) *result = res;
+  if (stats) *stats = acc;
   return CVR_OK;
 }
 

@@ -58,8 +58,11 @@ bool wpool_pair_built();
 // cells and bounds, 5 waves per SIMD, no records / in-launch output; else k_wpool).
 // naive_mk: naiveMK's walk on the wave pool (5 waves per SIMD, no records / in-launch output).
 // count_words: sparse media, the counting instance (CVR_OPT_COUNT_WORDS: brick words loaded).
+// moments: the second-moment instance (CVR_OPT_MOMENTS): L.out holds 2 * tile_px float4, the
+// moments behind the tile; 5 waves per SIMD, generic dense or fp32 sparse layout only.
 hipError_t launch_wpool(const MediumParams& m, const LaunchParams& L, bool scatter_eps, int waves, uint32_t grid,
-                        hipStream_t s, bool pair = false, bool naive_mk = false, bool count_words = false);
+                        hipStream_t s, bool pair = false, bool naive_mk = false, bool count_words = false,
+                        bool moments = false);
 // Resident waves per CU of the wave-pool instance (workgroups per CU x waves per workgroup).
 hipError_t wpool_occupancy(bool scatter_eps, int waves, bool sparse, int* waves_per_cu);
 // Pool slots per wave of the wave-pool kernel instance (LaunchParams::pool_T
@@ -118,5 +121,33 @@ hipError_t launch_build_cells(const float* density, uint32_t rx, uint32_t ry, ui
 hipError_t launch_to_half(const float* src, void* dst, size_t n, hipStream_t s);
 hipError_t launch_tile_to_image(const float4* tile, uint32_t tw, uint32_t th, float4* image, uint32_t iw,
                                 uint32_t ox, uint32_t oy, float scale, hipStream_t s);
+// Adaptive sampling (cvr_adaptive_*).  The error metric of one pixel from its sums (cvr.h,
+// cvr_block_error): the one definition, compiled for the host and for k_block_error.
+//   m_c = S1_c / N, v_c = max(0, S2_c / N - m_c^2) / (N - 1),
+//   e = sqrt(v_r + v_g + v_b) / (m_r + m_g + m_b + floor), all in fp64
+// A NaN or infinite sum gives +inf (such a pixel never converges), a zero denominator 0.
+__host__ __device__ inline double pixel_error(const float s1[3], const float s2[3], uint32_t n_samples, float floor) {
+  const double N = (double)n_samples;
+  double v = 0.0, m = (double)floor;
+  for (int c = 0; c < 3; ++c) {
+    const double a = (double)s1[c], b = (double)s2[c];
+    if (!(a - a == 0.0) || !(b - b == 0.0)) return __builtin_huge_val();
+    const double mc = a / N;
+    const double d = b / N - mc * mc;
+    v += (d > 0.0 ? d : 0.0) / (N - 1.0);
+    m += mc;
+  }
+  if (m == 0.0) return 0.0;
+  const double e = __builtin_sqrt(v) / m;
+  return e == e ? e : __builtin_huge_val();
+}
+// errors[i] = the mean pixel_error over the 64 pixels of tile block blocks[i] (8x8 pixels,
+// row-major block ids), each with n_samples samples; `moments` = tile + tile_px.
+hipError_t launch_block_error(const float4* tile, uint32_t tile_px, uint32_t tile_w, const uint32_t* blocks,
+                              uint32_t n, uint32_t n_samples, float floor, double* errors, hipStream_t s);
+// k_tile_to_image with every pixel divided by its own 8x8 block's sample count (0: the pixel is 0);
+// `image` is tile-sized device memory or the device address of a pinned host image.
+hipError_t launch_tile_to_image_counts(const float4* tile, uint32_t tw, uint32_t th, const uint32_t* counts,
+                                       float4* image, hipStream_t s);
 
 }  // namespace cvr

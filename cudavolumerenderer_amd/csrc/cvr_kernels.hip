@@ -659,6 +659,50 @@ __global__ __launch_bounds__(256) void k_tile_to_image(const float4* __restrict_
   image[(size_t)(y + oy) * iw + (x + ox)] = make_float4(v.x / scale, v.y / scale, v.z / scale, v.w / scale);
 }
 
+// Adaptive sampling (cvr_adaptive_image): the tile normalised per 8x8 block, every pixel
+// divided by the samples its own block received (counts, row-major tile blocks; sides are
+// multiples of 8).  A block without samples stores 0.  `image` may be a pinned host image.
+__global__ __launch_bounds__(256) void k_tile_to_image_counts(const float4* __restrict__ tile, uint32_t tw,
+                                                              uint32_t th, const uint32_t* __restrict__ counts,
+                                                              float4* __restrict__ image) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= tw * th) return;
+  const uint32_t x = i % tw, y = i / tw;
+  const uint32_t n = counts[(y >> 3) * (tw >> 3) + (x >> 3)];
+  const float4 v = tile[i];
+  const float scale = (float)n;
+  const float4 o = n ? make_float4(v.x / scale, v.y / scale, v.z / scale, v.w / scale) : make_float4(0.f, 0.f, 0.f, 0.f);
+  __builtin_nontemporal_store(o.x, &image[i].x);
+  __builtin_nontemporal_store(o.y, &image[i].y);
+  __builtin_nontemporal_store(o.z, &image[i].z);
+  __builtin_nontemporal_store(o.w, &image[i].w);
+}
+
+// Adaptive sampling (cvr_adaptive_pass): the error metric of the listed tile blocks, one
+// wave per block, one lane per pixel.  Lane l takes pixel (l & 7, l >> 3) of its block, so
+// each 8-pixel row is one 128-byte load of the framebuffer and one of the moments (the
+// second float4 per pixel, tile_px behind the tile).  pixel_error (cvr_kernels.h) in fp64
+// per lane, summed over the wave by xor shuffles; lane 0 stores the block's mean.
+__global__ __launch_bounds__(256) void k_block_error(const float4* __restrict__ tile, uint32_t tile_px,
+                                                     uint32_t tile_w, const uint32_t* __restrict__ blocks,
+                                                     uint32_t n, uint32_t n_samples, float floor,
+                                                     double* __restrict__ errors) {
+  const uint32_t w = blockIdx.x * 4u + (threadIdx.x >> 6), lane = threadIdx.x & 63u;
+  if (w >= n) return;  // whole waves leave: the shuffles below run on full waves
+  const uint32_t b = blocks[w], bxn = tile_w >> 3;
+  const uint32_t by = b / bxn, bx = b - by * bxn;
+  const uint32_t pix = (by * 8u + (lane >> 3)) * tile_w + bx * 8u + (lane & 7u);
+  double e = 0.0;
+  if (pix < tile_px) {  // (a listed block lies in the tile: the host checks its ids)
+    const float4 s1 = tile[pix], s2 = tile[(size_t)tile_px + pix];
+    const float a[3] = {s1.x, s1.y, s1.z}, q[3] = {s2.x, s2.y, s2.z};
+    e = pixel_error(a, q, n_samples, floor);
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) e += __shfl_xor(e, off);
+  if (lane == 0) errors[w] = e / 64.0;
+}
+
 // Normalise + store into pinned host memory in one kernel (the transfer
 // delegate's Scale functor and its D->H copy, ImageBufferTransfer.cu:61-78,
 // UtilityFunctors::Scale x/scale, Utilities.h:6-15): the GPU writes the host
@@ -964,6 +1008,24 @@ hipError_t launch_tile_to_image(const float4* tile, uint32_t tw, uint32_t th, fl
   if (n == 0) return hipSuccess;
   hipLaunchKernelGGL(k_tile_to_image, dim3((n + 255u) / 256u), dim3(256), 0, s, tile, tw, th, image, iw, ox, oy,
                      scale);
+  return hipGetLastError();
+}
+
+hipError_t launch_tile_to_image_counts(const float4* tile, uint32_t tw, uint32_t th, const uint32_t* counts,
+                                       float4* image, hipStream_t s) {
+  const uint32_t n = tw * th;
+  if (n == 0) return hipSuccess;
+  if (tw % 8u || th % 8u) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_tile_to_image_counts, dim3((n + 255u) / 256u), dim3(256), 0, s, tile, tw, th, counts, image);
+  return hipGetLastError();
+}
+
+hipError_t launch_block_error(const float4* tile, uint32_t tile_px, uint32_t tile_w, const uint32_t* blocks,
+                              uint32_t n, uint32_t n_samples, float floor, double* errors, hipStream_t s) {
+  if (n == 0) return hipSuccess;
+  if (tile_w % 8u || tile_w == 0 || n_samples < 2) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_block_error, dim3((n + 3u) / 4u), dim3(256), 0, s, tile, tile_px, tile_w, blocks, n, n_samples,
+                     floor, errors);
   return hipGetLastError();
 }
 

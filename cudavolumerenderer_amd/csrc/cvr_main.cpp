@@ -11,7 +11,11 @@
 //   --devices N|d0,d1,... (one context per device, each on its own host
 //   thread: tile k -> device k mod N for --number-of-tiles, else 8x8-block
 //   shards of the one tile; every device stores its pixels straight into one
-//   pinned host image), --pfm (also write the float image as <output>.pfm)
+//   pinned host image), --pfm (also write the float image as <output>.pfm),
+//   --noise-target F [--min-iterations N] [--pass-iterations N] (an adaptive
+//   render, cvr_render_adaptive: every 8x8 block is sampled until its relative
+//   standard error is at most F, -i being the cap; also writes the samples map
+//   as <output>_samples.hdr)
 //
 // Differences from the reference, on purpose: the timer is wall clock (the
 // reference uses clock(), i.e. CPU time, Main.cpp:51-77); main does not wait
@@ -37,6 +41,9 @@ struct Options {
   std::string devices;  // --devices: a count or a comma list of device ids
   std::string medium_format = "float";  // --medium-format
   bool pfm = false;
+  bool adaptive = false;  // --noise-target given
+  float noise_target = 0.0f;
+  unsigned min_iterations = 8, pass_iterations = 4;
   std::vector<float> default_albedo;
   bool interactive = true, unified = false;
   unsigned trials = 1, iterations = 20, device = 0, seed = 0;
@@ -72,6 +79,12 @@ void usage() {
       "                                     the device: half rounds every voxel to IEEE binary16 and halves\n"
       "                                     their bytes (wave-pool scheduler; see CVR_OPT_MEDIUM_FORMAT)\n"
       "  --pfm                              also write the float image as <output>.pfm\n"
+      "  --noise-target F                   adaptive render: sample every 8x8-pixel block until its relative\n"
+      "                                     standard error (cvr_block_error, floor 0.01) is at most F, with\n"
+      "                                     --iterations as the cap per block; prints the paths traced and\n"
+      "                                     writes the samples map as <output>_samples.hdr (one device, one tile)\n"
+      "  --min-iterations N (=8)            adaptive render: samples of every block before the first check\n"
+      "  --pass-iterations N (=4)           adaptive render: samples added per pass (min and cap: multiples)\n"
       "  --rng-binding path|thread (=path)  regenerationSK: thread = the reference's Rng(seed + tid)\n"
       "                                     per persistent thread (non-deterministic, SURVEY Q2)\n"
       "  --default-albedo r g b             VDB files without an albedo grid load with this albedo\n"
@@ -119,6 +132,12 @@ int parse(int argc, char** argv, Options& o) {
     else if (a == "--devices") o.devices = need("devices");
     else if (a == "--medium-format") o.medium_format = need("medium-format");
     else if (a == "--pfm") o.pfm = true;
+    else if (a == "--noise-target") {
+      o.noise_target = strtof(need("noise-target").c_str(), nullptr);
+      o.adaptive = true;
+    }
+    else if (a == "--min-iterations") o.min_iterations = (unsigned)strtoul(need("min-iterations").c_str(), nullptr, 10);
+    else if (a == "--pass-iterations") o.pass_iterations = (unsigned)strtoul(need("pass-iterations").c_str(), nullptr, 10);
     else if (a == "--rng-binding") o.rng_binding = need("rng-binding");
     else if (a == "--seed") o.seed = (unsigned)strtoul(need("seed").c_str(), nullptr, 10);
     else if (a == "--world-to-aabb") o.world_to_aabb = need("world-to-aabb");
@@ -322,6 +341,11 @@ int main(int argc, char** argv) {
   }
   const unsigned ntiles = o.tiles[0] * o.tiles[1];
   size_t n_dev = devs.size();
+  if (o.adaptive && (n_dev > 1 || ntiles > 1)) {
+    fprintf(stderr, "[ConfigParser] Error: --noise-target renders one tile on one device (no --devices > 1, no "
+                    "--number-of-tiles above 1 1)\n");
+    return 2;
+  }
   const bool tile_mode = ntiles > 1;
   if (n_dev > 1 && !tile_mode && (W % 8 || H % 8)) {
     printf("[Devices] one tile of %ux%u: block shards need sides that are multiples of 8; rendering on device %d\n", W,
@@ -365,7 +389,22 @@ int main(int argc, char** argv) {
     }
     cvr_stats st{};
     const auto t0 = std::chrono::steady_clock::now();
-    if (n_dev == 1) {
+    cvr_adaptive_result ares{};
+    std::vector<uint32_t> block_samples;
+    if (o.adaptive) {
+      // cvr_render_adaptive's steps, with the samples map read before the session ends
+      cvr_ctx* c = ctxs[0];
+      const cvr_adaptive_desc ad = {o.min_iterations, o.iterations, o.pass_iterations, o.noise_target, 0.01f};
+      block_samples.assign((size_t)(W / 8) * (H / 8), 0u);
+      r = cvr_set_resolution(c, W, H);
+      if (!r) r = cvr_set_offset(c, 0, 0);
+      if (!r) r = cvr_render_adaptive(c, &ad, image.data(), image.size(), &ares, &st);
+      if (!r) r = cvr_adaptive_maps(c, nullptr, block_samples.data());
+      if (r != CVR_OK) {
+        fprintf(stderr, "Error: %s\n", cvr_last_error(c));
+        return 1;
+      }
+    } else if (n_dev == 1) {
       r = cvr_render_image(ctxs[0], &d, nullptr, image.data(), &st);
       if (r != CVR_OK) {
         fprintf(stderr, "Error: %s\n", cvr_last_error(ctxs[0]));
@@ -411,6 +450,26 @@ int main(int argc, char** argv) {
     printf("rendering time      : %.2f sec \n", sec);
     printf("total traced rays %llu (woodcock steps %llu)\n", (unsigned long long)st.segments,
            (unsigned long long)st.steps);
+    if (o.adaptive) {
+      const unsigned long long uniform = (unsigned long long)W * H * o.iterations;
+      printf("adaptive render     : %u passes, %llu paths traced (%.1f%% of the uniform render's %llu), "
+             "max block error %.6g, mean %.6g\n",
+             ares.passes, (unsigned long long)ares.paths, 100.0 * (double)ares.paths / (double)uniform, uniform,
+             ares.max_error, ares.mean_error);
+      // the samples map, one grey value per pixel of its block, normalised by the maximum
+      uint32_t smax = 1;
+      for (uint32_t v : block_samples) smax = std::max(smax, v);
+      std::vector<float> smap((size_t)W * H * 4, 1.0f);
+      for (unsigned y = 0; y < H; ++y)
+        for (unsigned x = 0; x < W; ++x) {
+          const float v = (float)block_samples[(size_t)(y / 8) * (W / 8) + x / 8] / (float)smax;
+          for (int ch = 0; ch < 3; ++ch) smap[((size_t)y * W + x) * 4 + ch] = v;
+        }
+      if (cvr_write_hdr((o.output + "_samples.hdr").c_str(), smap.data(), W, H) != CVR_OK) {
+        fprintf(stderr, "Error: could not write %s_samples.hdr\n", o.output.c_str());
+        return 1;
+      }
+    }
     struct cvr_medium_info mi;
     if (cvr_medium_info(ctxs[0], &mi) == CVR_OK)
       printf("medium on device    : %s, %llu bytes (density %llu, cells %llu, albedo %llu, bounds %llu)\n",

@@ -636,11 +636,36 @@ constexpr int kMedCount = 8;
 // (MediumParams::format 1) as a compile-time constant, the instances without it format
 // 0, as albedo_uniform is pinned; the generic kMedDense instances read it at run time.
 constexpr int kMedHalf = 16;
+// kMedMoments (or-ed into kMed): the second-moment instance of CVR_OPT_MOMENTS.  The
+// context's framebuffer allocation holds a second float4 per pixel directly behind the
+// tile, moments[i] = L.out[L.tile_px + i] = (sum fl(T.r T.r), sum fl(T.g T.g),
+// sum fl(T.b T.b), escapes splatted into the pixel), which an escape adds to after its
+// splat.  The buffer sits at a fixed offset from `out` so that the kernel parameters do
+// not change: every other instance keeps its kernel-argument layout, its LDS copy of
+// the launch parameters and its pool slot count (PoolSize derives from sizeof).
+constexpr int kMedMoments = 32;
+static_assert(sizeof(LaunchParams) == 256 && sizeof(MediumParams) == 256,
+              "the moments buffer is addressed from LaunchParams::out: the parameter structs keep their size");
+// An escape's squares and its count, after splat(): agent-scope relaxed atomics performed
+// at the memory side, as the framebuffer's.  A zero square is not added (a sum is never
+// -0: cleared to +0, every square is >= +0 or NaN).  The count is an fp32 add of 1,
+// exact below 2^24 escapes per pixel.
+__device__ __forceinline__ void splat_moments(const LaunchParams& L, const PathState& ps) {
+  gptr_t<float> px = gmem(reinterpret_cast<float*>(L.out + L.tile_px + ps.image_id));
+  const float xx = ps.T.x * ps.T.x, yy = ps.T.y * ps.T.y, zz = ps.T.z * ps.T.z;
+  if (xx != 0.0f) __hip_atomic_fetch_add(px + 0, xx, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  if (yy != 0.0f) __hip_atomic_fetch_add(px + 1, yy, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  if (zz != 0.0f) __hip_atomic_fetch_add(px + 2, zz, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  __hip_atomic_fetch_add(px + 3, 1.0f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
 template <bool kScatterEps, int kWaves, int kMedMk, bool kRecord, bool kFlush>
 __global__ __launch_bounds__(64 * wpg_of(kMedMk, kWaves), kWaves) void k_wpool(MediumParams mk, LaunchParams Lk) {
   constexpr bool kMK = (kMedMk & kMedMK) != 0;
   constexpr bool kCountWords = (kMedMk & kMedCount) != 0;
+  constexpr bool kMoments = (kMedMk & kMedMoments) != 0;
   constexpr int kMed = kMedMk & 3;
+  static_assert(!kMoments || (!kMK && !kRecord && !kFlush && !kCountWords && !(kMedMk & kMedHalf)),
+                "moments: no naiveMK walk, records, in-launch output, word counts or pinned half format");
   static_assert(!kMK || (kScatterEps && !kRecord && !kFlush), "naiveMK: scatter -eps, no records / in-launch output");
   constexpr bool kSparse = kMed == kMedSparse;
   // Sparse media defer their cell fetches to the end of the track iteration
@@ -1218,7 +1243,11 @@ __global__ __launch_bounds__(64 * wpg_of(kMedMk, kWaves), kWaves) void k_wpool(M
       }
       // the batch's escapes (camera rays that miss the box, survivors leaving it), per pixel
       // (the in-launch output instance splats per lane: combining cost it 2 VGPR spills)
-      splat_wave<!kFlush>(S, L, ps, escaped, s, lane);
+      // (the moments instance too: a sum of squares cannot be combined through a sum)
+      splat_wave<!kFlush && !kMoments>(S, L, ps, escaped, s, lane);
+      if constexpr (kMoments) {
+        if (escaped) splat_moments(L, ps);
+      }
       // a path's segments are the increments of its nseg (each counted once, as
       // the reference's per-iteration RAYS_STATISTICS count)
       {
@@ -1898,8 +1927,25 @@ static const void* wpool_mk_fn(bool sparse, bool full, bool uniform, bool half) 
 }
 
 hipError_t launch_wpool(const MediumParams& m, const LaunchParams& L, bool scatter_eps, int waves, uint32_t grid,
-                        hipStream_t s, bool pair, bool naive_mk, bool count_words) {
+                        hipStream_t s, bool pair, bool naive_mk, bool count_words, bool moments) {
   if (L.path_count == 0) return hipSuccess;
+  if (moments) {
+    // the moments instances (CVR_OPT_MOMENTS): 5 waves per SIMD, the generic dense layout (cells,
+    // bounds, uniform albedo and the half format read at run time) and the fp32 sparse one; no
+    // records, in-launch output, naiveMK walk, pairs or word counts (cvr_launch_render refuses them first)
+    const bool sp = m.leaves != nullptr;
+    if (waves != 5 || pair || naive_mk || count_words || L.rec || L.frame_done || (sp && m.format != 0u))
+      return hipErrorInvalidValue;
+    if (grid % wpool_wpg(waves, sp)) return hipErrorInvalidValue;
+#define CVR_WPM(E, M) reinterpret_cast<const void*>(&k_wpool<E, 5, (M) | kMedMoments, false, false>)
+    const void* fm = scatter_eps ? (sp ? CVR_WPM(true, kMedSparse) : CVR_WPM(true, kMedDense))
+                                 : (sp ? CVR_WPM(false, kMedSparse) : CVR_WPM(false, kMedDense));
+#undef CVR_WPM
+    MediumParams mm = m;
+    LaunchParams ll = L;
+    void* args[] = {&mm, &ll};
+    return hipLaunchKernel(fm, dim3(grid / wpool_wpg(waves, sp)), dim3(64 * wpool_wpg(waves, sp)), args, 0, s);
+  }
   const bool sparse = m.leaves != nullptr;
   const bool flush = L.frame_done != nullptr;
   const bool full = !sparse && m.cells != nullptr && m.bounds != nullptr;

@@ -24,8 +24,20 @@
 extern "C" {
 #endif
 
-#define CVR_ABI_VERSION 5  /* 3: cvr_render_frame takes the host buffer size; 4: cvr_stats.words;
-                              5: CVR_OPT_MEDIUM_FORMAT, cvr_half_round, cvr_medium_info */
+/* ABI history: 3: cvr_render_frame takes the host buffer size; 4: cvr_stats.words;
+ *              5: CVR_OPT_MEDIUM_FORMAT, cvr_half_round, cvr_medium_info;
+ *              6: CVR_OPT_MOMENTS, cvr_copy_moments, cvr_block_error, cvr_adaptive_*
+ * CVR_ABI_VERSION is the ABI this header declares: 6, the library's (cvr_abi_version()).  ABI 6 only
+ * adds to ABI 5, so a host that must also load an ABI 5 library can hold itself to that surface:
+ * with CVR_ABI_TARGET defined as 5 before the include, the ABI 6 functions and structs are not
+ * declared (a use of one then fails to compile) and CVR_ABI_VERSION is 5. */
+#if defined(CVR_ABI_TARGET) && CVR_ABI_TARGET == 5
+#define CVR_ABI_VERSION 5
+#elif defined(CVR_ABI_TARGET) && CVR_ABI_TARGET != 6
+#error "CVR_ABI_TARGET must be 5 or 6"
+#else
+#define CVR_ABI_VERSION 6
+#endif
 
 enum {
   CVR_OK = 0,
@@ -198,6 +210,24 @@ typedef enum {
                                  in cvr_trace_paths; with another CVR_OPT_SCHEDULER or CVR_OPT_WAVES value,
                                  CVR_OPT_RNG_BINDING 1, CVR_OPT_COUNT_WORDS 1, CVR_OPT_MK_COMPACTION 1 or
                                  CVR_OPT_WAVE_PAIR 1 a launch on a format-1 medium returns CVR_ERR_UNSUPPORTED. */
+  CVR_OPT_MOMENTS = 31,        /* wave-pool scheduler: 0 (default) off; 1 every launch also accumulates per-pixel
+                                 second moments.  The context's own framebuffer allocation then holds a
+                                 second float4 per pixel directly behind the tile (tile_w * tile_h float4
+                                 after cvr_output_ptr): (sum fl(T.r T.r), sum fl(T.g T.g), sum fl(T.b T.b),
+                                 the escapes splatted into the pixel: an fp32 count, exact below 2^24),
+                                 read with cvr_copy_moments and cleared with the tile by cvr_clear_output.
+                                 Turning it on may reallocate the framebuffer (both halves then start
+                                 cleared).  Other values: CVR_ERR_INVALID.  The framebuffer half, the
+                                 counters and every path are those of the same launch with the option off
+                                 (pixels up to fp32 summation order).  Runs on the wave-pool scheduler at 5
+                                 waves per SIMD with its generic dense instance (cells, bounds, uniform
+                                 albedo and the half format read at run time) or the fp32 sparse one.  A
+                                 caller's output buffer (cvr_set_output) with moments on is
+                                 CVR_ERR_UNSUPPORTED, and so is a launch with another CVR_OPT_SCHEDULER or
+                                 CVR_OPT_WAVES value, CVR_OPT_RNG_BINDING 1, CVR_OPT_COUNT_WORDS 1,
+                                 CVR_OPT_WAVE_PAIR 1, CVR_OPT_MK_COMPACTION 1, kernel id naiveMK, a sparse
+                                 half medium, cvr_trace_launch, cvr_render_frame, cvr_render_image,
+                                 cvr_render_tiles or cvr_render_share_to_host. */
   /* 21: unused (a drain-time path migration between waves, measured slower: DESIGN.md §6) */
   CVR_OPT_DRAIN = 22,          /* wave-pool scheduler, once the queues are empty: an event batch runs as
                                  soon as the waiting segments x d >= the tracking ones (d = 0: only when
@@ -393,6 +423,12 @@ int cvr_clear_output(cvr_ctx* ctx);
 int cvr_get_stats(cvr_ctx* ctx, cvr_stats* stats);
 /* D->H copy of the tile buffer, every component divided by `scale`. */
 int cvr_copy_output(cvr_ctx* ctx, float* host_rgba, float scale);
+#if CVR_ABI_VERSION >= 6
+/* CVR_OPT_MOMENTS 1: D->H copy of the raw sums, unscaled: host_sum_rgba the tile buffer,
+ * host_m2_rgba the moments (each tile_w * tile_h * 4 floats; either may be NULL).
+ * Synchronous.  CVR_ERR_STATE with the option off. */
+int cvr_copy_moments(cvr_ctx* ctx, float* host_sum_rgba, float* host_m2_rgba);
+#endif
 /* Extension, asynchronous on `stream` (a hipStream_t; NULL = the null
  * stream): host_dst[i] = device_src[i] / scale for n_floats floats, written by
  * a kernel straight into pinned (hipHostMalloc) or registered (hipHostRegister)
@@ -496,6 +532,71 @@ int cvr_render_tiles(cvr_ctx* ctx, const cvr_render_desc* desc, uint32_t first_t
  * stats cover this share. */
 int cvr_render_share_to_host(cvr_ctx* ctx, const cvr_render_desc* desc, uint32_t first_tile, uint32_t tile_stride,
                              float* host_image, size_t host_floats, cvr_stats* stats);
+#if CVR_ABI_VERSION >= 6
+/* ---- adaptive sampling (extension, ABI 6) ------------------------------- */
+/* Host only (no GPU): the noise metric the adaptive render stops on, the written statement
+ * of what the device computes (k_block_error).  For n_pixels pixels that have each received
+ * n_samples samples, with sums S1 (sum_rgba, the framebuffer) and S2 (m2_rgba, the moments;
+ * 4 floats per pixel each, the w components unused), per channel c, in fp64:
+ *   m_c = S1_c / N, v_c = max(0, S2_c / N - m_c^2) / (N - 1),
+ *   e_pixel = sqrt(v_r + v_g + v_b) / (m_r + m_g + m_b + floor),
+ * the relative standard error of the pixel's mean, and *out = the mean of e_pixel over the
+ * pixels (an 8x8 block: e_block).  A pixel with a NaN (or infinite) sum has e_pixel = +inf,
+ * one whose denominator is 0 (black, floor 0) has 0.  n_samples < 2: CVR_ERR_INVALID. */
+int cvr_block_error(const float* sum_rgba, const float* m2_rgba, uint32_t n_pixels, uint32_t n_samples, float floor,
+                    double* out);
+typedef struct cvr_adaptive_desc {
+  uint32_t min_iterations;   /* samples every block gets before the first check (>= 2) */
+  uint32_t max_iterations;   /* cap per block */
+  uint32_t pass_iterations;  /* samples added per pass; min and max are multiples of it */
+  float target;              /* a block stops once e_block <= target; negative: never */
+  float floor;               /* the metric's floor (the CLI default is 0.01) */
+} cvr_adaptive_desc;
+typedef struct cvr_adaptive_result {
+  uint32_t passes, blocks, blocks_active;  /* active = still sampling after this pass */
+  uint64_t paths;                          /* paths traced so far */
+  double max_error, mean_error;            /* over all blocks, each at its last check */
+  int32_t done;                            /* 1: nothing active, or max reached */
+} cvr_adaptive_result;
+/* A noise-targeted render of the context's tile: every 8x8-pixel block is sampled until its
+ * e_block (cvr_block_error) is at most desc->target or it has max_iterations samples.
+ * cvr_adaptive_begin opens the session: CVR_OPT_MOMENTS on, both buffers cleared, every
+ * block active with 0 samples.  It needs tile sides that are multiples of 8, one tile (the
+ * context's resolution, offset and camera as set), no block shard and no path range, the
+ * pixel-block work order (CVR_OPT_ORDER 1 or 2) and what CVR_OPT_MOMENTS needs
+ * (CVR_ERR_UNSUPPORTED otherwise); a bad descriptor is CVR_ERR_INVALID.  The context's
+ * iteration count is max_iterations until cvr_adaptive_end.
+ * cvr_adaptive_pass: the first pass renders samples [0, min_iterations) of every block,
+ * each later one pass_iterations more samples of the active blocks only, as one launch whose
+ * block list is the active blocks (a cvr_set_block_order table is ignored meanwhile).  The
+ * path ids are those of one launch of max_iterations, so every path is that launch's path,
+ * wherever its block stops.  Then the active blocks' errors are computed on the device and
+ * read back (one small copy per pass), and the blocks with e_block <= target, or with
+ * max_iterations samples, leave the list.  result (may be NULL) is the state after the
+ * pass.  A pass after done is CVR_ERR_STATE.
+ * cvr_adaptive_maps: every block's error at its last check and its sample count, tile
+ * blocks row-major (tile_w / 8 per row); either pointer may be NULL.  The last session's
+ * maps stay readable after its cvr_adaptive_end.
+ * cvr_adaptive_image: the image, every pixel divided by its own block's sample count
+ * (host_floats >= tile_w * tile_h * 4), stored by a kernel straight into pinned or
+ * registered host memory, through a staging copy otherwise.  Synchronous.
+ * cvr_adaptive_end: restores CVR_OPT_MOMENTS, the iteration count and the block list, and
+ * advances the seed exactly as one cvr_reset after a launch of max_iterations would.
+ * Between begin and end every other render call, cvr_set_option and the setters of the
+ * launch (medium, camera, resolution, offset, iterations, path range, block shard, seed,
+ * output, stream, cvr_clear_output, cvr_reset) return CVR_ERR_STATE; cvr_get_stats (the last
+ * pass's launch), cvr_synchronize, cvr_copy_moments and cvr_copy_output stay available. */
+int cvr_adaptive_begin(cvr_ctx* ctx, const cvr_adaptive_desc* desc);
+int cvr_adaptive_pass(cvr_ctx* ctx, cvr_adaptive_result* result);
+int cvr_adaptive_maps(cvr_ctx* ctx, double* block_error, uint32_t* block_samples);
+int cvr_adaptive_image(cvr_ctx* ctx, float* host_rgba, size_t host_floats);
+int cvr_adaptive_end(cvr_ctx* ctx);
+/* begin, passes until done, image, end.  result and stats may be NULL; stats are the
+ * passes' summed counters, kernel_ms the sum of their launches' device times. */
+int cvr_render_adaptive(cvr_ctx* ctx, const cvr_adaptive_desc* desc, float* host_rgba, size_t host_floats,
+                        cvr_adaptive_result* result, cvr_stats* stats);
+#endif /* CVR_ABI_VERSION >= 6 */
+
 /* Pinned, device-mapped host memory for cvr_render_share_to_host /
  * cvr_render_frame's in-launch output (hipHostMalloc, mapped + portable: every
  * device can store into it), and its release. */
