@@ -251,7 +251,8 @@ typedef struct cvr_medium_desc {
   float box_max[3];
   float scale;            /* density scale (VDB 100, Raw 40) */
   float max_density;      /* majorant / scale */
-  float g;                /* HG asymmetry; the reference never uploads it (Q7): 0 */
+  float g;                /* HG asymmetry; the reference never uploads it (Q7): 0.  A negative g scatters
+                             as |g|: ImportanceSampleHG divides by 2|g| (HG.h:51, Q24) */
   float roughness[2];     /* GGX alpha (0.1, 0.1) */
   float eta;              /* int_ior / ext_ior (1.05f / 1.01f) */
 } cvr_medium_desc;

@@ -1384,6 +1384,41 @@ EXPORT void oracle_hg(const float v[3], float g, float e1, float e2, float out[3
 EXPORT float oracle_fresnel(float eta, float ndotwi, float* ndotwt) {
   return fresnel_dielectric(eta, ndotwi, ndotwt);
 }
+EXPORT float oracle_ggx_g1(float ax, float ay, const float v[3], const float m[3]) {
+  return ggx_g1(ax, ay, mk3(v[0], v[1], v[2]), mk3(m[0], m[1], m[2]));
+}
+EXPORT void oracle_ggx_vndf(const float wi[3], float ax, float ay, float sx, float sy, float out[3]) {
+  f3 r = ggx_sample_vndf(mk3(wi[0], wi[1], wi[2]), ax, ay, sx, sy);
+  out[0] = r.x;
+  out[1] = r.y;
+  out[2] = r.z;
+}
+/* out: wo[3] and the weight.  wo starts as NaN: a failed sample may leave it unwritten (Q8). */
+EXPORT int oracle_ggx_sample(const float roughness[2], float eta, const float wi[3], int32_t seed, float out[4]) {
+  oracle_medium m;
+  memset(&m, 0, sizeof(m));
+  m.roughness[0] = roughness[0];
+  m.roughness[1] = roughness[1];
+  m.eta = eta;
+  xorwow_t rng;
+  rng_init(&rng, seed);
+  const float nan = __builtin_nanf("");
+  f3 wo = mk3(nan, nan, nan);
+  float weight = nan;
+  int ok = ggx_sample(&m, mk3(wi[0], wi[1], wi[2]), &rng, &wo, &weight);
+  out[0] = wo.x;
+  out[1] = wo.y;
+  out[2] = wo.z;
+  out[3] = weight;
+  return ok;
+}
+/* out: the frame's x, y and z axes, three floats each */
+EXPORT void oracle_frame(const float n[3], float out[9]) {
+  frame_t f = frame_from_z(mk3(n[0], n[1], n[2]));
+  out[0] = f.x.x; out[1] = f.x.y; out[2] = f.x.z;
+  out[3] = f.y.x; out[4] = f.y.y; out[5] = f.y.z;
+  out[6] = f.z.x; out[7] = f.z.y; out[8] = f.z.z;
+}
 EXPORT void oracle_camera_ray(const oracle_launch* L, uint32_t path_id, float out[6]) {
   const uint32_t tile_px = (uint32_t)(L->tile_res[0] * L->tile_res[1]);
   const uint32_t image_id = path_id % tile_px;

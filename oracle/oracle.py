@@ -98,6 +98,12 @@ def load():
     lib.oracle_hg.argtypes = [P, C.c_float, C.c_float, C.c_float, P]
     lib.oracle_fresnel.argtypes = [C.c_float, C.c_float, C.POINTER(C.c_float)]
     lib.oracle_fresnel.restype = C.c_float
+    lib.oracle_ggx_g1.argtypes = [C.c_float, C.c_float, P, P]
+    lib.oracle_ggx_g1.restype = C.c_float
+    lib.oracle_ggx_vndf.argtypes = [P, C.c_float, C.c_float, C.c_float, C.c_float, P]
+    lib.oracle_ggx_sample.argtypes = [P, C.c_float, P, C.c_int32, P]
+    lib.oracle_ggx_sample.restype = C.c_int
+    lib.oracle_frame.argtypes = [P, P]
     lib.oracle_camera_ray.argtypes = [C.POINTER(OracleLaunch), C.c_uint32, P]
     lib.oracle_detmath.argtypes = [C.c_int, P, P, C.c_uint32, P]
     _lib = lib
@@ -307,6 +313,51 @@ def hg(v, g, e1, e2):
     out = np.zeros(3, np.float32)
     lib.oracle_hg(_p(v), g, e1, e2, _p(out))
     return out
+
+
+def fresnel(eta, ndotwi):
+    """(F, ndotwt) of fresnel_dielectric (GGX.h:13-38)."""
+    lib = load()
+    t = C.c_float()
+    f = lib.oracle_fresnel(eta, ndotwi, C.byref(t))
+    return f, t.value
+
+
+def ggx_g1(ax, ay, v, m):
+    """ggx_g1 (GGX.h:227-255) of direction v and microfacet normal m, both local."""
+    lib = load()
+    v = np.asarray(v, np.float32)
+    m = np.asarray(m, np.float32)
+    return lib.oracle_ggx_g1(ax, ay, _p(v), _p(m))
+
+
+def ggx_vndf(wi, ax, ay, sx, sy):
+    """ggx_sample_vndf (GGX.h:146-181): the sampled microfacet normal."""
+    lib = load()
+    wi = np.asarray(wi, np.float32)
+    out = np.zeros(3, np.float32)
+    lib.oracle_ggx_vndf(_p(wi), ax, ay, sx, sy, _p(out))
+    return out
+
+
+def ggx_sample(roughness, eta, wi, seed):
+    """(ok, wo, weight) of ggx_sample (GGX.h:265-326) with the draws of rng_init(seed); wo is NaN
+    where a failed sample left it unwritten."""
+    lib = load()
+    r = np.asarray(roughness, np.float32)
+    wi = np.asarray(wi, np.float32)
+    out = np.zeros(4, np.float32)
+    ok = lib.oracle_ggx_sample(_p(r), eta, _p(wi), seed, _p(out))
+    return bool(ok), out[:3], out[3]
+
+
+def frame(n):
+    """frame_from_z (CVRMath.h:58-91): rows x, y, z."""
+    lib = load()
+    n = np.asarray(n, np.float32)
+    out = np.zeros(9, np.float32)
+    lib.oracle_frame(_p(n), _p(out))
+    return out.reshape(3, 3)
 
 
 def camera_ray(L: OracleLaunch, path_id: int):
