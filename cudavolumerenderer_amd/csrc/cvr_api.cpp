@@ -918,7 +918,7 @@ static void fill_medium_common(cvr::MediumParams& m, const uint32_t res[3], cons
 int cvr_set_medium(cvr_ctx* c, const cvr_medium_desc* md) {
   if (!c || !md) return set_err(c ? &c->err : nullptr, CVR_ERR_INVALID, "NULL argument");
   CVR_NOT_IN_SESSION(c, "cvr_set_medium");
-  if (!md->density || !md->albedo) return set_err(&c->err, CVR_ERR_INVALID, "density/albedo is NULL");
+  // (the shape is judged first, from the numbers alone, then the arrays)
   if (md->res[0] == 0 || md->res[1] == 0 || md->res[2] == 0)
     return set_err(&c->err, CVR_ERR_INVALID, "empty grid");
   const size_t n = (size_t)md->res[0] * md->res[1] * md->res[2];
@@ -927,6 +927,13 @@ int cvr_set_medium(cvr_ctx* c, const cvr_medium_desc* md) {
   if ((uint64_t)md->res[1] * md->res[2] >= (1ull << 24) || (uint64_t)md->res[0] * md->res[1] >= (1ull << 24))
     return set_err(&c->err, CVR_ERR_UNSUPPORTED, "dense grid with y*z or x*y >= 2^24: use cvr_set_medium_sparse");
   const uint32_t fmt = (uint32_t)c->medium_format;
+  // an fp32 cell is two float4: dense_cell doubles the u32 cell index (the half format's cell is one)
+  if (!fmt && c->use_cells && n >= (1ull << 31))
+    return set_err(&c->err, CVR_ERR_UNSUPPORTED,
+                   "dense fp32 grid of %zu voxels (>= 2^31) with density cells: use CVR_OPT_MEDIUM_FORMAT 1, "
+                   "CVR_OPT_CELLS 0 or cvr_set_medium_sparse",
+                   n);
+  if (!md->density || !md->albedo) return set_err(&c->err, CVR_ERR_INVALID, "density/albedo is NULL");
   // bytes per density voxel / cell / albedo voxel
   const size_t dB = fmt ? 2 : sizeof(float), cB = fmt ? 16 : 2 * sizeof(float4), aB = fmt ? 8 : sizeof(float4);
   if (fmt) {
@@ -1054,6 +1061,23 @@ int cvr_set_medium_sparse(cvr_ctx* c, const cvr_sparse_medium_desc* sd) {
   const uint32_t lnx = sd->leaf_dims[0], lny = sd->leaf_dims[1], lnz = sd->leaf_dims[2];
   const size_t nleaf = (size_t)lnx * lny * lnz;
   if (nleaf > 0xFFFFFFFFull) return set_err(&c->err, CVR_ERR_INVALID, "leaf table exceeds 2^32 entries");
+  // (as in cvr_set_medium, the shape is judged first, from the numbers alone, then the arrays)
+  // bricks of 2^bshift <= 8 cells (within one leaf); bounds off -> q = 255.
+  // Default 8^3 cells per brick: one brick word per leaf's cells (C5: 33.6 MB
+  // of words instead of 268 MB at 4^3, so they stay in L2 / Infinity Cache;
+  // 12% faster at an unchanged fetch rate, clouds being empty or dense).
+  const uint32_t bshift = !c->bound_shift_set ? 3u : c->bound_shift == 0 ? 2u : std::min(c->bound_shift, 3u);
+  const uint32_t B = 1u << bshift;
+  const uint32_t bnx = (res[0] + B - 1) / B, bny = (res[1] + B - 1) / B, bnz = (res[2] + B - 1) / B;
+  const size_t nb = (size_t)bnx * bny * bnz;
+  // the kernels index brick words and leaves with 24-bit multiplies, bz * (bnx bny) + by * bnx + bx
+  // and (lz * lny + ly) * lnx + lx, and a u32 sum (refused before anything is read or the previous
+  // medium is dropped)
+  if ((uint64_t)bnx * bny >= (1ull << 24) || bnz > (1u << 24) || nb >= 0xFFFFFFFFull)
+    return set_err(&c->err, CVR_ERR_UNSUPPORTED,
+                   "sparse grid of %ux%ux%u bricks: x*y >= 2^24, z > 2^24 or %zu bricks >= 2^32 - 1 (a larger "
+                   "CVR_OPT_BOUNDS brick, up to 8 cells, has fewer)",
+                   bnx, bny, bnz, nb);
   if (!sd->leaf_table || (sd->n_leaves && !sd->leaf_density))
     return set_err(&c->err, CVR_ERR_INVALID, "leaf table / density pool is NULL");
   // cell leaves: a leaf's cells read the corners in it and its forward
@@ -1147,21 +1171,12 @@ int cvr_set_medium_sparse(cvr_ctx* c, const cvr_sparse_medium_desc* sd) {
   m.lny = lny;
   m.albedo_bg = cvr::V3{sd->albedo_background[0], sd->albedo_background[1], sd->albedo_background[2]};
   if (fmt) m.albedo_bg = cvr::V3{half_round1(m.albedo_bg.x), half_round1(m.albedo_bg.y), half_round1(m.albedo_bg.z)};
-  // bricks of 2^bshift <= 8 cells (within one leaf); bounds off -> q = 255
   const float sigma = sd->scale * max_density;
   const int unbounded = !(c->bound_shift && sigma > 0.0f && std::isfinite(sigma) && sd->scale > 0.0f);
-  // Default 8^3 cells per brick: one brick word per leaf's cells (C5: 33.6 MB
-  // of words instead of 268 MB at 4^3, so they stay in L2 / Infinity Cache;
-  // 12% faster at an unchanged fetch rate, clouds being empty or dense).
-  m.bshift = !c->bound_shift_set ? 3u : c->bound_shift == 0 ? 2u : std::min(c->bound_shift, 3u);
-  const uint32_t B = 1u << m.bshift;
-  m.bnx = (res[0] + B - 1) / B;
-  m.bny = (res[1] + B - 1) / B;
-  const uint32_t bnz = (res[2] + B - 1) / B;
-  const size_t nb = (size_t)m.bnx * m.bny * bnz;
-  m.bnxy = m.bnx * m.bny;
-  if ((uint64_t)m.bnx * m.bny >= (1ull << 24) || nb >= 0xFFFFFFFFull)
-    return set_err(&c->err, CVR_ERR_UNSUPPORTED, "sparse grid has too many bricks (%zu)", nb);
+  m.bshift = bshift;
+  m.bnx = bnx;
+  m.bny = bny;
+  m.bnxy = bnx * bny;
   m.bsentinel = (uint32_t)nb;  // the no-bound word past the last brick (k_build_sparse_bounds writes it)
   HIP_TRY(c, hipMalloc(&c->d_sbounds, (nb + 1) * sizeof(uint32_t)));
   if (c->use_cells) HIP_TRY(c, hipMalloc(&c->d_cells, ncl * 512 * cB));
@@ -1693,6 +1708,12 @@ int cvr_launch_render(cvr_ctx* c) {
     if (c->out_owned_px < 2 * (size_t)c->tile_w * c->tile_h || c->d_out != c->d_out_owned)
       return set_err(&c->err, CVR_ERR_STATE, "the framebuffer holds no moments (cvr_set_resolution)");
   }
+  // a range as the caller gave it (count UINT64_MAX: to the end) names u32 path ids; past the
+  // tile's n_paths it is clipped, past 2^32 - 1 it is a mistake
+  if (c->range_count != UINT64_MAX &&
+      (c->range_first > 0xFFFFFFFFull || c->range_count > 0xFFFFFFFFull || c->range_first + c->range_count > 0xFFFFFFFFull))
+    return set_err(&c->err, CVR_ERR_INVALID, "path range [%llu, +%llu) ends past the 32-bit path ids (2^32 - 1)",
+                   (unsigned long long)c->range_first, (unsigned long long)c->range_count);
   uint64_t first, count;
   compute_range(c, &first, &count);
   cvr::LaunchParams L{};
@@ -1931,6 +1952,33 @@ int cvr_debug_counters(cvr_ctx* c, uint64_t out[16]) {
   if (!c || !out) return set_err(c ? &c->err : nullptr, CVR_ERR_INVALID, "NULL argument");
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   HIP_TRY(c, hipMemcpy(out, c->d_work + kWorkDebug, 16 * sizeof(uint64_t), hipMemcpyDeviceToHost));
+  return CVR_OK;
+}
+
+// Debug (tests; like cvr_debug_tailstamps not part of cvr.h): q[i] = u[i] / d by make_fastdiv(d)'s
+// constants.  on_device 0: the formula of cvr_walk.h fastdiv restated on the host (no GPU is
+// touched); 1: cvr::fastdiv itself in a trivial kernel on the current device.
+int cvr_debug_fastdiv(uint32_t d, const uint32_t* u, uint32_t* q, size_t n, int on_device) {
+  if (d == 0 || (n && (!u || !q))) return set_err(nullptr, CVR_ERR_INVALID, "cvr_debug_fastdiv: d = 0 or NULL array");
+  const cvr::FastDiv f = make_fastdiv(d);
+  if (!on_device) {
+    for (size_t i = 0; i < n; ++i) {
+      const uint32_t t = (uint32_t)(((uint64_t)u[i] * f.m) >> 32);
+      q[i] = (t + ((u[i] - t) >> (f.sh & 0xFFu))) >> (f.sh >> 8);
+    }
+    return CVR_OK;
+  }
+  if (n == 0) return CVR_OK;
+  uint32_t *d_u = nullptr, *d_q = nullptr;
+  hipError_t e = hipMalloc(&d_u, n * sizeof(uint32_t));
+  if (e == hipSuccess) e = hipMalloc(&d_q, n * sizeof(uint32_t));
+  if (e == hipSuccess) e = hipMemcpy(d_u, u, n * sizeof(uint32_t), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = cvr::launch_debug_fastdiv(f, d_u, d_q, n, nullptr);
+  if (e == hipSuccess) e = hipDeviceSynchronize();
+  if (e == hipSuccess) e = hipMemcpy(q, d_q, n * sizeof(uint32_t), hipMemcpyDeviceToHost);
+  if (d_u) (void)hipFree(d_u);
+  if (d_q) (void)hipFree(d_q);
+  if (e != hipSuccess) return set_err(nullptr, CVR_ERR_HIP, "cvr_debug_fastdiv: %s", hipGetErrorString(e));
   return CVR_OK;
 }
 

@@ -119,6 +119,8 @@ hipError_t launch_build_cells(const float* density, uint32_t rx, uint32_t ry, ui
 // The half storage format (MediumParams::format 1; `format` above: `density` holds halves and
 // the cells are written as 8 halves): n fp32 values -> n binary16, round to nearest even.
 hipError_t launch_to_half(const float* src, void* dst, size_t n, hipStream_t s);
+// cvr_debug_fastdiv (tests): q[i] = fastdiv(u[i], f) on the device, u and q device arrays.
+hipError_t launch_debug_fastdiv(FastDiv f, const uint32_t* u, uint32_t* q, size_t n, hipStream_t s);
 hipError_t launch_tile_to_image(const float4* tile, uint32_t tw, uint32_t th, float4* image, uint32_t iw,
                                 uint32_t ox, uint32_t oy, float scale, hipStream_t s);
 // Adaptive sampling (cvr_adaptive_*).  The error metric of one pixel from its sums (cvr.h,

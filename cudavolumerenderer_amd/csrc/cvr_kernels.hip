@@ -1051,6 +1051,19 @@ hipError_t launch_to_half(const float* src, void* dst, size_t n, hipStream_t s) 
   return hipGetLastError();
 }
 
+// cvr_debug_fastdiv: q[i] = fastdiv(u[i], f), the device function itself (tests only).
+__global__ void k_debug_fastdiv(FastDiv f, const uint32_t* u, uint32_t* q, size_t n) {
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
+    q[i] = fastdiv(u[i], f);
+}
+
+hipError_t launch_debug_fastdiv(FastDiv f, const uint32_t* u, uint32_t* q, size_t n, hipStream_t s) {
+  if (n == 0) return hipSuccess;
+  const uint32_t grid = (uint32_t)std::min<size_t>((n + 255) / 256, 8192);
+  hipLaunchKernelGGL(k_debug_fastdiv, dim3(grid), dim3(256), 0, s, f, u, q, n);
+  return hipGetLastError();
+}
+
 hipError_t launch_build_sparse(const MediumParams& m, const uint32_t* coords, size_t n_cell_leaves,
                                const uint32_t* cell_slot, uint32_t bnz, float max_density, int unbounded,
                                float4* cells, uint32_t* sbounds, hipStream_t s) {

@@ -577,9 +577,16 @@ CVR_DEV WoodcockPoint woodcock_point(const MediumParams& m, V3 o, V3 d, float t)
   woodcock_coords(m, o, d, t, P);
   // The cell and brick indices only mean something when in: off the grid the
   // brick index is replaced by the sentinel entry (no bound) and the cell
-  // pointer is never used (the 8-tap gather).  In the grid 0 <= cx < 2^24, so
-  // the truncating conversion is floor(cx) (Volume.h:52, (int)floorf) with no
-  // v_floor.  24-bit multiplies: the host keeps bnx*bny, rx*ry and ry*rz below 2^24.
+  // pointer is never used (the 8-tap gather).  In the grid 0 <= cx < res <
+  // 2^32, where the truncating conversion is floor(cx) (Volume.h:52,
+  // (int)floorf) with no v_floor.  A dense axis has fewer than 2^24 cells; a
+  // sparse one may have up to 2^27 (the brick guard; fres_* is exact for whole
+  // leaves, and otherwise errs only towards the gather), and from 2^24 on cx is an
+  // integer: floor(cx) = cx and v_fract gives 0, which are the x1 and
+  // fx = cx - x1 of Volume.h:52-56 (only every second cell, then every fourth,
+  // can be addressed there, in the reference too; pinned by
+  // tests/test_gpu_limits.py sparse_long_x).  24-bit multiplies: the host keeps
+  // bnx*bny, rx*ry and ry*rz below 2^24; a coordinate is never a multiplicand.
   const uint32_t x1 = (uint32_t)P.cx, y1 = (uint32_t)P.cy, z1 = (uint32_t)P.cz;
   const uint32_t bx = x1 >> m.bshift, by = y1 >> m.bshift, bz = z1 >> m.bshift;
   const uint32_t bi = P.in ? __umul24(bz, m.bnxy) + __umul24(by, m.bnx) + bx : m.bsentinel;

@@ -340,11 +340,27 @@ const char* cvr_last_error(const cvr_ctx* ctx); /* ctx may be NULL */
 int cvr_abi_version(void);
 
 /* setScene + createTextureWithVolume (CudaVolPath.cpp:88-186): copies the
- * host volumes into HBM (the caller keeps ownership of the host arrays). */
+ * host volumes into HBM (the caller keeps ownership of the host arrays).
+ * Limits (the kernels index with 24-bit multiplies and 32-bit sums), judged from res alone before
+ * the arrays are looked at, the context keeping its previous medium:
+ *  - an empty grid, or more than 2^32 - 1 voxels: CVR_ERR_INVALID;
+ *  - res[0] * res[1] >= 2^24 or res[1] * res[2] >= 2^24: CVR_ERR_UNSUPPORTED (use the sparse upload);
+ *  - 2^31 voxels or more in CVR_FORMAT_F32 with CVR_OPT_CELLS 1: CVR_ERR_UNSUPPORTED (use
+ *    CVR_OPT_MEDIUM_FORMAT 1, CVR_OPT_CELLS 0 or the sparse upload). */
 int cvr_set_medium(cvr_ctx* ctx, const cvr_medium_desc* medium);
 /* Sparse upload: leaf pools go to HBM as they are; the density cells and
  * brick bounds are built on the device for the leaves whose cells can
- * interpolate a non-zero density (a brick-pool instead of dense cells). */
+ * interpolate a non-zero density (a brick-pool instead of dense cells).
+ * Limits, with B the brick size in cells (8; CVR_OPT_BOUNDS 1 or 2: 2 or 4; CVR_OPT_BOUNDS 0: 4) and
+ * bn = ceil(res / B) per axis:
+ *  - an empty grid, leaf_dims != ceil(res / 8), more than 2^32 - 1 leaf table entries: CVR_ERR_INVALID;
+ *  - bn[0] * bn[1] >= 2^24, bn[2] > 2^24 or 2^32 - 1 bricks or more: CVR_ERR_UNSUPPORTED, judged
+ *    from res alone before anything is read (an axis may so have up to 2^27 cells; grid
+ *    coordinates of 2^24 and above are whole numbers in fp32, in the reference too);
+ *  - more than 2^24 cell leaves (the leaves that exist or have an existing forward neighbour,
+ *    plus one): CVR_ERR_UNSUPPORTED, and an entry >= n_leaves: CVR_ERR_INVALID, both after the
+ *    shape has passed, the arrays are non-NULL and the leaf table has been read.
+ * In each of these cases the context keeps its previous medium. */
 int cvr_set_medium_sparse(cvr_ctx* ctx, const cvr_sparse_medium_desc* medium);
 /* Extension: `ctx` renders the medium of `src` (same device) without a copy:
  * its kernels read src's device buffers, which stay owned by src (destroy
@@ -362,7 +378,9 @@ int cvr_half_round(const float* in, float* out, size_t n);
 /* copyInvViewMatrix (12 floats), copyRasterToView, copyPixelIndexRange */
 int cvr_set_camera(cvr_ctx* ctx, const float inv_view[12], const float raster_to_view[2],
                    const float full_res[2]);
-/* setResolution(tile_dim) */
+/* setResolution(tile_dim).  CVR_ERR_INVALID: a zero side, more than 2^24 pixels (the reference's
+ * float pixel row, floor((float)id / w)), or tile_w * tile_h * iterations above 2^32 - 1 (the
+ * reference's uint32 path ids; cvr_set_iterations checks the same product). */
 int cvr_set_resolution(cvr_ctx* ctx, uint32_t tile_w, uint32_t tile_h);
 /* The tile resolution the context renders now (set by cvr_set_resolution, or
  * by cvr_render_image / cvr_render_tiles to their tile size): the size of the
@@ -373,7 +391,11 @@ int cvr_set_offset(cvr_ctx* ctx, uint32_t x, uint32_t y);
 /* setNIterations: n_paths = tile_w * tile_h * iterations */
 int cvr_set_iterations(cvr_ctx* ctx, uint32_t iterations);
 /* Extension for sharding: launch only path ids [first, first+count) of the
- * tile's n_paths (default: all). */
+ * tile's n_paths (default: all; count UINT64_MAX: to the end).  The part of a range past
+ * n_paths is clipped.  A range that ends past 2^32 - 1 (other than count UINT64_MAX) is a
+ * mistake: the setter stores it and every launch returns CVR_ERR_INVALID; so does a launch
+ * whose queue heads could pass 2^32 - 1 (a range in path-id order within a few chunks per
+ * wave of 2^32).  More than 2^20 whole samples in one launch run in path-id order. */
 int cvr_set_path_range(cvr_ctx* ctx, uint64_t first, uint64_t count);
 /* Extension for multi-GPU strong scaling: restrict every launch to shard
  * `rank` of `world` of the tile's work.  Launches in the pixel-block work

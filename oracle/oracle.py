@@ -118,11 +118,18 @@ class Oracle:
     """Scene + launch description for the oracle; arrays are kept alive here."""
 
     def __init__(self, density, albedo, box_min=(-0.5,) * 3, box_max=(0.5,) * 3, scale=100.0,
-                 max_density=None, g=0.0, roughness=(0.1, 0.1), eta=None):
+                 max_density=None, g=0.0, roughness=(0.1, 0.1), eta=None, copy=True):
         self.lib = load()
-        # own copies: a Scene's arrays are views of memory the scene frees
-        self.density = np.array(density, np.float32, order="C", copy=True)
-        self.albedo = np.array(albedo, np.float32, order="C", copy=True)
+        if copy:
+            # own copies: a Scene's arrays are views of memory the scene frees
+            self.density = np.array(density, np.float32, order="C", copy=True)
+            self.albedo = np.array(albedo, np.float32, order="C", copy=True)
+        else:
+            # the caller's arrays themselves (see over()): referenced here, never written
+            for a in (density, albedo):
+                if not (isinstance(a, np.ndarray) and a.dtype == np.float32 and a.flags.c_contiguous):
+                    raise ValueError("Oracle(copy=False) needs C-contiguous float32 arrays")
+            self.density, self.albedo = density, albedo
         nz, ny, nx = self.density.shape
         m = OracleMedium()
         m.res[:] = (nx, ny, nz)
@@ -136,6 +143,14 @@ class Oracle:
         m.roughness[:] = roughness
         m.eta = np.float32(np.float32(1.05) / np.float32(1.01)) if eta is None else eta
         self.m = m
+
+    @classmethod
+    def over(cls, density, albedo, box_min=(-0.5,) * 3, box_max=(0.5,) * 3, scale=100.0, max_density=None, g=0.0,
+             roughness=(0.1, 0.1), eta=None):
+        """The oracle over the caller's own arrays, without the copy Oracle() makes (grids of
+        hundreds of MB): C-contiguous float32, which must not change or be freed by other means
+        while the oracle lives (it holds references)."""
+        return cls(density, albedo, box_min, box_max, scale, max_density, g, roughness, eta, copy=False)
 
     @classmethod
     def from_leaves(cls, res, table, leaf_density, leaf_albedo, albedo_bg, box_min=(-0.5,) * 3,
