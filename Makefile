@@ -11,7 +11,8 @@ CSRC := $(PKG)/csrc
 HIPFLAGS := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -ffp-contract=off \
             -fhip-fp32-correctly-rounded-divide-sqrt -Iinclude -I$(CSRC) -Wall -Wno-unused-function
 OBJDIR := build/obj
-SRCS_HIP := $(CSRC)/cvr_kernels.hip $(CSRC)/cvr_persistent.hip $(CSRC)/cvr_pool.hip $(CSRC)/cvr_wpool.hip $(CSRC)/cvr_wavefront.hip
+SRCS_HIP := $(CSRC)/cvr_kernels.hip $(CSRC)/cvr_persistent.hip $(CSRC)/cvr_pool.hip $(CSRC)/cvr_wpool.hip $(CSRC)/cvr_wavefront.hip \
+            $(CSRC)/cvr_denoise.hip
 SRCS_CPP := $(CSRC)/cvr_api.cpp $(CSRC)/cvr_scene.cpp $(CSRC)/cvr_vdb.cpp $(CSRC)/cvr_mhd.cpp $(CSRC)/cvr_xml.cpp
 OBJS := $(patsubst $(CSRC)/%.hip,$(OBJDIR)/%.o,$(SRCS_HIP)) $(patsubst $(CSRC)/%.cpp,$(OBJDIR)/%.o,$(SRCS_CPP))
 HDRS := include/cvr.h include/cvr_detmath.h $(wildcard $(CSRC)/*.h)
@@ -68,6 +69,14 @@ variant: $(SRCS_HIP) $(SRCS_CPP) $(HDRS)
 variant-pair:
 	$(MAKE) variant NAME=pair DEFS="-DCVR_WPOOL_PAIR=1"
 .PHONY: variant-pair
+# The denoiser with global-memory taps in every pass (the A/B partner of the LDS-staged steps 1 and
+# 2: profiles/denoise/README.md); only cvr_denoise.hip differs from the in-tree library
+variant-dnplain: $(OBJS)
+	@mkdir -p build/variants/dnplain
+	$(HIPCC) $(HIPFLAGS) -DCVR_DENOISE_LDS=0 -c $(CSRC)/cvr_denoise.hip -o build/variants/dnplain/cvr_denoise.o
+	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o build/variants/dnplain/libcvr.so \
+	    $(filter-out $(OBJDIR)/cvr_denoise.o,$(OBJS)) build/variants/dnplain/cvr_denoise.o -Wl,-soname,libcvr.so -lz
+.PHONY: variant-dnplain
 # Cell fetches as track-ready work (round-6 experiment, measured slower: profiles/round6/ab/fetch_list/)
 variant-fetchlist:
 	$(MAKE) variant NAME=fetchlist DEFS="-DCVR_WPOOL_FETCH_LIST=1"

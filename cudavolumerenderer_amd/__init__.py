@@ -10,6 +10,7 @@ from ._lib import (  # noqa: F401
     OPT_SCHEDULER, OPT_POOL, OPT_TIMING, OPT_CELLS, OPT_WAVES, OPT_ORDER, OPT_QUEUES, OPT_BOUNDS, OPT_TAIL, OPT_BATCH, OPT_RNG_BINDING, OPT_MORTON, OPT_WORLD_TO_AABB, OPT_MK_COMPACTION, OPT_SUBQUEUES, OPT_DRAIN, OPT_INFLIGHT, OPT_FRAME_FLUSH, OPT_UNIFORM_ALBEDO, OPT_WAVE_PAIR, OPT_SAMPLE_ORDER, OPT_EMPTY_MASK, OPT_COUNT_WORDS,
     OPT_MEDIUM_FORMAT, FORMAT_F32, FORMAT_F16, MediumInfo, half_round,
     OPT_MOMENTS, AdaptiveDesc, AdaptiveResult, AdaptiveSession, block_error,
+    DenoiseDesc, denoise_host,
     PATH_RECORD_DTYPE, CvrError, Context, MediumDesc, PinnedImage, Scene, Stats, default_camera, load,
     medium_from_arrays, tile_origin, tiling, write_hdr, LIB_PATH,
 )
@@ -19,4 +20,5 @@ __all__ = [
     "tile_origin", "write_hdr", "medium_from_arrays", "load", "LIB_PATH", "PATH_RECORD_DTYPE",
     "OPT_MEDIUM_FORMAT", "FORMAT_F32", "FORMAT_F16", "MediumInfo", "half_round",
     "OPT_MOMENTS", "AdaptiveDesc", "AdaptiveResult", "AdaptiveSession", "block_error",
+    "DenoiseDesc", "denoise_host",
 ]

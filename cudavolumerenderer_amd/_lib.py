@@ -126,6 +126,15 @@ class AdaptiveResult(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class DenoiseDesc(C.Structure):
+    """cvr_denoise_desc: the variance-guided a-trous filter's parameters (passes 1..6, pass k with
+    step 2^k; sigma: width of the edge-stopping term in standard deviations; floor > 0)."""
+    _fields_ = [("passes", C.c_uint32), ("sigma", C.c_float), ("floor", C.c_float), ("flags", C.c_uint32)]
+
+    def __init__(self, passes=5, sigma=4.0, floor=0.01, flags=0):
+        super().__init__(passes, sigma, floor, flags)
+
+
 _lib = None
 
 
@@ -208,6 +217,9 @@ def load() -> C.CDLL:
         "cvr_adaptive_end": (I32, [P]),
         "cvr_render_adaptive": (I32, [P, C.POINTER(AdaptiveDesc), P, C.c_size_t, C.POINTER(AdaptiveResult),
                                       C.POINTER(Stats)]),
+        "cvr_denoise_host": (I32, [P, P, U32, U32, U32, P, C.POINTER(DenoiseDesc), P, P]),
+        "cvr_denoise_buffers": (I32, [P, P, P, U32, U32, U32, P, C.POINTER(DenoiseDesc), P, P]),
+        "cvr_denoise": (I32, [P, C.POINTER(DenoiseDesc), U32, P, C.c_size_t]),
     }
     # an older experiment build (tools' --lib, A/B against a previous commit) may lack newer entry
     # points; the in-tree library must export every one (tests/test_host_abi.py)
@@ -254,6 +266,39 @@ def block_error(sum_rgba, m2_rgba, n_samples: int, floor: float) -> float:
     out = C.c_double()
     _check(load().cvr_block_error(_fp(a), _fp(b), a.shape[0], n_samples, floor, C.byref(out)))
     return out.value
+
+
+def denoise_host(sum_rgba, m2_rgba, n_samples: Optional[int] = None, block_samples=None,
+                 desc: Optional[DenoiseDesc] = None):
+    """The denoiser's written statement on the CPU (cvr_denoise_host; no GPU): the raw sums
+    `sum_rgba` and second moments `m2_rgba`, (h, w, 4) floats each (Context.copy_moments), with
+    n_samples per pixel or a (h / 8, w / 8) map of per-block counts -> (rgba (h, w, 4), var (h, w)):
+    the filtered image (w: the pixel's escapes per sample) and the filtered variance of the pixel
+    mean's luminance, -1 where no valid pixel reached.  The device paths return the same bits."""
+    s1 = np.ascontiguousarray(sum_rgba, dtype=np.float32)
+    s2 = np.ascontiguousarray(m2_rgba, dtype=np.float32)
+    if s1.ndim != 3 or s1.shape[2] != 4 or s1.shape != s2.shape:
+        raise CvrError(-1, "denoise_host: sum and m2 must both be (h, w, 4)")
+    h, w = s1.shape[:2]
+    counts = None
+    if block_samples is not None:
+        counts = np.ascontiguousarray(block_samples, dtype=np.uint32)
+        if counts.size != (h // 8) * (w // 8):
+            raise CvrError(-1, "denoise_host: block_samples must hold (h / 8) * (w / 8) counts")
+    desc = DenoiseDesc() if desc is None else desc
+    rgba = np.zeros((h, w, 4), np.float32)
+    var = np.zeros((h, w), np.float32)
+    _check(load().cvr_denoise_host(s1.ctypes.data, s2.ctypes.data, w, h, n_samples or 0,
+                                   None if counts is None else counts.ctypes.data, C.byref(desc), rgba.ctypes.data,
+                                   var.ctypes.data))
+    return rgba, var
+
+
+def _device_ptr(a):
+    """An int address, or an object with data_ptr() (a torch tensor); None stays None."""
+    if a is None:
+        return None
+    return int(a.data_ptr()) if hasattr(a, "data_ptr") else int(a)
 
 
 def default_camera(width: int, height: int):
@@ -571,6 +616,32 @@ class Context:
         self._c(load().cvr_copy_moments(self._h, _fp(s1), _fp(s2)))
         return s1, s2
 
+    def denoise(self, desc: Optional[DenoiseDesc] = None, n_samples: Optional[int] = None, host_ptr=None) -> np.ndarray:
+        """The context's framebuffer filtered with its second moments (cvr_denoise; OPT_MOMENTS 1):
+        n_samples (>= 2) is the number of samples accumulated since the last clear; inside an
+        adaptive session it stays None and every block has its own count.  Synchronous; the
+        buffers are only read.  host_ptr: a PinnedImage to store into (returned as its array)."""
+        desc = DenoiseDesc() if desc is None else desc
+        if isinstance(host_ptr, PinnedImage):
+            self._c(load().cvr_denoise(self._h, C.byref(desc), n_samples or 0, host_ptr.ptr, host_ptr.floats))
+            return host_ptr.array
+        w, h = self.resolution
+        img = np.zeros((h, w, 4), np.float32)
+        self._c(load().cvr_denoise(self._h, C.byref(desc), n_samples or 0, C.c_void_p(img.ctypes.data), img.size))
+        return img
+
+    def denoise_buffers(self, sum_rgba, m2_rgba, width: int, height: int, out_rgba, n_samples: Optional[int] = None,
+                        block_samples=None, desc: Optional[DenoiseDesc] = None, out_var=None):
+        """The denoiser on device buffers of any origin (cvr_denoise_buffers), asynchronous on the
+        context's stream: each buffer an int device address or an object with data_ptr() (a torch
+        tensor).  sum_rgba / m2_rgba / out_rgba: width * height * 4 floats, 16-byte aligned;
+        block_samples: (height / 8) * (width / 8) uint32 on the device, or None with n_samples;
+        out_var: width * height floats or None."""
+        desc = DenoiseDesc() if desc is None else desc
+        self._c(load().cvr_denoise_buffers(self._h, _device_ptr(sum_rgba), _device_ptr(m2_rgba), width, height,
+                                           n_samples or 0, _device_ptr(block_samples), C.byref(desc),
+                                           _device_ptr(out_rgba), _device_ptr(out_var)))
+
     def adaptive(self, desc: AdaptiveDesc) -> "AdaptiveSession":
         """A noise-targeted render of the set tile as a context manager (cvr_adaptive_begin ..
         cvr_adaptive_end): `with ctx.adaptive(desc) as a: while not a.step().done: ...; img = a.image()`."""
@@ -754,6 +825,11 @@ class AdaptiveSession:
         img = np.zeros((h, w, 4), np.float32)
         self.ctx._c(load().cvr_adaptive_image(self.ctx._h, C.c_void_p(img.ctypes.data), img.size))
         return img
+
+    def denoised(self, desc: Optional[DenoiseDesc] = None, host_ptr=None) -> np.ndarray:
+        """The session's image filtered with its moments, every block at its own sample count
+        (Context.denoise inside the session)."""
+        return self.ctx.denoise(desc, None, host_ptr)
 
 
 class PinnedImage:

@@ -263,6 +263,9 @@ struct cvr_ctx {
     uint32_t saved_iterations = 1;
     cvr_stats acc{};
   } ad;
+  // cvr_denoise*: the two scratch images the passes alternate between (dn_px pixels each)
+  float4* d_dn = nullptr;
+  size_t dn_px = 0;
 };
 // Calls that are out of order inside an adaptive session (the session's own launches pass).
 #define CVR_NOT_IN_SESSION(c, what)                                                                       \
@@ -857,6 +860,7 @@ int cvr_destroy(cvr_ctx* c) {
   if (c->d_active) (void)hipFree(c->d_active);
   if (c->ad.d_err) (void)hipFree(c->ad.d_err);
   if (c->ad.d_counts) (void)hipFree(c->ad.d_counts);
+  if (c->d_dn) (void)hipFree(c->d_dn);
   if (c->ev_start) (void)hipEventDestroy(c->ev_start);
   if (c->ev_stop) (void)hipEventDestroy(c->ev_stop);
   if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
@@ -2705,6 +2709,141 @@ int cvr_render_adaptive(cvr_ctx* c, const cvr_adaptive_desc* d, float* host, siz
   if (r2) return r2;
   if (result) *result = res;
   if (stats) *stats = acc;
+  return CVR_OK;
+}
+
+// ------------------------------------------------------------ denoiser ----
+// The variance-guided a-trous filter of cvr.h.  The host statement and the kernels
+// (cvr_denoise.hip) run the same per-pixel functions of cvr_kernels.h.
+static int denoise_check(std::string* err, const cvr_denoise_desc* d, uint32_t w, uint32_t h, uint32_t n_samples,
+                         bool have_map) {
+  if (d->passes < 1u || d->passes > 6u) return set_err(err, CVR_ERR_INVALID, "denoise: passes %u not in 1..6", d->passes);
+  if (!(d->sigma >= 0.0f) || !std::isfinite(d->sigma) || !(d->floor > 0.0f) || !std::isfinite(d->floor))
+    return set_err(err, CVR_ERR_INVALID, "denoise: sigma must be finite and >= 0, floor finite and > 0");
+  if (d->flags != 0u) return set_err(err, CVR_ERR_INVALID, "denoise: flags must be 0");
+  if (w == 0 || h == 0 || (uint64_t)w * h > (1ull << 24))
+    return set_err(err, CVR_ERR_INVALID, "denoise: a %ux%u image (1 to 2^24 pixels)", w, h);
+  if (have_map && (w % 8u || h % 8u))
+    return set_err(err, CVR_ERR_INVALID, "denoise: a block-sample map needs sides that are multiples of 8, not %ux%u", w,
+                   h);
+  if (!have_map && n_samples < 2u) return set_err(err, CVR_ERR_INVALID, "denoise: the variance needs at least 2 samples");
+  return CVR_OK;
+}
+
+int cvr_denoise_host(const float* sum_rgba, const float* m2_rgba, uint32_t w, uint32_t h, uint32_t n_samples,
+                     const uint32_t* block_samples, const cvr_denoise_desc* desc, float* out_rgba, float* out_var) {
+  if (!sum_rgba || !m2_rgba || !desc || !out_rgba) return set_err(nullptr, CVR_ERR_INVALID, "NULL argument");
+  int r = denoise_check(nullptr, desc, w, h, n_samples, block_samples != nullptr);
+  if (r) return r;
+  const size_t px = (size_t)w * h;
+  // (floats, not float4: the caller's arrays need no 16-byte alignment)
+  auto at = [](const float* a, size_t i) { return make_float4(a[4 * i], a[4 * i + 1], a[4 * i + 2], a[4 * i + 3]); };
+  std::vector<float4> a(px), b(px);
+  for (uint32_t y = 0; y < h; ++y)
+    for (uint32_t x = 0; x < w; ++x) {
+      const size_t i = (size_t)y * w + x;
+      a[i] = cvr::denoise_prepare(at(sum_rgba, i), at(m2_rgba, i), cvr::denoise_count(block_samples, n_samples, w, x, y));
+    }
+  for (uint32_t k = 0; k < desc->passes; ++k) {
+    for (uint32_t y = 0; y < h; ++y)
+      for (uint32_t x = 0; x < w; ++x)
+        b[(size_t)y * w + x] = cvr::denoise_pass(a.data(), w, h, x, y, 1u << k, desc->sigma, desc->floor);
+    a.swap(b);
+  }
+  for (uint32_t y = 0; y < h; ++y)
+    for (uint32_t x = 0; x < w; ++x) {
+      const size_t i = (size_t)y * w + x;
+      const float4 f = a[i];
+      const float4 o = cvr::denoise_final(f, at(sum_rgba, i), cvr::denoise_count(block_samples, n_samples, w, x, y));
+      out_rgba[4 * i] = o.x;
+      out_rgba[4 * i + 1] = o.y;
+      out_rgba[4 * i + 2] = o.z;
+      out_rgba[4 * i + 3] = o.w;
+      if (out_var) out_var[i] = f.w < 0.0f ? -1.0f : f.w;
+    }
+  return CVR_OK;
+}
+
+// prepare + passes on the context's stream, the last pass storing into out (checked arguments)
+static int denoise_launch(cvr_ctx* c, const float4* sum, const float4* m2, uint32_t w, uint32_t h, uint32_t n_samples,
+                          const uint32_t* d_counts, const cvr_denoise_desc* d, float4* out, float* out_var) {
+  const size_t px = (size_t)w * h;
+  if (c->dn_px < px) {
+    HIP_TRY(c, hipStreamSynchronize(c->stream));  // an earlier filter may still read the old images
+    if (c->d_dn) (void)hipFree(c->d_dn);
+    c->d_dn = nullptr;
+    c->dn_px = 0;
+    HIP_TRY(c, hipMalloc(&c->d_dn, 2 * px * sizeof(float4)));
+    c->dn_px = px;
+  }
+  float4* img[2] = {c->d_dn, c->d_dn + c->dn_px};
+  HIP_TRY(c, cvr::launch_denoise_prepare(sum, m2, w, h, n_samples, d_counts, img[0], c->stream));
+  for (uint32_t k = 0; k + 1 < d->passes; ++k)
+    HIP_TRY(c, cvr::launch_denoise_pass(img[k & 1u], img[(k & 1u) ^ 1u], w, h, 1u << k, d->sigma, d->floor, c->stream));
+  const uint32_t last = d->passes - 1u;
+  HIP_TRY(c, cvr::launch_denoise_last(img[last & 1u], w, h, 1u << last, d->sigma, d->floor, sum, n_samples, d_counts, out,
+                                      out_var, c->stream));
+  return CVR_OK;
+}
+
+int cvr_denoise_buffers(cvr_ctx* c, const float* d_sum_rgba, const float* d_m2_rgba, uint32_t w, uint32_t h,
+                        uint32_t n_samples, const uint32_t* d_block_samples, const cvr_denoise_desc* desc,
+                        float* d_out_rgba, float* d_out_var) {
+  if (!c) return set_err(nullptr, CVR_ERR_INVALID, "NULL ctx");
+  if (!d_sum_rgba || !d_m2_rgba || !desc || !d_out_rgba) return set_err(&c->err, CVR_ERR_INVALID, "NULL argument");
+  int r = denoise_check(&c->err, desc, w, h, n_samples, d_block_samples != nullptr);
+  if (r) return r;
+  if ((((uintptr_t)d_sum_rgba) | ((uintptr_t)d_m2_rgba) | ((uintptr_t)d_out_rgba)) & 15u)
+    return set_err(&c->err, CVR_ERR_INVALID, "denoise: the rgba buffers must be 16-byte aligned");
+  if ((uintptr_t)d_out_var & 3u) return set_err(&c->err, CVR_ERR_INVALID, "denoise: out_var must be 4-byte aligned");
+  if ((r = ensure_device(c))) return r;
+  return denoise_launch(c, reinterpret_cast<const float4*>(d_sum_rgba), reinterpret_cast<const float4*>(d_m2_rgba), w, h,
+                        n_samples, d_block_samples, desc, reinterpret_cast<float4*>(d_out_rgba), d_out_var);
+}
+
+int cvr_denoise(cvr_ctx* c, const cvr_denoise_desc* desc, uint32_t n_samples, float* host, size_t host_floats) {
+  if (!c) return set_err(nullptr, CVR_ERR_INVALID, "NULL ctx");
+  if (!desc || !host) return set_err(&c->err, CVR_ERR_INVALID, "NULL argument");
+  if (!c->moments) return set_err(&c->err, CVR_ERR_STATE, "second moments are off (CVR_OPT_MOMENTS)");
+  const size_t px = (size_t)c->tile_w * c->tile_h;
+  if (!c->d_out || c->d_out != c->d_out_owned || c->out_owned_px < 2 * px || px == 0)
+    return set_err(&c->err, CVR_ERR_STATE, "the framebuffer holds no moments (cvr_set_resolution)");
+  cvr_ctx::Adaptive& a = c->ad;
+  if (a.on && n_samples != 0)
+    return set_err(&c->err, CVR_ERR_INVALID,
+                   "denoise: inside an adaptive session n_samples must be 0 (every block has its own count)");
+  int r = denoise_check(&c->err, desc, c->tile_w, c->tile_h, n_samples, a.on);
+  if (r) return r;
+  if (host_floats < px * 4u)
+    return set_err(&c->err, CVR_ERR_INVALID, "host image holds %zu floats, the %ux%u tile needs %zu", host_floats,
+                   c->tile_w, c->tile_h, px * 4u);
+  if ((r = ensure_device(c))) return r;
+  const uint32_t* d_counts = nullptr;
+  if (a.on) {
+    HIP_TRY(c, hipMemcpyAsync(a.d_counts, a.samples.data(), (size_t)a.n_blocks * sizeof(uint32_t), hipMemcpyHostToDevice,
+                              c->stream));
+    d_counts = a.d_counts;
+  }
+  void* dhost = nullptr;  // pinned or registered memory: the last pass stores the image itself
+  if (((uintptr_t)host & 15u) || hipHostGetDevicePointer(&dhost, host, 0) != hipSuccess) {
+    (void)hipGetLastError();  // pageable memory: not an error, the staging copy below
+    dhost = nullptr;
+  }
+  if (dhost) {
+    if ((r = denoise_launch(c, c->d_out, c->d_out + px, c->tile_w, c->tile_h, n_samples, d_counts, desc,
+                            static_cast<float4*>(dhost), nullptr)))
+      return r;
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return CVR_OK;
+  }
+  float4* stage = nullptr;
+  HIP_TRY(c, hipMalloc(&stage, px * sizeof(float4)));
+  r = denoise_launch(c, c->d_out, c->d_out + px, c->tile_w, c->tile_h, n_samples, d_counts, desc, stage, nullptr);
+  hipError_t e = hipStreamSynchronize(c->stream);
+  if (!r && e == hipSuccess) e = hipMemcpy(host, stage, px * sizeof(float4), hipMemcpyDeviceToHost);
+  (void)hipFree(stage);
+  if (r) return r;
+  if (e != hipSuccess) return set_err(&c->err, CVR_ERR_HIP, "denoise: %s", hipGetErrorString(e));
   return CVR_OK;
 }
 

@@ -152,4 +152,104 @@ hipError_t launch_block_error(const float4* tile, uint32_t tile_px, uint32_t til
 hipError_t launch_tile_to_image_counts(const float4* tile, uint32_t tw, uint32_t th, const uint32_t* counts,
                                        float4* image, hipStream_t s);
 
+// Denoiser (cvr_denoise*).  The per-pixel bodies of the filter cvr.h states: the one definition,
+// compiled for the host (cvr_denoise_host) and for k_denoise_prepare / k_denoise_pass.  fp32
+// only, every operation in the written order (-ffp-contract=off, correctly rounded / and sqrt),
+// so both sides return the same bits.  An image pixel is (m_r, m_g, m_b, v); v < 0: invalid.
+__host__ __device__ inline bool denoise_finite3(const float4 s) {
+  return s.x - s.x == 0.0f && s.y - s.y == 0.0f && s.z - s.z == 0.0f;
+}
+__host__ __device__ inline float denoise_luma(float r, float g, float b) {
+  return (0.2126f * r + 0.7152f * g) + 0.0722f * b;
+}
+// One pixel's samples: n_samples, or the count of its 8x8 block (counts: w / 8 entries per row).
+__host__ __device__ inline uint32_t denoise_count(const uint32_t* counts, uint32_t n_samples, uint32_t w, uint32_t x,
+                                                  uint32_t y) {
+  return counts ? counts[(y >> 3) * (w >> 3) + (x >> 3)] : n_samples;
+}
+// Prepare: the sums s1, s2 of one pixel with n samples -> (mean rgb, variance of the mean's luminance).
+__host__ __device__ inline float4 denoise_prepare(const float4 s1, const float4 s2, uint32_t n) {
+  if (n < 2u || !denoise_finite3(s1) || !denoise_finite3(s2)) return make_float4(0.0f, 0.0f, 0.0f, -1.0f);
+  const float N = (float)n, N1 = N - 1.0f;
+  const float mr = s1.x / N, mg = s1.y / N, mb = s1.z / N;
+  const float dr = s2.x / N - mr * mr, dg = s2.y / N - mg * mg, db = s2.z / N - mb * mb;
+  const float vr = (dr > 0.0f ? dr : 0.0f) / N1, vg = (dg > 0.0f ? dg : 0.0f) / N1, vb = (db > 0.0f ? db : 0.0f) / N1;
+  const float v = ((0.2126f * 0.2126f) * vr + (0.7152f * 0.7152f) * vg) + (0.0722f * 0.0722f) * vb;
+  return make_float4(mr, mg, mb, v);
+}
+// One a-trous pass at pixel (x, y) of a w x h image, step `step`: the filtered pixel.  tap(qx, qy)
+// returns the image's pixel at a coordinate inside the image (it is asked for no other), from
+// wherever the caller keeps it: the order of the arithmetic does not depend on that.
+template <class Tap>
+__host__ __device__ __forceinline__ float4 denoise_pass_at(const Tap& tap, uint32_t w, uint32_t h, uint32_t x,
+                                                           uint32_t y, uint32_t step, float sigma, float floor) {
+  const float G[3] = {0.25f, 0.5f, 0.25f};
+  const float K[5] = {0.0625f, 0.25f, 0.375f, 0.25f, 0.0625f};
+  const int iw = (int)w, ih = (int)h, px = (int)x, py = (int)y, s = (int)step;
+  const float4 p = tap(px, py);
+  const bool valid = !(p.w < 0.0f);
+  float den = 1.0f, lp = 0.0f;
+  if (valid) {
+    float gs = 0.0f, gw = 0.0f;
+    for (int j = -1; j <= 1; ++j)
+      for (int i = -1; i <= 1; ++i) {
+        const int qx = px + i, qy = py + j;
+        if (qx < 0 || qx >= iw || qy < 0 || qy >= ih) continue;
+        const float vq = tap(qx, qy).w;
+        if (vq < 0.0f) continue;
+        const float wt = G[j + 1] * G[i + 1];
+        gs += wt * vq;
+        gw += wt;
+      }
+    den = sigma * sqrtf(gs / gw) + floor;
+    lp = denoise_luma(p.x, p.y, p.z);
+  }
+  float cr = 0.0f, cg = 0.0f, cb = 0.0f, vs = 0.0f, ws = 0.0f;
+  for (int j = -2; j <= 2; ++j)
+    for (int i = -2; i <= 2; ++i) {
+      const int qx = px + s * i, qy = py + s * j;
+      if (qx < 0 || qx >= iw || qy < 0 || qy >= ih) continue;
+      const float4 q = tap(qx, qy);
+      if (q.w < 0.0f) continue;
+      float wt = K[j + 2] * K[i + 2];
+      if (valid) {
+        const float a = fabsf(denoise_luma(q.x, q.y, q.z) - lp) / den;
+        const float u = 1.0f + a * a;
+        wt = wt / (u * u);
+      }
+      cr += wt * q.x;
+      cg += wt * q.y;
+      cb += wt * q.z;
+      vs += (wt * wt) * q.w;
+      ws += wt;
+    }
+  if (ws == 0.0f) return make_float4(0.0f, 0.0f, 0.0f, -1.0f);
+  return make_float4(cr / ws, cg / ws, cb / ws, vs / (ws * ws));
+}
+// The image in plain memory, row-major: the host statement and the kernels' global loads.
+struct DenoiseImage {
+  const float4* src;
+  uint32_t w;
+  __host__ __device__ float4 operator()(int qx, int qy) const { return src[(size_t)qy * w + (size_t)qx]; }
+};
+__host__ __device__ __forceinline__ float4 denoise_pass(const float4* src, uint32_t w, uint32_t h, uint32_t x,
+                                                        uint32_t y, uint32_t step, float sigma, float floor) {
+  return denoise_pass_at(DenoiseImage{src, w}, w, h, x, y, step, sigma, floor);
+}
+// The output pixel from the last pass's result f, the pixel's sum s1 and its n samples.
+__host__ __device__ inline float4 denoise_final(const float4 f, const float4 s1, uint32_t n) {
+  const float a = n >= 2u ? s1.w / (float)n : 0.0f;
+  return f.w < 0.0f ? make_float4(0.0f, 0.0f, 0.0f, a) : make_float4(f.x, f.y, f.z, a);
+}
+// Device side (cvr_denoise.hip): prepare into `img`, or one pass src -> dst; the last pass (sum
+// non-null) stores denoise_final into out_rgba (device memory or the device address of pinned
+// host memory) and the filtered v, -1 for an invalid pixel, into out_var (may be null).
+hipError_t launch_denoise_prepare(const float4* sum, const float4* m2, uint32_t w, uint32_t h, uint32_t n_samples,
+                                  const uint32_t* counts, float4* img, hipStream_t s);
+hipError_t launch_denoise_pass(const float4* src, float4* dst, uint32_t w, uint32_t h, uint32_t step, float sigma,
+                               float floor, hipStream_t s);
+hipError_t launch_denoise_last(const float4* src, uint32_t w, uint32_t h, uint32_t step, float sigma, float floor,
+                               const float4* sum, uint32_t n_samples, const uint32_t* counts, float4* out_rgba,
+                               float* out_var, hipStream_t s);
+
 }  // namespace cvr

@@ -15,7 +15,8 @@
 //   --noise-target F [--min-iterations N] [--pass-iterations N] (an adaptive
 //   render, cvr_render_adaptive: every 8x8 block is sampled until its relative
 //   standard error is at most F, -i being the cap; also writes the samples map
-//   as <output>_samples.hdr)
+//   as <output>_samples.hdr), --denoise [--denoise-sigma F] [--denoise-passes N] (also
+//   write the variance-guided filter of the render, cvr_denoise, as <output>_denoised.hdr)
 //
 // Differences from the reference, on purpose: the timer is wall clock (the
 // reference uses clock(), i.e. CPU time, Main.cpp:51-77); main does not wait
@@ -44,6 +45,9 @@ struct Options {
   bool adaptive = false;  // --noise-target given
   float noise_target = 0.0f;
   unsigned min_iterations = 8, pass_iterations = 4;
+  bool denoise = false;  // --denoise given
+  float denoise_sigma = 4.0f;
+  unsigned denoise_passes = 5;
   std::vector<float> default_albedo;
   bool interactive = true, unified = false;
   unsigned trials = 1, iterations = 20, device = 0, seed = 0;
@@ -85,6 +89,15 @@ void usage() {
       "                                     writes the samples map as <output>_samples.hdr (one device, one tile)\n"
       "  --min-iterations N (=8)            adaptive render: samples of every block before the first check\n"
       "  --pass-iterations N (=4)           adaptive render: samples added per pass (min and cap: multiples)\n"
+      "  --denoise                          also write the render filtered by the variance-guided denoiser\n"
+      "                                     (cvr_denoise, floor 0.01) as <output>_denoised.hdr (and .pfm with\n"
+      "                                     --pfm); with --noise-target the adaptive session is filtered, else\n"
+      "                                     the render runs as a session in which every block takes all\n"
+      "                                     --iterations (>= 2) samples, two in the first launch and one per\n"
+      "                                     later launch, which makes the output the same bits in every run\n"
+      "                                     (one device, one tile)\n"
+      "  --denoise-sigma F (=4)             denoiser: width of the edge-stopping term in standard deviations\n"
+      "  --denoise-passes N (=5)            denoiser: a-trous passes, 1..6 (pass k has step 2^k)\n"
       "  --rng-binding path|thread (=path)  regenerationSK: thread = the reference's Rng(seed + tid)\n"
       "                                     per persistent thread (non-deterministic, SURVEY Q2)\n"
       "  --default-albedo r g b             VDB files without an albedo grid load with this albedo\n"
@@ -138,6 +151,9 @@ int parse(int argc, char** argv, Options& o) {
     }
     else if (a == "--min-iterations") o.min_iterations = (unsigned)strtoul(need("min-iterations").c_str(), nullptr, 10);
     else if (a == "--pass-iterations") o.pass_iterations = (unsigned)strtoul(need("pass-iterations").c_str(), nullptr, 10);
+    else if (a == "--denoise") o.denoise = true;
+    else if (a == "--denoise-sigma") o.denoise_sigma = strtof(need("denoise-sigma").c_str(), nullptr);
+    else if (a == "--denoise-passes") o.denoise_passes = (unsigned)strtoul(need("denoise-passes").c_str(), nullptr, 10);
     else if (a == "--rng-binding") o.rng_binding = need("rng-binding");
     else if (a == "--seed") o.seed = (unsigned)strtoul(need("seed").c_str(), nullptr, 10);
     else if (a == "--world-to-aabb") o.world_to_aabb = need("world-to-aabb");
@@ -341,9 +357,13 @@ int main(int argc, char** argv) {
   }
   const unsigned ntiles = o.tiles[0] * o.tiles[1];
   size_t n_dev = devs.size();
-  if (o.adaptive && (n_dev > 1 || ntiles > 1)) {
-    fprintf(stderr, "[ConfigParser] Error: --noise-target renders one tile on one device (no --devices > 1, no "
-                    "--number-of-tiles above 1 1)\n");
+  if ((o.adaptive || o.denoise) && (n_dev > 1 || ntiles > 1)) {
+    fprintf(stderr, "[ConfigParser] Error: %s renders one tile on one device (no --devices > 1, no "
+                    "--number-of-tiles above 1 1)\n", o.adaptive ? "--noise-target" : "--denoise");
+    return 2;
+  }
+  if (o.denoise && !o.adaptive && o.iterations < 2) {
+    fprintf(stderr, "[ConfigParser] Error: --denoise needs --iterations of at least 2 (a variance per pixel)\n");
     return 2;
   }
   const bool tile_mode = ntiles > 1;
@@ -391,7 +411,48 @@ int main(int argc, char** argv) {
     const auto t0 = std::chrono::steady_clock::now();
     cvr_adaptive_result ares{};
     std::vector<uint32_t> block_samples;
-    if (o.adaptive) {
+    std::vector<float> denoised;
+    if (o.denoise) {
+      // the session step by step, filtered (cvr_denoise) before it ends.  Without --noise-target a
+      // session that never stops a block: every block takes every sample, the plain render's
+      // paths.  It takes two samples in its first pass and one in each later pass, so that no
+      // launch adds more than two values into a pixel on top of nothing, or one on top of a sum:
+      // the float atomics' arrival order then cannot change a bit (fp32 addition commutes, it
+      // does not associate), and the sums, the image and the filtered image are the same bits in
+      // every run.  One launch of all samples is faster and differs from run to run by an ulp in
+      // a few pixels (profiles/denoise/README.md).
+      cvr_ctx* c = ctxs[0];
+      const cvr_adaptive_desc ad = o.adaptive ? cvr_adaptive_desc{o.min_iterations, o.iterations, o.pass_iterations,
+                                                                  o.noise_target, 0.01f}
+                                              : cvr_adaptive_desc{2u, o.iterations, 1u, -1.0f, 0.01f};
+      const cvr_denoise_desc dd = {o.denoise_passes, o.denoise_sigma, 0.01f, 0u};
+      block_samples.assign((size_t)(W / 8) * (H / 8), 0u);
+      denoised.assign((size_t)W * H * 4, 0.0f);
+      r = cvr_set_resolution(c, W, H);
+      if (!r) r = cvr_set_offset(c, 0, 0);
+      if (!r) r = cvr_adaptive_begin(c, &ad);
+      while (!r && !ares.done) {
+        cvr_stats ps{};
+        if ((r = cvr_adaptive_pass(c, &ares)) || (r = cvr_get_stats(c, &ps))) break;
+        st.paths += ps.paths;
+        st.segments += ps.segments;
+        st.steps += ps.steps;
+        st.density += ps.density;
+        st.albedo += ps.albedo;
+        st.escaped += ps.escaped;
+        st.truncated += ps.truncated;
+        st.fetches += ps.fetches;
+        st.kernel_ms += ps.kernel_ms;
+      }
+      if (!r) r = cvr_adaptive_image(c, image.data(), image.size());
+      if (!r) r = cvr_adaptive_maps(c, nullptr, block_samples.data());
+      if (!r) r = cvr_denoise(c, &dd, 0, denoised.data(), denoised.size());
+      if (!r) r = cvr_adaptive_end(c);
+      if (r != CVR_OK) {
+        fprintf(stderr, "Error: %s\n", cvr_last_error(c));
+        return 1;
+      }
+    } else if (o.adaptive) {
       // cvr_render_adaptive's steps, with the samples map read before the session ends
       cvr_ctx* c = ctxs[0];
       const cvr_adaptive_desc ad = {o.min_iterations, o.iterations, o.pass_iterations, o.noise_target, 0.01f};
@@ -484,6 +545,11 @@ int main(int argc, char** argv) {
     cvr_write_hdr((o.output + ".hdr").c_str(), image.data(), W, H);
     if (o.pfm && write_pfm(o.output + ".pfm", image.data(), W, H)) {
       fprintf(stderr, "Error: could not write %s.pfm\n", o.output.c_str());
+      return 1;
+    }
+    if (o.denoise && (cvr_write_hdr((o.output + "_denoised.hdr").c_str(), denoised.data(), W, H) != CVR_OK ||
+                      (o.pfm && write_pfm(o.output + "_denoised.pfm", denoised.data(), W, H)))) {
+      fprintf(stderr, "Error: could not write %s_denoised.hdr%s\n", o.output.c_str(), o.pfm ? " / .pfm" : "");
       return 1;
     }
   }

@@ -27,6 +27,7 @@ extern "C" {
 /* ABI history: 3: cvr_render_frame takes the host buffer size; 4: cvr_stats.words;
  *              5: CVR_OPT_MEDIUM_FORMAT, cvr_half_round, cvr_medium_info;
  *              6: CVR_OPT_MOMENTS, cvr_copy_moments, cvr_block_error, cvr_adaptive_*
+ *              6 + CVR_HAS_DENOISE (no new number, an addition within 6): cvr_denoise_desc, cvr_denoise*
  * CVR_ABI_VERSION is the ABI this header declares: 6, the library's (cvr_abi_version()).  ABI 6 only
  * adds to ABI 5, so a host that must also load an ABI 5 library can hold itself to that surface:
  * with CVR_ABI_TARGET defined as 5 before the include, the ABI 6 functions and structs are not
@@ -608,7 +609,7 @@ typedef struct cvr_adaptive_result {
  * Between begin and end every other render call, cvr_set_option and the setters of the
  * launch (medium, camera, resolution, offset, iterations, path range, block shard, seed,
  * output, stream, cvr_clear_output, cvr_reset) return CVR_ERR_STATE; cvr_get_stats (the last
- * pass's launch), cvr_synchronize, cvr_copy_moments and cvr_copy_output stay available. */
+ * pass's launch), cvr_synchronize, cvr_copy_moments, cvr_copy_output and cvr_denoise stay available. */
 int cvr_adaptive_begin(cvr_ctx* ctx, const cvr_adaptive_desc* desc);
 int cvr_adaptive_pass(cvr_ctx* ctx, cvr_adaptive_result* result);
 int cvr_adaptive_maps(cvr_ctx* ctx, double* block_error, uint32_t* block_samples);
@@ -618,6 +619,58 @@ int cvr_adaptive_end(cvr_ctx* ctx);
  * passes' summed counters, kernel_ms the sum of their launches' device times. */
 int cvr_render_adaptive(cvr_ctx* ctx, const cvr_adaptive_desc* desc, float* host_rgba, size_t host_floats,
                         cvr_adaptive_result* result, cvr_stats* stats);
+
+/* ---- variance-guided denoiser (extension within ABI 6: CVR_HAS_DENOISE) -- */
+/* An edge-avoiding a-trous wavelet filter on colour alone, its edge-stopping term scaled by the
+ * local standard deviation of the pixel mean, which the second moments give.  Every operation is
+ * fp32 +, -, x, /, sqrt in the order written here, no fused multiply-add, so the device kernels
+ * and cvr_denoise_host return the same bits (one definition compiles for both, cvr_kernels.h).
+ * Per pixel N is n_samples, or with block_samples the entry of the pixel's 8x8 block (row-major,
+ * w / 8 per row).  A pixel is valid if N >= 2 and the r, g, b of both of its sums are finite.
+ * Prepare, per valid pixel and channel c:  m_c = S1_c / N, d_c = S2_c / N - m_c m_c,
+ *   v_c = max(d_c, 0) / (N - 1);  l = (k_r m_r + k_g m_g) + k_b m_b,
+ *   v = ((k_r k_r) v_r + (k_g k_g) v_g) + (k_b k_b) v_b, k = (0.2126f, 0.7152f, 0.0722f).
+ *   It stores (m_r, m_g, m_b, v); an invalid pixel stores (0, 0, 0, -1): v < 0 marks it.
+ * Pass k = 0 .. passes - 1, step s = 2^k, between two buffers; a tap counts only if it lies in
+ * the image and is valid.  For a valid centre p, over the 3x3 taps q = p + (i, j), rows first,
+ * G = (1/4, 1/2, 1/4):  w = G_j G_i, gs += w v(q), gw += w;  den = sigma sqrt(gs / gw) + floor.
+ * Then over the 5x5 taps q = p + s (i, j), rows first, h = (1/16, 1/4, 3/8, 1/4, 1/16), l(.)
+ * recomputed from the stored rgb:  a = |l(q) - l(p)| / den, u = 1 + a a, w = (h_j h_i) / (u u),
+ *   cs_c += w c_c(q), vs += (w w) v(q), ws += w;  out = (cs_r / ws, cs_g / ws, cs_b / ws,
+ *   vs / (ws ws)).  An invalid centre runs the 5x5 loop with w = h_j h_i (no edge term: it is
+ * in-painted from its valid taps) and stays (0, 0, 0, -1) if ws == 0.
+ * Output: out_rgba = (r, g, b, S1_w / N) (w: 0 where N < 2; rgb 0 where still invalid);
+ * out_var = the filtered v, -1 where invalid.
+ * passes 1..6, sigma >= 0 and finite, floor > 0 and finite, flags 0: else CVR_ERR_INVALID.
+ * The defaults of the bindings and the CLI are 5, 4.0 and 0.01. */
+#define CVR_HAS_DENOISE 1
+typedef struct cvr_denoise_desc {
+  uint32_t passes;
+  float sigma;
+  float floor;
+  uint32_t flags;
+} cvr_denoise_desc; /* 16 bytes */
+/* Host only, no GPU: the written statement of the filter.  sum_rgba / m2_rgba: w * h * 4 floats
+ * (the layout of cvr_copy_moments).  block_samples may be NULL (uniform n_samples >= 2); with a
+ * map w and h are multiples of 8 and n_samples is ignored.  out_var (w * h floats) may be NULL.
+ * More than 2^24 pixels: CVR_ERR_INVALID. */
+int cvr_denoise_host(const float* sum_rgba, const float* m2_rgba, uint32_t w, uint32_t h, uint32_t n_samples,
+                     const uint32_t* block_samples, const cvr_denoise_desc* desc, float* out_rgba, float* out_var);
+/* The same on device buffers of any origin (e.g. torch tensors; the rgba ones 16-byte aligned),
+ * asynchronous on the context's stream; the two scratch images are owned by the context (a
+ * larger image than before synchronises the stream once to grow them).  d_out_rgba may be the
+ * device address of pinned host memory.  The inputs are only read. */
+int cvr_denoise_buffers(cvr_ctx* ctx, const float* d_sum_rgba, const float* d_m2_rgba, uint32_t w, uint32_t h,
+                        uint32_t n_samples, const uint32_t* d_block_samples, const cvr_denoise_desc* desc,
+                        float* d_out_rgba, float* d_out_var);
+/* The context's own framebuffer and moments (CVR_OPT_MOMENTS 1, else CVR_ERR_STATE), filtered
+ * into host_rgba (tile_w * tile_h * 4 floats; host_floats smaller: CVR_ERR_INVALID).  Synchronous.
+ * Pinned or registered host memory is stored into by the kernel, other memory through a staging
+ * copy (as cvr_adaptive_image).  Inside an adaptive session n_samples must be 0 and every block
+ * has its own count (cvr_adaptive_maps); outside one n_samples >= 2 is the number of samples
+ * accumulated since the last clear (else CVR_ERR_INVALID).  Reads the framebuffer and the
+ * moments and never writes them.  Available between cvr_adaptive_begin and cvr_adaptive_end. */
+int cvr_denoise(cvr_ctx* ctx, const cvr_denoise_desc* desc, uint32_t n_samples, float* host_rgba, size_t host_floats);
 #endif /* CVR_ABI_VERSION >= 6 */
 
 /* Pinned, device-mapped host memory for cvr_render_share_to_host /
