@@ -64,11 +64,6 @@ variant: $(SRCS_HIP) $(SRCS_CPP) $(HDRS)
 	@mkdir -p build/variants/$(NAME)
 	$(HIPCC) $(HIPFLAGS) $(DEFS) -shared -o build/variants/$(NAME)/libcvr.so $(SRCS_HIP) $(patsubst %,-x hip %,$(SRCS_CPP)) -lz
 .PHONY: variant
-# The workgroup-shared event-list experiment (k_wpair), kept out of libcvr.so:
-#   make variant-pair; CVR_LIB=build/variants/pair/libcvr.so pytest tests/test_wave_pair.py -m gpu
-variant-pair:
-	$(MAKE) variant NAME=pair DEFS="-DCVR_WPOOL_PAIR=1"
-.PHONY: variant-pair
 # The denoiser with global-memory taps in every pass (the A/B partner of the LDS-staged steps 1 and
 # 2: profiles/denoise/README.md); only cvr_denoise.hip differs from the in-tree library
 variant-dnplain: $(OBJS)
@@ -77,7 +72,3 @@ variant-dnplain: $(OBJS)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o build/variants/dnplain/libcvr.so \
 	    $(filter-out $(OBJDIR)/cvr_denoise.o,$(OBJS)) build/variants/dnplain/cvr_denoise.o -Wl,-soname,libcvr.so -lz
 .PHONY: variant-dnplain
-# Cell fetches as track-ready work (round-6 experiment, measured slower: profiles/round6/ab/fetch_list/)
-variant-fetchlist:
-	$(MAKE) variant NAME=fetchlist DEFS="-DCVR_WPOOL_FETCH_LIST=1"
-.PHONY: variant-fetchlist

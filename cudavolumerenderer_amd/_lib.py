@@ -15,8 +15,8 @@ import numpy as np
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _DEFAULT_LIB = os.path.abspath(os.path.join(_HERE, "libcvr.so"))
-# CVR_LIB: an experiment build instead of the in-tree library (e.g. `make variant-pair`'s,
-# for tests/test_wave_pair.py); unset, the in-tree libcvr.so
+# CVR_LIB: an experiment build instead of the in-tree library (e.g. `make variant NAME=u2 ...`'s
+# build/variants/u2/libcvr.so); unset, the in-tree libcvr.so
 LIB_PATH = os.environ.get("CVR_LIB") or _DEFAULT_LIB
 
 CVR_OK = 0

@@ -192,7 +192,6 @@ struct cvr_ctx {
   // 0 = the default, 5 (dense and sparse, split slots)
   int wpool_waves = 0;
   int morton = 0;  // CVR_OPT_MORTON
-  int wave_pair = 0;  // CVR_OPT_WAVE_PAIR
   int sample_order = -1;  // CVR_OPT_SAMPLE_ORDER (-1: the default, 0)
   int empty_mask = 1;     // CVR_OPT_EMPTY_MASK
   int count_words = 0;    // CVR_OPT_COUNT_WORDS
@@ -352,7 +351,6 @@ const char* moments_refusal(const cvr_ctx* c) {
          : wpool_waves_for(c, sparse) != 5     ? "CVR_OPT_WAVES other than 5"
          : c->mk_compaction                    ? "CVR_OPT_MK_COMPACTION 1"
          : c->count_words                      ? "CVR_OPT_COUNT_WORDS 1"
-         : c->wave_pair                        ? "CVR_OPT_WAVE_PAIR 1"
          : (sparse && c->m.format != 0u)       ? "a sparse half medium"
                                                : nullptr;
 }
@@ -1560,10 +1558,9 @@ int cvr_set_option(cvr_ctx* c, int opt, int64_t v) {
       return CVR_OK;
     case CVR_OPT_WAVE_PAIR:
       if (v < 0 || v > 1) return set_err(&c->err, CVR_ERR_INVALID, "wave pair must be 0 or 1");
-      if (v == 1 && !cvr::wpool_pair_built())
+      if (v == 1)
         return set_err(&c->err, CVR_ERR_UNSUPPORTED,
-                       "wave pair (k_wpair) is an experiment built only into `make variant-pair`");
-      c->wave_pair = (int)v;
+                       "wave pair (workgroup-shared event lists) was an experiment and has been removed");
       return CVR_OK;
     case CVR_OPT_UNIFORM_ALBEDO:
       // takes effect at the next cvr_set_medium
@@ -1699,7 +1696,6 @@ int cvr_launch_render(cvr_ctx* c) {
                       : wpool_waves_for(c, sparse) != 5    ? "CVR_OPT_WAVES other than 5"
                       : c->mk_compaction                   ? "CVR_OPT_MK_COMPACTION 1"
                       : c->count_words                     ? "CVR_OPT_COUNT_WORDS 1"
-                      : c->wave_pair                       ? "CVR_OPT_WAVE_PAIR 1"
                                                            : nullptr;
     if (why) return set_err(&c->err, CVR_ERR_UNSUPPORTED, "the half medium format does not run with %s", why);
   }
@@ -1821,8 +1817,8 @@ int cvr_launch_render(cvr_ctx* c) {
                        4 * cvr::kFrameFlushers);
       L.frame_done = c->frame_done_active;
     }
-    HIP_TRY(c, cvr::launch_wpool(launch_medium(c), L, eps, waves, grid, c->stream, c->wave_pair != 0,
-                                 c->kernel == CVR_KERNEL_NAIVE_MK, c->count_words != 0, c->moments != 0));
+    HIP_TRY(c, cvr::launch_wpool(launch_medium(c), L, eps, waves, grid, c->stream, c->kernel == CVR_KERNEL_NAIVE_MK,
+                                 c->count_words != 0, c->moments != 0));
   } else if (L.path_count > 0) {
     if ((r = wf_render(c, L, eps))) return r;
   }
@@ -2283,7 +2279,6 @@ static void copy_settings(cvr_ctx* d, const cvr_ctx* s) {
   d->pool_tail = s->pool_tail;
   d->wpool_waves = s->wpool_waves;
   d->morton = s->morton;
-  d->wave_pair = s->wave_pair;
   d->swap_batch = s->swap_batch;
   d->scheduler = s->scheduler;
   d->waves = s->waves;

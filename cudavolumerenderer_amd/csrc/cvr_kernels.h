@@ -52,17 +52,12 @@ hipError_t launch_trace(const MediumParams& m, const LaunchParams& L, bool scatt
                         hipStream_t s);
 hipError_t launch_pool(const MediumParams& m, const LaunchParams& L, bool scatter_eps, uint32_t grid, hipStream_t s);
 hipError_t pool_occupancy(bool scatter_eps, int* blocks_per_cu);
-// whether this build carries k_wpair (CVR_WPOOL_PAIR; only `make variant-pair`)
-bool wpool_pair_built();
-// pair: two waves per workgroup sharing their event lists (k_wpair; dense media with
-// cells and bounds, 5 waves per SIMD, no records / in-launch output; else k_wpool).
 // naive_mk: naiveMK's walk on the wave pool (5 waves per SIMD, no records / in-launch output).
 // count_words: sparse media, the counting instance (CVR_OPT_COUNT_WORDS: brick words loaded).
 // moments: the second-moment instance (CVR_OPT_MOMENTS): L.out holds 2 * tile_px float4, the
 // moments behind the tile; 5 waves per SIMD, generic dense or fp32 sparse layout only.
 hipError_t launch_wpool(const MediumParams& m, const LaunchParams& L, bool scatter_eps, int waves, uint32_t grid,
-                        hipStream_t s, bool pair = false, bool naive_mk = false, bool count_words = false,
-                        bool moments = false);
+                        hipStream_t s, bool naive_mk = false, bool count_words = false, bool moments = false);
 // Resident waves per CU of the wave-pool instance (workgroups per CU x waves per workgroup).
 hipError_t wpool_occupancy(bool scatter_eps, int waves, bool sparse, int* waves_per_cu);
 // Pool slots per wave of the wave-pool kernel instance (LaunchParams::pool_T

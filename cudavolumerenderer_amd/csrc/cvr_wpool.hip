@@ -50,45 +50,19 @@
 #endif
 // Tentative points per lane per Woodcock group (the lookahead below).  The
 // track loop runs CVR_WPOOL_UNROLL / kLook groups between swap checks.
+#ifndef CVR_WPOOL_LOOK
+#define CVR_WPOOL_LOOK 2
+#endif
 // Sparse instances: a point that needs its cell parks until the end of the track
 // iteration (kLookDefer below).
 #ifndef CVR_WPOOL_SPARSE_DEFER
 #define CVR_WPOOL_SPARSE_DEFER 1
-#endif
-// The workgroup-shared event lists (k_wpair, CVR_OPT_WAVE_PAIR): an experiment
-// that lost 4.1x, built only into `make variant-pair`.
-#ifndef CVR_WPOOL_PAIR
-#define CVR_WPOOL_PAIR 0
 #endif
 // Diagnostic build (make variant NAME=tail DEFS=-DCVR_WPOOL_TAILSTAMP=1, tools/tail_wpool.py):
 // per wave, s_memrealtime at its start, when it first finds every queue exhausted and at its
 // end, with its live paths and event batches after that point.
 #ifndef CVR_WPOOL_TAILSTAMP
 #define CVR_WPOOL_TAILSTAMP 0
-#endif
-// The drain's wide track (round 6, wide_track): once every queue is exhausted and
-// at most 64 / CVR_WPOOL_WIDE paths are ready, each gets CVR_WPOOL_WIDE lanes that
-// evaluate its next CVR_WPOOL_WIDE tentative points at once.  0: off, the default:
-// bit-exact but no faster (K 16 / 8 / 4: one render at a time +0.1-0.3%, the 1/8
-// block shard +1%, renders in flight -0.5-1%; profiles/round6/ab/wide_drain_ab.log),
-// since half of a draining wave's time is its event batches, which stay one lane
-// per path (profiles/round6/tail_c2_stamps.log).
-#ifndef CVR_WPOOL_WIDE
-#define CVR_WPOOL_WIDE 0
-#endif
-#ifndef CVR_WPOOL_LOOK
-#define CVR_WPOOL_LOOK 2
-#endif
-// Cell fetches as track-ready work (round-6 experiment, dense instances with cells and
-// bounds; 0: off, the default and the only form in libcvr.so).  A point the brick bound
-// does not settle ends the lane's turn: the path's (t, rng) go back to the pool and its slot
-// joins the track-ready ring marked "fetch pending" (bit 7 of the ring entry); the lanes
-// that pull marked entries at a swap fetch their cells together and either file a
-// collision or track on, so no lane idles for another lane's cell and the two per-group
-// fetch blocks of the track loop (~5% lane fill) go away.  The same points and draws: the
-// test value is the path's last draw, re-derived from the stored XORWOW state.
-#ifndef CVR_WPOOL_FETCH_LIST
-#define CVR_WPOOL_FETCH_LIST 0
 #endif
 constexpr int kLook = CVR_WPOOL_LOOK;
 // The track loop runs CVR_WPOOL_UNROLL / kLook groups: a variant build with
@@ -510,102 +484,6 @@ __device__ void frame_flusher(const LaunchParams& L, uint32_t f, uint32_t lane) 
   if (lane == 0) __hip_atomic_store(F.status + f, stored, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
-// ---- the launch's drain: one path's Woodcock points across K lanes -----------
-// Once every queue is exhausted a wave's pool only drains: fewer paths than lanes
-// are left, and the last ones run one segment at a time, each Woodcock group a
-// dependent brick-word load (round-6 tail stamps, tools/tail_wpool.py: half of a
-// draining wave's time is its track loop).  The points of a segment depend on
-// nothing but its RNG stream, so with few paths left each ready path gets K
-// lanes (one group of a DPP row): lane p of the group takes the path's draws
-// 2p + 1 and 2p + 2 (every lane steps the XORWOW sequence up to its own pair),
-// the distances follow the sequential chain t_p = fma(-log xi_p, inv_sigma,
-// t_{p-1}) in order (one row shift per point), and all K brick words (and the
-// cells the bounds do not settle) load at once.  The first point of the group
-// that ends the segment (past max_t, or a real collision) is found by a ballot;
-// the points after it are dropped, as in the two-point lookahead, and the path's
-// t and RNG are that point's (its lane stores them into the slot).  The same
-// candidates in the same order: the same results, steps and fetch counts as one
-// point at a time (Utilities.cuh:147-152, tests/test_gpu_records.py).  On exit
-// lane 0 of each group holds its path's finished segment, filed by the next
-// swap.  Groups past `ngroups` repeat group 0's path and write nothing.
-template <int K, int kSlots, int kEm, class Pool, class EmWords>
-__device__ __forceinline__ void wide_track(Pool& S, const EmWords& em, const MediumParams& m, uint32_t lane,
-                                           uint32_t ready_head,
-                                           uint32_t ngroups, int& slot, int& fst, V3& o, V3& d, Rng& rng,
-                                           float& t, float& max_t, uint32_t& c_steps, uint32_t& c_fetch) {
-  static_assert(K >= 2 && K <= 16 && (K & (K - 1)) == 0, "a group lies within one 16-lane DPP row");
-  constexpr uint32_t kGroupMask = K == 32 ? 0xFFFFFFFFu : (1u << K) - 1u;
-  // (through an empty asm: lane / K and lane % K are loop-invariant, and hoisted to the
-  // prologue they would hold two VGPRs across the track loop)
-  uint32_t ln = lane;
-  asm volatile("" : "+v"(ln));
-  const uint32_t g = ln / K, p = ln % K;
-  const bool real = g < ngroups;
-  const uint32_t r = ready_head + (real ? g : 0u);
-  const uint32_t s = S.ready[r >= (uint32_t)kSlots ? r - kSlots : r];
-  V3 go, gd;
-  Rng gr;
-  float gt, gmax;
-  load_track(S, s, go, gd, gr, gt, gmax);
-  int res = 0;        // the group's segment result once it ended: 1 past max_t, 2 accepted
-  bool open = real;   // group-uniform: the segment has not ended
-  for (;;) {
-    // lane p: draws 2p + 1, 2p + 2 of the group's stream (divergent loop, K rounds)
-    Rng lr = gr;
-    float xi = 0.0f, xt = 0.0f;
-    for (uint32_t i = 0; i <= p; ++i) {
-      xi = rng_float(lr);
-      xt = rng_float(lr);
-    }
-    const float a = -det_logf_normal(__builtin_fmaxf(xi, CVR_EPSILON_F));
-    // t_p = fma(a_p, inv_sigma, t_{p-1}) in order: woodcock_advance's chain, one row shift per point
-    float tp = det_fmaf(a, m.inv_sigma, gt);
-#pragma unroll
-    for (int j = 1; j < K; ++j) {
-      const float prev = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(tp), 0x111 /* row_shr:1 */,
-                                                                    0xF, 0xF, false));
-      const float tn = det_fmaf(a, m.inv_sigma, prev);
-      tp = p == (uint32_t)j ? tn : tp;
-    }
-    WoodcockPoint P;
-    if constexpr (kEm != 0)
-      P = woodcock_point_em<kEm>(m, go, gd, tp, em);
-    else
-      P = woodcock_point(m, go, gd, tp);
-    int rr = 0;
-    bool fetched = false;
-    if (!(tp <= gmax)) {
-      rr = 1;
-    } else if (!(P.qb < xt)) {
-      fetched = true;
-      const float rho = m.scale * woodcock_density(m, P);
-      if (!(rho * m.inv_sigma < xt)) rr = 2;
-    }
-    const unsigned long long me = __ballot(rr != 0), m1 = __ballot(rr == 1);
-    const uint32_t gb = (uint32_t)(me >> (g * K)) & kGroupMask;
-    const uint32_t end = gb ? (uint32_t)__builtin_ctz(gb) : (uint32_t)K;
-    if (open) {
-      c_fetch += (fetched && p <= end) ? 1u : 0u;
-      if (p == 0) c_steps += end < (uint32_t)K ? end + 1u : (uint32_t)K;
-      // the group's new track state: the ending point's, or the last point's
-      if (p == (end < (uint32_t)K ? end : (uint32_t)K - 1u)) store_track(S, s, tp, lr);
-      if (end < (uint32_t)K) {
-        res = ((m1 >> (g * K + end)) & 1ull) ? 1 : 2;
-        open = false;
-      }
-    }
-    if (__ballot(open) == 0ull) break;
-    if (open) {  // the next K points from the state just stored (one wave: LDS in order)
-      V3 o2, d2;
-      load_track(S, s, o2, d2, gr, gt, gmax);
-    }
-  }
-  if (real && p == 0) {
-    slot = (int)s;
-    fst = res;
-    load_track(S, s, o, d, rng, t, max_t);
-  }
-}
 
 }  // namespace
 
@@ -671,7 +549,6 @@ __global__ __launch_bounds__(64 * wpg_of(kMedMk, kWaves), kWaves) void k_wpool(M
   // Sparse media defer their cell fetches to the end of the track iteration
   // (the lookahead below): C5 -3.0%; the dense instances lose 5-8% with it.
   constexpr bool kLookDefer = kSparse && CVR_WPOOL_SPARSE_DEFER;
-  constexpr bool kFetchList = CVR_WPOOL_FETCH_LIST && !kMK && (kMed == kMedDenseFull || kMed == kMedDenseFullUniform);
   // (dense media: +7% C2, +6% C3 with a 16-word mask)
   constexpr int kEm = kSparse && CVR_WPOOL_EMASK ? kEmaskWords : 0;
   // waves per workgroup, each with a pool of its own (kWpgSparse on sparse media)
@@ -722,7 +599,6 @@ __global__ __launch_bounds__(64 * wpg_of(kMedMk, kWaves), kWaves) void k_wpool(M
                     (size_t)PoolSize<kWaves, 0, kWpg>::kBudget,
                 "wave pools exceed the LDS budget of kWaves waves per SIMD");
   static_assert(kSlots <= 256, "the pool's rings and stacks hold slot indices as uint8_t");
-  static_assert(!kFetchList || kSlots <= 128, "fetch-pending ring entries carry bit 7");
   __shared__ WavePool<kSlots> Sw[kWpg];
   WavePool<kSlots>& S = Sw[wv];
   // the empty-region mask (sparse media), one copy per workgroup
@@ -781,7 +657,8 @@ __global__ __launch_bounds__(64 * wpg_of(kMedMk, kWaves), kWaves) void k_wpool(M
     // density); filed at the next swap.  The track loop sets 2 for every
     // accepted point; filing turns an acceptance at t == max_t into 3 (the
     // reference scatters iff t < max_t), so the step carries no compare for it.
-    // 4 (sparse only): cell fetch pending, resolved to 0 or 2 before the next
+    // 4 (kLookDefer, sparse media only): the deferred cell fetch is pending; it
+    // is resolved to 0 or 2 at the end of the track iteration, before the next
     // swap check.
     int fst = 0;
     V3 o = mk3(0, 0, 0), d = mk3(0, 0, 0);
@@ -789,17 +666,6 @@ __global__ __launch_bounds__(64 * wpg_of(kMedMk, kWaves), kWaves) void k_wpool(M
     float t = 0.0f, max_t = 0.0f;
     const float4* pcp = nullptr;  // kLookDefer: the pending fetch's cell and test value
     float pxt = 0.0f;
-    if constexpr (CVR_WPOOL_WIDE != 0) {
-      // the drain (every queue exhausted) with at most 64 / K paths ready: K lanes per path
-      // (wide_track); the segments end there and the first swap below files them
-      if (n_ready != 0u && n_ready <= 64u / CVR_WPOOL_WIDE && (S.cur[2] & kCurExhausted)) {
-        wide_track<CVR_WPOOL_WIDE, kSlots, kEm>(S, EM, m, lane, ready_head, n_ready, slot, fst, o, d, rng, t, max_t,
-                                                c_steps, c_fetch);
-        ready_head += n_ready;
-        if (ready_head >= (uint32_t)kSlots) ready_head -= kSlots;
-        n_ready = 0;
-      }
-    }
     for (;;) {
       const unsigned long long trk = (__ballot(slot >= 0) & __ballot(fst == 0));
       const uint32_t n_trk = (uint32_t)__popcll(trk);
@@ -813,46 +679,24 @@ __global__ __launch_bounds__(64 * wpg_of(kMedMk, kWaves), kWaves) void k_wpool(M
         n_lc += (uint32_t)__popcll(mc);
         n_lb += (uint32_t)__popcll(mb);
         n_over += (uint32_t)__popcll(__ballot(fst == 1));
-        if constexpr (kFetchList) {  // fetch pending: back to the ready ring, marked
-          const unsigned long long mf = __ballot(fst == 4);
-          if (fst == 4) S.ready[(ready_head + n_ready + lane_rank(mf)) % kSlots] = (uint8_t)(slot | 0x80);
-          n_ready += (uint32_t)__popcll(mf);
-        }
         if (fst != 0) {
           slot = -1;
           fst = 0;
         }
         const unsigned long long idle = __ballot(slot < 0);
         const uint32_t k = min((uint32_t)__popcll(idle), n_ready), rank = lane_rank(idle);
-        bool pend = false;
         if (slot < 0 && rank < k) {
           const uint32_t r = ready_head + rank;
-          uint32_t s = S.ready[r >= (uint32_t)kSlots ? r - kSlots : r];
-          if constexpr (kFetchList) {
-            pend = (s & 0x80u) != 0u;
-            s &= 0x7Fu;
-          }
+          const uint32_t s = S.ready[r >= (uint32_t)kSlots ? r - kSlots : r];
           slot = (int)s;
           load_track(S, s, o, d, rng, t, max_t);
         }
         ready_head += k;
         if (ready_head >= (uint32_t)kSlots) ready_head -= kSlots;
         n_ready -= k;
-        if constexpr (kFetchList) {
-          if (pend) {  // the pending point's cell, fetched by every lane that pulled one
-            ++c_fetch;
-            WoodcockPoint P;
-            woodcock_coords(m, o, d, t, P);
-            const uint32_t x1 = (uint32_t)P.cx, y1 = (uint32_t)P.cy, z1 = (uint32_t)P.cz;
-            P.cp = dense_cell(m, x1, y1, z1);
-            const float xt = det_fmaf((float)(rng.v4 + rng.d), 2.3283064e-10f, 1.1641532e-10f);  // its test draw
-            const float rho = m.scale * woodcock_density(m, P);
-            fst = !(rho * m.inv_sigma < xt) ? 2 : 0;
-          }
-        }
       }
       const uint32_t n_act = (uint32_t)__popcll((__ballot(slot >= 0) & __ballot(fst == 0)));
-      const uint32_t n_fin = (uint32_t)__popcll(__ballot(fst != 0 && (!kFetchList || fst != 4)));
+      const uint32_t n_fin = (uint32_t)__popcll(__ballot(fst != 0));
       // EVENT next: a full wave of waiting events, slots never filled, or
       // nothing left to track.  Park: tracking lanes return (t, rng) to the
       // pool, finished lanes are filed.  (Once the queues are empty n_ln is a
@@ -860,10 +704,9 @@ __global__ __launch_bounds__(64 * wpg_of(kMedMk, kWaves), kWaves) void k_wpool(M
       if (n_lb + n_lc + n_ln + n_fin >= 64u || (n_act == 0u && n_ready == 0u)) {
         if (fst == 2 && !(t < max_t)) fst = 3;
         if (slot >= 0) store_track(S, (uint32_t)slot, t, rng);
-        const unsigned long long mr = (__ballot(slot >= 0) & __ballot(fst == 0 || (kFetchList && fst == 4)));
+        const unsigned long long mr = (__ballot(slot >= 0) & __ballot(fst == 0));
         const unsigned long long mc = __ballot(fst == 2), mb = __ballot(fst & 1);
-        if (slot >= 0 && (fst == 0 || (kFetchList && fst == 4)))
-          S.ready[(ready_head + n_ready + lane_rank(mr)) % kSlots] = (uint8_t)(slot | (fst == 4 ? 0x80 : 0));
+        if (slot >= 0 && fst == 0) S.ready[(ready_head + n_ready + lane_rank(mr)) % kSlots] = (uint8_t)slot;
         if (fst == 2) S.lc[n_lc + lane_rank(mc)] = (uint8_t)slot;
         if (fst & 1) S.lb[n_lb + lane_rank(mb)] = (uint8_t)slot;
         n_over += (uint32_t)__popcll(__ballot(fst == 1));
@@ -928,9 +771,6 @@ __global__ __launch_bounds__(64 * wpg_of(kMedMk, kWaves), kWaves) void k_wpool(M
                   end = k;
                   pcp = Pk[k].cp;
                   pxt = xtk[k];
-                } else if constexpr (kFetchList) {
-                  fst = 4;  // cell fetch pending: filed as marked track-ready work at the next swap
-                  end = k;
                 } else {
                   ++c_fetch;
                   const float rho = m.scale * woodcock_density(m, Pk[k]);
@@ -1356,518 +1196,6 @@ __global__ __launch_bounds__(64 * wpg_of(kMedMk, kWaves), kWaves) void k_wpool(M
   }
 }
 
-#if CVR_WPOOL_PAIR  // experiment build only: make variant-pair (round-6 verdict: 4.1x slower, not in libcvr.so)
-// ---- workgroup-shared event lists (CVR_OPT_WAVE_PAIR 1, round 5) ------------
-// The round-3/4 verdicts' "event list shared by the waves of a workgroup": two
-// waves per workgroup, one unified slot array (2 x kPairSlots paths), each wave
-// with its own track-ready ring, new-path stack and queue cursor (wave-uniform
-// scalars, as k_wpool), but ONE boundary list and ONE collision list for both:
-// 256-entry LDS rings that either wave files into (ds_add_rtn on the list's
-// tail reserves the entries) and either wave takes a batch from (a CAS on the
-// packed heads claims them; entries are 0xFF until written, so a taker that
-// meets a reserved but unwritten entry waits for it).  A batch thus sees both
-// waves' events, so kind-major batches (48 boundary / 24 collision events of
-// one kind) fill twice as fast.  A path that a wave takes from the shared lists
-// becomes that wave's: it goes to its ready ring, to the shared boundary list or
-// to its new-path stack.  Dense media with cells and brick bounds only (C2 /
-// C3), no in-launch output, no records.  The same walk, the same per-path
-// results: only which wave runs which event changes.
-template <int kWaves>
-struct PairSize {
-  // LDS bytes per two-wave workgroup: twice a one-wave workgroup's budget
-  static constexpr int kBudget = 2 * (163840 / (4 * kWaves) / kLdsGranule * kLdsGranule);
-  static constexpr int kParams = (int)((sizeof(LaunchParams) + 15) / 16 * 16);
-  static constexpr int kHeader = 2 * (4 * STAT_COUNT + 8 + 12 + 4) + 16;
-  // unified slots of the pair: 60 bytes of path state each + a ready-ring and a
-  // new-path-stack entry per wave (a wave may come to own every slot)
-  static constexpr int value = (kBudget - kParams - kHeader - 512) / 64;
-  static_assert(value <= 254, "slot ids are u8 with 0xFF as the empty ring entry");
-};
-template <int kN>
-struct PairPool {
-  float4 a[kN], b[kN];
-  uint4 c[kN];
-  uint2 e[kN];
-  uint32_t meta[kN];
-  uint8_t ready[2][kN];  // each wave's ring of track-ready slots
-  uint8_t ln[2][kN];     // each wave's stack of slots waiting for a new path
-  uint8_t lb[256];       // shared ring of boundary events (0xFF: not written yet / taken)
-  uint8_t lc[256];       // shared ring of real collisions
-  uint32_t tail[2];      // lb, lc tails (entries reserved so far)
-  uint32_t heads;        // lb head | lc head << 16 (mod 2^16; claimed by CAS)
-  uint32_t cnt[2][STAT_COUNT];
-  unsigned long long dead[2];
-  uint32_t cur[2][3];
-  uint32_t gone[2];      // the wave has left its loop (every queue was found empty)
-};
-// events of list k (0 boundary, 1 collision) reserved and not yet claimed
-__device__ __forceinline__ uint32_t pair_avail(uint32_t heads, uint32_t tail, uint32_t k) {
-  return (tail - (heads >> (16 * k))) & 0xFFFFu;
-}
-
-template <bool kScatterEps, int kWaves, int kMed>
-__global__ __launch_bounds__(128, kWaves) void k_wpair(MediumParams mk, LaunchParams Lk) {
-  static_assert(kMed == kMedDenseFull || kMed == kMedDenseFullUniform, "paired waves: dense media with cells and bounds");
-  constexpr int kN = PairSize<kWaves>::value;  // unified slots of the pair
-  MediumParams m = mk;
-  m.leaves = nullptr;
-  m.leaf_density = nullptr;
-  m.leaf_albedo = nullptr;
-  m.sbounds = nullptr;
-  __builtin_assume(m.cells != nullptr);
-  __builtin_assume(m.bounds != nullptr);
-  m.albedo_uniform = kMed == kMedDenseFullUniform ? 1u : 0u;
-  m.format = 0u;  // (launch_wpool keeps half-format media off the paired instances)
-  static_assert(sizeof(PairPool<kN>) + sizeof(LaunchParams) <= (size_t)PairSize<kWaves>::kBudget,
-                "paired pool exceeds the LDS budget of kWaves waves per SIMD");
-  __shared__ PairPool<kN> S;
-  __shared__ LaunchParams L;
-  const uint32_t lane = threadIdx.x & 63u;
-  const uint32_t wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  if (threadIdx.x == 0) {
-    L = Lk;
-    S.tail[0] = S.tail[1] = 0u;
-    S.heads = 0u;
-    S.gone[0] = S.gone[1] = 0u;
-  }
-  for (uint32_t i = threadIdx.x; i < 256u; i += 128u) {
-    S.lb[i] = 0xFFu;
-    S.lc[i] = 0xFFu;
-  }
-  uint32_t c_steps = 0, c_fetch = 0;
-  if (lane < (uint32_t)STAT_COUNT) S.cnt[wv][lane] = 0u;
-  if (lane == 0) {
-    S.dead[wv] = 0ull;
-    S.cur[wv][0] = S.cur[wv][1] = 0u;
-  }
-  __syncthreads();
-  uint32_t n_over = 0;
-  if (lane == 0) {
-    const uint32_t vw = 2u * blockIdx.x + wv;  // the wave's index as a one-wave launch would number it
-    S.cur[wv][2] = (((__builtin_amdgcn_s_getreg((3 << 11) | (0 << 6) | 20) & 7u) % (L.n_queues / L.sub)) * L.sub +
-                    (vw >> 4) % L.sub)
-                   << 8;
-  }
-  const uint32_t batch = L.batch;
-  uint32_t ready_head = 0, n_ready = 0;
-  // this wave's half of the slots starts free
-  uint32_t n_ln = kN / 2;
-  for (uint32_t i = lane; i < (uint32_t)kN / 2; i += 64u) S.ln[wv][i] = (uint8_t)(wv * (kN / 2) + i);
-  float4* __restrict__ gT = L.pool_T + (size_t)blockIdx.x * kN;  // the pair's event-only slot part
-
-  // File lanes' slots into the shared lists: mb boundary, mc collision lanes.
-  // The slot's LDS state is written before: the release fence orders it (and
-  // the wave's pool_T stores) before the list entries the other wave may read.
-  // full: the entries follow global pool_T stores of this batch (vmcnt wait); from the
-  // track loop only LDS state precedes them, and one wave's LDS operations are performed in
-  // order, so a compiler barrier suffices.
-  auto file_shared = [&](bool is_b, bool is_c, uint32_t s, bool full) {
-    const unsigned long long mb = __ballot(is_b), mc = __ballot(is_c);
-    const uint32_t kb = (uint32_t)__popcll(mb), kc = (uint32_t)__popcll(mc);
-    if ((kb | kc) == 0u) return;
-    uint32_t tb0 = 0, tc0 = 0;
-    if (lane == 0) {
-      if (kb) tb0 = __hip_atomic_fetch_add(&S.tail[0], kb, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-      if (kc) tc0 = __hip_atomic_fetch_add(&S.tail[1], kc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    }
-    tb0 = __builtin_amdgcn_readfirstlane(tb0);
-    tc0 = __builtin_amdgcn_readfirstlane(tc0);
-    if (full) __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    else __atomic_signal_fence(__ATOMIC_SEQ_CST);
-    // An entry is written only once the taker of the same ring position one lap earlier
-    // has read it (it writes 0xFF back): a taker that claimed its entries but was kept from
-    // reading them (its wave starved at a lower priority while the rings went round) would
-    // otherwise read a later lap's entry and leave the later taker waiting for ever.
-    if (is_b || is_c) {
-      uint8_t* e = is_b ? &S.lb[(tb0 + lane_rank(mb)) & 255u] : &S.lc[(tc0 + lane_rank(mc)) & 255u];
-      uint32_t spins = 0;
-      while (__hip_atomic_load(e, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) != 0xFFu && ++spins < (1u << 16)) {
-      }
-      if (spins >= (1u << 16)) atomicAdd(&S.cnt[wv][STAT_TRUNCATED], 1u);  // (bug report, as below)
-      __hip_atomic_store(e, (uint8_t)s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    }
-  };
-
-  // Watchdog (the variant is an experiment): a wave that runs more outer iterations than
-  // any launch needs (C2: a wave runs ~10^3-10^4 batches) leaves its loop and reports
-  // it in the truncated counter (+2^20 per wave), so a scheduling bug ends the launch
-  // with wrong counters instead of hanging the GPU.
-  uint32_t watchdog = 0;
-  uint32_t n_mine = 0;  // events this wave filed since its last batch (its batch trigger)
-  for (;;) {
-    if (++watchdog > (1u << 22)) {
-      if (lane == 0) {
-        atomicAdd(&S.cnt[wv][STAT_TRUNCATED], 1u << 20);
-        __hip_atomic_store(&S.gone[wv], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-      }
-      break;
-    }
-    __builtin_amdgcn_s_setprio(kPrioTrack);
-    int slot = -1;
-    int fst = 0;
-    V3 o = mk3(0, 0, 0), d = mk3(0, 0, 0);
-    Rng rng{0, 0, 0, 0, 0, 0};
-    float t = 0.0f, max_t = 0.0f;
-    uint32_t tracks = 0;
-    for (;;) {
-      if (++tracks > (1u << 24)) {  // (watchdog, as above: no segment takes this long)
-        if (lane == 0) atomicAdd(&S.cnt[wv][STAT_TRUNCATED], 1u << 20);
-        watchdog = 1u << 22;
-        break;
-      }
-      const unsigned long long trk = (__ballot(slot >= 0) & __ballot(fst == 0));
-      const uint32_t n_trk = (uint32_t)__popcll(trk);
-      if (64u - n_trk >= batch || n_trk == 0u) {
-        if (fst == 2 && !(t < max_t)) fst = 3;
-        if (fst != 0) store_track(S, (uint32_t)slot, t, rng);
-        n_over += (uint32_t)__popcll(__ballot(fst == 1));
-        n_mine += (uint32_t)__popcll(__ballot(fst != 0));
-        file_shared((fst & 1) != 0, fst == 2, (uint32_t)slot, false);
-        if (fst != 0) {
-          slot = -1;
-          fst = 0;
-        }
-        const unsigned long long idle = __ballot(slot < 0);
-        const uint32_t k = min((uint32_t)__popcll(idle), n_ready), rank = lane_rank(idle);
-        if (slot < 0 && rank < k) {
-          const uint32_t r = ready_head + rank;
-          const uint32_t s = S.ready[wv][r >= (uint32_t)kN ? r - kN : r];
-          slot = (int)s;
-          load_track(S, s, o, d, rng, t, max_t);
-        }
-        ready_head += k;
-        if (ready_head >= (uint32_t)kN) ready_head -= kN;
-        n_ready -= k;
-      }
-      const uint32_t n_act = (uint32_t)__popcll((__ballot(slot >= 0) & __ballot(fst == 0)));
-      const uint32_t n_fin = (uint32_t)__popcll(__ballot(fst != 0));
-      // the trigger counts this wave's own filings since its last batch (registers only, as
-      // k_wpool); the batch then takes what both waves have filed
-      if (n_mine + n_ln + n_fin >= 64u || (n_act == 0u && n_ready == 0u)) {
-        if (fst == 2 && !(t < max_t)) fst = 3;
-        if (slot >= 0) store_track(S, (uint32_t)slot, t, rng);
-        const unsigned long long mr = (__ballot(slot >= 0) & __ballot(fst == 0));
-        if (slot >= 0 && fst == 0) S.ready[wv][(ready_head + n_ready + lane_rank(mr)) % kN] = (uint8_t)slot;
-        n_over += (uint32_t)__popcll(__ballot(fst == 1));
-        n_ready += (uint32_t)__popcll(mr);
-        file_shared((fst & 1) != 0, fst == 2, (uint32_t)slot, false);
-        break;
-      }
-#pragma unroll
-      for (int u = 0; u < CVR_WPOOL_UNROLL / kLook; ++u) {
-        if (slot >= 0 && fst == 0) {
-          float tk[kLook], xtk[kLook];
-          uint32_t sva[kLook], svb[kLook];
-          WoodcockPoint Pk[kLook];
-          float tt = t;
-#pragma unroll
-          for (int k = 0; k < kLook; ++k) {
-            const float xi = rng_float(rng);
-            xtk[k] = rng_float(rng);
-            sva[k] = rng.v0;
-            svb[k] = rng.v1;
-            tt = woodcock_advance(m, xi, tt);
-            tk[k] = tt;
-          }
-#pragma unroll
-          for (int k = 0; k < kLook; ++k) Pk[k] = woodcock_point(m, o, d, tk[k]);
-          int end = kLook;
-#pragma unroll
-          for (int k = 0; k < kLook; ++k) {
-            if (end == kLook) {
-              if (!(tk[k] <= max_t)) {
-                fst = 1;
-                end = k;
-              } else if (!(Pk[k].qb < xtk[k])) {
-                ++c_fetch;
-                const float rho = m.scale * woodcock_density(m, Pk[k]);
-                if (!(rho * m.inv_sigma < xtk[k])) {
-                  fst = 2;
-                  end = k;
-                }
-              }
-            }
-          }
-          c_steps += end == kLook ? kLook : end + 1;
-          t = tk[kLook - 1];
-#pragma unroll
-          for (int k = 0; k < kLook - 1; ++k)
-            if (end == k) t = tk[k];
-          if (end < kLook - 1) {
-            uint32_t w[2 * kLook + 5];
-#pragma unroll
-            for (int k = 0; k < kLook - 1; ++k) {
-              w[2 * k + 2] = sva[k];
-              w[2 * k + 3] = svb[k];
-            }
-            w[2 * kLook] = rng.v0;
-            w[2 * kLook + 1] = rng.v1;
-            w[2 * kLook + 2] = rng.v2;
-            w[2 * kLook + 3] = rng.v3;
-            w[2 * kLook + 4] = rng.v4;
-#pragma unroll
-            for (int j = 1; j < kLook; ++j) {
-              if (end + 1 == j) {
-                rng.v0 = w[2 * j];
-                rng.v1 = w[2 * j + 1];
-                rng.v2 = w[2 * j + 2];
-                rng.v3 = w[2 * j + 3];
-                rng.v4 = w[2 * j + 4];
-              }
-            }
-            rng.d -= (uint32_t)(2 * (kLook - 1 - end)) * 362437u;
-          }
-        }
-      }
-    }
-    // claim the batch's events from the shared lists (kind-major thresholds as k_wpool), at
-    // the top priority until they are read (see file_shared)
-    __builtin_amdgcn_s_setprio(3);
-    uint32_t tb = 0, tc = 0, hb = 0, hc = 0;
-    {
-      uint32_t h = __builtin_amdgcn_readfirstlane(S.heads);
-      for (;;) {
-        const uint32_t ab = pair_avail(h, __builtin_amdgcn_readfirstlane(S.tail[0]), 0);
-        const uint32_t ac = pair_avail(h, __builtin_amdgcn_readfirstlane(S.tail[1]), 1);
-        if (ab >= (uint32_t)CVR_WPOOL_KIND_MIN) {
-          tb = min(ab, 64u);
-          tc = 0;
-        } else if (ac >= (uint32_t)CVR_WPOOL_KIND_MIN_C) {
-          tb = 0;
-          tc = min(ac, 64u);
-        } else {
-          tb = min(ab, 64u);
-          tc = min(ac, 64u - tb);
-        }
-        if ((tb | tc) == 0u) break;
-        const uint32_t want = ((h + tb) & 0xFFFFu) | (((h >> 16) + tc) << 16);
-        uint32_t got = 0;
-        if (lane == 0) {
-          got = h;
-          __hip_atomic_compare_exchange_strong(&S.heads, &got, want, __ATOMIC_RELAXED, __ATOMIC_RELAXED,
-                                               __HIP_MEMORY_SCOPE_WORKGROUP);
-        }
-        got = __builtin_amdgcn_readfirstlane(got);
-        if (got == h) break;
-        h = got;  // the other wave claimed first: retry with its heads
-      }
-      hb = h & 0xFFFFu;
-      hc = h >> 16;
-    }
-    const bool any_event = (tb | tc) != 0u;
-    if (!any_event && n_ready == 0u) {
-      const uint32_t hs = __builtin_amdgcn_readfirstlane(S.heads);
-      const bool shared_empty = pair_avail(hs, __builtin_amdgcn_readfirstlane(S.tail[0]), 0) +
-                                    pair_avail(hs, __builtin_amdgcn_readfirstlane(S.tail[1]), 1) ==
-                                0u;
-      // no path left: nothing to track, nothing shared, no new path to start
-      if (shared_empty && (S.cur[wv][2] & kCurExhausted)) {
-        if (lane == 0) __hip_atomic_store(&S.gone[wv], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        break;
-      }
-      // holding no slot at all while the other wave has left (with every slot free): this
-      // wave takes all of them and goes on with its queue cursor
-      if (shared_empty && n_ln == 0u &&
-          __hip_atomic_load(&S.gone[wv ^ 1u], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) != 0u) {
-        for (uint32_t i = lane; i < (uint32_t)kN; i += 64u) S.ln[wv][i] = (uint8_t)i;
-        n_ln = kN;
-        continue;
-      }
-      // the other wave holds every slot (this wave has none free and none ready): wait for
-      // it to file events this wave can take, without taking its issue slots meanwhile
-      if (n_ln == 0u) {
-        __builtin_amdgcn_s_sleep(4);
-        continue;
-      }
-    }
-    MediumParams me = m;
-    me.g = opaque_s(m.g);
-    me.ax = opaque_s(m.ax);
-    me.ay = opaque_s(m.ay);
-    me.eta = opaque_s(m.eta);
-    me.inv_eta = opaque_s(m.inv_eta);
-    me.bmin = mk3(opaque_s(m.bmin.x), opaque_s(m.bmin.y), opaque_s(m.bmin.z));
-    me.bmax = mk3(opaque_s(m.bmax.x), opaque_s(m.bmax.y), opaque_s(m.bmax.z));
-    me.albedo_bg = mk3(opaque_s(m.albedo_bg.x), opaque_s(m.albedo_bg.y), opaque_s(m.albedo_bg.z));
-    {
-      uint32_t tn;
-      if (tb >= (uint32_t)CVR_WPOOL_KIND_MIN) tn = min(n_ln, 64u - tb);
-      else if (tc >= (uint32_t)CVR_WPOOL_KIND_MIN_C) tn = n_ln < 64u ? 0u : min(n_ln, 64u - tc);
-      else tn = min(n_ln, 64u - tb - tc);
-      uint32_t kind = K_NONE, s = 0;
-      if (lane < tb + tc) {
-        // a claimed entry may be reserved but not yet written by the other wave: wait for it
-        uint8_t* q = lane < tb ? &S.lb[(hb + lane) & 255u] : &S.lc[(hc + lane - tb) & 255u];
-        uint32_t v, spins = 0;
-        do {
-          v = __hip_atomic_load(q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        } while (v == 0xFFu && ++spins < (1u << 16));
-        // (a bounded wait: an entry that never appears would be a bug; the item is then
-        // dropped and counted as truncated, so the launch ends and the counters differ)
-        __hip_atomic_store(q, (uint8_t)0xFFu, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        s = v;
-        kind = v == 0xFFu ? K_NONE : lane < tb ? K_BOUNDARY : K_COLLIDE;
-        if (v == 0xFFu) atomicAdd(&S.cnt[wv][STAT_TRUNCATED], 1u);
-      } else if (lane < tb + tc + tn) {
-        kind = K_NEW;
-        s = S.ln[wv][n_ln - 1u - (lane - tb - tc)];
-      }
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");  // the filer's slot state and pool_T stores
-      __builtin_amdgcn_s_setprio(kPrioEvent);
-      n_ln -= tn;
-      PathState ps{};
-      Isect is{};
-      uint32_t nseg = 0;
-      float t_hit = 0.0f;
-      bool to_ready = false, to_lb = false, to_ln = false;
-      bool truncated = false, escaped = false, seg_first = false, seg_next = false;
-      const unsigned long long want = __ballot(kind == K_NEW);
-      if (want != 0ull) {
-        const uint32_t rank = lane_rank(want);
-        bool got = false;
-        uint32_t given = 0;
-        uint32_t cnext = __builtin_amdgcn_readfirstlane(S.cur[wv][0]), cend = __builtin_amdgcn_readfirstlane(S.cur[wv][1]);
-        uint32_t cqh = __builtin_amdgcn_readfirstlane(S.cur[wv][2]);
-        while (given < (uint32_t)__popcll(want) && !(cqh & kCurExhausted)) {
-          if (cnext == cend) {
-            uint32_t b = 0xFFFFFFFFu, qsel = 0;
-            if (lane == 0) {
-              unsigned long long dead = S.dead[wv];
-              for (uint32_t k = 0; k < L.n_queues; ++k) {
-                const uint32_t q = ((cqh >> 8) + k) % L.n_queues;
-                if ((dead >> q) & 1ull) continue;
-                const uint32_t g = atomicAdd(L.queue + 16 * q, L.chunk);
-                if (g < queue_units(L, q)) {
-                  b = g;
-                  qsel = q;
-                  break;
-                }
-                dead |= 1ull << q;
-              }
-              S.dead[wv] = dead;
-            }
-            b = __shfl(b, 0);
-            qsel = __shfl(qsel, 0);
-            if (b == 0xFFFFFFFFu) {
-              cqh |= kCurExhausted;
-              break;
-            }
-            cqh = qsel | qsel << 8;
-            cnext = b;
-            cend = min(b + L.chunk, queue_units(L, qsel));
-          }
-          const uint32_t take = min((uint32_t)__popcll(want) - given, cend - cnext);
-          if (kind == K_NEW && rank >= given && rank < given + take) {
-            const uint32_t pid = unit_to_path(L, cqh & 0xFFu, cnext + (rank - given));
-            path_begin(L, pid, ps);
-            is.normal = mk3(0, 0, 0);
-            nseg = 0;
-            got = true;
-          }
-          cnext += take;
-          given += take;
-        }
-        if (lane == 0) {
-          S.cur[wv][0] = cnext;
-          S.cur[wv][1] = cend;
-          S.cur[wv][2] = cqh;
-        }
-        const uint32_t n_got = (uint32_t)__popcll(__ballot(got));
-        if (lane == 0) S.cnt[wv][STAT_PATHS] += n_got;
-        if (got) {
-          if (L.max_segments && nseg >= L.max_segments) {
-            truncated = true;
-            to_ln = true;
-          } else {
-            ++nseg;
-            seg_first = true;
-            if (!aabb_intersect(me, ps.o, ps.d, is)) {
-              escaped = true;
-              to_ln = true;
-            } else if (is.inside) {
-              store_full(S, gT, s, ps, is, nseg, ps.image_id);
-              to_ready = true;
-            } else {
-              kind = K_BOUNDARY;
-            }
-          }
-        }
-      }
-      const bool filed = lane < tb + tc && kind != K_NONE;  // (K_NONE: a dropped entry, see above)
-      if (filed) load_full(S, gT, s, ps, is, nseg, t_hit);
-      if (filed && lane < tb && !(t_hit <= is.dist)) rng_undo(ps.rng);
-      bool alive = false;
-      if (kind == K_BOUNDARY) {
-        boundary_event(me, ps, is);
-        alive = roulette(ps);
-      }
-      if (kind == K_COLLIDE) {
-        scatter_event<kScatterEps>(me, ps, t_hit);
-        alive = roulette(ps);
-      }
-      const uint32_t n_alb = (uint32_t)__popcll(__ballot(kind == K_COLLIDE));
-      if ((kind == K_BOUNDARY || kind == K_COLLIDE) && !alive) to_ln = true;
-      if (alive) {
-        if (L.max_segments && nseg >= L.max_segments) {
-          truncated = true;
-          to_ln = true;
-        } else {
-          ++nseg;
-          seg_next = true;
-          if (!aabb_intersect(me, ps.o, ps.d, is)) {
-            escaped = true;
-            to_ln = true;
-          } else {
-            store_full(S, gT, s, ps, is, nseg, ps.image_id);
-            to_ready = is.inside;
-            to_lb = !is.inside;
-          }
-        }
-      }
-      splat_wave<true>(S, L, ps, escaped, s, lane);
-      {
-        const uint32_t n_seg = (uint32_t)(__popcll(__ballot(seg_first)) + __popcll(__ballot(seg_next)));
-        const uint32_t n_esc = (uint32_t)__popcll(__ballot(escaped)), n_tr = (uint32_t)__popcll(__ballot(truncated));
-        if (lane == 0) {
-          S.cnt[wv][STAT_SEGMENTS] += n_seg;
-          S.cnt[wv][STAT_ALBEDO] += n_alb;
-          S.cnt[wv][STAT_ESCAPED] += n_esc;
-          S.cnt[wv][STAT_TRUNCATED] += n_tr;
-        }
-      }
-      const unsigned long long mr = __ballot(to_ready), mn = __ballot(to_ln);
-      if (to_ready) S.ready[wv][(ready_head + n_ready + lane_rank(mr)) % kN] = (uint8_t)s;
-      if (to_ln) S.ln[wv][n_ln + lane_rank(mn)] = (uint8_t)s;
-      n_ready += (uint32_t)__popcll(mr);
-      n_ln += (uint32_t)__popcll(mn);
-      n_mine = (uint32_t)__popcll(__ballot(to_lb));
-      file_shared(to_lb, false, s, true);
-    }
-    if (S.cur[wv][2] & kCurExhausted) {
-      const uint32_t hs = __builtin_amdgcn_readfirstlane(S.heads);
-      const uint32_t n_live = n_ready + pair_avail(hs, __builtin_amdgcn_readfirstlane(S.tail[0]), 0) +
-                              pair_avail(hs, __builtin_amdgcn_readfirstlane(S.tail[1]), 1);
-      const uint32_t dr = fresh(L).wflags & kDrainMask;
-      n_ln = dr ? 64u - min(64u, (n_live * dr + dr) / (dr + 1u)) : 0u;
-    }
-  }
-  {
-    unsigned long long steps = c_steps, fetch = c_fetch;
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-      steps += __shfl_xor(steps, off);
-      fetch += __shfl_xor(fetch, off);
-    }
-    const unsigned long long w[STAT_COUNT] = {S.cnt[wv][STAT_PATHS], S.cnt[wv][STAT_SEGMENTS], steps, steps - n_over,
-                                              S.cnt[wv][STAT_ALBEDO], S.cnt[wv][STAT_ESCAPED], S.cnt[wv][STAT_TRUNCATED],
-                                              fetch};
-    if (lane < (uint32_t)STAT_COUNT && w[lane])
-      __hip_atomic_fetch_add(gmem(L.stats + lane), w[lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
-}
-
-#endif  // CVR_WPOOL_PAIR
-
 // Instances: 5 waves per SIMD (the default budget) for every medium layout, with and
 // without the in-launch output; the other budgets for the generic layouts.
 template <bool E>
@@ -1927,57 +1255,41 @@ static const void* wpool_mk_fn(bool sparse, bool full, bool uniform, bool half) 
 }
 
 hipError_t launch_wpool(const MediumParams& m, const LaunchParams& L, bool scatter_eps, int waves, uint32_t grid,
-                        hipStream_t s, bool pair, bool naive_mk, bool count_words, bool moments) {
+                        hipStream_t s, bool naive_mk, bool count_words, bool moments) {
   if (L.path_count == 0) return hipSuccess;
-  if (moments) {
-    // the moments instances (CVR_OPT_MOMENTS): 5 waves per SIMD, the generic dense layout (cells,
-    // bounds, uniform albedo and the half format read at run time) and the fp32 sparse one; no
-    // records, in-launch output, naiveMK walk, pairs or word counts (cvr_launch_render refuses them first)
-    const bool sp = m.leaves != nullptr;
-    if (waves != 5 || pair || naive_mk || count_words || L.rec || L.frame_done || (sp && m.format != 0u))
-      return hipErrorInvalidValue;
-    if (grid % wpool_wpg(waves, sp)) return hipErrorInvalidValue;
-#define CVR_WPM(E, M) reinterpret_cast<const void*>(&k_wpool<E, 5, (M) | kMedMoments, false, false>)
-    const void* fm = scatter_eps ? (sp ? CVR_WPM(true, kMedSparse) : CVR_WPM(true, kMedDense))
-                                 : (sp ? CVR_WPM(false, kMedSparse) : CVR_WPM(false, kMedDense));
-#undef CVR_WPM
+  const bool sparse = m.leaves != nullptr;
+  // one launch of instance fn over a grid of whole workgroups (pool_T and the record ids
+  // are sized for grid waves)
+  auto launch = [&](const void* fn) {
+    const uint32_t wpg = wpool_wpg(waves, sparse);
+    if (!fn || grid % wpg) return hipErrorInvalidValue;
     MediumParams mm = m;
     LaunchParams ll = L;
     void* args[] = {&mm, &ll};
-    return hipLaunchKernel(fm, dim3(grid / wpool_wpg(waves, sp)), dim3(64 * wpool_wpg(waves, sp)), args, 0, s);
+    return hipLaunchKernel(fn, dim3(grid / wpg), dim3(64 * wpg), args, 0, s);
+  };
+  if (moments) {
+    // the moments instances (CVR_OPT_MOMENTS): 5 waves per SIMD, the generic dense layout (cells,
+    // bounds, uniform albedo and the half format read at run time) and the fp32 sparse one; no
+    // records, in-launch output, naiveMK walk or word counts (cvr_launch_render refuses them first)
+    if (waves != 5 || naive_mk || count_words || L.rec || L.frame_done || (sparse && m.format != 0u))
+      return hipErrorInvalidValue;
+#define CVR_WPM(E, M) reinterpret_cast<const void*>(&k_wpool<E, 5, (M) | kMedMoments, false, false>)
+    return launch(scatter_eps ? (sparse ? CVR_WPM(true, kMedSparse) : CVR_WPM(true, kMedDense))
+                              : (sparse ? CVR_WPM(false, kMedSparse) : CVR_WPM(false, kMedDense)));
+#undef CVR_WPM
   }
-  const bool sparse = m.leaves != nullptr;
   const bool flush = L.frame_done != nullptr;
   const bool full = !sparse && m.cells != nullptr && m.bounds != nullptr;
   const bool uniform = m.albedo_uniform != 0u;
   const bool half = m.format != 0u;
-  // the half format has no paired, counting or other-budget instances (cvr_launch_render refuses them first)
-  if (half && (pair || count_words || waves != 5)) return hipErrorInvalidValue;
+  // the half format has no counting or other-budget instances (cvr_launch_render refuses them first)
+  if (half && (count_words || waves != 5)) return hipErrorInvalidValue;
   if (L.rec && flush) return hipErrorInvalidValue;
   if (naive_mk) {
     if (waves != 5 || flush || L.rec) return hipErrorInvalidValue;
-    if (grid % wpool_wpg(waves, sparse)) return hipErrorInvalidValue;
-    MediumParams mm = m;
-    LaunchParams ll = L;
-    void* args[] = {&mm, &ll};
-    return hipLaunchKernel(wpool_mk_fn(sparse, full, uniform, half), dim3(grid / wpool_wpg(waves, sparse)),
-                           dim3(64 * wpool_wpg(waves, sparse)), args, 0, s);
+    return launch(wpool_mk_fn(sparse, full, uniform, half));
   }
-#if CVR_WPOOL_PAIR
-  if (pair && waves == 5 && full && !flush && !L.rec && grid >= 2) {
-    // paired waves (workgroup-shared event lists): two waves per workgroup
-#define CVR_WPAIR(E, M) reinterpret_cast<const void*>(&k_wpair<E, 5, M>)
-    const void* fn = scatter_eps ? (uniform ? CVR_WPAIR(true, kMedDenseFullUniform) : CVR_WPAIR(true, kMedDenseFull))
-                                 : (uniform ? CVR_WPAIR(false, kMedDenseFullUniform) : CVR_WPAIR(false, kMedDenseFull));
-#undef CVR_WPAIR
-    MediumParams mm = m;
-    LaunchParams ll = L;
-    void* args[] = {&mm, &ll};
-    return hipLaunchKernel(fn, dim3(grid / 2), dim3(128), args, 0, s);
-  }
-#else
-  if (pair) return hipErrorInvalidValue;  // (cvr_set_option refuses it first)
-#endif
   const void* fn = L.rec ? (scatter_eps ? wpool_record_fn<true>(waves, sparse, half)
                                         : wpool_record_fn<false>(waves, sparse, half))
                          : (scatter_eps ? wpool_fn<true>(waves, sparse, full, flush, uniform, half)
@@ -1987,16 +1299,8 @@ hipError_t launch_wpool(const MediumParams& m, const LaunchParams& L, bool scatt
   if (count_words && sparse && waves == 5 && !L.rec && !flush)
     fn = scatter_eps ? reinterpret_cast<const void*>(&k_wpool<true, 5, kMedSparse | kMedCount, false, false>)
                      : reinterpret_cast<const void*>(&k_wpool<false, 5, kMedSparse | kMedCount, false, false>);
-  if (!fn) return hipErrorInvalidValue;  // no record / in-launch output instance for this register budget
-  // (a grid of whole workgroups: pool_T and the record ids are sized for grid waves)
-  if (grid % wpool_wpg(waves, sparse)) return hipErrorInvalidValue;
-  MediumParams mm = m;
-  LaunchParams ll = L;
-  void* args[] = {&mm, &ll};
-  return hipLaunchKernel(fn, dim3(grid / wpool_wpg(waves, sparse)), dim3(64 * wpool_wpg(waves, sparse)), args, 0, s);
+  return launch(fn);  // (null: no record / in-launch output instance for this register budget)
 }
-
-bool wpool_pair_built() { return CVR_WPOOL_PAIR != 0; }
 
 #if CVR_WPOOL_TAILSTAMP
 // (diagnostic build) the per-wave stamps of the last launch, 8 u64 per wave

@@ -166,13 +166,7 @@ typedef enum {
                                  order 0 and per-lane atomics).  -1 (default) = 0: order 1 costs C2 / C3 2.7% / 3.6%
                                  and C5 2.2% (with the empty-region mask).
                                  Scheduling and summation order only. */
-  CVR_OPT_WAVE_PAIR = 26,      /* wave-pool scheduler, dense media with cells and bounds: 1 runs two waves
-                                 per workgroup whose boundary and collision event lists are shared
-                                 (k_wpair: either wave files into them and runs a batch from them; round
-                                 5, 4.1x slower: profiles/round5/README.md); 0 (default) one wave per
-                                 workgroup, private lists.  Only `make variant-pair` builds k_wpair: the
-                                 in-tree libcvr.so refuses 1 with CVR_ERR_UNSUPPORTED.  Scheduling only:
-                                 results are unchanged. */
+  CVR_OPT_WAVE_PAIR = 26,      /* retired experiment; 0 accepted, 1 refused */
   CVR_OPT_EMPTY_MASK = 28,     /* wave-pool scheduler, sparse media: 1 (default) each workgroup (four
                                  wave-private pools) stages the medium's empty-region mask (one bit per
                                  super-brick of whole leaves, 256 bytes) in LDS once for its waves, which
@@ -209,8 +203,8 @@ typedef enum {
                                  Runs on the wave-pool scheduler at 5 waves per SIMD (every kernel id,
                                  cvr_render_frame's in-launch output, cvr_trace_launch, CVR_OPT_CELLS 0 too) and
                                  in cvr_trace_paths; with another CVR_OPT_SCHEDULER or CVR_OPT_WAVES value,
-                                 CVR_OPT_RNG_BINDING 1, CVR_OPT_COUNT_WORDS 1, CVR_OPT_MK_COMPACTION 1 or
-                                 CVR_OPT_WAVE_PAIR 1 a launch on a format-1 medium returns CVR_ERR_UNSUPPORTED. */
+                                 CVR_OPT_RNG_BINDING 1, CVR_OPT_COUNT_WORDS 1 or CVR_OPT_MK_COMPACTION 1 a
+                                 launch on a format-1 medium returns CVR_ERR_UNSUPPORTED. */
   CVR_OPT_MOMENTS = 31,        /* wave-pool scheduler: 0 (default) off; 1 every launch also accumulates per-pixel
                                  second moments.  The context's own framebuffer allocation then holds a
                                  second float4 per pixel directly behind the tile (tile_w * tile_h float4
@@ -226,9 +220,9 @@ typedef enum {
                                  caller's output buffer (cvr_set_output) with moments on is
                                  CVR_ERR_UNSUPPORTED, and so is a launch with another CVR_OPT_SCHEDULER or
                                  CVR_OPT_WAVES value, CVR_OPT_RNG_BINDING 1, CVR_OPT_COUNT_WORDS 1,
-                                 CVR_OPT_WAVE_PAIR 1, CVR_OPT_MK_COMPACTION 1, kernel id naiveMK, a sparse
-                                 half medium, cvr_trace_launch, cvr_render_frame, cvr_render_image,
-                                 cvr_render_tiles or cvr_render_share_to_host. */
+                                 CVR_OPT_MK_COMPACTION 1, kernel id naiveMK, a sparse half medium,
+                                 cvr_trace_launch, cvr_render_frame, cvr_render_image, cvr_render_tiles or
+                                 cvr_render_share_to_host. */
   /* 21: unused (a drain-time path migration between waves, measured slower: DESIGN.md §6) */
   CVR_OPT_DRAIN = 22,          /* wave-pool scheduler, once the queues are empty: an event batch runs as
                                  soon as the waiting segments x d >= the tracking ones (d = 0: only when

@@ -10,6 +10,8 @@ import os
 import numpy as np
 import pytest
 
+from parity_util import COUNTERS, assert_pixels_close
+
 pytestmark = pytest.mark.gpu
 
 NTHREADS = min(16, os.cpu_count() or 1)
@@ -127,3 +129,32 @@ def test_launches_without_work(cvr):
     ctx.launch_render()
     assert ctx.stats().paths == 0
     assert not ctx.copy_output(16, 16)[..., :3].any()
+
+
+def test_retired_wave_pair_option(cvr):
+    """CVR_OPT_WAVE_PAIR keeps its number after the experiment's removal: 0 is accepted and
+    does nothing, 1 is refused with CVR_ERR_UNSUPPORTED (-5), and a context that saw both
+    renders what a context that never touched the option renders."""
+    s = cvr.Scene.synthetic("bucky")
+    W = H = 64
+    iters = 1
+    out = []
+    for touch in (True, False):
+        ctx = cvr.Context(0, "regenerationSK")
+        if touch:
+            ctx.set_option(cvr.OPT_WAVE_PAIR, 0)
+            with pytest.raises(cvr.CvrError) as e:
+                ctx.set_option(cvr.OPT_WAVE_PAIR, 1)
+            assert e.value.code == -5
+        ctx.set_medium(s.medium)
+        iv, r2v = cvr.default_camera(W, H)
+        ctx.set_camera(iv, r2v, (W, H))
+        ctx.init()
+        out.append(ctx.render_image(W, H, (1, 1), iters))
+        ctx.close()
+    (i1, s1), (i0, s0) = out
+    for k in COUNTERS + ("fetches",):
+        assert getattr(s1, k) == getattr(s0, k), k
+    assert s0.paths == W * H * iters
+    assert np.array_equal(i1[..., 3], i0[..., 3])
+    assert_pixels_close(i1[..., :3], i0[..., :3], iters, "after the refused option vs an untouched context")

@@ -3,7 +3,7 @@
 # (counter set, scene, variant) over tools/tune.py (2 launches each).
 #   tools/pmc_tune.sh "CTR1 CTR2" SCENES NAME=TUNE_VARIANT [NAME=TUNE_VARIANT ...]
 #   e.g. tools/pmc_tune.sh "SQ_INSTS_VALU SQ_THREAD_CYCLES_VALU GRBM_GUI_ACTIVE" manix,hetvol \
-#          one=regenerationSK: pair=regenerationSK:pair=1
+#          one=regenerationSK: ev48=regenerationSK:ev=48
 # Output: gpurun_out/pmcab/<name>_<scene>_<ctrs>/ ; summary: tools/pmc_ab_summary.py
 set -u
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"

@@ -98,8 +98,6 @@ def main():
             c.set_option(cvr.OPT_MORTON, d["morton"])
         if "pool" in d:
             c.set_option(cvr.OPT_POOL, d["pool"])
-        if "pair" in d:
-            c.set_option(cvr.OPT_WAVE_PAIR, d["pair"])
         if "sorder" in d:
             c.set_option(cvr.OPT_SAMPLE_ORDER, d["sorder"])
         if "em" in d:
