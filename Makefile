@@ -9,7 +9,7 @@ ARCH ?= gfx950
 PKG := cudavolumerenderer_amd
 CSRC := $(PKG)/csrc
 HIPFLAGS := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -ffp-contract=off \
-            -fhip-fp32-correctly-rounded-divide-sqrt -Iinclude -I$(CSRC) -Wall -Wno-unused-function
+            -fhip-fp32-correctly-rounded-divide-sqrt -Iinclude -I$(CSRC) -Wall
 OBJDIR := build/obj
 SRCS_HIP := $(CSRC)/cvr_kernels.hip $(CSRC)/cvr_persistent.hip $(CSRC)/cvr_pool.hip $(CSRC)/cvr_wpool.hip $(CSRC)/cvr_wavefront.hip \
             $(CSRC)/cvr_denoise.hip
@@ -17,7 +17,7 @@ SRCS_CPP := $(CSRC)/cvr_api.cpp $(CSRC)/cvr_scene.cpp $(CSRC)/cvr_vdb.cpp $(CSRC
 OBJS := $(patsubst $(CSRC)/%.hip,$(OBJDIR)/%.o,$(SRCS_HIP)) $(patsubst $(CSRC)/%.cpp,$(OBJDIR)/%.o,$(SRCS_CPP))
 HDRS := include/cvr.h include/cvr_detmath.h $(wildcard $(CSRC)/*.h)
 
-all: $(PKG)/libcvr.so $(PKG)/cvr build/launcher_order oracle
+all: $(PKG)/libcvr.so $(PKG)/cvr build/launcher_order build/wpool_select oracle
 
 $(OBJDIR)/%.o: $(CSRC)/%.hip $(HDRS)
 	@mkdir -p $(OBJDIR)
@@ -39,6 +39,12 @@ build/launcher_order: tests/cpp/launcher_order.cpp include/cvr_launcher.hpp incl
 	@mkdir -p build
 	g++ -O2 -std=c++17 -Wall -D__HIP_PLATFORM_AMD__ -Iinclude -I/opt/rocm/include -o $@ $< \
 	    -L$(PKG) -lcvr -L/opt/rocm/lib -lamdhip64 -Wl,-rpath,'$$ORIGIN/../$(PKG)' -Wl,-rpath,/opt/rocm/lib
+
+# Host-only C++ test: the wave pool's instance selection over its whole request space
+# (tests/test_wpool_select.py); no HIP.
+build/wpool_select: tests/cpp/wpool_select.cpp $(CSRC)/cvr_wpool_select.h
+	@mkdir -p build
+	g++ -O2 -std=c++17 -Wall -Wextra -I$(CSRC) -o $@ $<
 
 oracle:
 	$(MAKE) -C oracle

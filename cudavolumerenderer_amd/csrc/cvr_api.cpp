@@ -326,33 +326,48 @@ bool scatter_eps_for(const cvr_ctx* c) {
 // kernel 8% slower on C2 and 7% on C3.
 bool morton_for(const cvr_ctx* c) { return c->morton > 0; }
 
-int wpool_waves_for(const cvr_ctx* c, bool sparse) {
-  if (c->wpool_waves) return c->wpool_waves;
-  return 5;  // dense and sparse (split slots: DESIGN.md §6)
-}
-
-// naiveMK runs the wave pool (k_wpool's kMedMK instances: d_init + d_extend per path, RNG
-// re-seeded per bounce; C2 27.5 -> ~4.5 ms) unless another scheduler or budget is asked
-// for, the reference's per-bounce compaction (CVR_OPT_MK_COMPACTION 1) or the in-launch
-// output (cvr_render_frame then copies after the launch).
-bool mk_on_wpool(const cvr_ctx* c) {
-  return c->kernel == CVR_KERNEL_NAIVE_MK && scheduler_for(c) == 3 && !c->mk_compaction &&
-         wpool_waves_for(c, c->m.leaves != nullptr) == 5;
-}
-
-// CVR_OPT_MOMENTS: what the context's configuration has that the moments instances (wave pool,
-// 5 waves per SIMD, generic dense / fp32 sparse layout) do not run with, or null.
-const char* moments_refusal(const cvr_ctx* c) {
+// dense and sparse at the default (split slots: DESIGN.md §6)
+int wpool_waves_for(const cvr_ctx* c) { return c->wpool_waves ? c->wpool_waves : cvr::kWpoolWaves; }
+// What the context's wave-pool launch asks of k_wpool; cvr::wpool_select says which instance runs it, if any.
+cvr::WpoolRequest wpool_request(const cvr_ctx* c, bool record, bool flush) {
   const bool sparse = c->m.leaves != nullptr;
-  return c->external_out                       ? "a caller's output buffer (cvr_set_output)"
-         : c->kernel == CVR_KERNEL_NAIVE_MK    ? "kernel id naiveMK"
-         : c->rng_binding                      ? "CVR_OPT_RNG_BINDING 1"
-         : scheduler_for(c) != 3               ? "a scheduler other than the wave pool (CVR_OPT_SCHEDULER 3)"
-         : wpool_waves_for(c, sparse) != 5     ? "CVR_OPT_WAVES other than 5"
-         : c->mk_compaction                    ? "CVR_OPT_MK_COMPACTION 1"
-         : c->count_words                      ? "CVR_OPT_COUNT_WORDS 1"
-         : (sparse && c->m.format != 0u)       ? "a sparse half medium"
-                                               : nullptr;
+  return {scatter_eps_for(c), wpool_waves_for(c), sparse, !sparse && c->m.cells && c->m.bounds,
+          c->m.albedo_uniform != 0u, c->m.format != 0u, c->kernel == CVR_KERNEL_NAIVE_MK, c->count_words != 0,
+          c->moments != 0, record, flush};
+}
+// The generic instance of a layout at the context's budget (never refused): do_init's grids, every such instance's wpg.
+cvr::WpoolInstance wpool_generic(const cvr_ctx* c, bool sparse) {
+  cvr::WpoolInstance k{};
+  (void)cvr::wpool_select({scatter_eps_for(c), wpool_waves_for(c), sparse}, &k);
+  return k;
+}
+
+// naiveMK runs the wave pool (k_wpool's kMedMK instances: d_init + d_extend per path, RNG re-seeded per bounce;
+// C2 27.5 -> ~4.5 ms) unless another scheduler, a budget without such an instance or the reference's per-bounce
+// compaction is asked for.  The request is the walk alone: cvr_launch_render refuses what else no instance runs.
+bool mk_on_wpool(const cvr_ctx* c) {
+  cvr::WpoolInstance k;
+  return c->kernel == CVR_KERNEL_NAIVE_MK && scheduler_for(c) == 3 && !c->mk_compaction &&
+         cvr::wpool_select({true, wpool_waves_for(c), false, false, false, false, /*naive_mk*/ true}, &k);
+}
+
+// What the context has that the half-format (kForHalf) or the moments instances (kForMoments: generic dense / fp32
+// sparse layout) do not run with: the first entry of the feature's that holds, or null.
+enum : unsigned { kForHalf = 1, kForMoments = 2, kForBoth = 3 };
+const char* wpool_refusal(const cvr_ctx* c, unsigned feature) {
+  const struct { unsigned features; bool holds; const char* text; } list[] = {
+      {kForMoments, c->external_out, "a caller's output buffer (cvr_set_output)"},
+      {kForMoments, c->kernel == CVR_KERNEL_NAIVE_MK, "kernel id naiveMK"},
+      {kForBoth, c->rng_binding != 0, "CVR_OPT_RNG_BINDING 1"},
+      {kForBoth, scheduler_for(c) != 3, "a scheduler other than the wave pool (CVR_OPT_SCHEDULER 3)"},
+      {kForBoth, wpool_waves_for(c) != cvr::kWpoolWaves, "CVR_OPT_WAVES other than 5"},
+      {kForBoth, c->mk_compaction != 0, "CVR_OPT_MK_COMPACTION 1"},
+      {kForBoth, c->count_words != 0, "CVR_OPT_COUNT_WORDS 1"},
+      {kForMoments, c->m.leaves && c->m.format != 0u, "a sparse half medium"},
+  };
+  for (const auto& e : list)
+    if ((e.features & feature) && e.holds) return e.text;
+  return nullptr;
 }
 
 // Wave-pool grid of a launch of n_paths (one wave per workgroup): CVR_OPT_GRID,
@@ -369,7 +384,7 @@ const char* moments_refusal(const cvr_ctx* c) {
 // profiles/round4/shard_grid.log); alone the full grid is faster.
 // The grid counts waves, in whole workgroups of the instance (cvr::wpool_wpg).
 uint32_t wpool_launch_grid(const cvr_ctx* c, uint64_t n_paths) {
-  const uint32_t wpg = cvr::wpool_wpg(wpool_waves_for(c, c->m.leaves != nullptr), c->m.leaves != nullptr);
+  const uint32_t wpg = cvr::wpool_wpg(wpool_generic(c, c->m.leaves != nullptr));
   auto whole = [wpg](uint32_t g) { return std::max(wpg, g / wpg * wpg); };
   if (c->grid_override) return whole(c->grid_override);
   const uint32_t full = (uint32_t)(c->m.leaves ? c->wpool_grid_sparse : c->wpool_grid);
@@ -554,10 +569,10 @@ int do_init(cvr_ctx* c) {
   if (pbpc < 1) pbpc = 1;
   c->pool_grid = pbpc * c->cu_count;
   int wbpc = 0;
-  HIP_TRY(c, cvr::wpool_occupancy(scatter_eps_for(c), wpool_waves_for(c, false), false, &wbpc));
+  HIP_TRY(c, cvr::wpool_occupancy(wpool_generic(c, false), &wbpc));
   if (wbpc < 1) wbpc = 1;
   c->wpool_grid = wbpc * c->cu_count;
-  HIP_TRY(c, cvr::wpool_occupancy(scatter_eps_for(c), wpool_waves_for(c, true), true, &wbpc));
+  HIP_TRY(c, cvr::wpool_occupancy(wpool_generic(c, true), &wbpc));
   if (wbpc < 1) wbpc = 1;
   c->wpool_grid_sparse = wbpc * c->cu_count;
   int tbpc = 0;
@@ -1690,18 +1705,12 @@ int cvr_launch_render(cvr_ctx* c) {
   if ((r = do_init(c))) return r;
   if (c->m.format != 0u) {
     // the half storage format: the wave-pool scheduler's 5-wave instances only
-    const bool sparse = c->m.leaves != nullptr;
-    const char* why = c->rng_binding                       ? "CVR_OPT_RNG_BINDING 1"
-                      : scheduler_for(c) != 3              ? "a scheduler other than the wave pool (CVR_OPT_SCHEDULER 3)"
-                      : wpool_waves_for(c, sparse) != 5    ? "CVR_OPT_WAVES other than 5"
-                      : c->mk_compaction                   ? "CVR_OPT_MK_COMPACTION 1"
-                      : c->count_words                     ? "CVR_OPT_COUNT_WORDS 1"
-                                                           : nullptr;
+    const char* why = wpool_refusal(c, kForHalf);
     if (why) return set_err(&c->err, CVR_ERR_UNSUPPORTED, "the half medium format does not run with %s", why);
   }
   if (c->moments) {
     // second moments: the wave pool's two moments instances only, into the context's own buffer
-    const char* why = moments_refusal(c);
+    const char* why = wpool_refusal(c, kForMoments);
     if (!why && c->d_rec_active) why = "cvr_trace_launch";
     if (!why && c->frame_done_active) why = "cvr_render_frame's in-launch output";
     if (why) return set_err(&c->err, CVR_ERR_UNSUPPORTED, "second moments (CVR_OPT_MOMENTS 1) do not run with %s", why);
@@ -1797,10 +1806,10 @@ int cvr_launch_render(cvr_ctx* c) {
     const uint32_t grid = c->grid_override ? c->grid_override : (uint32_t)c->pool_grid;
     HIP_TRY(c, cvr::launch_pool(launch_medium(c), L, eps, grid, c->stream));
   } else if (scheduler_for(c) == 3) {
-    const bool sparse = c->m.leaves != nullptr;
-    const int waves = wpool_waves_for(c, sparse);
+    const cvr::WpoolRequest q = wpool_request(c, c->d_rec_active != nullptr, c->frame_done_active != nullptr);
+    cvr::WpoolInstance k;
     const uint32_t grid = wpool_launch_grid(c, L.path_count);
-    const size_t need = (size_t)grid * cvr::wpool_slots(waves, sparse);
+    const size_t need = cvr::wpool_select(q, &k) ? (size_t)grid * cvr::wpool_slots(k) : 0;  // (0: launch_wpool refuses)
     if (need > c->pool_T_n) {
       if (c->d_pool_T) (void)hipFree(c->d_pool_T);
       c->d_pool_T = nullptr;
@@ -1817,8 +1826,7 @@ int cvr_launch_render(cvr_ctx* c) {
                        4 * cvr::kFrameFlushers);
       L.frame_done = c->frame_done_active;
     }
-    HIP_TRY(c, cvr::launch_wpool(launch_medium(c), L, eps, waves, grid, c->stream, c->kernel == CVR_KERNEL_NAIVE_MK,
-                                 c->count_words != 0, c->moments != 0));
+    HIP_TRY(c, cvr::launch_wpool(launch_medium(c), L, q, grid, c->stream));
   } else if (L.path_count > 0) {
     if ((r = wf_render(c, L, eps))) return r;
   }
@@ -2002,6 +2010,7 @@ int cvr_trace_launch(cvr_ctx* c, cvr_path_record* out, uint64_t n_out) {
   int r = check_ready(c);
   if (r) return r;
   if ((r = do_init(c))) return r;
+  // (no walk of naiveMK's has a record instance; a budget without one is launch_wpool's to refuse, CVR_ERR_HIP)
   if (scheduler_for(c) != 3 || c->rng_binding || c->kernel == CVR_KERNEL_NAIVE_MK)
     return set_err(&c->err, CVR_ERR_UNSUPPORTED, "cvr_trace_launch traces the wave-pool scheduler only");
   uint64_t first, count;
@@ -2009,11 +2018,12 @@ int cvr_trace_launch(cvr_ctx* c, cvr_path_record* out, uint64_t n_out) {
   if (n_out != count)
     return set_err(&c->err, CVR_ERR_INVALID, "record buffer holds %llu records, the launch range %llu",
                    (unsigned long long)n_out, (unsigned long long)count);
-  const bool sparse = c->m.leaves != nullptr;
   cvr::LaunchParams Lq{};
   fill_launch(c, Lq, first, count);
   const uint64_t grid = wpool_launch_grid(c, Lq.path_count);
-  const size_t pid_bytes = (size_t)grid * cvr::wpool_slots(wpool_waves_for(c, sparse), sparse) * sizeof(uint32_t);
+  cvr::WpoolInstance k;  // (none: no ids, and the launch below fails)
+  const bool have = cvr::wpool_select(wpool_request(c, true, false), &k);
+  const size_t pid_bytes = have ? (size_t)grid * cvr::wpool_slots(k) * sizeof(uint32_t) : 0;
   const size_t rec_bytes = (size_t)count * sizeof(cvr_path_record);
   // the traced launch splats into a scratch framebuffer, not the context's
   const size_t out_bytes = (size_t)c->tile_w * c->tile_h * sizeof(float4);
@@ -2399,12 +2409,13 @@ int cvr_render_frame(cvr_ctx* c, float* host_image, size_t host_floats, uint32_t
       row0[k + 1] = k + 1 == parts ? brows : (uint32_t)((uint64_t)brows * acc / shares);
     }
   }
-  // in-launch output (CVR_OPT_FRAME_FLUSH): one part on the wave pool, and a host image
-  // the GPU can store into
+  // in-launch output (CVR_OPT_FRAME_FLUSH): one part on the wave pool, an instance with that
+  // output for the launch, and a host image the GPU can store into
   void* dhost = nullptr;
-  if (c->frame_flush && parts == 1 && brows && scheduler_for(c) == 3 && !c->d_rec_active &&
-      c->kernel != CVR_KERNEL_NAIVE_MK &&  // (no in-launch output instance of naiveMK's walk)
-      wpool_waves_for(c, c->m.leaves != nullptr) == 5 && wpool_launch_grid(c, L0.path_count) > 4 * cvr::kFrameFlushers) {
+  cvr::WpoolInstance inst;
+  if (c->frame_flush && parts == 1 && brows && scheduler_for(c) == 3 &&
+      cvr::wpool_select(wpool_request(c, c->d_rec_active != nullptr, true), &inst) &&
+      wpool_launch_grid(c, L0.path_count) > 4 * cvr::kFrameFlushers) {
     if (hipHostGetDevicePointer(&dhost, host_image, 0) != hipSuccess) {
       (void)hipGetLastError();  // pageable memory: not an error, the copy path below
       dhost = nullptr;
@@ -2539,7 +2550,7 @@ int cvr_adaptive_begin(cvr_ctx* c, const cvr_adaptive_desc* d) {
                     : c->shard_world != 1                   ? "a block shard (cvr_set_block_shard)"
                     : (rf != 0 || rc != c->n_paths)         ? "a path range (cvr_set_path_range)"
                     : c->order == 0                         ? "CVR_OPT_ORDER 0 (no pixel-block work order)"
-                                                            : moments_refusal(c);
+                                                            : wpool_refusal(c, kForMoments);
   if (why) return set_err(&c->err, CVR_ERR_UNSUPPORTED, "an adaptive render does not run with %s", why);
   if ((r = ensure_device(c)) || (r = do_init(c)) || (r = ensure_output(c))) return r;
   cvr_ctx::Adaptive& a = c->ad;

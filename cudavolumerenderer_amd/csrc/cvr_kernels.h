@@ -5,6 +5,7 @@
 #include <stdint.h>
 
 #include "cvr_walk.h"
+#include "cvr_wpool_select.h"
 
 namespace cvr {
 
@@ -52,21 +53,21 @@ hipError_t launch_trace(const MediumParams& m, const LaunchParams& L, bool scatt
                         hipStream_t s);
 hipError_t launch_pool(const MediumParams& m, const LaunchParams& L, bool scatter_eps, uint32_t grid, hipStream_t s);
 hipError_t pool_occupancy(bool scatter_eps, int* blocks_per_cu);
-// naive_mk: naiveMK's walk on the wave pool (5 waves per SIMD, no records / in-launch output).
-// count_words: sparse media, the counting instance (CVR_OPT_COUNT_WORDS: brick words loaded).
-// moments: the second-moment instance (CVR_OPT_MOMENTS): L.out holds 2 * tile_px float4, the
-// moments behind the tile; 5 waves per SIMD, generic dense or fp32 sparse layout only.
-hipError_t launch_wpool(const MediumParams& m, const LaunchParams& L, bool scatter_eps, int waves, uint32_t grid,
-                        hipStream_t s, bool naive_mk = false, bool count_words = false, bool moments = false);
+// The wave pool: the instance wpool_select (cvr_wpool_select.h) gives for request q, which the
+// caller fills to describe m and L (q.moments: L.out holds 2 * tile_px float4, the moments behind
+// the tile).  hipErrorInvalidValue: no instance runs q, or grid is not whole workgroups.
+hipError_t launch_wpool(const MediumParams& m, const LaunchParams& L, const WpoolRequest& q, uint32_t grid,
+                        hipStream_t s);
+// The three below take an instance that wpool_select returned.
 // Resident waves per CU of the wave-pool instance (workgroups per CU x waves per workgroup).
-hipError_t wpool_occupancy(bool scatter_eps, int waves, bool sparse, int* waves_per_cu);
+hipError_t wpool_occupancy(const WpoolInstance& k, int* waves_per_cu);
 // Pool slots per wave of the wave-pool kernel instance (LaunchParams::pool_T
 // needs grid * slots float4).
-uint32_t wpool_slots(int waves, bool sparse);
+uint32_t wpool_slots(const WpoolInstance& k);
 // Waves per workgroup of the wave-pool instance: 1 for dense media; sparse media run
 // several wave-private pools per workgroup that share one LDS copy of the launch
 // parameters and the empty-region mask.  A wave-pool grid (in waves) is a multiple.
-uint32_t wpool_wpg(int waves, bool sparse);
+uint32_t wpool_wpg(const WpoolInstance& k);
 // regenerationSK with the RNG bound to the persistent thread (CVR_OPT_RNG_BINDING 1):
 // `grid` one-wave workgroups, path ids from the launch's single queue head.
 hipError_t launch_regen_thread(const MediumParams& m, const LaunchParams& L, bool scatter_eps, uint32_t grid,

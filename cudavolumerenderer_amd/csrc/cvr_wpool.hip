@@ -487,41 +487,15 @@ __device__ void frame_flusher(const LaunchParams& L, uint32_t f, uint32_t lane) 
 
 }  // namespace
 
-// kMed: the medium layout the instance is compiled for (kMedDense any dense medium,
-// kMedSparse leaves + brick words, kMedDenseFull a dense medium with density cells
-// and brick bounds, the defaults: its null checks fold away, C2 -0.6%, C3 -1.8%;
-// kMedDenseFullUniform the same with a uniform albedo, MediumParams::albedo_uniform,
-// whose check would otherwise cost the non-uniform instance 1.5% on C2).
-// kFlush: the in-launch output instance (cvr_render_frame, CVR_OPT_FRAME_FLUSH);
-// the other instances carry none of its code.
-enum : int { kMedDense = 0, kMedSparse = 1, kMedDenseFull = 2, kMedDenseFullUniform = 3 };
+// k_wpool's instances (kMed* layouts and bits: cvr_wpool_select.h).  kMedDenseFull is the defaults' layout, its
+// null checks fold away (C2 -0.6%, C3 -1.8%); kMedDenseFullUniform pins the uniform albedo, whose check would cost
+// the non-uniform instance 1.5% on C2.  Only the kFlush, kRecord, kMedCount, kMedMoments instances carry that code.
 #if CVR_WPOOL_TAILSTAMP
 constexpr uint32_t kTailWaves = 16384;
 __device__ unsigned long long g_tail[8 * kTailWaves];
 #endif
-// kMedMK (or-ed into kMed): naiveMK's walk (NaiveVolPTmk_kernel.cuh:20-151) on the wave
-// pool, round 5: a new path runs d_init (camera ray on the (iteration, pixel, 0) stream,
-// AABB, the GGX sample at the box, Q12) and every segment starts as d_extend does, with
-// the RNG re-seeded from (iteration, pixel, depth) and three unused draws; the slot's
-// event-only word holds the path id (iteration and pixel) instead of the pixel.
-constexpr int kMedMK = 4;
-// kMedCount (or-ed into kMed, sparse media only): the counting instance of
-// CVR_OPT_COUNT_WORDS, which also counts the brick words its Woodcock points load
-// (the empty-region mask skips the rest), so that the launch's algorithmic bytes are
-// exact; the benchmarked instances carry no counter.
-constexpr int kMedCount = 8;
-// kMedHalf (or-ed into kMed): the instance reads the half storage format
-// (MediumParams::format 1) as a compile-time constant, the instances without it format
-// 0, as albedo_uniform is pinned; the generic kMedDense instances read it at run time.
-constexpr int kMedHalf = 16;
-// kMedMoments (or-ed into kMed): the second-moment instance of CVR_OPT_MOMENTS.  The
-// context's framebuffer allocation holds a second float4 per pixel directly behind the
-// tile, moments[i] = L.out[L.tile_px + i] = (sum fl(T.r T.r), sum fl(T.g T.g),
-// sum fl(T.b T.b), escapes splatted into the pixel), which an escape adds to after its
-// splat.  The buffer sits at a fixed offset from `out` so that the kernel parameters do
-// not change: every other instance keeps its kernel-argument layout, its LDS copy of
-// the launch parameters and its pool slot count (PoolSize derives from sizeof).
-constexpr int kMedMoments = 32;
+// kMedMoments: moments[i] = L.out[L.tile_px + i], a fixed offset, so that every other instance keeps its
+// kernel-argument layout, its LDS copy of the launch parameters and its pool slot count (PoolSize: sizeof).
 static_assert(sizeof(LaunchParams) == 256 && sizeof(MediumParams) == 256,
               "the moments buffer is addressed from LaunchParams::out: the parameter structs keep their size");
 // An escape's squares and its count, after splat(): agent-scope relaxed atomics performed
@@ -1196,110 +1170,70 @@ __global__ __launch_bounds__(64 * wpg_of(kMedMk, kWaves), kWaves) void k_wpool(M
   }
 }
 
-// Instances: 5 waves per SIMD (the default budget) for every medium layout, with and
-// without the in-launch output; the other budgets for the generic layouts.
-template <bool E>
-static const void* wpool_fn(int waves, bool sparse, bool full, bool flush = false, bool uniform = false,
-                            bool half = false) {
-#define CVR_WP(W, M, F) reinterpret_cast<const void*>(&k_wpool<E, W, M, false, F>)
-  if (half) {
-    // the half storage format: 5 waves per SIMD; the generic dense instance reads the format at run time
-    if (waves != 5) return nullptr;
-    if (sparse) return flush ? CVR_WP(5, kMedSparse | kMedHalf, true) : CVR_WP(5, kMedSparse | kMedHalf, false);
-    if (full && uniform)
-      return flush ? CVR_WP(5, kMedDenseFullUniform | kMedHalf, true) : CVR_WP(5, kMedDenseFullUniform | kMedHalf, false);
-    if (full) return flush ? CVR_WP(5, kMedDenseFull | kMedHalf, true) : CVR_WP(5, kMedDenseFull | kMedHalf, false);
-    return flush ? CVR_WP(5, kMedDense, true) : CVR_WP(5, kMedDense, false);
-  }
-  if (waves == 5) {
-    if (sparse) return flush ? CVR_WP(5, kMedSparse, true) : CVR_WP(5, kMedSparse, false);
-    if (full && uniform) return flush ? CVR_WP(5, kMedDenseFullUniform, true) : CVR_WP(5, kMedDenseFullUniform, false);
-    if (full) return flush ? CVR_WP(5, kMedDenseFull, true) : CVR_WP(5, kMedDenseFull, false);
-    return flush ? CVR_WP(5, kMedDense, true) : CVR_WP(5, kMedDense, false);
-  }
-  if (flush) return nullptr;
-  if (sparse) return CVR_WP(4, kMedSparse, false);
-  if (waves == 6) return CVR_WP(6, kMedDense, false);
-  if (waves == 3) return CVR_WP(3, kMedDense, false);
-  return CVR_WP(4, kMedDense, false);
-#undef CVR_WP
+// The instances the library ships: every one wpool_select (cvr_wpool_select.h) can return and no
+// other.  A row's id, kernel, waves per workgroup and pool slots all come from one argument list.
+struct WpoolRow { WpoolInstance id; void (*fn)(MediumParams, LaunchParams); uint32_t wpg, slots; };
+constexpr int em_bytes_of(int med) { return (med & 3) == kMedSparse && CVR_WPOOL_EMASK ? 4 * kEmaskWords : 0; }
+#define CVR_WP_ROW(E, W, M, R, F) \
+  {{E, W, (M), R, F}, &k_wpool<E, W, (M), R, F>, wpg_of((M), W), PoolSize<W, em_bytes_of(M), wpg_of((M), W)>::value}
+#define CVR_WP_ROWS(W, M, R, F) CVR_WP_ROW(false, W, M, R, F), CVR_WP_ROW(true, W, M, R, F)
+#define CVR_WP_ROWS5(M) CVR_WP_ROWS(5, M, false, false), CVR_WP_ROWS(5, M, false, true)
+#define CVR_WP_ROWMK(M) CVR_WP_ROW(true, 5, (M) | kMedMK, false, false)
+constexpr WpoolRow kWpoolTable[] = {
+    // 5 waves per SIMD (the default budget): every layout, fp32 and half, without and with the in-launch output
+    CVR_WP_ROWS5(kMedDense), CVR_WP_ROWS5(kMedSparse), CVR_WP_ROWS5(kMedDenseFull), CVR_WP_ROWS5(kMedDenseFullUniform),
+    CVR_WP_ROWS5(kMedSparse | kMedHalf), CVR_WP_ROWS5(kMedDenseFull | kMedHalf),
+    CVR_WP_ROWS5(kMedDenseFullUniform | kMedHalf),
+    // the other budgets (CVR_OPT_WAVES): the generic layouts
+    CVR_WP_ROWS(3, kMedDense, false, false), CVR_WP_ROWS(4, kMedDense, false, false),
+    CVR_WP_ROWS(6, kMedDense, false, false), CVR_WP_ROWS(4, kMedSparse, false, false),
+    // records (cvr_trace_launch; debug only, so the production kernels carry none of the record code)
+    CVR_WP_ROWS(5, kMedDense, true, false), CVR_WP_ROWS(5, kMedSparse, true, false),
+    CVR_WP_ROWS(5, kMedSparse | kMedHalf, true, false), CVR_WP_ROWS(4, kMedSparse, true, false),
+    // second moments, word counts
+    CVR_WP_ROWS(5, kMedDense | kMedMoments, false, false), CVR_WP_ROWS(5, kMedSparse | kMedMoments, false, false),
+    CVR_WP_ROWS(5, kMedSparse | kMedCount, false, false),
+    // naiveMK's walk: scatter -eps
+    CVR_WP_ROWMK(kMedDense), CVR_WP_ROWMK(kMedSparse), CVR_WP_ROWMK(kMedDenseFull), CVR_WP_ROWMK(kMedDenseFullUniform),
+    CVR_WP_ROWMK(kMedSparse | kMedHalf), CVR_WP_ROWMK(kMedDenseFull | kMedHalf),
+    CVR_WP_ROWMK(kMedDenseFullUniform | kMedHalf),
+};
+#undef CVR_WP_ROWMK
+#undef CVR_WP_ROWS5
+#undef CVR_WP_ROWS
+#undef CVR_WP_ROW
+constexpr int kWpoolRows = (int)(sizeof(kWpoolTable) / sizeof(kWpoolTable[0]));
+constexpr const WpoolRow* wpool_row(const WpoolInstance& k) {
+  for (const WpoolRow& r : kWpoolTable)
+    if (r.id == k) return &r;
+  return nullptr;
 }
-// Record instances (cvr_trace_launch; debug only, so the production kernels
-// carry none of the record code): the default register budgets, generic layouts.
-template <bool E>
-static const void* wpool_record_fn(int waves, bool sparse, bool half) {
-  if (half)
-    return waves != 5 ? nullptr
-           : sparse   ? reinterpret_cast<const void*>(&k_wpool<E, 5, kMedSparse | kMedHalf, true, false>)
-                      : reinterpret_cast<const void*>(&k_wpool<E, 5, kMedDense, true, false>);
-  if (sparse) return waves == 5   ? reinterpret_cast<const void*>(&k_wpool<E, 5, kMedSparse, true, false>)
-                    : waves == 4 ? reinterpret_cast<const void*>(&k_wpool<E, 4, kMedSparse, true, false>)
-                                 : nullptr;
-  return waves == 5 ? reinterpret_cast<const void*>(&k_wpool<E, 5, kMedDense, true, false>) : nullptr;
+// Over the whole request space: every instance selected is a row, and every row is selected.
+constexpr bool wpool_table_is_the_selection() {
+  bool hit[kWpoolRows] = {};
+  WpoolInstance k{};
+  for (int i = 0; i < kWpoolRequests; ++i)
+    if (wpool_select(wpool_request_at(i), &k)) {
+      const WpoolRow* r = wpool_row(k);
+      if (!r) return false;
+      hit[r - kWpoolTable] = true;
+    }
+  for (bool h : hit)
+    if (!h) return false;
+  return true;
 }
+static_assert(kWpoolRows == 57 && wpool_table_is_the_selection(), "the instance table and wpool_select disagree");
 
-// naiveMK instances (kMedMK): 5 waves per SIMD, every medium layout, scatter -eps.
-static const void* wpool_mk_fn(bool sparse, bool full, bool uniform, bool half) {
-#define CVR_WPMK(M) reinterpret_cast<const void*>(&k_wpool<true, 5, (M) | kMedMK, false, false>)
-  if (half) {
-    if (sparse) return CVR_WPMK(kMedSparse | kMedHalf);
-    if (full && uniform) return CVR_WPMK(kMedDenseFullUniform | kMedHalf);
-    if (full) return CVR_WPMK(kMedDenseFull | kMedHalf);
-    return CVR_WPMK(kMedDense);
-  }
-  if (sparse) return CVR_WPMK(kMedSparse);
-  if (full && uniform) return CVR_WPMK(kMedDenseFullUniform);
-  if (full) return CVR_WPMK(kMedDenseFull);
-  return CVR_WPMK(kMedDense);
-#undef CVR_WPMK
-}
-
-hipError_t launch_wpool(const MediumParams& m, const LaunchParams& L, bool scatter_eps, int waves, uint32_t grid,
-                        hipStream_t s, bool naive_mk, bool count_words, bool moments) {
+hipError_t launch_wpool(const MediumParams& m, const LaunchParams& L, const WpoolRequest& q, uint32_t grid,
+                        hipStream_t s) {
   if (L.path_count == 0) return hipSuccess;
-  const bool sparse = m.leaves != nullptr;
-  // one launch of instance fn over a grid of whole workgroups (pool_T and the record ids
-  // are sized for grid waves)
-  auto launch = [&](const void* fn) {
-    const uint32_t wpg = wpool_wpg(waves, sparse);
-    if (!fn || grid % wpg) return hipErrorInvalidValue;
-    MediumParams mm = m;
-    LaunchParams ll = L;
-    void* args[] = {&mm, &ll};
-    return hipLaunchKernel(fn, dim3(grid / wpg), dim3(64 * wpg), args, 0, s);
-  };
-  if (moments) {
-    // the moments instances (CVR_OPT_MOMENTS): 5 waves per SIMD, the generic dense layout (cells,
-    // bounds, uniform albedo and the half format read at run time) and the fp32 sparse one; no
-    // records, in-launch output, naiveMK walk or word counts (cvr_launch_render refuses them first)
-    if (waves != 5 || naive_mk || count_words || L.rec || L.frame_done || (sparse && m.format != 0u))
-      return hipErrorInvalidValue;
-#define CVR_WPM(E, M) reinterpret_cast<const void*>(&k_wpool<E, 5, (M) | kMedMoments, false, false>)
-    return launch(scatter_eps ? (sparse ? CVR_WPM(true, kMedSparse) : CVR_WPM(true, kMedDense))
-                              : (sparse ? CVR_WPM(false, kMedSparse) : CVR_WPM(false, kMedDense)));
-#undef CVR_WPM
-  }
-  const bool flush = L.frame_done != nullptr;
-  const bool full = !sparse && m.cells != nullptr && m.bounds != nullptr;
-  const bool uniform = m.albedo_uniform != 0u;
-  const bool half = m.format != 0u;
-  // the half format has no counting or other-budget instances (cvr_launch_render refuses them first)
-  if (half && (count_words || waves != 5)) return hipErrorInvalidValue;
-  if (L.rec && flush) return hipErrorInvalidValue;
-  if (naive_mk) {
-    if (waves != 5 || flush || L.rec) return hipErrorInvalidValue;
-    return launch(wpool_mk_fn(sparse, full, uniform, half));
-  }
-  const void* fn = L.rec ? (scatter_eps ? wpool_record_fn<true>(waves, sparse, half)
-                                        : wpool_record_fn<false>(waves, sparse, half))
-                         : (scatter_eps ? wpool_fn<true>(waves, sparse, full, flush, uniform, half)
-                                        : wpool_fn<false>(waves, sparse, full, flush, uniform, half));
-  // the counting instances (CVR_OPT_COUNT_WORDS): sparse media, 5 waves per SIMD, no records
-  // or in-launch output (other launches count nothing: cvr_stats.words stays 0)
-  if (count_words && sparse && waves == 5 && !L.rec && !flush)
-    fn = scatter_eps ? reinterpret_cast<const void*>(&k_wpool<true, 5, kMedSparse | kMedCount, false, false>)
-                     : reinterpret_cast<const void*>(&k_wpool<false, 5, kMedSparse | kMedCount, false, false>);
-  return launch(fn);  // (null: no record / in-launch output instance for this register budget)
+  WpoolInstance k{};
+  if (!wpool_select(q, &k)) return hipErrorInvalidValue;
+  // a grid of whole workgroups (pool_T and the record ids are sized for grid waves)
+  const WpoolRow& row = *wpool_row(k);
+  if (grid % row.wpg) return hipErrorInvalidValue;
+  void* args[] = {const_cast<MediumParams*>(&m), const_cast<LaunchParams*>(&L)};  // (copied by the launch)
+  return hipLaunchKernel(reinterpret_cast<const void*>(row.fn), dim3(grid / row.wpg), dim3(64 * row.wpg), args, 0, s);
 }
 
 #if CVR_WPOOL_TAILSTAMP
@@ -1315,23 +1249,14 @@ extern "C" int cvr_debug_tailstamps_clear() {
 }
 #endif
 
-uint32_t wpool_wpg(int waves, bool sparse) { return (uint32_t)wpg_of(sparse ? kMedSparse : kMedDense, waves); }
-
-uint32_t wpool_slots(int waves, bool sparse) {
-  constexpr int kEmB = CVR_WPOOL_EMASK ? 4 * kEmaskWords : 0;
-  if (sparse)
-    return waves == 5 ? PoolSize<5, kEmB, wpg_of(kMedSparse, 5)>::value : PoolSize<4, kEmB, wpg_of(kMedSparse, 4)>::value;
-  return waves == 5   ? PoolSize<5, 0, wpg_of(kMedDense, 5)>::value
-         : waves == 6 ? PoolSize<6, 0, wpg_of(kMedDense, 6)>::value
-         : waves == 3 ? PoolSize<3, 0, wpg_of(kMedDense, 3)>::value
-                      : PoolSize<4, 0, wpg_of(kMedDense, 4)>::value;
-}
-
-hipError_t wpool_occupancy(bool scatter_eps, int waves, bool sparse, int* waves_per_cu) {
-  const void* fn = scatter_eps ? wpool_fn<true>(waves, sparse, false) : wpool_fn<false>(waves, sparse, false);
-  int blocks = 0;
-  const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks, fn, 64 * wpool_wpg(waves, sparse), 0);
-  *waves_per_cu = blocks * (int)wpool_wpg(waves, sparse);
+// k: an instance wpool_select returned (so a row: the static_assert above)
+uint32_t wpool_wpg(const WpoolInstance& k) { return wpool_row(k)->wpg; }
+uint32_t wpool_slots(const WpoolInstance& k) { return wpool_row(k)->slots; }
+hipError_t wpool_occupancy(const WpoolInstance& k, int* waves_per_cu) {
+  const WpoolRow& row = *wpool_row(k);
+  const void* fn = reinterpret_cast<const void*>(row.fn);
+  const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(waves_per_cu, fn, 64 * row.wpg, 0);
+  *waves_per_cu *= (int)row.wpg;
   return e;
 }
 

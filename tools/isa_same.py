@@ -38,11 +38,18 @@ def kernels(path, tmp, pattern):
     txt = subprocess.check_output([f"{LLVM}/llvm-objdump", "-d", "--demangle", "--no-show-raw-insn",
                                    "--no-leading-addr", code_object(path, tmp)], text=True)
     res, name, body = {}, None, []
+
+    def keep():
+        # "..." is objdump's mark for zero bytes it skipped.  As a kernel's last line it is the fill up to
+        # the next kernel's alignment, which every kernel but the section's last has: no instruction, and
+        # it moves with the order the kernels are emitted in.  Anywhere else it stays and is compared.
+        if name is not None:
+            res[name] = body[:-1] if body and body[-1] == "..." else body
+
     for line in txt.splitlines():
         m = re.match(r"^[0-9a-f]* ?<(.*)>:$", line)
         if m:
-            if name is not None:
-                res[name] = body
+            keep()
             name, body = m.group(1), []
             if not pattern.search(name):
                 name = None
@@ -52,8 +59,7 @@ def kernels(path, tmp, pattern):
         ins = line.split("//")[0].strip()  # drop the address / encoding comment
         if ins:
             body.append(ins)
-    if name is not None:
-        res[name] = body
+    keep()
     return res
 
 
