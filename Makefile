@@ -10,22 +10,32 @@ PKG := cudavolumerenderer_amd
 CSRC := $(PKG)/csrc
 HIPFLAGS := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -ffp-contract=off \
             -fhip-fp32-correctly-rounded-divide-sqrt -Iinclude -I$(CSRC) -Wall
-OBJDIR := build/obj
+OBJDIR ?= build/obj
 SRCS_HIP := $(CSRC)/cvr_kernels.hip $(CSRC)/cvr_persistent.hip $(CSRC)/cvr_pool.hip $(CSRC)/cvr_wpool.hip $(CSRC)/cvr_wavefront.hip \
             $(CSRC)/cvr_denoise.hip
 SRCS_CPP := $(CSRC)/cvr_api.cpp $(CSRC)/cvr_scene.cpp $(CSRC)/cvr_vdb.cpp $(CSRC)/cvr_mhd.cpp $(CSRC)/cvr_xml.cpp
 OBJS := $(patsubst $(CSRC)/%.hip,$(OBJDIR)/%.o,$(SRCS_HIP)) $(patsubst $(CSRC)/%.cpp,$(OBJDIR)/%.o,$(SRCS_CPP))
 HDRS := include/cvr.h include/cvr_detmath.h $(wildcard $(CSRC)/*.h)
+# Per-file flags, HIPFLAGS_<file name without .hip>; every rule that compiles a .hip file goes through
+# hipflags, so the library, `variant`, `stamps`, `resource-usage` and `census-asm` agree.
+# cvr_wpool.hip, SLP vectorisation off: at -O3 the SLP vectoriser pairs adjacent fp32 multiplies, adds
+# and fmas of k_wpool into v_pk_{mul,add,fma}_f32.  A wave64 fp32 op already issues at the SIMD's whole
+# fp32 rate, so a packed op does two ops' work in no less than two ops' time; what the packing adds is
+# the moves that assemble register pairs, SALU and SGPR spill traffic (DESIGN.md §3.2, §8;
+# profiles/round7/README.md).  Packed and plain ops are the same IEEE operations per component, so
+# results do not change; tests/test_wpool_unpacked.py fails if the packing comes back.
+HIPFLAGS_cvr_wpool := -fno-slp-vectorize
+hipflags = $(HIPFLAGS) $(HIPFLAGS_$(basename $(notdir $(1)))) $(DEFS)
 
 all: $(PKG)/libcvr.so $(PKG)/cvr build/launcher_order build/wpool_select oracle
 
 $(OBJDIR)/%.o: $(CSRC)/%.hip $(HDRS)
 	@mkdir -p $(OBJDIR)
-	$(HIPCC) $(HIPFLAGS) -c $< -o $@
+	$(HIPCC) $(call hipflags,$<) -c $< -o $@
 
 $(OBJDIR)/%.o: $(CSRC)/%.cpp $(HDRS)
 	@mkdir -p $(OBJDIR)
-	$(HIPCC) $(HIPFLAGS) -x hip -c $< -o $@
+	$(HIPCC) $(call hipflags,$<) -x hip -c $< -o $@
 
 $(PKG)/libcvr.so: $(OBJS)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $(OBJS) -Wl,-soname,libcvr.so -lz
@@ -50,26 +60,33 @@ oracle:
 	$(MAKE) -C oracle
 
 resource-usage:
-	for f in $(SRCS_HIP); do $(HIPCC) $(HIPFLAGS) -Rpass-analysis=kernel-resource-usage -c $$f -o /dev/null; done
+	$(foreach f,$(SRCS_HIP),$(HIPCC) $(call hipflags,$(f)) -Rpass-analysis=kernel-resource-usage -c $(f) -o /dev/null &&) true
+
+# Device assembly of the wave-pool kernels with line tables, the input of tools/isa_census.py
+census-asm: build/census/cvr_wpool.s
+build/census/cvr_wpool.s: $(CSRC)/cvr_wpool.hip $(HDRS)
+	@mkdir -p build/census
+	$(HIPCC) $(call hipflags,$<) -gline-tables-only --cuda-device-only -S $< -o $@
 
 clean:
 	rm -rf build $(PKG)/libcvr.so $(PKG)/cvr
 	$(MAKE) -C oracle clean
 
-.PHONY: all oracle clean resource-usage
+.PHONY: all oracle clean resource-usage census-asm
 
 # Diagnostic build with in-kernel phase stamps (never the shipped library).
-stamps: build/stamps/libcvr.so
-build/stamps/libcvr.so: $(SRCS_HIP) $(SRCS_CPP) $(HDRS)
-	@mkdir -p build/stamps
-	$(HIPCC) $(HIPFLAGS) -DCVR_STAMPS=1 -shared -o $@ $(SRCS_HIP) $(patsubst %,-x hip %,$(SRCS_CPP)) -lz
+stamps:
+	$(MAKE) OBJDIR=build/stamps/obj DEFS=-DCVR_STAMPS=1 build/stamps/libcvr.so
 .PHONY: stamps
 
 # Experiment builds: make variant NAME=u2 DEFS="-DCVR_WPOOL_UNROLL=2" -> build/variants/u2/libcvr.so
-variant: $(SRCS_HIP) $(SRCS_CPP) $(HDRS)
-	@mkdir -p build/variants/$(NAME)
-	$(HIPCC) $(HIPFLAGS) $(DEFS) -shared -o build/variants/$(NAME)/libcvr.so $(SRCS_HIP) $(patsubst %,-x hip %,$(SRCS_CPP)) -lz
+# (objects through the rules above in a directory of the build's own, so per-file flags hold; always from scratch)
+variant:
+	rm -rf build/variants/$(NAME)/obj
+	$(MAKE) OBJDIR=build/variants/$(NAME)/obj DEFS="$(DEFS)" build/variants/$(NAME)/libcvr.so
 .PHONY: variant
+build/%/libcvr.so: $(OBJS)
+	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $(OBJS) -lz
 # The denoiser with global-memory taps in every pass (the A/B partner of the LDS-staged steps 1 and
 # 2: profiles/denoise/README.md); only cvr_denoise.hip differs from the in-tree library
 variant-dnplain: $(OBJS)

@@ -120,7 +120,7 @@ struct MediumParams {
   // Corner-replicated copy of the density for the Woodcock gathers: cell
   // (x,y,z) holds its 8 trilinear corners (texel-clamped as the reference's
   // point-sampled texture) in two float4 = 32 contiguous bytes, z planes
-  // interleaved for the packed lerps (trilerp_cell), so one
+  // interleaved (trilerp_cell names the corners), so one
   // evaluation is 2 x 16-byte loads from one cache line instead of 8 scattered
   // dword gathers.  Cells exist for 0 <= x1 < rx etc.; other corners (the Q5
   // uint wrap at -1, far out-of-range taps) use `density`.
@@ -402,26 +402,20 @@ CVR_DEV Tri tri_setup(const MediumParams& m, V3 p, float gx, float gy, float gz)
   t.zb = texel(z1 + 1, m.rz);
   return t;
 }
-// Trilinear of one corner-replicated cell, the two z planes side by side so
-// the x and y lerps run as packed pairs (v_pk_mul_f32 / v_pk_fma_f32): cell
-// lo = (d000, d100, d001, d101), hi = (d010, d110, d011, d111), d{z}{y}{x}.
-// Per value the operations are trilerp8's (x, then y, then z).
-typedef float cvr_f2 __attribute__((ext_vector_type(2)));
-CVR_DEV float trilerp_cell(float4 lo, float4 hi, float fx, float fy, float fz) {
-  const cvr_f2 fx2 = {fx, fx}, fxi2 = {1.0f - fx, 1.0f - fx};
-  const cvr_f2 fy2 = {fy, fy}, fyi2 = {1.0f - fy, 1.0f - fy};
-  const cvr_f2 a0 = {lo.x, lo.y}, b0 = {lo.z, lo.w}, a1 = {hi.x, hi.y}, b1 = {hi.z, hi.w};
-  const cvr_f2 x0 = __builtin_elementwise_fma(b0, fx2, a0 * fxi2);  // (z0 y0, z1 y0)
-  const cvr_f2 x1 = __builtin_elementwise_fma(b1, fx2, a1 * fxi2);  // (z0 y1, z1 y1)
-  const cvr_f2 y = __builtin_elementwise_fma(x1, fy2, x0 * fyi2);   // (z0, z1)
-  return lerpf(y.x, y.y, fz, 1.0f - fz);
-}
 CVR_DEV float trilerp8(float d000, float d001, float d010, float d011, float d100, float d101, float d110,
                        float d111, float fx, float fy, float fz) {
   const float _fx = 1.0f - fx, _fy = 1.0f - fy, _fz = 1.0f - fz;
   const float a = lerpf(lerpf(d000, d001, fx, _fx), lerpf(d010, d011, fx, _fx), fy, _fy);
   const float b = lerpf(lerpf(d100, d101, fx, _fx), lerpf(d110, d111, fx, _fx), fy, _fy);
   return lerpf(a, b, fz, _fz);
+}
+// Trilinear of one corner-replicated cell: lo = (d000, d100, d001, d101),
+// hi = (d010, d110, d011, d111), d{z}{y}{x}, the two z planes side by side (the
+// order k_build_cells writes; it once fed packed x / y lerps, which plain ones
+// replaced: a v_pk_*_f32 costs no less than its two plain ops).
+// The operations are trilerp8's on the cell's eight corners.
+CVR_DEV float trilerp_cell(float4 lo, float4 hi, float fx, float fy, float fz) {
+  return trilerp8(lo.x, lo.z, hi.x, hi.z, lo.y, lo.w, hi.y, hi.w, fx, fy, fz);
 }
 
 // Texel fetch from the dense grid or the sparse leaves (same value).

@@ -1056,7 +1056,9 @@ __global__ __launch_bounds__(64 * wpg_of(kMedMk, kWaves), kWaves) void k_wpool(M
         }
       }
       // the batch's escapes (camera rays that miss the box, survivors leaving it), per pixel
-      // (the in-launch output instance splats per lane: combining cost it 2 VGPR spills)
+      // (the in-launch output instance splats per lane: combining once cost it 2 VGPR spills; without
+      // packed fp32 it fits in 96 VGPRs, and the synchronous render gains 0.26 % from it, inside the
+      // run-to-run spread: profiles/round7/README.md)
       // (the moments instance too: a sum of squares cannot be combined through a sum)
       splat_wave<!kFlush && !kMoments>(S, L, ps, escaped, s, lane);
       if constexpr (kMoments) {

@@ -24,19 +24,32 @@ LLVM = os.environ.get("ROCM_LLVM", "/opt/rocm/llvm/bin")
 DEFAULT = r"k_wpool<(true|false), 5, [123], false, (true|false)>"
 
 
-def code_object(path, tmp):
-    out = os.path.join(tmp, os.path.basename(path) + ".co")
-    # objects and shared libraries carry the offload bundle in their .hip_fatbin section
+BUNDLE_MAGIC = b"__CLANG_OFFLOAD_BUNDLE__"
+
+
+def code_objects(path, tmp):
+    """The gfx950 code objects of an object (one) or a shared library (one per .hip file)."""
+    # objects and shared libraries carry their offload bundles in the .hip_fatbin section, a library
+    # one bundle per linked object, each at its own alignment
     fat = os.path.join(tmp, os.path.basename(path) + ".fatbin")
     subprocess.check_call([f"{LLVM}/llvm-objcopy", "-O", "binary", "--only-section=.hip_fatbin", path, fat])
-    subprocess.check_call([f"{LLVM}/clang-offload-bundler", "--unbundle", "--type=o",
-                           "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", f"--input={fat}", f"--output={out}"])
-    return out
+    data = open(fat, "rb").read()
+    starts = [m.start() for m in re.finditer(re.escape(BUNDLE_MAGIC), data)] or [0]
+    outs = []
+    for i, (a, b) in enumerate(zip(starts, starts[1:] + [len(data)])):
+        part, out = f"{fat}.{i}", os.path.join(tmp, f"{os.path.basename(path)}.{i}.co")
+        with open(part, "wb") as f:
+            f.write(data[a:b])
+        subprocess.check_call([f"{LLVM}/clang-offload-bundler", "--unbundle", "--type=o",
+                               "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", f"--input={part}", f"--output={out}"])
+        if os.path.getsize(out):
+            outs.append(out)
+    return outs
 
 
 def kernels(path, tmp, pattern):
-    txt = subprocess.check_output([f"{LLVM}/llvm-objdump", "-d", "--demangle", "--no-show-raw-insn",
-                                   "--no-leading-addr", code_object(path, tmp)], text=True)
+    txt = "\n".join(subprocess.check_output([f"{LLVM}/llvm-objdump", "-d", "--demangle", "--no-show-raw-insn",
+                                             "--no-leading-addr", co], text=True) for co in code_objects(path, tmp))
     res, name, body = {}, None, []
 
     def keep():
@@ -54,6 +67,9 @@ def kernels(path, tmp, pattern):
             if not pattern.search(name):
                 name = None
             continue
+        if re.search(r":\s+file format \S+$", line):  # the next code object's header ends the last kernel
+            keep()
+            name = None
         if name is None or not line.strip():
             continue
         ins = line.split("//")[0].strip()  # drop the address / encoding comment
