@@ -11,6 +11,7 @@ from ._lib import (  # noqa: F401
     OPT_MEDIUM_FORMAT, FORMAT_F32, FORMAT_F16, MediumInfo, half_round,
     OPT_MOMENTS, AdaptiveDesc, AdaptiveResult, AdaptiveSession, block_error,
     DenoiseDesc, denoise_host,
+    DeviceMediumDesc, MediumLayout, DEVMED_SPARSE, DEVMED_CONST_ALBEDO, DEVMED_MAX_DENSITY,
     PATH_RECORD_DTYPE, CvrError, Context, MediumDesc, PinnedImage, Scene, Stats, default_camera, load,
     medium_from_arrays, tile_origin, tiling, write_hdr, LIB_PATH,
 )
@@ -21,4 +22,5 @@ __all__ = [
     "OPT_MEDIUM_FORMAT", "FORMAT_F32", "FORMAT_F16", "MediumInfo", "half_round",
     "OPT_MOMENTS", "AdaptiveDesc", "AdaptiveResult", "AdaptiveSession", "block_error",
     "DenoiseDesc", "denoise_host",
+    "DeviceMediumDesc", "MediumLayout", "DEVMED_SPARSE", "DEVMED_CONST_ALBEDO", "DEVMED_MAX_DENSITY",
 ]

@@ -135,6 +135,28 @@ class DenoiseDesc(C.Structure):
         super().__init__(passes, sigma, floor, flags)
 
 
+DEVMED_SPARSE, DEVMED_CONST_ALBEDO, DEVMED_MAX_DENSITY = 1, 2, 4
+
+
+class DeviceMediumDesc(C.Structure):
+    """cvr_device_medium_desc: a dense grid in device memory (cvr_set_medium_device)."""
+    _fields_ = [("res", C.c_uint32 * 3), ("flags", C.c_uint32), ("d_density", C.c_void_p),
+                ("d_albedo", C.c_void_p), ("const_albedo", C.c_float * 4), ("box_min", C.c_float * 3),
+                ("box_max", C.c_float * 3), ("scale", C.c_float), ("max_density", C.c_float),
+                ("g", C.c_float), ("roughness", C.c_float * 2), ("eta", C.c_float)]
+
+
+class MediumLayout(C.Structure):
+    """cvr_medium_layout: what an upload built (either path)."""
+    _fields_ = [("sparse", C.c_uint32), ("albedo_uniform", C.c_uint32), ("n_leaves", C.c_uint32),
+                ("n_cell_leaves", C.c_uint32), ("brick_shift", C.c_uint32), ("mask_shift", C.c_uint32),
+                ("albedo_bg", C.c_float * 3), ("mask", C.c_uint32 * 64)]
+
+    def as_dict(self):
+        return {k: (list(getattr(self, k)) if k in ("albedo_bg", "mask") else getattr(self, k))
+                for k, _ in self._fields_}
+
+
 _lib = None
 
 
@@ -220,6 +242,9 @@ def load() -> C.CDLL:
         "cvr_denoise_host": (I32, [P, P, U32, U32, U32, P, C.POINTER(DenoiseDesc), P, P]),
         "cvr_denoise_buffers": (I32, [P, P, P, U32, U32, U32, P, C.POINTER(DenoiseDesc), P, P]),
         "cvr_denoise": (I32, [P, C.POINTER(DenoiseDesc), U32, P, C.c_size_t]),
+        "cvr_set_medium_device": (I32, [P, C.POINTER(DeviceMediumDesc)]),
+        "cvr_medium_layout": (I32, [P, C.POINTER(MediumLayout)]),
+        "cvr_debug_device_medium_ms": (I32, [P, C.POINTER(C.c_double)]),
     }
     # an older experiment build (tools' --lib, A/B against a previous commit) may lack newer entry
     # points; the in-tree library must export every one (tests/test_host_abi.py)
@@ -299,6 +324,24 @@ def _device_ptr(a):
     if a is None:
         return None
     return int(a.data_ptr()) if hasattr(a, "data_ptr") else int(a)
+
+
+def _check_device_grid(name, t, shape, device):
+    """ValueError unless the tensor-like `t` (an object with data_ptr()) is a contiguous float32
+    array of `shape` on cuda device `device`; attributes it does not have are not judged."""
+    dtype = getattr(t, "dtype", None)
+    if dtype is not None and str(dtype).split(".")[-1] != "float32":
+        raise ValueError(f"{name}: dtype {dtype}, expected float32")
+    contiguous = getattr(t, "is_contiguous", None)
+    if contiguous is not None and not contiguous():
+        raise ValueError(f"{name}: not contiguous")
+    if tuple(t.shape) != tuple(shape):
+        raise ValueError(f"{name}: shape {tuple(t.shape)}, expected {tuple(shape)}")
+    dev = getattr(t, "device", None)
+    if dev is not None:
+        kind, index = getattr(dev, "type", None), getattr(dev, "index", None)
+        if kind != "cuda" or (index is not None and index != device):
+            raise ValueError(f"{name}: on {dev}, the context is on cuda:{device}")
 
 
 def default_camera(width: int, height: int):
@@ -492,6 +535,7 @@ class Context:
         _check(lib.cvr_create(device, kid, C.byref(h)))
         self._h = h
         self.kernel = kid
+        self.device = device
 
     def _c(self, code):
         _check(code, self._h)
@@ -501,6 +545,69 @@ class Context:
 
     def set_medium_sparse(self, desc: SparseMediumDesc):
         self._c(load().cvr_set_medium_sparse(self._h, C.byref(desc)))
+
+    def set_medium_device(self, density, albedo=None, *, const_albedo=None, sparse=False, max_density=None,
+                          res=None, box_min=(-0.5,) * 3, box_max=(0.5,) * 3, scale=100.0, g=0.0,
+                          roughness=(0.1, 0.1), eta=None):
+        """The medium from device memory, no host copy (cvr_set_medium_device): the state
+        set_medium / set_medium_sparse leave on host copies of the same arrays.  density: (z, y, x)
+        float32; albedo: (z, y, x, 4) float32, or None with const_albedo (4 floats: every voxel's
+        albedo).  Each an object with data_ptr() (a torch tensor on the context's device,
+        contiguous: checked here, ValueError) or an int device address (then res = (x, y, z) is
+        required and nothing is checked here).  sparse: store as 8^3 leaves by the rule of cvr.h.
+        max_density None: the largest density, found on the device.  Synchronous; torch's current
+        stream is synchronised first, the tensors are only read and may be freed afterwards."""
+        if (albedo is None) == (const_albedo is None):
+            raise ValueError("set_medium_device: give exactly one of albedo and const_albedo")
+        tensors = [t for t in (density, albedo) if hasattr(t, "data_ptr")]
+        if res is None:
+            if not hasattr(density, "data_ptr"):
+                raise ValueError("set_medium_device: res is required with an int address")
+            if len(density.shape) != 3:
+                raise ValueError(f"density: shape {tuple(density.shape)}, expected (z, y, x)")
+            nz, ny, nx = (int(v) for v in density.shape)
+        else:
+            nx, ny, nz = (int(v) for v in res)
+        if hasattr(density, "data_ptr"):
+            _check_device_grid("density", density, (nz, ny, nx), self.device)
+        if hasattr(albedo, "data_ptr"):
+            _check_device_grid("albedo", albedo, (nz, ny, nx, 4), self.device)
+        if const_albedo is not None and len(const_albedo) != 4:
+            raise ValueError("const_albedo: expected 4 floats")
+        d = DeviceMediumDesc()
+        d.res[:] = (nx, ny, nz)
+        d.flags = ((DEVMED_SPARSE if sparse else 0) | (DEVMED_CONST_ALBEDO if albedo is None else 0)
+                   | (DEVMED_MAX_DENSITY if max_density is None else 0))
+        d.d_density = _device_ptr(density)
+        d.d_albedo = _device_ptr(albedo)
+        if const_albedo is not None:
+            d.const_albedo[:] = [float(v) for v in const_albedo]
+        d.box_min[:] = box_min
+        d.box_max[:] = box_max
+        d.scale = scale
+        d.max_density = 0.0 if max_density is None else max_density
+        d.g = g
+        d.roughness[:] = roughness
+        d.eta = np.float32(np.float32(1.05) / np.float32(1.01)) if eta is None else eta
+        if any(type(t).__module__.split(".")[0] == "torch" for t in tensors):
+            import torch
+            torch.cuda.current_stream(self.device).synchronize()
+        self._c(load().cvr_set_medium_device(self._h, C.byref(d)))
+
+    def medium_layout(self) -> MediumLayout:
+        """What the upload built (cvr_medium_layout): sparse or dense, uniform albedo and its value,
+        leaves, cell leaves, brick and mask shifts and the empty-region mask's 64 words."""
+        ml = MediumLayout()
+        self._c(load().cvr_medium_layout(self._h, C.byref(ml)))
+        return ml
+
+    def device_medium_ms(self):
+        """Device ms of the last set_medium_device by group, with OPT_TIMING 1
+        (cvr_debug_device_medium_ms): density scan, albedo scan, leaf flags, scans and scatters,
+        copy / gather, cells + bounds + brick words."""
+        out = (C.c_double * 6)()
+        self._c(load().cvr_debug_device_medium_ms(self._h, out))
+        return list(out)
 
     def set_camera(self, inv_view, raster_to_view, full_res):
         iv = np.ascontiguousarray(inv_view, np.float32)

@@ -212,6 +212,9 @@ struct cvr_ctx {
   uint64_t last_iterations = 0;
   double last_track_ms = 0, last_events_ms = 0;
   bool wf_timing = false;
+  // cvr_set_medium_device with CVR_OPT_TIMING: device ms of its last call's density scan, albedo
+  // scan, leaf flags, scans and scatters, gather, and cells / bounds / brick words
+  double devmed_ms[6] = {0, 0, 0, 0, 0, 0};
 
   cvr_stats last{};
 
@@ -1254,6 +1257,463 @@ int cvr_set_medium_sparse(cvr_ctx* c, const cvr_sparse_medium_desc* sd) {
   c->minfo.bounds_bytes = (nb + 1 + nleaf + (c->d_emask ? cvr::kEmaskWords : 0)) * sizeof(uint32_t);
   c->minfo.total_bytes = c->minfo.density_bytes + c->minfo.cells_bytes + c->minfo.albedo_bytes + c->minfo.bounds_bytes;
   c->have_medium = true;
+  return CVR_OK;
+}
+
+// ---- media built from device memory (cvr_set_medium_device) ----------------
+namespace {
+// Device allocations of one call, freed on every way out of it (keep(): the context owns it now)
+struct DevTemps {
+  std::vector<void*> p;
+  ~DevTemps() {
+    for (void* q : p) (void)hipFree(q);
+  }
+  hipError_t alloc(void** out, size_t bytes) {
+    const hipError_t e = hipMalloc(out, bytes ? bytes : 4);
+    if (e == hipSuccess) p.push_back(*out);
+    return e;
+  }
+  void keep(void* q) { p.erase(std::remove(p.begin(), p.end(), q), p.end()); }
+};
+// Device time of the launches between begin() and end(i), added to devmed_ms[i] (CVR_OPT_TIMING)
+struct DevmedTimer {
+  cvr_ctx* c;
+  hipEvent_t a = nullptr, b = nullptr;
+  bool on;
+  explicit DevmedTimer(cvr_ctx* ctx) : c(ctx), on(ctx->wf_timing) {
+    for (double& v : c->devmed_ms) v = 0.0;
+    if (on) on = hipEventCreate(&a) == hipSuccess && hipEventCreate(&b) == hipSuccess;
+  }
+  ~DevmedTimer() {
+    if (a) (void)hipEventDestroy(a);
+    if (b) (void)hipEventDestroy(b);
+  }
+  void begin() {
+    if (on) (void)hipEventRecord(a, c->stream);
+  }
+  void end(int i) {
+    float ms = 0.f;
+    if (on && hipEventRecord(b, c->stream) == hipSuccess && hipEventSynchronize(b) == hipSuccess &&
+        hipEventElapsedTime(&ms, a, b) == hipSuccess)
+      c->devmed_ms[i] += ms;
+  }
+};
+// p is memory the context's device can read, by what the runtime knows of it: device memory of
+// that device, managed memory, or mapped host memory (an address HIP does not know is refused)
+bool device_readable(const cvr_ctx* c, const void* p) {
+  hipPointerAttribute_t at{};
+  if (hipPointerGetAttributes(&at, p) != hipSuccess) {
+    (void)hipGetLastError();
+    return false;
+  }
+  if (at.type == hipMemoryTypeDevice) return at.device == c->device;
+  return (at.type == hipMemoryTypeManaged || at.type == hipMemoryTypeHost) && at.devicePointer != nullptr;
+}
+bool overflows_half(float f) { return std::fabs(f) >= 65520.0f && std::isfinite(f); }
+
+// The dense half of cvr_set_medium_device: cvr_set_medium from its upload on, the grids copied
+// (format 1: converted) from the caller's device arrays.  `first`: voxel 0's albedo.
+int devmed_dense(cvr_ctx* c, const cvr_device_medium_desc* d, uint32_t fmt, float max_density,
+                 const cvr::MedScan& scan, const float first_rgba[4], DevmedTimer& tm) {
+  const size_t n = (size_t)d->res[0] * d->res[1] * d->res[2];
+  const size_t dB = fmt ? 2 : sizeof(float), cB = fmt ? 16 : 2 * sizeof(float4), aB = fmt ? 8 : sizeof(float4);
+  const bool konst = (d->flags & CVR_DEVMED_CONST_ALBEDO) != 0;
+  free_sparse(c);
+  c->have_medium = false;
+  if (n != c->n_voxels || !c->d_density || c->grids_format != fmt) {
+    if (c->d_density) (void)hipFree(c->d_density);
+    if (c->d_albedo) (void)hipFree(c->d_albedo);
+    c->d_density = nullptr;
+    c->d_albedo = nullptr;
+    c->n_voxels = 0;
+    HIP_TRY(c, hipMalloc(&c->d_density, n * dB));
+    HIP_TRY(c, hipMalloc(&c->d_albedo, n * aB));
+    c->n_voxels = n;
+    c->grids_format = fmt;
+  }
+  tm.begin();
+  if (fmt) {
+    // straight from the caller's fp32 arrays: no staging buffer
+    HIP_TRY(c, cvr::launch_to_half(d->d_density, c->d_density, n, c->stream));
+    if (!konst) HIP_TRY(c, cvr::launch_to_half(d->d_albedo, c->d_albedo, 4 * n, c->stream));
+  } else {
+    HIP_TRY(c, hipMemcpyAsync(c->d_density, d->d_density, n * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
+    if (!konst)
+      HIP_TRY(c, hipMemcpyAsync(c->d_albedo, d->d_albedo, n * sizeof(float4), hipMemcpyDeviceToDevice, c->stream));
+  }
+  if (konst) HIP_TRY(c, cvr::launch_fill_albedo(c->d_albedo, n, fmt, d->const_albedo, c->stream));
+  tm.end(4);
+  if (c->d_cells) (void)hipFree(c->d_cells);
+  c->d_cells = nullptr;
+  tm.begin();
+  if (c->use_cells) {
+    HIP_TRY(c, hipMalloc(&c->d_cells, n * cB));
+    HIP_TRY(c, cvr::launch_build_cells(c->d_density, d->res[0], d->res[1], d->res[2], c->d_cells, c->stream, fmt));
+  }
+  if (c->d_bounds) (void)hipFree(c->d_bounds);
+  c->d_bounds = nullptr;
+  const float sigma = d->scale * max_density;
+  size_t bounds_bytes = 0;
+  uint32_t bnx = 0, bny = 0, bsentinel = 0;
+  if (c->bound_shift && sigma > 0.0f && std::isfinite(sigma) && d->scale > 0.0f) {
+    const uint32_t B = 1u << c->bound_shift;
+    bnx = (d->res[0] + B - 1) / B;
+    bny = (d->res[1] + B - 1) / B;
+    const size_t nb = (size_t)bnx * bny * ((d->res[2] + B - 1) / B);
+    bsentinel = (uint32_t)nb;
+    HIP_TRY(c, hipMalloc(&c->d_bounds, nb + 1));
+    bounds_bytes = nb + 1;
+    HIP_TRY(c, cvr::launch_build_bounds(c->d_density, d->res[0], d->res[1], d->res[2], c->bound_shift, max_density,
+                                        c->d_bounds, c->stream, fmt));
+  }
+  tm.end(5);
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  cvr::MediumParams& m = c->m;
+  m = cvr::MediumParams{};
+  m.bounds = c->d_bounds;
+  m.bshift = c->bound_shift;
+  m.bnx = bnx;
+  m.bny = bny;
+  m.bnxy = bnx * bny;
+  m.bsentinel = bsentinel;
+  m.cells = c->d_cells;
+  m.density = c->d_density;
+  m.albedo = c->d_albedo;
+  fill_medium_common(m, d->res, d->box_min, d->box_max, d->scale, max_density, d->g, d->roughness, d->eta);
+  m.format = fmt;
+  if (c->uniform_albedo && (konst || !(scan.albedo_flags & 1u))) {
+    float first[3] = {first_rgba[0], first_rgba[1], first_rgba[2]};
+    if (fmt)
+      for (float& v : first) v = half_round1(v);
+    m.albedo_uniform = 1u;
+    m.albedo_bg = cvr::V3{first[0], first[1], first[2]};
+  }
+  c->minfo = {};
+  c->minfo.format = (int32_t)fmt;
+  c->minfo.max_density_eff = max_density;
+  c->minfo.density_bytes = n * dB;
+  c->minfo.cells_bytes = c->d_cells ? n * cB : 0;
+  c->minfo.albedo_bytes = n * aB;
+  c->minfo.bounds_bytes = bounds_bytes;
+  c->minfo.total_bytes = c->minfo.density_bytes + c->minfo.cells_bytes + c->minfo.albedo_bytes + c->minfo.bounds_bytes;
+  c->have_medium = true;
+  return CVR_OK;
+}
+
+// The sparse half: the leaf rule on the device, then cvr_set_medium_sparse from its upload on.
+// `bg`: voxel 0's albedo, or the constant.
+int devmed_sparse(cvr_ctx* c, const cvr_device_medium_desc* d, uint32_t fmt, float max_density, uint32_t bshift,
+                  const cvr::MedScan& scan, const float bg[4], cvr::MedScan* d_scan, DevTemps& tmp, DevmedTimer& tm) {
+  const uint32_t* res = d->res;
+  const uint32_t ln[3] = {(res[0] + 7u) / 8u, (res[1] + 7u) / 8u, (res[2] + 7u) / 8u};
+  const size_t nleaf = (size_t)ln[0] * ln[1] * ln[2];
+  const uint32_t B = 1u << bshift;
+  const uint32_t bnx = (res[0] + B - 1) / B, bny = (res[1] + B - 1) / B, bnz = (res[2] + B - 1) / B;
+  const size_t nb = (size_t)bnx * bny * bnz;
+  const bool konst = (d->flags & CVR_DEVMED_CONST_ALBEDO) != 0;
+  // the leaf albedo pool is kept iff some voxel's 16 bytes differ from the background; if none
+  // does, no leaf exists through its albedo either and the albedo is not read again
+  const bool keep_albedo = !konst && (scan.albedo_flags & 2u);
+  const float* albedo = keep_albedo ? d->d_albedo : nullptr;
+  hipStream_t s = c->stream;
+  uint32_t *d_flags = nullptr, *d_sums = nullptr, *d_table = nullptr, *d_slot_leaf = nullptr, *d_slot = nullptr,
+           *d_coords = nullptr;
+  HIP_TRY(c, tmp.alloc((void**)&d_flags, nleaf * sizeof(uint32_t)));
+  HIP_TRY(c, tmp.alloc((void**)&d_sums, cvr::flag_scan_tiles(nleaf) * sizeof(uint32_t)));
+  HIP_TRY(c, tmp.alloc((void**)&d_table, nleaf * sizeof(uint32_t)));
+  uint32_t totals[2] = {0, 0};
+  // leaves: flags -> scan -> table and slots
+  tm.begin();
+  HIP_TRY(c, cvr::launch_leaf_flags(d->d_density, albedo, res, ln, d_flags, s));
+  tm.end(2);
+  tm.begin();
+  HIP_TRY(c, cvr::launch_flag_scan(d_flags, nleaf, d_sums, &d_scan->total[0], s));
+  tm.end(3);
+  HIP_TRY(c, hipStreamSynchronize(s));
+  HIP_TRY(c, hipMemcpy(&totals[0], &d_scan->total[0], sizeof(uint32_t), hipMemcpyDeviceToHost));
+  const uint32_t n_leaves = totals[0];
+  const size_t np = (size_t)n_leaves * 512;
+  HIP_TRY(c, tmp.alloc((void**)&d_slot_leaf, (size_t)n_leaves * sizeof(uint32_t)));
+  tm.begin();
+  HIP_TRY(c, cvr::launch_scatter_leaves(d_flags, nleaf, d_sums, d_table, d_slot_leaf, s));
+  // cell leaves: a leaf's cells read the corners in it and its forward neighbours
+  HIP_TRY(c, cvr::launch_cell_leaf_flags(d_table, ln, d_flags, s));
+  HIP_TRY(c, cvr::launch_flag_scan(d_flags, nleaf, d_sums, &d_scan->total[1], s));
+  tm.end(3);
+  HIP_TRY(c, hipStreamSynchronize(s));
+  HIP_TRY(c, hipMemcpy(&totals[1], &d_scan->total[1], sizeof(uint32_t), hipMemcpyDeviceToHost));
+  const size_t ncl = (size_t)totals[1] + 1;  // slot 0: the zero leaf
+  if (ncl > (1u << 24))
+    return set_err(&c->err, CVR_ERR_UNSUPPORTED, "sparse medium needs %zu cell leaves (> 2^24)", ncl);
+  const size_t dB = fmt ? 2 : sizeof(float), cB = fmt ? 16 : 2 * sizeof(float4), aB = fmt ? 8 : sizeof(float4);
+  if (fmt) {
+    // cvr_set_medium_sparse names the pools' first overflowing index: when the scans of the grid
+    // saw an overflow, the gather runs once without storing to find that index
+    size_t at = 0;
+    const char* what = nullptr;
+    float value = 0.0f;
+    if (scan.ovf_density != ~0ull || scan.ovf_albedo != ~0ull) {
+      cvr::MedScan chk = scan;
+      chk.ovf_density = chk.ovf_albedo = ~0ull;
+      HIP_TRY(c, hipMemcpy(d_scan, &chk, sizeof(chk), hipMemcpyHostToDevice));
+      HIP_TRY(c, cvr::launch_gather_leaves(d->d_density, albedo, res, ln, d_slot_leaf, n_leaves, bg, fmt, nullptr,
+                                           nullptr, d_scan, s));
+      HIP_TRY(c, hipStreamSynchronize(s));
+      HIP_TRY(c, hipMemcpy(&chk, d_scan, sizeof(chk), hipMemcpyDeviceToHost));
+      const bool in_density = chk.ovf_density != ~0ull;
+      if (in_density || chk.ovf_albedo != ~0ull) {
+        what = in_density ? "leaf density" : "leaf albedo";
+        at = (size_t)(in_density ? chk.ovf_density : chk.ovf_albedo);
+        // the value, for the message: the pool voxel's grid voxel, or the background's channel
+        const size_t p = in_density ? at : at / 4;
+        uint32_t leaf = 0;
+        HIP_TRY(c, hipMemcpy(&leaf, d_slot_leaf + (p >> 9), sizeof(leaf), hipMemcpyDeviceToHost));
+        const uint32_t local = (uint32_t)(p & 511u);
+        const uint32_t x = (leaf % ln[0]) * 8u + (local & 7u), y = ((leaf / ln[0]) % ln[1]) * 8u + ((local >> 3) & 7u),
+                       z = (leaf / (ln[0] * ln[1])) * 8u + (local >> 6);
+        const size_t i = ((size_t)z * res[1] + y) * res[0] + x;
+        if (x < res[0] && y < res[1] && z < res[2])
+          HIP_TRY(c, hipMemcpy(&value, in_density ? d->d_density + i : d->d_albedo + 4 * i + at % 4, sizeof(float),
+                               hipMemcpyDeviceToHost));
+        else
+          value = in_density ? 0.0f : bg[at % 4];
+      }
+    }
+    for (size_t k = 0; k < 3 && !what; ++k)
+      if (overflows_half(bg[k])) what = "albedo_background", at = k, value = bg[k];
+    if (what) {
+      c->have_medium = false;
+      return set_err(&c->err, CVR_ERR_INVALID, "medium format half: %s value %g at index %zu rounds to infinity", what,
+                     (double)value, at);
+    }
+  }
+  // drop the previous medium (dense or sparse)
+  if (c->d_density) (void)hipFree(c->d_density);
+  if (c->d_albedo) (void)hipFree(c->d_albedo);
+  if (c->d_cells) (void)hipFree(c->d_cells);
+  if (c->d_bounds) (void)hipFree(c->d_bounds);
+  c->d_density = nullptr;
+  c->d_albedo = nullptr;
+  c->d_cells = nullptr;
+  c->d_bounds = nullptr;
+  c->n_voxels = 0;
+  c->have_medium = false;
+  free_sparse(c);
+  tmp.keep(d_table);
+  c->d_leaves = d_table;
+  HIP_TRY(c, hipMalloc(&c->d_leaf_density, (np ? np : 1) * dB));
+  if (keep_albedo && np) HIP_TRY(c, hipMalloc(&c->d_leaf_albedo, np * aB));
+  tm.begin();
+  HIP_TRY(c, cvr::launch_gather_leaves(d->d_density, c->d_leaf_albedo ? albedo : nullptr, res, ln, d_slot_leaf,
+                                       n_leaves, bg, fmt, c->d_leaf_density, c->d_leaf_albedo, nullptr, s));
+  tm.end(4);
+  cvr::MediumParams& m = c->m;
+  m = cvr::MediumParams{};
+  fill_medium_common(m, res, d->box_min, d->box_max, d->scale, max_density, d->g, d->roughness, d->eta);
+  m.format = fmt;
+  m.leaves = c->d_leaves;
+  m.leaf_density = c->d_leaf_density;
+  m.leaf_albedo = c->d_leaf_albedo;
+  m.lnx = ln[0];
+  m.lny = ln[1];
+  m.albedo_bg = cvr::V3{bg[0], bg[1], bg[2]};
+  if (fmt) m.albedo_bg = cvr::V3{half_round1(bg[0]), half_round1(bg[1]), half_round1(bg[2])};
+  const float sigma = d->scale * max_density;
+  const int unbounded = !(c->bound_shift && sigma > 0.0f && std::isfinite(sigma) && d->scale > 0.0f);
+  m.bshift = bshift;
+  m.bnx = bnx;
+  m.bny = bny;
+  m.bnxy = bnx * bny;
+  m.bsentinel = (uint32_t)nb;
+  HIP_TRY(c, hipMalloc(&c->d_sbounds, (nb + 1) * sizeof(uint32_t)));
+  if (c->use_cells) HIP_TRY(c, hipMalloc(&c->d_cells, ncl * 512 * cB));
+  // the empty-region mask's geometry, as cvr_set_medium_sparse derives it
+  uint32_t es = 3, lx = 0, ly = 0;
+  if (!unbounded) {
+    auto log2up = [](uint32_t v) {
+      uint32_t l = 0;
+      while ((1u << l) < v) ++l;
+      return l;
+    };
+    lx = log2up(ln[0]);
+    ly = log2up(ln[1]);
+    uint32_t lz = log2up(ln[2]);
+    while (lx + ly + lz > log2up(32u * cvr::kEmaskWords)) {
+      ++es;
+      lx -= lx > 0;
+      ly -= ly > 0;
+      lz -= lz > 0;
+    }
+    HIP_TRY(c, hipMalloc(&c->d_emask, cvr::kEmaskWords * sizeof(uint32_t)));
+    HIP_TRY(c, hipMemsetAsync(c->d_emask, 0, cvr::kEmaskWords * sizeof(uint32_t), s));
+    m.eshift = es;
+    m.eshy = lx;
+    m.eshz = lx + ly;
+    m.emask = c->d_emask;
+  }
+  HIP_TRY(c, tmp.alloc((void**)&d_slot, nleaf * sizeof(uint32_t)));
+  HIP_TRY(c, tmp.alloc((void**)&d_coords, 3 * ncl * sizeof(uint32_t)));
+  tm.begin();
+  HIP_TRY(c, cvr::launch_scatter_cell_leaves(d_flags, nleaf, d_sums, ln, d_slot, d_coords, c->d_emask, es - 3u, lx,
+                                             lx + ly, s));
+  tm.end(3);
+  tm.begin();
+  HIP_TRY(c, cvr::launch_build_sparse(m, d_coords, c->use_cells ? ncl : 0, d_slot, bnz, max_density, unbounded,
+                                      c->d_cells, c->d_sbounds, s));
+  tm.end(5);
+  HIP_TRY(c, hipStreamSynchronize(s));
+  m.cells = c->d_cells;
+  m.sbounds = c->d_sbounds;
+  c->n_cell_leaves = ncl;
+  c->minfo = {};
+  c->minfo.format = (int32_t)fmt;
+  c->minfo.max_density_eff = max_density;
+  c->minfo.density_bytes = (np ? np : 1) * dB;
+  c->minfo.cells_bytes = c->d_cells ? ncl * 512 * cB : 0;
+  c->minfo.albedo_bytes = c->d_leaf_albedo ? np * aB : 0;
+  c->minfo.bounds_bytes = (nb + 1 + nleaf + (c->d_emask ? cvr::kEmaskWords : 0)) * sizeof(uint32_t);
+  c->minfo.total_bytes = c->minfo.density_bytes + c->minfo.cells_bytes + c->minfo.albedo_bytes + c->minfo.bounds_bytes;
+  c->have_medium = true;
+  return CVR_OK;
+}
+}  // namespace
+
+int cvr_set_medium_device(cvr_ctx* c, const cvr_device_medium_desc* d) {
+  if (!c || !d) return set_err(c ? &c->err : nullptr, CVR_ERR_INVALID, "NULL argument");
+  CVR_NOT_IN_SESSION(c, "cvr_set_medium_device");
+  const uint32_t* res = d->res;
+  const bool sparse = (d->flags & CVR_DEVMED_SPARSE) != 0, konst = (d->flags & CVR_DEVMED_CONST_ALBEDO) != 0;
+  const uint32_t fmt = (uint32_t)c->medium_format;
+  // the host calls' shape guards, in their order and words, from res alone
+  if (res[0] == 0 || res[1] == 0 || res[2] == 0) return set_err(&c->err, CVR_ERR_INVALID, "empty grid");
+  const size_t n = (size_t)res[0] * res[1] * res[2];
+  uint32_t bshift = 0;
+  if (!sparse) {
+    if (n > 0xFFFFFFFFull) return set_err(&c->err, CVR_ERR_INVALID, "grid exceeds 2^32 voxels");
+    if ((uint64_t)res[1] * res[2] >= (1ull << 24) || (uint64_t)res[0] * res[1] >= (1ull << 24))
+      return set_err(&c->err, CVR_ERR_UNSUPPORTED, "dense grid with y*z or x*y >= 2^24: use cvr_set_medium_sparse");
+    if (!fmt && c->use_cells && n >= (1ull << 31))
+      return set_err(&c->err, CVR_ERR_UNSUPPORTED,
+                     "dense fp32 grid of %zu voxels (>= 2^31) with density cells: use CVR_OPT_MEDIUM_FORMAT 1, "
+                     "CVR_OPT_CELLS 0 or cvr_set_medium_sparse",
+                     n);
+  } else {
+    const size_t nleaf = (size_t)((res[0] + 7u) / 8u) * ((res[1] + 7u) / 8u) * ((res[2] + 7u) / 8u);
+    if (nleaf > 0xFFFFFFFFull) return set_err(&c->err, CVR_ERR_INVALID, "leaf table exceeds 2^32 entries");
+    bshift = !c->bound_shift_set ? 3u : c->bound_shift == 0 ? 2u : std::min(c->bound_shift, 3u);
+    const uint32_t B = 1u << bshift;
+    const uint32_t bnx = (res[0] + B - 1) / B, bny = (res[1] + B - 1) / B, bnz = (res[2] + B - 1) / B;
+    const size_t nb = (size_t)bnx * bny * bnz;
+    if ((uint64_t)bnx * bny >= (1ull << 24) || bnz > (1u << 24) || nb >= 0xFFFFFFFFull)
+      return set_err(&c->err, CVR_ERR_UNSUPPORTED,
+                     "sparse grid of %ux%ux%u bricks: x*y >= 2^24, z > 2^24 or %zu bricks >= 2^32 - 1 (a larger "
+                     "CVR_OPT_BOUNDS brick, up to 8 cells, has fewer)",
+                     bnx, bny, bnz, nb);
+  }
+  // then the flags and the pointers
+  if (d->flags & ~(uint32_t)(CVR_DEVMED_SPARSE | CVR_DEVMED_CONST_ALBEDO | CVR_DEVMED_MAX_DENSITY))
+    return set_err(&c->err, CVR_ERR_INVALID, "unknown cvr_device_medium_desc flags 0x%x", d->flags);
+  if (!d->d_density || (!konst && !d->d_albedo)) return set_err(&c->err, CVR_ERR_INVALID, "d_density/d_albedo is NULL");
+  if (konst && d->d_albedo)
+    return set_err(&c->err, CVR_ERR_INVALID, "d_albedo must be NULL with CVR_DEVMED_CONST_ALBEDO");
+  int r = ensure_device(c);
+  if (r) return r;
+  if (!device_readable(c, d->d_density) || (!konst && !device_readable(c, d->d_albedo)))
+    return set_err(&c->err, CVR_ERR_INVALID, "d_density/d_albedo is not device-accessible memory of device %d",
+                   c->device);
+  if (((uintptr_t)d->d_density & 3u) || ((uintptr_t)d->d_albedo & 15u))
+    return set_err(&c->err, CVR_ERR_INVALID, "d_density must be 4-byte and d_albedo 16-byte aligned");
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  DevTemps tmp;
+  DevmedTimer tm(c);
+  // the value scans: majorant, binary16 overflow, albedo sameness
+  cvr::MedScan scan{~0ull, ~0ull, 0u, 0u, {0u, 0u}};
+  cvr::MedScan* d_scan = nullptr;
+  HIP_TRY(c, tmp.alloc((void**)&d_scan, sizeof(scan)));
+  HIP_TRY(c, hipMemcpy(d_scan, &scan, sizeof(scan), hipMemcpyHostToDevice));
+  float first[4] = {d->const_albedo[0], d->const_albedo[1], d->const_albedo[2], d->const_albedo[3]};
+  if (fmt || (d->flags & CVR_DEVMED_MAX_DENSITY)) {
+    tm.begin();
+    HIP_TRY(c, cvr::launch_scan_density(d->d_density, n, fmt, d_scan, c->stream));
+    tm.end(0);
+  }
+  if (!konst) {
+    if (fmt || sparse || c->uniform_albedo) {
+      tm.begin();
+      HIP_TRY(c, cvr::launch_scan_albedo(d->d_albedo, n, fmt, d_scan, c->stream));
+      tm.end(1);
+    }
+    HIP_TRY(c, hipMemcpyAsync(first, d->d_albedo, sizeof(first), hipMemcpyDeviceToHost, c->stream));
+  }
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  HIP_TRY(c, hipMemcpy(&scan, d_scan, sizeof(scan), hipMemcpyDeviceToHost));
+  float max_density = d->max_density;
+  if (d->flags & CVR_DEVMED_MAX_DENSITY) memcpy(&max_density, &scan.max_bits, sizeof(float));
+  if (fmt) max_density = half_majorant(max_density);
+  if (sparse) return devmed_sparse(c, d, fmt, max_density, bshift, scan, first, d_scan, tmp, tm);
+  if (fmt) {
+    // cvr_set_medium's refusal: density before albedo, the smallest index (a constant albedo's
+    // grid overflows first at voxel 0)
+    const bool bad_d = scan.ovf_density != ~0ull;
+    size_t at = (size_t)scan.ovf_density;
+    float value = 0.0f;
+    bool bad_a = false;
+    if (bad_d) {
+      HIP_TRY(c, hipMemcpy(&value, d->d_density + at, sizeof(float), hipMemcpyDeviceToHost));
+    } else if (konst) {
+      for (size_t k = 0; k < 3 && !bad_a; ++k)
+        if (overflows_half(first[k])) bad_a = true, at = k, value = first[k];
+    } else if (scan.ovf_albedo != ~0ull) {
+      bad_a = true;
+      at = (size_t)scan.ovf_albedo;
+      HIP_TRY(c, hipMemcpy(&value, d->d_albedo + at, sizeof(float), hipMemcpyDeviceToHost));
+    }
+    if (bad_d || bad_a) {
+      c->have_medium = false;
+      return set_err(&c->err, CVR_ERR_INVALID, "medium format half: %s value %g at index %zu rounds to infinity",
+                     bad_d ? "density" : "albedo", (double)value, at);
+    }
+  }
+  return devmed_dense(c, d, fmt, max_density, scan, first, tm);
+}
+
+int cvr_debug_device_medium_ms(const cvr_ctx* c, double out[6]) {
+  if (!c || !out) return set_err(nullptr, CVR_ERR_INVALID, "NULL argument");
+  for (int i = 0; i < 6; ++i) out[i] = c->devmed_ms[i];
+  return CVR_OK;
+}
+
+int cvr_medium_layout(const cvr_ctx* c, struct cvr_medium_layout* out) {
+  if (!c || !out) return set_err(nullptr, CVR_ERR_INVALID, "NULL argument");
+  if (!c->have_medium) {
+    cvr::set_last_error("no medium");
+    return CVR_ERR_STATE;
+  }
+  const cvr::MediumParams& m = c->m;
+  struct cvr_medium_layout l {};
+  l.sparse = m.leaves != nullptr;
+  l.albedo_uniform = m.albedo_uniform;
+  if (l.sparse) {
+    // (the leaf pool holds 512 voxels per leaf, one voxel when there is no leaf)
+    l.n_leaves = (uint32_t)(c->minfo.density_bytes / (512u * (m.format ? 2u : 4u)));
+    l.n_cell_leaves = (uint32_t)c->n_cell_leaves;
+  }
+  l.brick_shift = m.bshift;
+  l.mask_shift = m.eshift;
+  if (l.sparse || m.albedo_uniform) {
+    l.albedo_bg[0] = m.albedo_bg.x;
+    l.albedo_bg[1] = m.albedo_bg.y;
+    l.albedo_bg[2] = m.albedo_bg.z;
+  }
+  if (m.emask) {
+    // the medium's own mask (a shared medium: the source context's buffer)
+    if (hipSetDevice(c->device) != hipSuccess ||
+        hipMemcpy(l.mask, m.emask, sizeof(l.mask), hipMemcpyDeviceToHost) != hipSuccess) {
+      cvr::set_last_error("cvr_medium_layout: reading the mask failed");
+      return CVR_ERR_HIP;
+    }
+  }
+  *out = l;
   return CVR_OK;
 }
 

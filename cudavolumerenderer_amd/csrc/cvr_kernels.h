@@ -115,6 +115,44 @@ hipError_t launch_build_cells(const float* density, uint32_t rx, uint32_t ry, ui
 // The half storage format (MediumParams::format 1; `format` above: `density` holds halves and
 // the cells are written as 8 halves): n fp32 values -> n binary16, round to nearest even.
 hipError_t launch_to_half(const float* src, void* dst, size_t n, hipStream_t s);
+// Media built from device memory (cvr_set_medium_device; cvr_medium_build.hip).  Every array below
+// is device memory; the launches are asynchronous on s and none waits on another workgroup.
+// What the value scans find, in device memory; the host sets ovf_* to ~0 and the rest to 0 first.
+struct MedScan {
+  unsigned long long ovf_density;  // smallest index whose finite value rounds to +-inf in binary16 (format 1)
+  unsigned long long ovf_albedo;   // the same over the albedo's r, g, b (index 4 voxel + channel)
+  uint32_t max_bits;               // bits of max(0, every non-NaN density)
+  uint32_t albedo_flags;           // bit 0: an rgb (format 1: rounded to half) differs from voxel 0's;
+                                   // bit 1: a voxel's 16 bytes differ from voxel 0's
+  uint32_t total[2];               // totals of the two flag scans (launch_flag_scan)
+};
+hipError_t launch_scan_density(const float* density, size_t n, uint32_t format, MedScan* out, hipStream_t s);
+hipError_t launch_scan_albedo(const float* albedo, size_t n, uint32_t format, MedScan* out, hipStream_t s);
+// n albedo voxels of the context's grid (float4, format 1: 4 halves) set to `value`
+hipError_t launch_fill_albedo(void* albedo, size_t n, uint32_t format, const float value[4], hipStream_t s);
+// The leaf rule of cvr.h: flags[leaf] = the leaf exists (albedo null: by density alone); ln = ceil(res / 8).
+hipError_t launch_leaf_flags(const float* density, const float* albedo, const uint32_t res[3], const uint32_t ln[3],
+                             uint32_t* flags, hipStream_t s);
+// flags[leaf] = the leaf or one of its 7 forward neighbours is in `table`
+hipError_t launch_cell_leaf_flags(const uint32_t* table, const uint32_t ln[3], uint32_t* flags, hipStream_t s);
+// Exclusive scan of n 0/1 flags, first two launches: sums (flag_scan_tiles(n) words) receives the
+// number of set flags before each tile, *total their number.  The scatters below finish it.
+size_t flag_scan_tiles(size_t n);
+hipError_t launch_flag_scan(const uint32_t* flags, size_t n, uint32_t* sums, uint32_t* total, hipStream_t s);
+// table[leaf] = slot or CVR_NO_LEAF, slots in leaf order; slot_leaf[slot] = leaf (*total words)
+hipError_t launch_scatter_leaves(const uint32_t* flags, size_t n, const uint32_t* sums, uint32_t* table,
+                                 uint32_t* slot_leaf, hipStream_t s);
+// launch_build_sparse's cell_slot and coords (3 (*total + 1) words, slot 0 the zero leaf), and the
+// empty-region mask's bits (emask: kEmaskWords zeroed words or null; super-bricks of 2^(3 + k_shift) cells)
+hipError_t launch_scatter_cell_leaves(const uint32_t* flags, size_t n, const uint32_t* sums, const uint32_t ln[3],
+                                      uint32_t* cell_slot, uint32_t* coords, uint32_t* emask, uint32_t k_shift,
+                                      uint32_t shy, uint32_t shz, hipStream_t s);
+// The stored leaves' pools from the grid (albedo null: none), out-of-grid voxels (0, bg), format 1
+// converted to binary16.  check non-null: nothing is stored; check->ovf_* receive the smallest pool
+// index that overflows binary16.
+hipError_t launch_gather_leaves(const float* density, const float* albedo, const uint32_t res[3], const uint32_t ln[3],
+                                const uint32_t* slot_leaf, size_t n_leaves, const float bg[4], uint32_t format,
+                                void* leaf_density, void* leaf_albedo, MedScan* check, hipStream_t s);
 // cvr_debug_fastdiv (tests): q[i] = fastdiv(u[i], f) on the device, u and q device arrays.
 hipError_t launch_debug_fastdiv(FastDiv f, const uint32_t* u, uint32_t* q, size_t n, hipStream_t s);
 hipError_t launch_tile_to_image(const float4* tile, uint32_t tw, uint32_t th, float4* image, uint32_t iw,

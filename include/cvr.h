@@ -28,6 +28,8 @@ extern "C" {
  *              5: CVR_OPT_MEDIUM_FORMAT, cvr_half_round, cvr_medium_info;
  *              6: CVR_OPT_MOMENTS, cvr_copy_moments, cvr_block_error, cvr_adaptive_*
  *              6 + CVR_HAS_DENOISE (no new number, an addition within 6): cvr_denoise_desc, cvr_denoise*
+ *              6 + CVR_HAS_DEVICE_MEDIUM (likewise): cvr_device_medium_desc, cvr_set_medium_device,
+ *                  cvr_medium_layout
  * CVR_ABI_VERSION is the ABI this header declares: 6, the library's (cvr_abi_version()).  ABI 6 only
  * adds to ABI 5, so a host that must also load an ABI 5 library can hold itself to that surface:
  * with CVR_ABI_TARGET defined as 5 before the include, the ABI 6 functions and structs are not
@@ -665,6 +667,66 @@ int cvr_denoise_buffers(cvr_ctx* ctx, const float* d_sum_rgba, const float* d_m2
  * accumulated since the last clear (else CVR_ERR_INVALID).  Reads the framebuffer and the
  * moments and never writes them.  Available between cvr_adaptive_begin and cvr_adaptive_end. */
 int cvr_denoise(cvr_ctx* ctx, const cvr_denoise_desc* desc, uint32_t n_samples, float* host_rgba, size_t host_floats);
+
+/* ---- media built from device memory (extension within ABI 6: CVR_HAS_DEVICE_MEDIUM) -- */
+/* The dense grid of cvr_medium_desc, read from device memory (a torch tensor, a simulation's
+ * output): no array of the medium crosses to the host, only scalars do (counts, flags, the
+ * majorant, the first overflowing index, voxel 0's albedo and the 256 bytes of the mask).
+ * The call leaves the context in the state the host call leaves it in on host copies of the same
+ * arrays: the same cvr_medium_info and cvr_medium_layout, the same paths bit for bit.
+ *  - without CVR_DEVMED_SPARSE the host call is cvr_set_medium;
+ *  - with it, cvr_set_medium_sparse on the leaves of this rule (the one cvr_scene_sparse_medium
+ *    applies): leaves in z, y, x order, x fastest, slots numbered in that order; a leaf exists
+ *    iff one of its in-grid voxels has density != 0.0f (-0 makes none, NaN makes one) or 16
+ *    albedo bytes that differ from voxel (0,0,0)'s, which are the background; out-of-grid voxels
+ *    of a stored leaf hold density 0 and the background; the leaf albedo pool is dropped when no
+ *    in-grid voxel differs from the background;
+ *  - CVR_DEVMED_CONST_ALBEDO is the host call on a grid filled with const_albedo (dense: the
+ *    context's albedo grid is filled on the device; sparse: the constant is the background, no
+ *    leaf albedo, leaves exist by density alone);
+ *  - CVR_DEVMED_MAX_DENSITY takes max(0, every non-NaN voxel) for max_density.
+ * Refusals: the shape guards of the host call, in its order, with its codes and texts, from res
+ * alone and before any pointer is looked at (the previous medium is kept); unknown flags, a NULL
+ * pointer (d_albedo: NULL without CVR_DEVMED_CONST_ALBEDO, non-NULL with it) or one that
+ * hipPointerGetAttributes does not report as device-accessible memory of the context's device:
+ * CVR_ERR_INVALID (previous medium kept); CVR_FORMAT_F16 overflow: the host call's code and
+ * message (density before albedo, the smallest index; the context is left without a medium);
+ * more than 2^24 cell leaves: CVR_ERR_UNSUPPORTED; inside an adaptive session: CVR_ERR_STATE.
+ * Synchronous; reads the arrays on the context's stream, so the caller has made them ready
+ * before the call.  The context copies what it keeps: the arrays are only read and may be freed
+ * afterwards.  In CVR_FORMAT_F16 the halves are converted straight from the caller's fp32 arrays:
+ * there is no fp32 staging buffer (the host calls allocate one of the albedo's fp32 size), so the
+ * upload's peak device memory is the stored medium plus, for CVR_DEVMED_SPARSE, the build tables
+ * (up to three words per leaf and three per cell leaf).
+ * Not supported: aliasing the caller's arrays (the context always copies), partial updates. */
+#define CVR_HAS_DEVICE_MEDIUM 1
+enum { CVR_DEVMED_SPARSE = 1,        /* store as 8^3 leaves (the rule above) */
+       CVR_DEVMED_CONST_ALBEDO = 2,  /* d_albedo is NULL: every voxel has const_albedo */
+       CVR_DEVMED_MAX_DENSITY = 4 }; /* ignore max_density: use max(0, every non-NaN voxel), found on the device */
+typedef struct cvr_device_medium_desc {
+  uint32_t res[3];
+  uint32_t flags;
+  const float* d_density; /* device, res product fp32, x fastest, contiguous */
+  const float* d_albedo;  /* device, 4 floats per voxel (16-byte aligned), or NULL with CONST_ALBEDO */
+  float const_albedo[4];
+  float box_min[3], box_max[3];
+  float scale, max_density, g, roughness[2], eta;
+} cvr_device_medium_desc; /* 96 bytes */
+int cvr_set_medium_device(cvr_ctx* ctx, const cvr_device_medium_desc* medium);
+/* Measurement only: with CVR_OPT_TIMING 1, the device milliseconds (HIP events) the last
+ * cvr_set_medium_device spent in {density scan, albedo scan, leaf flags, scans and scatters,
+ * copy / conversion / gather, cells + bounds + brick words}; zeros otherwise.  Timing adds a host
+ * synchronisation per group. */
+int cvr_debug_device_medium_ms(const cvr_ctx* ctx, double out_ms[6]);
+
+/* What was built, by either upload path (a shared medium: the source's).  mask: the empty-region
+ * mask words, all 0 when there is none (dense media, bounds off).  CVR_ERR_STATE: no medium. */
+struct cvr_medium_layout {
+  uint32_t sparse, albedo_uniform, n_leaves, n_cell_leaves, brick_shift, mask_shift;
+  float albedo_bg[3];
+  uint32_t mask[64];
+};
+int cvr_medium_layout(const cvr_ctx* ctx, struct cvr_medium_layout* out);
 #endif /* CVR_ABI_VERSION >= 6 */
 
 /* Pinned, device-mapped host memory for cvr_render_share_to_host /
