@@ -1,5 +1,5 @@
-// cvr_api.cpp - C ABI implementation: contexts (kernel launchers), device
-// volume upload, the CudaVolPath tile loop, camera/tiling helpers.
+// cvr_api.cpp - C ABI implementation: contexts (kernel launchers), the
+// CudaVolPath tile loop, camera/tiling helpers (the medium: cvr_medium.cpp).
 //
 // Reference map:
 //   RenderKernelLauncher / VolPTKernelLauncher  RenderKernelLauncher.h:20-174,
@@ -18,13 +18,13 @@
 #include <string>
 #include <vector>
 
-#include "cvr.h"
-#include "cvr_kernels.h"
+#include "cvr_ctx.h"
 
 namespace {
-
 thread_local std::string g_last_error;
+}  // namespace
 
+namespace cvr {
 int set_err(std::string* dst, int code, const char* fmt, ...) {
   char buf[512];
   va_list ap;
@@ -36,9 +36,11 @@ int set_err(std::string* dst, int code, const char* fmt, ...) {
   return code;
 }
 
-}  // namespace
+int ensure_device(cvr_ctx* c) {
+  HIP_TRY(c, hipSetDevice(c->device));
+  return CVR_OK;
+}
 
-namespace cvr {
 void set_last_error(const std::string& msg) { g_last_error = msg; }
 
 // Camera(res, fov_x) then setResolution(w, h) -> setFovFromX (Camera.h:25-71),
@@ -56,238 +58,13 @@ void camera_for_fov(float fov_x, uint32_t w, uint32_t h, float inv_view[12], flo
 }
 }  // namespace cvr
 
-namespace {
-// f32 -> binary16 -> f32, round to nearest even, subnormals kept (CVR_OPT_MEDIUM_FORMAT 1).
-float half_round1(float f) {
-  uint32_t u;
-  memcpy(&u, &f, 4);
-  const uint32_t sign = u & 0x80000000u, a = u & 0x7FFFFFFFu;
-  uint32_t r;
-  if (a >= 0x7F800000u) {
-    // inf stays inf; NaN keeps its top 10 payload bits and stays NaN (quiet bit set if they are all 0)
-    r = a == 0x7F800000u ? a : ((a & 0xFFFFE000u) | 0x00400000u);
-  } else if (a >= 0x477FF000u) {
-    r = 0x7F800000u;  // >= 65520: rounds to inf
-  } else if (a >= 0x38800000u) {
-    // normal half: keep 10 mantissa bits, nearest even on the 13 dropped (a carry moves to the next
-    // exponent, at most to 65504's successor, excluded above)
-    r = (a + 0x00000FFFu + ((a >> 13) & 1u)) & 0xFFFFE000u;
-  } else {
-    // below 2^-14: multiples of 2^-24.  Adding 2^-1 (ulp 2^-24 in [0.5, 1)) rounds to nearest even.
-    float t;
-    memcpy(&t, &a, 4);
-    const float k = (t + 0.5f) - 0.5f;
-    memcpy(&r, &k, 4);
-  }
-  r |= sign;
-  float o;
-  memcpy(&o, &r, 4);
-  return o;
-}
-// first finite value of v[0..n) (of every `stride`-th group's first `take` values) that rounds to +-inf
-bool half_overflows(const float* v, size_t n, size_t stride, size_t take, size_t* at) {
-  for (size_t i = 0; i < n; ++i)
-    for (size_t k = 0; k < take; ++k) {
-      const float f = v[i * stride + k];
-      if (std::fabs(f) >= 65520.0f && std::isfinite(f)) {
-        *at = i * stride + k;
-        return true;
-      }
-    }
-  return false;
-}
-// the format-1 majorant: max(max_density, f32(f16(max_density))), max_density itself if that overflows
-float half_majorant(float max_density) {
-  const float h = half_round1(max_density);
-  return (std::isfinite(h) && h > max_density) ? h : max_density;
-}
-}  // namespace
-
-struct cvr_ctx {
-  int device = 0;
-  int kernel = CVR_KERNEL_REGENERATION_SK;
-  std::string err;
-
-  hipStream_t own_stream = nullptr;
-  hipStream_t stream = nullptr;
-  hipEvent_t ev_start = nullptr, ev_stop = nullptr;
-  bool timed = false;
-
-  // medium in HBM
-  float* d_density = nullptr;
-  float4* d_albedo = nullptr;
-  float4* d_cells = nullptr;  // corner-replicated density (MediumParams::cells)
-  bool use_cells = true;
-  bool uniform_albedo = true;  // CVR_OPT_UNIFORM_ALBEDO
-  uint8_t* d_bounds = nullptr;  // brick bounds (MediumParams::bounds)
-  uint32_t bound_shift = 2;     // log2 brick size, 0 = off
-  bool bound_shift_set = false; // CVR_OPT_BOUNDS given (else sparse media use 8^3 bricks)
-  size_t n_voxels = 0;
-  uint32_t grids_format = 0;  // format d_density / d_albedo were allocated for
-  // sparse medium (cvr_set_medium_sparse)
-  uint32_t* d_leaves = nullptr;
-  float* d_leaf_density = nullptr;
-  float4* d_leaf_albedo = nullptr;
-  uint32_t* d_sbounds = nullptr;
-  uint32_t* d_emask = nullptr;       // empty-region mask (MediumParams::emask)
-  uint32_t* d_block_perm = nullptr;  // cvr_set_block_order
-  void* d_rec_active = nullptr;      // cvr_trace_launch: records of the launch in progress
-  uint32_t block_perm_n = 0;
-  size_t n_cell_leaves = 0;  // cell-leaf pool slots (incl. the zero slot)
-  bool have_medium = false;
-  cvr::MediumParams m{};
-  int medium_format = 0;     // CVR_OPT_MEDIUM_FORMAT (the next set-medium's; the medium's own is m.format)
-  struct cvr_medium_info minfo{};  // cvr_medium_info of the medium in use (own or shared)
-
-  // launcher state (the reference's __constant__ symbols)
-  float inv_view[12] = {1, 0, 0, 0, 0, -1, 0, 0, 0, 0, -1, 100};
-  float r2v[2] = {0, 0};
-  float full_res[2] = {0, 0};
-  bool have_camera = false;
-  uint32_t tile_w = 0, tile_h = 0;
-  uint32_t off[2] = {0, 0};
-  uint32_t iterations = 1;
-  uint64_t n_paths = 0;
-  uint64_t range_first = 0, range_count = UINT64_MAX;
-  uint32_t shard_rank = 0, shard_world = 1;  // cvr_set_block_shard
-  uint32_t seed = 0;
-
-  float4* d_out_owned = nullptr;
-  size_t out_owned_px = 0;
-  float4* d_out = nullptr;  // active output (owned or external)
-  bool external_out = false;
-
-  unsigned char* d_work = nullptr;  // queue heads + stats counters (kWork* layout)
-  float4* d_pool_T = nullptr;       // wave-pool scheduler: event-only slot part (LaunchParams::pool_T)
-  unsigned char* d_smk = nullptr;   // thread-bound streamingMK: slot buffers, flags, RNG states, counters
-  size_t smk_n = 0;                 // threads d_smk is carved for
-  size_t pool_T_n = 0;
-  uint32_t n_queues = 8;            // work-order bands (one per XCD)
-  uint32_t subqueues = 8;           // wave pool: queues per band (CVR_OPT_SUBQUEUES)
-  int drain = -1;                   // wave pool: drain-mode event trigger (CVR_OPT_DRAIN; -1 = 1)
-  int order = 2;                    // 1: pixel-block/sample-inner order when the launch allows it; 2: blocks
-                                    // in 2-D Morton order within each band
-  // cached Morton permutation of the launch's blocks (order 2), for the block layout in zkey
-  uint32_t* d_zperm = nullptr;
-  std::vector<uint32_t> h_zperm;
-  uint64_t zkey[5] = {0, 0, 0, 0, 0};
-
-  // options
-  uint32_t max_segments = 1u << 20;
-  uint32_t chunk = 0;  // paths per wave dequeue; 0: auto (wave pool: 64..256 by the launch's size, others 256)
-  uint32_t ev_thresh = 56;
-  uint32_t grid_override = 0;
-  uint32_t inflight = 1;  // CVR_OPT_INFLIGHT: renders the caller keeps in flight (wave-pool grid rule)
-  int scatter_eps = -1;
-  int rng_binding = 0;  // CVR_OPT_RNG_BINDING
-  int world_to_aabb = 0;  // CVR_OPT_WORLD_TO_AABB (Q4)
-  int mk_compaction = 0;  // CVR_OPT_MK_COMPACTION (Q11)
-
-  int cu_count = 0;
-  int persistent_grid = 0;
-  int pool_grid = 0;
-  uint32_t pool_tail = 16;
-  int wpool_grid = 0, wpool_grid_sparse = 0;
-  // wave-pool register/LDS budget in waves per SIMD (CVR_OPT_WAVES: 3, 4, 5);
-  // 0 = the default, 5 (dense and sparse, split slots)
-  int wpool_waves = 0;
-  int morton = 0;  // CVR_OPT_MORTON
-  int sample_order = -1;  // CVR_OPT_SAMPLE_ORDER (-1: the default, 0)
-  int empty_mask = 1;     // CVR_OPT_EMPTY_MASK
-  int count_words = 0;    // CVR_OPT_COUNT_WORDS
-  uint32_t swap_batch = 8;
-  int track_grid = 0;
-  bool inited = false;
-  int scheduler = -1;  // 0 persistent, 1 wavefront pair, 2 workgroup pool, 3 wave-private pool, -1 per kernel id
-  int waves = 4;      // persistent kernel register budget (waves per SIMD)
-
-  // wavefront pool (cvr_wavefront.hip)
-  unsigned char* d_pool = nullptr;
-  size_t pool_bytes = 0;
-  uint32_t pool_cap = 0;  // slots the allocation holds
-  uint32_t pool_max = 1u << 21;
-  cvr::WfPool pool{};
-  unsigned int* h_alive = nullptr;  // pinned ring of per-iteration flags
-  std::vector<hipEvent_t> it_events;
-  uint64_t last_iterations = 0;
-  double last_track_ms = 0, last_events_ms = 0;
-  bool wf_timing = false;
-  // cvr_set_medium_device with CVR_OPT_TIMING: device ms of its last call's density scan, albedo
-  // scan, leaf flags, scans and scatters, gather, and cells / bounds / brick words
-  double devmed_ms[6] = {0, 0, 0, 0, 0, 0};
-
-  cvr_stats last{};
-
-  // cvr_render_frame: this launch's band of block rows (band_count 0: every block), the
-  // helper contexts that render the frame's other bands (each with its own stream and work
-  // queues, sharing this context's medium and framebuffer), the copy stream, and the
-  // normalised device image the bands are copied from
-  uint32_t band_first = 0, band_count = 0;
-  std::vector<cvr_ctx*> frame_kids;
-  hipStream_t frame_copy = nullptr;
-  hipEvent_t frame_ev[4] = {nullptr, nullptr, nullptr, nullptr};  // [0] cleared, [1 + k] band k rendered
-  float4* d_frame = nullptr;
-  size_t frame_px = 0;
-  // cvr_render_frame's in-launch output (CVR_OPT_FRAME_FLUSH, wave pool): [FrameFlush
-  // header | per-block ended-path counts], the flushers' status words (pinned), the
-  // header as last written, and the counts the next launch takes (null: none)
-  int frame_flush = 1;
-  unsigned char* d_flush = nullptr;
-  size_t flush_blocks = 0;
-  unsigned int* h_flush_status = nullptr;
-  cvr::FrameFlush flush_hdr{};
-  bool flush_hdr_valid = false;  // d_flush holds flush_hdr
-  unsigned int* frame_done_active = nullptr;
-  uint32_t flush_last_blocks = 0, flush_fallbacks = 0;
-
-  // CVR_OPT_MOMENTS: the owned framebuffer holds a second float4 per pixel behind the tile
-  int moments = 0;
-  // The active block list (cvr_adaptive_*): while active_on, a launch renders exactly the tile
-  // blocks of `active` (ascending ids), n_blocks = its length; d_active holds them in the
-  // launch's order (each XCD band in 2-D Morton order), h_active the same on the host.
-  bool active_on = false;
-  std::vector<uint32_t> active, h_active;
-  uint32_t* d_active = nullptr;  // tile_px / 64 entries
-  // the adaptive session
-  struct Adaptive {
-    bool on = false;        // between cvr_adaptive_begin and cvr_adaptive_end
-    bool internal = false;  // the session's own launch is running through the public entry points
-    cvr_adaptive_desc d{};
-    uint32_t n_blocks = 0, passes = 0;
-    int done = 0;
-    uint64_t paths = 0;
-    std::vector<uint32_t> samples;  // per tile block
-    std::vector<double> err;        // per tile block, at its last check
-    std::vector<double> h_err;      // the last pass's errors, in h_active order
-    double* d_err = nullptr;        // tile_px / 64 doubles
-    uint32_t* d_counts = nullptr;   // tile_px / 64 sample counts (cvr_adaptive_image)
-    int saved_moments = 0;
-    uint32_t saved_iterations = 1;
-    cvr_stats acc{};
-  } ad;
-  // cvr_denoise*: the two scratch images the passes alternate between (dn_px pixels each)
-  float4* d_dn = nullptr;
-  size_t dn_px = 0;
-};
-// Calls that are out of order inside an adaptive session (the session's own launches pass).
-#define CVR_NOT_IN_SESSION(c, what)                                                                       \
-  do {                                                                                                    \
-    if ((c)->ad.on && !(c)->ad.internal)                                                                  \
-      return set_err(&(c)->err, CVR_ERR_STATE, "%s inside an adaptive session (cvr_adaptive_end first)", what); \
-  } while (0)
-
+using cvr::ensure_device;
+using cvr::set_err;
 using cvr::kWorkDebug;
 using cvr::kWorkQueues;
 using cvr::kWorkStats;
 // d_work layout: cvr_kernels.h (stats, debug counters, queue heads)
 constexpr size_t kWorkBytes = cvr::kWorkBytesBase;
-
-#define HIP_TRY(ctx, expr)                                                                         \
-  do {                                                                                                  \
-    hipError_t e_ = (expr);                                                                             \
-    if (e_ != hipSuccess)                                                                               \
-      return set_err((ctx) ? &(ctx)->err : nullptr, CVR_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_)); \
-  } while (0)
 
 namespace {
 
@@ -395,11 +172,6 @@ uint32_t wpool_launch_grid(const cvr_ctx* c, uint64_t n_paths) {
   if (n_paths < 64ull * full) return whole(c->inflight > 1 ? quarter : half);
   if (c->inflight > 1 && n_paths < 2048ull * full) return whole(half);
   return whole(full);
-}
-
-int ensure_device(cvr_ctx* c) {
-  HIP_TRY(c, hipSetDevice(c->device));
-  return CVR_OK;
 }
 
 int ensure_output(cvr_ctx* c) {
@@ -852,8 +624,6 @@ int cvr_create(int device, int kernel, cvr_ctx** out) {
   return CVR_OK;
 }
 
-static void free_sparse(cvr_ctx* c);
-
 int cvr_destroy(cvr_ctx* c) {
   if (!c) return CVR_OK;
   (void)hipSetDevice(c->device);
@@ -862,11 +632,8 @@ int cvr_destroy(cvr_ctx* c) {
   c->frame_kids.clear();
   if (c->frame_copy) (void)hipStreamSynchronize(c->frame_copy);
   if (c->stream) (void)hipStreamSynchronize(c->stream);
-  if (c->d_density) (void)hipFree(c->d_density);
-  if (c->d_albedo) (void)hipFree(c->d_albedo);
-  if (c->d_cells) (void)hipFree(c->d_cells);
-  if (c->d_bounds) (void)hipFree(c->d_bounds);
-  free_sparse(c);
+  cvr::drop_dense(c);
+  cvr::free_sparse(c);
   if (c->d_out_owned) (void)hipFree(c->d_out_owned);
   if (c->d_work) (void)hipFree(c->d_work);
   if (c->d_pool_T) (void)hipFree(c->d_pool_T);
@@ -890,875 +657,6 @@ int cvr_destroy(cvr_ctx* c) {
   if (c->d_flush) (void)hipFree(c->d_flush);
   if (c->h_flush_status) (void)hipHostFree(c->h_flush_status);
   delete c;
-  return CVR_OK;
-}
-
-static void free_sparse(cvr_ctx* c) {
-  if (c->d_leaves) (void)hipFree(c->d_leaves);
-  if (c->d_leaf_density) (void)hipFree(c->d_leaf_density);
-  if (c->d_leaf_albedo) (void)hipFree(c->d_leaf_albedo);
-  if (c->d_sbounds) (void)hipFree(c->d_sbounds);
-  if (c->d_emask) (void)hipFree(c->d_emask);
-  c->d_emask = nullptr;
-  c->d_leaves = nullptr;
-  c->d_leaf_density = nullptr;
-  c->d_leaf_albedo = nullptr;
-  c->d_sbounds = nullptr;
-  c->n_cell_leaves = 0;
-}
-
-// Geometry, scale and BSDF parameters shared by the dense and sparse uploads
-// (HeterogeneousMedium + GGX, Medium.h:110-190).
-static void fill_medium_common(cvr::MediumParams& m, const uint32_t res[3], const float box_min[3],
-                               const float box_max[3], float scale, float max_density, float g,
-                               const float roughness[2], float eta) {
-  m.rx = res[0];
-  m.ry = res[1];
-  m.rz = res[2];
-  m.rxy = res[0] * res[1];  // only used by dense media, where it is < 2^24
-  m.fres_x = (float)res[0];
-  m.fres_y = (float)res[1];
-  m.fres_z = (float)res[2];
-  m.gx = m.agx = (float)(res[0] - 1u);
-  m.gy = m.agy = (float)(res[1] - 1u);
-  m.gz = m.agz = (float)(res[2] - 1u);
-  m.bmin = cvr::V3{box_min[0], box_min[1], box_min[2]};
-  m.bmax = cvr::V3{box_max[0], box_max[1], box_max[2]};
-  const float ex = box_max[0] - box_min[0], ey = box_max[1] - box_min[1], ez = box_max[2] - box_min[2];
-  m.shift = cvr::V3{box_min[0] / ex, box_min[1] / ey, box_min[2] / ez};
-  m.scale = scale;
-  m.inv_sigma = 1.0f / (scale * max_density);
-  m.g = g;
-  m.ax = roughness[0];
-  m.ay = roughness[1];
-  m.eta = eta;
-  m.inv_eta = 1.0f / eta;
-}
-
-int cvr_set_medium(cvr_ctx* c, const cvr_medium_desc* md) {
-  if (!c || !md) return set_err(c ? &c->err : nullptr, CVR_ERR_INVALID, "NULL argument");
-  CVR_NOT_IN_SESSION(c, "cvr_set_medium");
-  // (the shape is judged first, from the numbers alone, then the arrays)
-  if (md->res[0] == 0 || md->res[1] == 0 || md->res[2] == 0)
-    return set_err(&c->err, CVR_ERR_INVALID, "empty grid");
-  const size_t n = (size_t)md->res[0] * md->res[1] * md->res[2];
-  if (n > 0xFFFFFFFFull) return set_err(&c->err, CVR_ERR_INVALID, "grid exceeds 2^32 voxels");
-  // the kernels index cells and bricks with 24-bit multiplies
-  if ((uint64_t)md->res[1] * md->res[2] >= (1ull << 24) || (uint64_t)md->res[0] * md->res[1] >= (1ull << 24))
-    return set_err(&c->err, CVR_ERR_UNSUPPORTED, "dense grid with y*z or x*y >= 2^24: use cvr_set_medium_sparse");
-  const uint32_t fmt = (uint32_t)c->medium_format;
-  // an fp32 cell is two float4: dense_cell doubles the u32 cell index (the half format's cell is one)
-  if (!fmt && c->use_cells && n >= (1ull << 31))
-    return set_err(&c->err, CVR_ERR_UNSUPPORTED,
-                   "dense fp32 grid of %zu voxels (>= 2^31) with density cells: use CVR_OPT_MEDIUM_FORMAT 1, "
-                   "CVR_OPT_CELLS 0 or cvr_set_medium_sparse",
-                   n);
-  if (!md->density || !md->albedo) return set_err(&c->err, CVR_ERR_INVALID, "density/albedo is NULL");
-  // bytes per density voxel / cell / albedo voxel
-  const size_t dB = fmt ? 2 : sizeof(float), cB = fmt ? 16 : 2 * sizeof(float4), aB = fmt ? 8 : sizeof(float4);
-  if (fmt) {
-    size_t at = 0;
-    const bool bad_d = half_overflows(md->density, n, 1, 1, &at);
-    const bool bad_a = !bad_d && half_overflows(md->albedo, n, 4, 3, &at);
-    if (bad_d || bad_a) {
-      c->have_medium = false;
-      return set_err(&c->err, CVR_ERR_INVALID, "medium format half: %s value %g at index %zu rounds to infinity",
-                     bad_d ? "density" : "albedo", (double)(bad_d ? md->density : md->albedo)[at], at);
-    }
-  }
-  const float max_density = fmt ? half_majorant(md->max_density) : md->max_density;
-  int r = ensure_device(c);
-  if (r) return r;
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  free_sparse(c);
-  c->have_medium = false;
-  if (n != c->n_voxels || !c->d_density || c->grids_format != fmt) {  // (the grids' bytes depend on the format too)
-    if (c->d_density) (void)hipFree(c->d_density);
-    if (c->d_albedo) (void)hipFree(c->d_albedo);
-    c->d_density = nullptr;
-    c->d_albedo = nullptr;
-    c->n_voxels = 0;
-    HIP_TRY(c, hipMalloc(&c->d_density, n * dB));
-    HIP_TRY(c, hipMalloc(&c->d_albedo, n * aB));
-    c->n_voxels = n;
-    c->grids_format = fmt;
-  }
-  if (fmt) {
-    // fp32 staging -> rounded half grids (converted on the device); the staging is freed before
-    // the cells and bounds are built, and in any case before this call returns
-    float* stage = nullptr;
-    HIP_TRY(c, hipMalloc(&stage, n * sizeof(float4)));
-    hipError_t e = hipMemcpy(stage, md->density, n * sizeof(float), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = cvr::launch_to_half(stage, c->d_density, n, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e == hipSuccess) e = hipMemcpy(stage, md->albedo, n * sizeof(float4), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = cvr::launch_to_half(stage, c->d_albedo, 4 * n, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    (void)hipFree(stage);
-    if (e != hipSuccess) return set_err(&c->err, CVR_ERR_HIP, "half medium upload: %s", hipGetErrorString(e));
-  } else {
-    HIP_TRY(c, hipMemcpy(c->d_density, md->density, n * sizeof(float), hipMemcpyHostToDevice));
-    HIP_TRY(c, hipMemcpy(c->d_albedo, md->albedo, n * sizeof(float4), hipMemcpyHostToDevice));
-  }
-  if (c->d_cells) (void)hipFree(c->d_cells);
-  c->d_cells = nullptr;
-  if (c->use_cells) {
-    HIP_TRY(c, hipMalloc(&c->d_cells, n * cB));
-    HIP_TRY(c, cvr::launch_build_cells(c->d_density, md->res[0], md->res[1], md->res[2], c->d_cells, c->stream, fmt));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-  }
-  if (c->d_bounds) (void)hipFree(c->d_bounds);
-  c->d_bounds = nullptr;
-  const float sigma = md->scale * max_density;
-  size_t bounds_bytes = 0;
-  uint32_t bnx = 0, bny = 0, bsentinel = 0;
-  if (c->bound_shift && sigma > 0.0f && std::isfinite(sigma) && md->scale > 0.0f) {
-    const uint32_t B = 1u << c->bound_shift;
-    bnx = (md->res[0] + B - 1) / B;
-    bny = (md->res[1] + B - 1) / B;
-    const size_t nb = (size_t)bnx * bny * ((md->res[2] + B - 1) / B);
-    bsentinel = (uint32_t)nb;  // the no-bound entry past the last brick (k_build_bounds writes it)
-    HIP_TRY(c, hipMalloc(&c->d_bounds, nb + 1));
-    bounds_bytes = nb + 1;
-    HIP_TRY(c, cvr::launch_build_bounds(c->d_density, md->res[0], md->res[1], md->res[2], c->bound_shift,
-                                        max_density, c->d_bounds, c->stream, fmt));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-  }
-  cvr::MediumParams& m = c->m;
-  m = cvr::MediumParams{};
-  m.bounds = c->d_bounds;
-  m.bshift = c->bound_shift;
-  m.bnx = bnx;
-  m.bny = bny;
-  m.bnxy = bnx * bny;
-  m.bsentinel = bsentinel;
-  m.cells = c->d_cells;
-  m.density = c->d_density;
-  m.albedo = c->d_albedo;
-  fill_medium_common(m, md->res, md->box_min, md->box_max, md->scale, max_density, md->g, md->roughness, md->eta);
-  m.format = fmt;
-  if (c->uniform_albedo) {
-    // every voxel's rgb bit-identical to the first (the XML smoke scene's constant albedo);
-    // format 1: the rounded rgb (voxels that differ may round to the same halves)
-    float first[3] = {md->albedo[0], md->albedo[1], md->albedo[2]};
-    if (fmt)
-      for (float& v : first) v = half_round1(v);
-    bool same = true;
-    for (size_t i = 1; i < n && same; ++i) {
-      same = memcmp(md->albedo + 4 * i, md->albedo, 3 * sizeof(float)) == 0;
-      if (!same && fmt) {
-        float v[3];
-        for (int k = 0; k < 3; ++k) v[k] = half_round1(md->albedo[4 * i + k]);
-        same = memcmp(v, first, sizeof(v)) == 0;
-      }
-    }
-    if (same) {
-      m.albedo_uniform = 1u;
-      m.albedo_bg = cvr::V3{first[0], first[1], first[2]};
-    }
-  }
-  c->minfo = {};
-  c->minfo.format = (int32_t)fmt;
-  c->minfo.max_density_eff = max_density;
-  c->minfo.density_bytes = n * dB;
-  c->minfo.cells_bytes = c->d_cells ? n * cB : 0;
-  c->minfo.albedo_bytes = n * aB;
-  c->minfo.bounds_bytes = bounds_bytes;
-  c->minfo.total_bytes = c->minfo.density_bytes + c->minfo.cells_bytes + c->minfo.albedo_bytes + c->minfo.bounds_bytes;
-  c->have_medium = true;
-  return CVR_OK;
-}
-
-int cvr_set_medium_sparse(cvr_ctx* c, const cvr_sparse_medium_desc* sd) {
-  if (!c || !sd) return set_err(c ? &c->err : nullptr, CVR_ERR_INVALID, "NULL argument");
-  CVR_NOT_IN_SESSION(c, "cvr_set_medium_sparse");
-  const uint32_t* res = sd->res;
-  if (res[0] == 0 || res[1] == 0 || res[2] == 0) return set_err(&c->err, CVR_ERR_INVALID, "empty grid");
-  for (int k = 0; k < 3; ++k)
-    if (sd->leaf_dims[k] != (res[k] + 7u) / 8u)
-      return set_err(&c->err, CVR_ERR_INVALID, "leaf_dims[%d] = %u, expected ceil(res/8) = %u", k, sd->leaf_dims[k],
-                     (res[k] + 7u) / 8u);
-  const uint32_t lnx = sd->leaf_dims[0], lny = sd->leaf_dims[1], lnz = sd->leaf_dims[2];
-  const size_t nleaf = (size_t)lnx * lny * lnz;
-  if (nleaf > 0xFFFFFFFFull) return set_err(&c->err, CVR_ERR_INVALID, "leaf table exceeds 2^32 entries");
-  // (as in cvr_set_medium, the shape is judged first, from the numbers alone, then the arrays)
-  // bricks of 2^bshift <= 8 cells (within one leaf); bounds off -> q = 255.
-  // Default 8^3 cells per brick: one brick word per leaf's cells (C5: 33.6 MB
-  // of words instead of 268 MB at 4^3, so they stay in L2 / Infinity Cache;
-  // 12% faster at an unchanged fetch rate, clouds being empty or dense).
-  const uint32_t bshift = !c->bound_shift_set ? 3u : c->bound_shift == 0 ? 2u : std::min(c->bound_shift, 3u);
-  const uint32_t B = 1u << bshift;
-  const uint32_t bnx = (res[0] + B - 1) / B, bny = (res[1] + B - 1) / B, bnz = (res[2] + B - 1) / B;
-  const size_t nb = (size_t)bnx * bny * bnz;
-  // the kernels index brick words and leaves with 24-bit multiplies, bz * (bnx bny) + by * bnx + bx
-  // and (lz * lny + ly) * lnx + lx, and a u32 sum (refused before anything is read or the previous
-  // medium is dropped)
-  if ((uint64_t)bnx * bny >= (1ull << 24) || bnz > (1u << 24) || nb >= 0xFFFFFFFFull)
-    return set_err(&c->err, CVR_ERR_UNSUPPORTED,
-                   "sparse grid of %ux%ux%u bricks: x*y >= 2^24, z > 2^24 or %zu bricks >= 2^32 - 1 (a larger "
-                   "CVR_OPT_BOUNDS brick, up to 8 cells, has fewer)",
-                   bnx, bny, bnz, nb);
-  if (!sd->leaf_table || (sd->n_leaves && !sd->leaf_density))
-    return set_err(&c->err, CVR_ERR_INVALID, "leaf table / density pool is NULL");
-  // cell leaves: a leaf's cells read the corners in it and its forward
-  // neighbours, so it needs a slot iff one of those 8 leaves exists
-  std::vector<uint32_t> cell_slot(nleaf, 0u), coords{0u, 0u, 0u};  // slot 0: the zero leaf
-  for (uint32_t z = 0; z < lnz; ++z)
-    for (uint32_t y = 0; y < lny; ++y)
-      for (uint32_t x = 0; x < lnx; ++x) {
-        const size_t i = ((size_t)z * lny + y) * lnx + x;
-        const uint32_t v = sd->leaf_table[i];
-        if (v != CVR_NO_LEAF && v >= sd->n_leaves)
-          return set_err(&c->err, CVR_ERR_INVALID, "leaf table entry %u >= n_leaves %u", v, sd->n_leaves);
-        bool any = false;
-        for (uint32_t dz = 0; dz < 2 && !any; ++dz)
-          for (uint32_t dy = 0; dy < 2 && !any; ++dy)
-            for (uint32_t dx = 0; dx < 2 && !any; ++dx)
-              if (x + dx < lnx && y + dy < lny && z + dz < lnz)
-                any = sd->leaf_table[((size_t)(z + dz) * lny + (y + dy)) * lnx + (x + dx)] != CVR_NO_LEAF;
-        if (any) {
-          cell_slot[i] = (uint32_t)(coords.size() / 3);
-          coords.insert(coords.end(), {x, y, z});
-        }
-      }
-  const size_t ncl = coords.size() / 3;
-  if (ncl > (1u << 24))
-    return set_err(&c->err, CVR_ERR_UNSUPPORTED, "sparse medium needs %zu cell leaves (> 2^24)", ncl);
-  const uint32_t fmt = (uint32_t)c->medium_format;
-  const size_t dB = fmt ? 2 : sizeof(float), cB = fmt ? 16 : 2 * sizeof(float4), aB = fmt ? 8 : sizeof(float4);
-  if (fmt) {
-    const size_t nv = (size_t)sd->n_leaves * 512;
-    size_t at = 0;
-    const char* what = nullptr;
-    const float* arr = nullptr;
-    if (half_overflows(sd->leaf_density, nv, 1, 1, &at)) what = "leaf density", arr = sd->leaf_density;
-    else if (sd->leaf_albedo && half_overflows(sd->leaf_albedo, nv, 4, 3, &at)) what = "leaf albedo", arr = sd->leaf_albedo;
-    else if (half_overflows(sd->albedo_background, 1, 4, 3, &at)) what = "albedo_background", arr = sd->albedo_background;
-    if (what) {
-      c->have_medium = false;
-      return set_err(&c->err, CVR_ERR_INVALID, "medium format half: %s value %g at index %zu rounds to infinity", what,
-                     (double)arr[at], at);
-    }
-  }
-  const float max_density = fmt ? half_majorant(sd->max_density) : sd->max_density;
-  int r = ensure_device(c);
-  if (r) return r;
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  // drop the previous medium (dense or sparse)
-  if (c->d_density) (void)hipFree(c->d_density);
-  if (c->d_albedo) (void)hipFree(c->d_albedo);
-  if (c->d_cells) (void)hipFree(c->d_cells);
-  if (c->d_bounds) (void)hipFree(c->d_bounds);
-  c->d_density = nullptr;
-  c->d_albedo = nullptr;
-  c->d_cells = nullptr;
-  c->d_bounds = nullptr;
-  c->n_voxels = 0;
-  c->have_medium = false;
-  free_sparse(c);
-  const size_t np = (size_t)sd->n_leaves * 512;
-  HIP_TRY(c, hipMalloc(&c->d_leaves, nleaf * sizeof(uint32_t)));
-  HIP_TRY(c, hipMemcpy(c->d_leaves, sd->leaf_table, nleaf * sizeof(uint32_t), hipMemcpyHostToDevice));
-  HIP_TRY(c, hipMalloc(&c->d_leaf_density, (np ? np : 1) * dB));
-  if (sd->leaf_albedo && np) HIP_TRY(c, hipMalloc(&c->d_leaf_albedo, np * aB));
-  if (fmt && np) {
-    // fp32 staging -> rounded half pools (converted on the device), freed before the cells are built
-    float* stage = nullptr;
-    HIP_TRY(c, hipMalloc(&stage, np * (c->d_leaf_albedo ? sizeof(float4) : sizeof(float))));
-    hipError_t e = hipMemcpy(stage, sd->leaf_density, np * sizeof(float), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = cvr::launch_to_half(stage, c->d_leaf_density, np, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e == hipSuccess && c->d_leaf_albedo) {
-      e = hipMemcpy(stage, sd->leaf_albedo, np * sizeof(float4), hipMemcpyHostToDevice);
-      if (e == hipSuccess) e = cvr::launch_to_half(stage, c->d_leaf_albedo, 4 * np, c->stream);
-      if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    }
-    (void)hipFree(stage);
-    if (e != hipSuccess) return set_err(&c->err, CVR_ERR_HIP, "half medium upload: %s", hipGetErrorString(e));
-  } else if (np) {
-    HIP_TRY(c, hipMemcpy(c->d_leaf_density, sd->leaf_density, np * sizeof(float), hipMemcpyHostToDevice));
-    if (c->d_leaf_albedo)
-      HIP_TRY(c, hipMemcpy(c->d_leaf_albedo, sd->leaf_albedo, np * sizeof(float4), hipMemcpyHostToDevice));
-  }
-  cvr::MediumParams& m = c->m;
-  m = cvr::MediumParams{};
-  fill_medium_common(m, res, sd->box_min, sd->box_max, sd->scale, max_density, sd->g, sd->roughness, sd->eta);
-  m.format = fmt;
-  m.leaves = c->d_leaves;
-  m.leaf_density = c->d_leaf_density;
-  m.leaf_albedo = c->d_leaf_albedo;
-  m.lnx = lnx;
-  m.lny = lny;
-  m.albedo_bg = cvr::V3{sd->albedo_background[0], sd->albedo_background[1], sd->albedo_background[2]};
-  if (fmt) m.albedo_bg = cvr::V3{half_round1(m.albedo_bg.x), half_round1(m.albedo_bg.y), half_round1(m.albedo_bg.z)};
-  const float sigma = sd->scale * max_density;
-  const int unbounded = !(c->bound_shift && sigma > 0.0f && std::isfinite(sigma) && sd->scale > 0.0f);
-  m.bshift = bshift;
-  m.bnx = bnx;
-  m.bny = bny;
-  m.bnxy = bnx * bny;
-  m.bsentinel = (uint32_t)nb;  // the no-bound word past the last brick (k_build_sparse_bounds writes it)
-  HIP_TRY(c, hipMalloc(&c->d_sbounds, (nb + 1) * sizeof(uint32_t)));
-  if (c->use_cells) HIP_TRY(c, hipMalloc(&c->d_cells, ncl * 512 * cB));
-  uint32_t *d_coords = nullptr, *d_slot = nullptr;
-  hipError_t e = hipMalloc(&d_coords, coords.size() * sizeof(uint32_t));
-  if (e == hipSuccess) e = hipMalloc(&d_slot, nleaf * sizeof(uint32_t));
-  if (e == hipSuccess) e = hipMemcpy(d_coords, coords.data(), coords.size() * sizeof(uint32_t), hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(d_slot, cell_slot.data(), nleaf * sizeof(uint32_t), hipMemcpyHostToDevice);
-  if (e == hipSuccess)
-    e = cvr::launch_build_sparse(m, d_coords, c->use_cells ? ncl : 0, d_slot, bnz, max_density, unbounded,
-                                 c->d_cells, c->d_sbounds, c->stream);
-  // Empty-region mask (MediumParams::emask): the smallest super-brick of 2^es
-  // cells per axis whose grid, each axis padded to a power of two, fits 32
-  // kEmaskWords bits; bit set iff a leaf in it has a cell leaf.  Clear
-  // super-bricks' brick words are 0 only when bounded.
-  if (e == hipSuccess && !unbounded) {
-    auto log2up = [](uint32_t v) {
-      uint32_t l = 0;
-      while ((1u << l) < v) ++l;
-      return l;
-    };
-    uint32_t es = 3, lx = log2up(lnx), ly = log2up(lny), lz = log2up(lnz);
-    while (lx + ly + lz > log2up(32u * cvr::kEmaskWords)) {
-      ++es;
-      lx -= lx > 0;
-      ly -= ly > 0;
-      lz -= lz > 0;
-    }
-    std::vector<uint32_t> em(cvr::kEmaskWords, 0u);
-    const uint32_t k = es - 3;
-    for (uint32_t z = 0; z < lnz; ++z)
-      for (uint32_t y = 0; y < lny; ++y)
-        for (uint32_t x = 0; x < lnx; ++x)
-          if (cell_slot[((size_t)z * lny + y) * lnx + x] != 0u) {
-            const uint32_t b = (z >> k) << (lx + ly) | (y >> k) << lx | (x >> k);
-            em[b >> 5] |= 1u << (b & 31u);
-          }
-    e = hipMalloc(&c->d_emask, em.size() * sizeof(uint32_t));
-    if (e == hipSuccess) e = hipMemcpy(c->d_emask, em.data(), em.size() * sizeof(uint32_t), hipMemcpyHostToDevice);
-    m.eshift = es;
-    m.eshy = lx;
-    m.eshz = lx + ly;
-    m.emask = c->d_emask;
-  }
-  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-  if (d_coords) (void)hipFree(d_coords);
-  if (d_slot) (void)hipFree(d_slot);
-  if (e != hipSuccess) return set_err(&c->err, CVR_ERR_HIP, "sparse medium build: %s", hipGetErrorString(e));
-  m.cells = c->d_cells;
-  m.sbounds = c->d_sbounds;
-  c->n_cell_leaves = ncl;
-  c->minfo = {};
-  c->minfo.format = (int32_t)fmt;
-  c->minfo.max_density_eff = max_density;
-  c->minfo.density_bytes = (np ? np : 1) * dB;
-  c->minfo.cells_bytes = c->d_cells ? ncl * 512 * cB : 0;
-  c->minfo.albedo_bytes = c->d_leaf_albedo ? np * aB : 0;
-  c->minfo.bounds_bytes = (nb + 1 + nleaf + (c->d_emask ? cvr::kEmaskWords : 0)) * sizeof(uint32_t);
-  c->minfo.total_bytes = c->minfo.density_bytes + c->minfo.cells_bytes + c->minfo.albedo_bytes + c->minfo.bounds_bytes;
-  c->have_medium = true;
-  return CVR_OK;
-}
-
-// ---- media built from device memory (cvr_set_medium_device) ----------------
-namespace {
-// Device allocations of one call, freed on every way out of it (keep(): the context owns it now)
-struct DevTemps {
-  std::vector<void*> p;
-  ~DevTemps() {
-    for (void* q : p) (void)hipFree(q);
-  }
-  hipError_t alloc(void** out, size_t bytes) {
-    const hipError_t e = hipMalloc(out, bytes ? bytes : 4);
-    if (e == hipSuccess) p.push_back(*out);
-    return e;
-  }
-  void keep(void* q) { p.erase(std::remove(p.begin(), p.end(), q), p.end()); }
-};
-// Device time of the launches between begin() and end(i), added to devmed_ms[i] (CVR_OPT_TIMING)
-struct DevmedTimer {
-  cvr_ctx* c;
-  hipEvent_t a = nullptr, b = nullptr;
-  bool on;
-  explicit DevmedTimer(cvr_ctx* ctx) : c(ctx), on(ctx->wf_timing) {
-    for (double& v : c->devmed_ms) v = 0.0;
-    if (on) on = hipEventCreate(&a) == hipSuccess && hipEventCreate(&b) == hipSuccess;
-  }
-  ~DevmedTimer() {
-    if (a) (void)hipEventDestroy(a);
-    if (b) (void)hipEventDestroy(b);
-  }
-  void begin() {
-    if (on) (void)hipEventRecord(a, c->stream);
-  }
-  void end(int i) {
-    float ms = 0.f;
-    if (on && hipEventRecord(b, c->stream) == hipSuccess && hipEventSynchronize(b) == hipSuccess &&
-        hipEventElapsedTime(&ms, a, b) == hipSuccess)
-      c->devmed_ms[i] += ms;
-  }
-};
-// p is memory the context's device can read, by what the runtime knows of it: device memory of
-// that device, managed memory, or mapped host memory (an address HIP does not know is refused)
-bool device_readable(const cvr_ctx* c, const void* p) {
-  hipPointerAttribute_t at{};
-  if (hipPointerGetAttributes(&at, p) != hipSuccess) {
-    (void)hipGetLastError();
-    return false;
-  }
-  if (at.type == hipMemoryTypeDevice) return at.device == c->device;
-  return (at.type == hipMemoryTypeManaged || at.type == hipMemoryTypeHost) && at.devicePointer != nullptr;
-}
-bool overflows_half(float f) { return std::fabs(f) >= 65520.0f && std::isfinite(f); }
-
-// The dense half of cvr_set_medium_device: cvr_set_medium from its upload on, the grids copied
-// (format 1: converted) from the caller's device arrays.  `first`: voxel 0's albedo.
-int devmed_dense(cvr_ctx* c, const cvr_device_medium_desc* d, uint32_t fmt, float max_density,
-                 const cvr::MedScan& scan, const float first_rgba[4], DevmedTimer& tm) {
-  const size_t n = (size_t)d->res[0] * d->res[1] * d->res[2];
-  const size_t dB = fmt ? 2 : sizeof(float), cB = fmt ? 16 : 2 * sizeof(float4), aB = fmt ? 8 : sizeof(float4);
-  const bool konst = (d->flags & CVR_DEVMED_CONST_ALBEDO) != 0;
-  free_sparse(c);
-  c->have_medium = false;
-  if (n != c->n_voxels || !c->d_density || c->grids_format != fmt) {
-    if (c->d_density) (void)hipFree(c->d_density);
-    if (c->d_albedo) (void)hipFree(c->d_albedo);
-    c->d_density = nullptr;
-    c->d_albedo = nullptr;
-    c->n_voxels = 0;
-    HIP_TRY(c, hipMalloc(&c->d_density, n * dB));
-    HIP_TRY(c, hipMalloc(&c->d_albedo, n * aB));
-    c->n_voxels = n;
-    c->grids_format = fmt;
-  }
-  tm.begin();
-  if (fmt) {
-    // straight from the caller's fp32 arrays: no staging buffer
-    HIP_TRY(c, cvr::launch_to_half(d->d_density, c->d_density, n, c->stream));
-    if (!konst) HIP_TRY(c, cvr::launch_to_half(d->d_albedo, c->d_albedo, 4 * n, c->stream));
-  } else {
-    HIP_TRY(c, hipMemcpyAsync(c->d_density, d->d_density, n * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
-    if (!konst)
-      HIP_TRY(c, hipMemcpyAsync(c->d_albedo, d->d_albedo, n * sizeof(float4), hipMemcpyDeviceToDevice, c->stream));
-  }
-  if (konst) HIP_TRY(c, cvr::launch_fill_albedo(c->d_albedo, n, fmt, d->const_albedo, c->stream));
-  tm.end(4);
-  if (c->d_cells) (void)hipFree(c->d_cells);
-  c->d_cells = nullptr;
-  tm.begin();
-  if (c->use_cells) {
-    HIP_TRY(c, hipMalloc(&c->d_cells, n * cB));
-    HIP_TRY(c, cvr::launch_build_cells(c->d_density, d->res[0], d->res[1], d->res[2], c->d_cells, c->stream, fmt));
-  }
-  if (c->d_bounds) (void)hipFree(c->d_bounds);
-  c->d_bounds = nullptr;
-  const float sigma = d->scale * max_density;
-  size_t bounds_bytes = 0;
-  uint32_t bnx = 0, bny = 0, bsentinel = 0;
-  if (c->bound_shift && sigma > 0.0f && std::isfinite(sigma) && d->scale > 0.0f) {
-    const uint32_t B = 1u << c->bound_shift;
-    bnx = (d->res[0] + B - 1) / B;
-    bny = (d->res[1] + B - 1) / B;
-    const size_t nb = (size_t)bnx * bny * ((d->res[2] + B - 1) / B);
-    bsentinel = (uint32_t)nb;
-    HIP_TRY(c, hipMalloc(&c->d_bounds, nb + 1));
-    bounds_bytes = nb + 1;
-    HIP_TRY(c, cvr::launch_build_bounds(c->d_density, d->res[0], d->res[1], d->res[2], c->bound_shift, max_density,
-                                        c->d_bounds, c->stream, fmt));
-  }
-  tm.end(5);
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  cvr::MediumParams& m = c->m;
-  m = cvr::MediumParams{};
-  m.bounds = c->d_bounds;
-  m.bshift = c->bound_shift;
-  m.bnx = bnx;
-  m.bny = bny;
-  m.bnxy = bnx * bny;
-  m.bsentinel = bsentinel;
-  m.cells = c->d_cells;
-  m.density = c->d_density;
-  m.albedo = c->d_albedo;
-  fill_medium_common(m, d->res, d->box_min, d->box_max, d->scale, max_density, d->g, d->roughness, d->eta);
-  m.format = fmt;
-  if (c->uniform_albedo && (konst || !(scan.albedo_flags & 1u))) {
-    float first[3] = {first_rgba[0], first_rgba[1], first_rgba[2]};
-    if (fmt)
-      for (float& v : first) v = half_round1(v);
-    m.albedo_uniform = 1u;
-    m.albedo_bg = cvr::V3{first[0], first[1], first[2]};
-  }
-  c->minfo = {};
-  c->minfo.format = (int32_t)fmt;
-  c->minfo.max_density_eff = max_density;
-  c->minfo.density_bytes = n * dB;
-  c->minfo.cells_bytes = c->d_cells ? n * cB : 0;
-  c->minfo.albedo_bytes = n * aB;
-  c->minfo.bounds_bytes = bounds_bytes;
-  c->minfo.total_bytes = c->minfo.density_bytes + c->minfo.cells_bytes + c->minfo.albedo_bytes + c->minfo.bounds_bytes;
-  c->have_medium = true;
-  return CVR_OK;
-}
-
-// The sparse half: the leaf rule on the device, then cvr_set_medium_sparse from its upload on.
-// `bg`: voxel 0's albedo, or the constant.
-int devmed_sparse(cvr_ctx* c, const cvr_device_medium_desc* d, uint32_t fmt, float max_density, uint32_t bshift,
-                  const cvr::MedScan& scan, const float bg[4], cvr::MedScan* d_scan, DevTemps& tmp, DevmedTimer& tm) {
-  const uint32_t* res = d->res;
-  const uint32_t ln[3] = {(res[0] + 7u) / 8u, (res[1] + 7u) / 8u, (res[2] + 7u) / 8u};
-  const size_t nleaf = (size_t)ln[0] * ln[1] * ln[2];
-  const uint32_t B = 1u << bshift;
-  const uint32_t bnx = (res[0] + B - 1) / B, bny = (res[1] + B - 1) / B, bnz = (res[2] + B - 1) / B;
-  const size_t nb = (size_t)bnx * bny * bnz;
-  const bool konst = (d->flags & CVR_DEVMED_CONST_ALBEDO) != 0;
-  // the leaf albedo pool is kept iff some voxel's 16 bytes differ from the background; if none
-  // does, no leaf exists through its albedo either and the albedo is not read again
-  const bool keep_albedo = !konst && (scan.albedo_flags & 2u);
-  const float* albedo = keep_albedo ? d->d_albedo : nullptr;
-  hipStream_t s = c->stream;
-  uint32_t *d_flags = nullptr, *d_sums = nullptr, *d_table = nullptr, *d_slot_leaf = nullptr, *d_slot = nullptr,
-           *d_coords = nullptr;
-  HIP_TRY(c, tmp.alloc((void**)&d_flags, nleaf * sizeof(uint32_t)));
-  HIP_TRY(c, tmp.alloc((void**)&d_sums, cvr::flag_scan_tiles(nleaf) * sizeof(uint32_t)));
-  HIP_TRY(c, tmp.alloc((void**)&d_table, nleaf * sizeof(uint32_t)));
-  uint32_t totals[2] = {0, 0};
-  // leaves: flags -> scan -> table and slots
-  tm.begin();
-  HIP_TRY(c, cvr::launch_leaf_flags(d->d_density, albedo, res, ln, d_flags, s));
-  tm.end(2);
-  tm.begin();
-  HIP_TRY(c, cvr::launch_flag_scan(d_flags, nleaf, d_sums, &d_scan->total[0], s));
-  tm.end(3);
-  HIP_TRY(c, hipStreamSynchronize(s));
-  HIP_TRY(c, hipMemcpy(&totals[0], &d_scan->total[0], sizeof(uint32_t), hipMemcpyDeviceToHost));
-  const uint32_t n_leaves = totals[0];
-  const size_t np = (size_t)n_leaves * 512;
-  HIP_TRY(c, tmp.alloc((void**)&d_slot_leaf, (size_t)n_leaves * sizeof(uint32_t)));
-  tm.begin();
-  HIP_TRY(c, cvr::launch_scatter_leaves(d_flags, nleaf, d_sums, d_table, d_slot_leaf, s));
-  // cell leaves: a leaf's cells read the corners in it and its forward neighbours
-  HIP_TRY(c, cvr::launch_cell_leaf_flags(d_table, ln, d_flags, s));
-  HIP_TRY(c, cvr::launch_flag_scan(d_flags, nleaf, d_sums, &d_scan->total[1], s));
-  tm.end(3);
-  HIP_TRY(c, hipStreamSynchronize(s));
-  HIP_TRY(c, hipMemcpy(&totals[1], &d_scan->total[1], sizeof(uint32_t), hipMemcpyDeviceToHost));
-  const size_t ncl = (size_t)totals[1] + 1;  // slot 0: the zero leaf
-  if (ncl > (1u << 24))
-    return set_err(&c->err, CVR_ERR_UNSUPPORTED, "sparse medium needs %zu cell leaves (> 2^24)", ncl);
-  const size_t dB = fmt ? 2 : sizeof(float), cB = fmt ? 16 : 2 * sizeof(float4), aB = fmt ? 8 : sizeof(float4);
-  if (fmt) {
-    // cvr_set_medium_sparse names the pools' first overflowing index: when the scans of the grid
-    // saw an overflow, the gather runs once without storing to find that index
-    size_t at = 0;
-    const char* what = nullptr;
-    float value = 0.0f;
-    if (scan.ovf_density != ~0ull || scan.ovf_albedo != ~0ull) {
-      cvr::MedScan chk = scan;
-      chk.ovf_density = chk.ovf_albedo = ~0ull;
-      HIP_TRY(c, hipMemcpy(d_scan, &chk, sizeof(chk), hipMemcpyHostToDevice));
-      HIP_TRY(c, cvr::launch_gather_leaves(d->d_density, albedo, res, ln, d_slot_leaf, n_leaves, bg, fmt, nullptr,
-                                           nullptr, d_scan, s));
-      HIP_TRY(c, hipStreamSynchronize(s));
-      HIP_TRY(c, hipMemcpy(&chk, d_scan, sizeof(chk), hipMemcpyDeviceToHost));
-      const bool in_density = chk.ovf_density != ~0ull;
-      if (in_density || chk.ovf_albedo != ~0ull) {
-        what = in_density ? "leaf density" : "leaf albedo";
-        at = (size_t)(in_density ? chk.ovf_density : chk.ovf_albedo);
-        // the value, for the message: the pool voxel's grid voxel, or the background's channel
-        const size_t p = in_density ? at : at / 4;
-        uint32_t leaf = 0;
-        HIP_TRY(c, hipMemcpy(&leaf, d_slot_leaf + (p >> 9), sizeof(leaf), hipMemcpyDeviceToHost));
-        const uint32_t local = (uint32_t)(p & 511u);
-        const uint32_t x = (leaf % ln[0]) * 8u + (local & 7u), y = ((leaf / ln[0]) % ln[1]) * 8u + ((local >> 3) & 7u),
-                       z = (leaf / (ln[0] * ln[1])) * 8u + (local >> 6);
-        const size_t i = ((size_t)z * res[1] + y) * res[0] + x;
-        if (x < res[0] && y < res[1] && z < res[2])
-          HIP_TRY(c, hipMemcpy(&value, in_density ? d->d_density + i : d->d_albedo + 4 * i + at % 4, sizeof(float),
-                               hipMemcpyDeviceToHost));
-        else
-          value = in_density ? 0.0f : bg[at % 4];
-      }
-    }
-    for (size_t k = 0; k < 3 && !what; ++k)
-      if (overflows_half(bg[k])) what = "albedo_background", at = k, value = bg[k];
-    if (what) {
-      c->have_medium = false;
-      return set_err(&c->err, CVR_ERR_INVALID, "medium format half: %s value %g at index %zu rounds to infinity", what,
-                     (double)value, at);
-    }
-  }
-  // drop the previous medium (dense or sparse)
-  if (c->d_density) (void)hipFree(c->d_density);
-  if (c->d_albedo) (void)hipFree(c->d_albedo);
-  if (c->d_cells) (void)hipFree(c->d_cells);
-  if (c->d_bounds) (void)hipFree(c->d_bounds);
-  c->d_density = nullptr;
-  c->d_albedo = nullptr;
-  c->d_cells = nullptr;
-  c->d_bounds = nullptr;
-  c->n_voxels = 0;
-  c->have_medium = false;
-  free_sparse(c);
-  tmp.keep(d_table);
-  c->d_leaves = d_table;
-  HIP_TRY(c, hipMalloc(&c->d_leaf_density, (np ? np : 1) * dB));
-  if (keep_albedo && np) HIP_TRY(c, hipMalloc(&c->d_leaf_albedo, np * aB));
-  tm.begin();
-  HIP_TRY(c, cvr::launch_gather_leaves(d->d_density, c->d_leaf_albedo ? albedo : nullptr, res, ln, d_slot_leaf,
-                                       n_leaves, bg, fmt, c->d_leaf_density, c->d_leaf_albedo, nullptr, s));
-  tm.end(4);
-  cvr::MediumParams& m = c->m;
-  m = cvr::MediumParams{};
-  fill_medium_common(m, res, d->box_min, d->box_max, d->scale, max_density, d->g, d->roughness, d->eta);
-  m.format = fmt;
-  m.leaves = c->d_leaves;
-  m.leaf_density = c->d_leaf_density;
-  m.leaf_albedo = c->d_leaf_albedo;
-  m.lnx = ln[0];
-  m.lny = ln[1];
-  m.albedo_bg = cvr::V3{bg[0], bg[1], bg[2]};
-  if (fmt) m.albedo_bg = cvr::V3{half_round1(bg[0]), half_round1(bg[1]), half_round1(bg[2])};
-  const float sigma = d->scale * max_density;
-  const int unbounded = !(c->bound_shift && sigma > 0.0f && std::isfinite(sigma) && d->scale > 0.0f);
-  m.bshift = bshift;
-  m.bnx = bnx;
-  m.bny = bny;
-  m.bnxy = bnx * bny;
-  m.bsentinel = (uint32_t)nb;
-  HIP_TRY(c, hipMalloc(&c->d_sbounds, (nb + 1) * sizeof(uint32_t)));
-  if (c->use_cells) HIP_TRY(c, hipMalloc(&c->d_cells, ncl * 512 * cB));
-  // the empty-region mask's geometry, as cvr_set_medium_sparse derives it
-  uint32_t es = 3, lx = 0, ly = 0;
-  if (!unbounded) {
-    auto log2up = [](uint32_t v) {
-      uint32_t l = 0;
-      while ((1u << l) < v) ++l;
-      return l;
-    };
-    lx = log2up(ln[0]);
-    ly = log2up(ln[1]);
-    uint32_t lz = log2up(ln[2]);
-    while (lx + ly + lz > log2up(32u * cvr::kEmaskWords)) {
-      ++es;
-      lx -= lx > 0;
-      ly -= ly > 0;
-      lz -= lz > 0;
-    }
-    HIP_TRY(c, hipMalloc(&c->d_emask, cvr::kEmaskWords * sizeof(uint32_t)));
-    HIP_TRY(c, hipMemsetAsync(c->d_emask, 0, cvr::kEmaskWords * sizeof(uint32_t), s));
-    m.eshift = es;
-    m.eshy = lx;
-    m.eshz = lx + ly;
-    m.emask = c->d_emask;
-  }
-  HIP_TRY(c, tmp.alloc((void**)&d_slot, nleaf * sizeof(uint32_t)));
-  HIP_TRY(c, tmp.alloc((void**)&d_coords, 3 * ncl * sizeof(uint32_t)));
-  tm.begin();
-  HIP_TRY(c, cvr::launch_scatter_cell_leaves(d_flags, nleaf, d_sums, ln, d_slot, d_coords, c->d_emask, es - 3u, lx,
-                                             lx + ly, s));
-  tm.end(3);
-  tm.begin();
-  HIP_TRY(c, cvr::launch_build_sparse(m, d_coords, c->use_cells ? ncl : 0, d_slot, bnz, max_density, unbounded,
-                                      c->d_cells, c->d_sbounds, s));
-  tm.end(5);
-  HIP_TRY(c, hipStreamSynchronize(s));
-  m.cells = c->d_cells;
-  m.sbounds = c->d_sbounds;
-  c->n_cell_leaves = ncl;
-  c->minfo = {};
-  c->minfo.format = (int32_t)fmt;
-  c->minfo.max_density_eff = max_density;
-  c->minfo.density_bytes = (np ? np : 1) * dB;
-  c->minfo.cells_bytes = c->d_cells ? ncl * 512 * cB : 0;
-  c->minfo.albedo_bytes = c->d_leaf_albedo ? np * aB : 0;
-  c->minfo.bounds_bytes = (nb + 1 + nleaf + (c->d_emask ? cvr::kEmaskWords : 0)) * sizeof(uint32_t);
-  c->minfo.total_bytes = c->minfo.density_bytes + c->minfo.cells_bytes + c->minfo.albedo_bytes + c->minfo.bounds_bytes;
-  c->have_medium = true;
-  return CVR_OK;
-}
-}  // namespace
-
-int cvr_set_medium_device(cvr_ctx* c, const cvr_device_medium_desc* d) {
-  if (!c || !d) return set_err(c ? &c->err : nullptr, CVR_ERR_INVALID, "NULL argument");
-  CVR_NOT_IN_SESSION(c, "cvr_set_medium_device");
-  const uint32_t* res = d->res;
-  const bool sparse = (d->flags & CVR_DEVMED_SPARSE) != 0, konst = (d->flags & CVR_DEVMED_CONST_ALBEDO) != 0;
-  const uint32_t fmt = (uint32_t)c->medium_format;
-  // the host calls' shape guards, in their order and words, from res alone
-  if (res[0] == 0 || res[1] == 0 || res[2] == 0) return set_err(&c->err, CVR_ERR_INVALID, "empty grid");
-  const size_t n = (size_t)res[0] * res[1] * res[2];
-  uint32_t bshift = 0;
-  if (!sparse) {
-    if (n > 0xFFFFFFFFull) return set_err(&c->err, CVR_ERR_INVALID, "grid exceeds 2^32 voxels");
-    if ((uint64_t)res[1] * res[2] >= (1ull << 24) || (uint64_t)res[0] * res[1] >= (1ull << 24))
-      return set_err(&c->err, CVR_ERR_UNSUPPORTED, "dense grid with y*z or x*y >= 2^24: use cvr_set_medium_sparse");
-    if (!fmt && c->use_cells && n >= (1ull << 31))
-      return set_err(&c->err, CVR_ERR_UNSUPPORTED,
-                     "dense fp32 grid of %zu voxels (>= 2^31) with density cells: use CVR_OPT_MEDIUM_FORMAT 1, "
-                     "CVR_OPT_CELLS 0 or cvr_set_medium_sparse",
-                     n);
-  } else {
-    const size_t nleaf = (size_t)((res[0] + 7u) / 8u) * ((res[1] + 7u) / 8u) * ((res[2] + 7u) / 8u);
-    if (nleaf > 0xFFFFFFFFull) return set_err(&c->err, CVR_ERR_INVALID, "leaf table exceeds 2^32 entries");
-    bshift = !c->bound_shift_set ? 3u : c->bound_shift == 0 ? 2u : std::min(c->bound_shift, 3u);
-    const uint32_t B = 1u << bshift;
-    const uint32_t bnx = (res[0] + B - 1) / B, bny = (res[1] + B - 1) / B, bnz = (res[2] + B - 1) / B;
-    const size_t nb = (size_t)bnx * bny * bnz;
-    if ((uint64_t)bnx * bny >= (1ull << 24) || bnz > (1u << 24) || nb >= 0xFFFFFFFFull)
-      return set_err(&c->err, CVR_ERR_UNSUPPORTED,
-                     "sparse grid of %ux%ux%u bricks: x*y >= 2^24, z > 2^24 or %zu bricks >= 2^32 - 1 (a larger "
-                     "CVR_OPT_BOUNDS brick, up to 8 cells, has fewer)",
-                     bnx, bny, bnz, nb);
-  }
-  // then the flags and the pointers
-  if (d->flags & ~(uint32_t)(CVR_DEVMED_SPARSE | CVR_DEVMED_CONST_ALBEDO | CVR_DEVMED_MAX_DENSITY))
-    return set_err(&c->err, CVR_ERR_INVALID, "unknown cvr_device_medium_desc flags 0x%x", d->flags);
-  if (!d->d_density || (!konst && !d->d_albedo)) return set_err(&c->err, CVR_ERR_INVALID, "d_density/d_albedo is NULL");
-  if (konst && d->d_albedo)
-    return set_err(&c->err, CVR_ERR_INVALID, "d_albedo must be NULL with CVR_DEVMED_CONST_ALBEDO");
-  int r = ensure_device(c);
-  if (r) return r;
-  if (!device_readable(c, d->d_density) || (!konst && !device_readable(c, d->d_albedo)))
-    return set_err(&c->err, CVR_ERR_INVALID, "d_density/d_albedo is not device-accessible memory of device %d",
-                   c->device);
-  if (((uintptr_t)d->d_density & 3u) || ((uintptr_t)d->d_albedo & 15u))
-    return set_err(&c->err, CVR_ERR_INVALID, "d_density must be 4-byte and d_albedo 16-byte aligned");
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  DevTemps tmp;
-  DevmedTimer tm(c);
-  // the value scans: majorant, binary16 overflow, albedo sameness
-  cvr::MedScan scan{~0ull, ~0ull, 0u, 0u, {0u, 0u}};
-  cvr::MedScan* d_scan = nullptr;
-  HIP_TRY(c, tmp.alloc((void**)&d_scan, sizeof(scan)));
-  HIP_TRY(c, hipMemcpy(d_scan, &scan, sizeof(scan), hipMemcpyHostToDevice));
-  float first[4] = {d->const_albedo[0], d->const_albedo[1], d->const_albedo[2], d->const_albedo[3]};
-  if (fmt || (d->flags & CVR_DEVMED_MAX_DENSITY)) {
-    tm.begin();
-    HIP_TRY(c, cvr::launch_scan_density(d->d_density, n, fmt, d_scan, c->stream));
-    tm.end(0);
-  }
-  if (!konst) {
-    if (fmt || sparse || c->uniform_albedo) {
-      tm.begin();
-      HIP_TRY(c, cvr::launch_scan_albedo(d->d_albedo, n, fmt, d_scan, c->stream));
-      tm.end(1);
-    }
-    HIP_TRY(c, hipMemcpyAsync(first, d->d_albedo, sizeof(first), hipMemcpyDeviceToHost, c->stream));
-  }
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  HIP_TRY(c, hipMemcpy(&scan, d_scan, sizeof(scan), hipMemcpyDeviceToHost));
-  float max_density = d->max_density;
-  if (d->flags & CVR_DEVMED_MAX_DENSITY) memcpy(&max_density, &scan.max_bits, sizeof(float));
-  if (fmt) max_density = half_majorant(max_density);
-  if (sparse) return devmed_sparse(c, d, fmt, max_density, bshift, scan, first, d_scan, tmp, tm);
-  if (fmt) {
-    // cvr_set_medium's refusal: density before albedo, the smallest index (a constant albedo's
-    // grid overflows first at voxel 0)
-    const bool bad_d = scan.ovf_density != ~0ull;
-    size_t at = (size_t)scan.ovf_density;
-    float value = 0.0f;
-    bool bad_a = false;
-    if (bad_d) {
-      HIP_TRY(c, hipMemcpy(&value, d->d_density + at, sizeof(float), hipMemcpyDeviceToHost));
-    } else if (konst) {
-      for (size_t k = 0; k < 3 && !bad_a; ++k)
-        if (overflows_half(first[k])) bad_a = true, at = k, value = first[k];
-    } else if (scan.ovf_albedo != ~0ull) {
-      bad_a = true;
-      at = (size_t)scan.ovf_albedo;
-      HIP_TRY(c, hipMemcpy(&value, d->d_albedo + at, sizeof(float), hipMemcpyDeviceToHost));
-    }
-    if (bad_d || bad_a) {
-      c->have_medium = false;
-      return set_err(&c->err, CVR_ERR_INVALID, "medium format half: %s value %g at index %zu rounds to infinity",
-                     bad_d ? "density" : "albedo", (double)value, at);
-    }
-  }
-  return devmed_dense(c, d, fmt, max_density, scan, first, tm);
-}
-
-int cvr_debug_device_medium_ms(const cvr_ctx* c, double out[6]) {
-  if (!c || !out) return set_err(nullptr, CVR_ERR_INVALID, "NULL argument");
-  for (int i = 0; i < 6; ++i) out[i] = c->devmed_ms[i];
-  return CVR_OK;
-}
-
-int cvr_medium_layout(const cvr_ctx* c, struct cvr_medium_layout* out) {
-  if (!c || !out) return set_err(nullptr, CVR_ERR_INVALID, "NULL argument");
-  if (!c->have_medium) {
-    cvr::set_last_error("no medium");
-    return CVR_ERR_STATE;
-  }
-  const cvr::MediumParams& m = c->m;
-  struct cvr_medium_layout l {};
-  l.sparse = m.leaves != nullptr;
-  l.albedo_uniform = m.albedo_uniform;
-  if (l.sparse) {
-    // (the leaf pool holds 512 voxels per leaf, one voxel when there is no leaf)
-    l.n_leaves = (uint32_t)(c->minfo.density_bytes / (512u * (m.format ? 2u : 4u)));
-    l.n_cell_leaves = (uint32_t)c->n_cell_leaves;
-  }
-  l.brick_shift = m.bshift;
-  l.mask_shift = m.eshift;
-  if (l.sparse || m.albedo_uniform) {
-    l.albedo_bg[0] = m.albedo_bg.x;
-    l.albedo_bg[1] = m.albedo_bg.y;
-    l.albedo_bg[2] = m.albedo_bg.z;
-  }
-  if (m.emask) {
-    // the medium's own mask (a shared medium: the source context's buffer)
-    if (hipSetDevice(c->device) != hipSuccess ||
-        hipMemcpy(l.mask, m.emask, sizeof(l.mask), hipMemcpyDeviceToHost) != hipSuccess) {
-      cvr::set_last_error("cvr_medium_layout: reading the mask failed");
-      return CVR_ERR_HIP;
-    }
-  }
-  *out = l;
-  return CVR_OK;
-}
-
-int cvr_share_medium(cvr_ctx* c, const cvr_ctx* src) {
-  if (!c || !src) return set_err(c ? &c->err : nullptr, CVR_ERR_INVALID, "NULL argument");
-  CVR_NOT_IN_SESSION(c, "cvr_share_medium");
-  if (c == src) return CVR_OK;
-  if (!src->have_medium) return set_err(&c->err, CVR_ERR_STATE, "source context has no medium");
-  if (src->device != c->device)
-    return set_err(&c->err, CVR_ERR_INVALID, "source context is on device %d, not %d", src->device, c->device);
-  int r = ensure_device(c);
-  if (r) return r;
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  // drop this context's own medium; the kernels read the source's buffers
-  if (c->d_density) (void)hipFree(c->d_density);
-  if (c->d_albedo) (void)hipFree(c->d_albedo);
-  if (c->d_cells) (void)hipFree(c->d_cells);
-  if (c->d_bounds) (void)hipFree(c->d_bounds);
-  c->d_density = nullptr;
-  c->d_albedo = nullptr;
-  c->d_cells = nullptr;
-  c->d_bounds = nullptr;
-  c->n_voxels = 0;
-  free_sparse(c);
-  c->m = src->m;
-  c->minfo = src->minfo;
-  c->n_cell_leaves = src->n_cell_leaves;
-  c->have_medium = true;
-  c->inited = false;
-  return CVR_OK;
-}
-
-int cvr_medium_info(const cvr_ctx* c, struct cvr_medium_info* out) {
-  if (!c || !out) return set_err(nullptr, CVR_ERR_INVALID, "NULL argument");
-  if (!c->have_medium) {
-    cvr::set_last_error("no medium");
-    return CVR_ERR_STATE;
-  }
-  *out = c->minfo;
-  return CVR_OK;
-}
-
-int cvr_half_round(const float* in, float* out, size_t n) {
-  if (n && (!in || !out)) return set_err(nullptr, CVR_ERR_INVALID, "NULL argument");
-  for (size_t i = 0; i < n; ++i) out[i] = half_round1(in[i]);
   return CVR_OK;
 }
 
@@ -1993,7 +891,7 @@ int cvr_set_option(cvr_ctx* c, int opt, int64_t v) {
       c->use_cells = v != 0;
       return CVR_OK;
     case CVR_OPT_MEDIUM_FORMAT:
-      // takes effect at the next cvr_set_medium / cvr_set_medium_sparse
+      // takes effect at the next medium upload (cvr_medium.cpp)
       if (v != CVR_FORMAT_F32 && v != CVR_FORMAT_F16)
         return set_err(&c->err, CVR_ERR_INVALID, "medium format must be 0 (fp32) or 1 (half)");
       c->medium_format = (int)v;

@@ -1,0 +1,206 @@
+// cvr_ctx.h - the context behind the C ABI's cvr_ctx handle and what its call sites need with it
+// (internal: cvr_api.cpp, cvr_medium.cpp).
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <string>
+#include <vector>
+
+#include "cvr.h"
+#include "cvr_kernels.h"
+
+struct cvr_ctx {
+  int device = 0;
+  int kernel = CVR_KERNEL_REGENERATION_SK;
+  std::string err;
+
+  hipStream_t own_stream = nullptr;
+  hipStream_t stream = nullptr;
+  hipEvent_t ev_start = nullptr, ev_stop = nullptr;
+  bool timed = false;
+
+  // medium in HBM
+  float* d_density = nullptr;
+  float4* d_albedo = nullptr;
+  float4* d_cells = nullptr;  // corner-replicated density (MediumParams::cells)
+  bool use_cells = true;
+  bool uniform_albedo = true;  // CVR_OPT_UNIFORM_ALBEDO
+  uint8_t* d_bounds = nullptr;  // brick bounds (MediumParams::bounds)
+  uint32_t bound_shift = 2;     // log2 brick size, 0 = off
+  bool bound_shift_set = false; // CVR_OPT_BOUNDS given (else sparse media use 8^3 bricks)
+  size_t n_voxels = 0;
+  uint32_t grids_format = 0;  // format d_density / d_albedo were allocated for
+  // sparse medium (cvr_set_medium_sparse)
+  uint32_t* d_leaves = nullptr;
+  float* d_leaf_density = nullptr;
+  float4* d_leaf_albedo = nullptr;
+  uint32_t* d_sbounds = nullptr;
+  uint32_t* d_emask = nullptr;       // empty-region mask (MediumParams::emask)
+  uint32_t* d_block_perm = nullptr;  // cvr_set_block_order
+  void* d_rec_active = nullptr;      // cvr_trace_launch: records of the launch in progress
+  uint32_t block_perm_n = 0;
+  size_t n_cell_leaves = 0;  // cell-leaf pool slots (incl. the zero slot)
+  bool have_medium = false;
+  cvr::MediumParams m{};
+  int medium_format = 0;     // CVR_OPT_MEDIUM_FORMAT (the next set-medium's; the medium's own is m.format)
+  struct cvr_medium_info minfo{};  // cvr_medium_info of the medium in use (own or shared)
+
+  // launcher state (the reference's __constant__ symbols)
+  float inv_view[12] = {1, 0, 0, 0, 0, -1, 0, 0, 0, 0, -1, 100};
+  float r2v[2] = {0, 0};
+  float full_res[2] = {0, 0};
+  bool have_camera = false;
+  uint32_t tile_w = 0, tile_h = 0;
+  uint32_t off[2] = {0, 0};
+  uint32_t iterations = 1;
+  uint64_t n_paths = 0;
+  uint64_t range_first = 0, range_count = UINT64_MAX;
+  uint32_t shard_rank = 0, shard_world = 1;  // cvr_set_block_shard
+  uint32_t seed = 0;
+
+  float4* d_out_owned = nullptr;
+  size_t out_owned_px = 0;
+  float4* d_out = nullptr;  // active output (owned or external)
+  bool external_out = false;
+
+  unsigned char* d_work = nullptr;  // queue heads + stats counters (kWork* layout)
+  float4* d_pool_T = nullptr;       // wave-pool scheduler: event-only slot part (LaunchParams::pool_T)
+  unsigned char* d_smk = nullptr;   // thread-bound streamingMK: slot buffers, flags, RNG states, counters
+  size_t smk_n = 0;                 // threads d_smk is carved for
+  size_t pool_T_n = 0;
+  uint32_t n_queues = 8;            // work-order bands (one per XCD)
+  uint32_t subqueues = 8;           // wave pool: queues per band (CVR_OPT_SUBQUEUES)
+  int drain = -1;                   // wave pool: drain-mode event trigger (CVR_OPT_DRAIN; -1 = 1)
+  int order = 2;                    // 1: pixel-block/sample-inner order when the launch allows it; 2: blocks
+                                    // in 2-D Morton order within each band
+  // cached Morton permutation of the launch's blocks (order 2), for the block layout in zkey
+  uint32_t* d_zperm = nullptr;
+  std::vector<uint32_t> h_zperm;
+  uint64_t zkey[5] = {0, 0, 0, 0, 0};
+
+  // options
+  uint32_t max_segments = 1u << 20;
+  uint32_t chunk = 0;  // paths per wave dequeue; 0: auto (wave pool: 64..256 by the launch's size, others 256)
+  uint32_t ev_thresh = 56;
+  uint32_t grid_override = 0;
+  uint32_t inflight = 1;  // CVR_OPT_INFLIGHT: renders the caller keeps in flight (wave-pool grid rule)
+  int scatter_eps = -1;
+  int rng_binding = 0;  // CVR_OPT_RNG_BINDING
+  int world_to_aabb = 0;  // CVR_OPT_WORLD_TO_AABB (Q4)
+  int mk_compaction = 0;  // CVR_OPT_MK_COMPACTION (Q11)
+
+  int cu_count = 0;
+  int persistent_grid = 0;
+  int pool_grid = 0;
+  uint32_t pool_tail = 16;
+  int wpool_grid = 0, wpool_grid_sparse = 0;
+  // wave-pool register/LDS budget in waves per SIMD (CVR_OPT_WAVES: 3, 4, 5);
+  // 0 = the default, 5 (dense and sparse, split slots)
+  int wpool_waves = 0;
+  int morton = 0;  // CVR_OPT_MORTON
+  int sample_order = -1;  // CVR_OPT_SAMPLE_ORDER (-1: the default, 0)
+  int empty_mask = 1;     // CVR_OPT_EMPTY_MASK
+  int count_words = 0;    // CVR_OPT_COUNT_WORDS
+  uint32_t swap_batch = 8;
+  int track_grid = 0;
+  bool inited = false;
+  int scheduler = -1;  // 0 persistent, 1 wavefront pair, 2 workgroup pool, 3 wave-private pool, -1 per kernel id
+  int waves = 4;      // persistent kernel register budget (waves per SIMD)
+
+  // wavefront pool (cvr_wavefront.hip)
+  unsigned char* d_pool = nullptr;
+  size_t pool_bytes = 0;
+  uint32_t pool_cap = 0;  // slots the allocation holds
+  uint32_t pool_max = 1u << 21;
+  cvr::WfPool pool{};
+  unsigned int* h_alive = nullptr;  // pinned ring of per-iteration flags
+  std::vector<hipEvent_t> it_events;
+  uint64_t last_iterations = 0;
+  double last_track_ms = 0, last_events_ms = 0;
+  bool wf_timing = false;
+  // cvr_set_medium_device with CVR_OPT_TIMING: device ms of its last call's density scan, albedo
+  // scan, leaf flags, scans and scatters, gather, and cells / bounds / brick words
+  double devmed_ms[6] = {0, 0, 0, 0, 0, 0};
+
+  cvr_stats last{};
+
+  // cvr_render_frame: this launch's band of block rows (band_count 0: every block), the
+  // helper contexts that render the frame's other bands (each with its own stream and work
+  // queues, sharing this context's medium and framebuffer), the copy stream, and the
+  // normalised device image the bands are copied from
+  uint32_t band_first = 0, band_count = 0;
+  std::vector<cvr_ctx*> frame_kids;
+  hipStream_t frame_copy = nullptr;
+  hipEvent_t frame_ev[4] = {nullptr, nullptr, nullptr, nullptr};  // [0] cleared, [1 + k] band k rendered
+  float4* d_frame = nullptr;
+  size_t frame_px = 0;
+  // cvr_render_frame's in-launch output (CVR_OPT_FRAME_FLUSH, wave pool): [FrameFlush
+  // header | per-block ended-path counts], the flushers' status words (pinned), the
+  // header as last written, and the counts the next launch takes (null: none)
+  int frame_flush = 1;
+  unsigned char* d_flush = nullptr;
+  size_t flush_blocks = 0;
+  unsigned int* h_flush_status = nullptr;
+  cvr::FrameFlush flush_hdr{};
+  bool flush_hdr_valid = false;  // d_flush holds flush_hdr
+  unsigned int* frame_done_active = nullptr;
+  uint32_t flush_last_blocks = 0, flush_fallbacks = 0;
+
+  // CVR_OPT_MOMENTS: the owned framebuffer holds a second float4 per pixel behind the tile
+  int moments = 0;
+  // The active block list (cvr_adaptive_*): while active_on, a launch renders exactly the tile
+  // blocks of `active` (ascending ids), n_blocks = its length; d_active holds them in the
+  // launch's order (each XCD band in 2-D Morton order), h_active the same on the host.
+  bool active_on = false;
+  std::vector<uint32_t> active, h_active;
+  uint32_t* d_active = nullptr;  // tile_px / 64 entries
+  // the adaptive session
+  struct Adaptive {
+    bool on = false;        // between cvr_adaptive_begin and cvr_adaptive_end
+    bool internal = false;  // the session's own launch is running through the public entry points
+    cvr_adaptive_desc d{};
+    uint32_t n_blocks = 0, passes = 0;
+    int done = 0;
+    uint64_t paths = 0;
+    std::vector<uint32_t> samples;  // per tile block
+    std::vector<double> err;        // per tile block, at its last check
+    std::vector<double> h_err;      // the last pass's errors, in h_active order
+    double* d_err = nullptr;        // tile_px / 64 doubles
+    uint32_t* d_counts = nullptr;   // tile_px / 64 sample counts (cvr_adaptive_image)
+    int saved_moments = 0;
+    uint32_t saved_iterations = 1;
+    cvr_stats acc{};
+  } ad;
+  // cvr_denoise*: the two scratch images the passes alternate between (dn_px pixels each)
+  float4* d_dn = nullptr;
+  size_t dn_px = 0;
+};
+
+namespace cvr {
+// The thread's last-error text, and *dst when given, become the formatted message; returns code.
+int set_err(std::string* dst, int code, const char* fmt, ...);
+int ensure_device(cvr_ctx* c);
+// The context's own medium buffers, freed and reset: the sparse medium's five, the dense medium's four grids.
+void free_sparse(cvr_ctx* c);
+void drop_dense(cvr_ctx* c);
+// f32 -> binary16 -> f32, round to nearest even, subnormals kept (CVR_OPT_MEDIUM_FORMAT 1)
+float half_round1(float f);
+// first finite value of v[0..n) (of every `stride`-th group's first `take` values) that rounds to +-inf
+bool half_overflows(const float* v, size_t n, size_t stride, size_t take, size_t* at);
+// the format-1 majorant: max(max_density, f32(f16(max_density))), max_density itself if that overflows
+float half_majorant(float max_density);
+}  // namespace cvr
+
+// Calls that are out of order inside an adaptive session (the session's own launches pass).
+#define CVR_NOT_IN_SESSION(c, what)                                                                       \
+  do {                                                                                                    \
+    if ((c)->ad.on && !(c)->ad.internal)                                                                  \
+      return cvr::set_err(&(c)->err, CVR_ERR_STATE, "%s inside an adaptive session (cvr_adaptive_end first)", what); \
+  } while (0)
+
+#define HIP_TRY(ctx, expr)                                                                         \
+  do {                                                                                                  \
+    hipError_t e_ = (expr);                                                                             \
+    if (e_ != hipSuccess)                                                                               \
+      return cvr::set_err((ctx) ? &(ctx)->err : nullptr, CVR_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_)); \
+  } while (0)

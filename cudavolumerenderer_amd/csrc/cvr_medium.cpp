@@ -1,0 +1,857 @@
+// cvr_medium.cpp - the medium of a context: the host uploads (dense, sparse) and the build from
+// device memory through one set of stages, and what the context tells of the result.
+//
+// Each rule is stated once: the shape guards (dense_shape_check, sparse_shape_check), the dense
+// build from the grids on (finish_dense), the sparse build from a leaf table in device memory on
+// (finish_sparse).  The cell-leaf rule and the empty-region mask's bits are cvr_medium_build.hip's.
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <vector>
+
+#include "cvr_ctx.h"
+
+using cvr::ensure_device;
+using cvr::set_err;
+
+namespace cvr {
+float half_round1(float f) {
+  uint32_t u;
+  memcpy(&u, &f, 4);
+  const uint32_t sign = u & 0x80000000u, a = u & 0x7FFFFFFFu;
+  uint32_t r;
+  if (a >= 0x7F800000u) {
+    // inf stays inf; NaN keeps its top 10 payload bits and stays NaN (quiet bit set if they are all 0)
+    r = a == 0x7F800000u ? a : ((a & 0xFFFFE000u) | 0x00400000u);
+  } else if (a >= 0x477FF000u) {
+    r = 0x7F800000u;  // >= 65520: rounds to inf
+  } else if (a >= 0x38800000u) {
+    // normal half: keep 10 mantissa bits, nearest even on the 13 dropped (a carry moves to the next
+    // exponent, at most to 65504's successor, excluded above)
+    r = (a + 0x00000FFFu + ((a >> 13) & 1u)) & 0xFFFFE000u;
+  } else {
+    // below 2^-14: multiples of 2^-24.  Adding 2^-1 (ulp 2^-24 in [0.5, 1)) rounds to nearest even.
+    float t;
+    memcpy(&t, &a, 4);
+    const float k = (t + 0.5f) - 0.5f;
+    memcpy(&r, &k, 4);
+  }
+  r |= sign;
+  float o;
+  memcpy(&o, &r, 4);
+  return o;
+}
+// f is finite and rounds to +-inf: 65520 <= |f| < inf, one unsigned compare of |f|'s bits
+static inline bool overflows_half(float f) {
+  uint32_t u;
+  memcpy(&u, &f, 4);
+  return (u & 0x7FFFFFFFu) - 0x477FF000u < 0x7F800000u - 0x477FF000u;
+}
+bool half_overflows(const float* v, size_t n, size_t stride, size_t take, size_t* at) {
+  // a block of groups at a time without an exit, which the compiler vectorises; a block that
+  // holds such a value is then searched in order
+  constexpr size_t kBlock = 1024;
+  for (size_t i0 = 0; i0 < n; i0 += kBlock) {
+    const size_t i1 = std::min(n, i0 + kBlock);
+    bool any = false;
+    for (size_t i = i0; i < i1; ++i)
+      for (size_t k = 0; k < take; ++k) any |= overflows_half(v[i * stride + k]);
+    if (!any) continue;
+    for (size_t i = i0; i < i1; ++i)
+      for (size_t k = 0; k < take; ++k)
+        if (overflows_half(v[i * stride + k])) {
+          *at = i * stride + k;
+          return true;
+        }
+  }
+  return false;
+}
+float half_majorant(float max_density) {
+  const float h = half_round1(max_density);
+  return (std::isfinite(h) && h > max_density) ? h : max_density;
+}
+
+void free_sparse(cvr_ctx* c) {
+  if (c->d_leaves) (void)hipFree(c->d_leaves);
+  if (c->d_leaf_density) (void)hipFree(c->d_leaf_density);
+  if (c->d_leaf_albedo) (void)hipFree(c->d_leaf_albedo);
+  if (c->d_sbounds) (void)hipFree(c->d_sbounds);
+  if (c->d_emask) (void)hipFree(c->d_emask);
+  c->d_emask = nullptr;
+  c->d_leaves = nullptr;
+  c->d_leaf_density = nullptr;
+  c->d_leaf_albedo = nullptr;
+  c->d_sbounds = nullptr;
+  c->n_cell_leaves = 0;
+}
+void drop_dense(cvr_ctx* c) {
+  if (c->d_density) (void)hipFree(c->d_density);
+  if (c->d_albedo) (void)hipFree(c->d_albedo);
+  if (c->d_cells) (void)hipFree(c->d_cells);
+  if (c->d_bounds) (void)hipFree(c->d_bounds);
+  c->d_density = nullptr;
+  c->d_albedo = nullptr;
+  c->d_cells = nullptr;
+  c->d_bounds = nullptr;
+  c->n_voxels = 0;
+}
+}  // namespace cvr
+
+using cvr::drop_dense;
+using cvr::free_sparse;
+using cvr::half_majorant;
+using cvr::half_overflows;
+using cvr::half_round1;
+
+namespace {
+// Device allocations of one call, freed on every way out of it (keep(): the context owns it now)
+struct DevTemps {
+  std::vector<void*> p;
+  ~DevTemps() {
+    for (void* q : p) (void)hipFree(q);
+  }
+  hipError_t alloc(void** out, size_t bytes) {
+    const hipError_t e = hipMalloc(out, bytes ? bytes : 4);
+    if (e == hipSuccess) p.push_back(*out);
+    return e;
+  }
+  void keep(void* q) { p.erase(std::remove(p.begin(), p.end(), q), p.end()); }
+};
+// Device time of the launches between begin() and end(i), added to devmed_ms[i] (CVR_OPT_TIMING;
+// without it no event and no synchronisation)
+struct DevmedTimer {
+  cvr_ctx* c;
+  hipEvent_t a = nullptr, b = nullptr;
+  bool on;
+  explicit DevmedTimer(cvr_ctx* ctx) : c(ctx), on(ctx->wf_timing) {
+    for (double& v : c->devmed_ms) v = 0.0;
+    if (on) on = hipEventCreate(&a) == hipSuccess && hipEventCreate(&b) == hipSuccess;
+  }
+  ~DevmedTimer() {
+    if (a) (void)hipEventDestroy(a);
+    if (b) (void)hipEventDestroy(b);
+  }
+  void begin() {
+    if (on) (void)hipEventRecord(a, c->stream);
+  }
+  void end(int i) {
+    float ms = 0.f;
+    if (on && hipEventRecord(b, c->stream) == hipSuccess && hipEventSynchronize(b) == hipSuccess &&
+        hipEventElapsedTime(&ms, a, b) == hipSuccess)
+      c->devmed_ms[i] += ms;
+  }
+};
+// p is memory the context's device can read, by what the runtime knows of it: device memory of
+// that device, managed memory, or mapped host memory (an address HIP does not know is refused)
+bool device_readable(const cvr_ctx* c, const void* p) {
+  hipPointerAttribute_t at{};
+  if (hipPointerGetAttributes(&at, p) != hipSuccess) {
+    (void)hipGetLastError();
+    return false;
+  }
+  if (at.type == hipMemoryTypeDevice) return at.device == c->device;
+  return (at.type == hipMemoryTypeManaged || at.type == hipMemoryTypeHost) && at.devicePointer != nullptr;
+}
+using cvr::overflows_half;
+
+// What the three descriptors say of the medium besides its arrays
+struct MediumView {
+  const uint32_t* res;
+  const float *box_min, *box_max;
+  float scale, g;
+  const float* roughness;
+  float eta;
+};
+template <class Desc>
+MediumView view_of(const Desc& d) {
+  return {d.res, d.box_min, d.box_max, d.scale, d.g, d.roughness, d.eta};
+}
+
+// Geometry, scale and BSDF parameters shared by the dense and sparse media
+// (HeterogeneousMedium + GGX, Medium.h:110-190).
+void fill_medium_common(cvr::MediumParams& m, const MediumView& v, float max_density) {
+  const uint32_t* res = v.res;
+  m.rx = res[0];
+  m.ry = res[1];
+  m.rz = res[2];
+  m.rxy = res[0] * res[1];  // only used by dense media, where it is < 2^24
+  m.fres_x = (float)res[0];
+  m.fres_y = (float)res[1];
+  m.fres_z = (float)res[2];
+  m.gx = m.agx = (float)(res[0] - 1u);
+  m.gy = m.agy = (float)(res[1] - 1u);
+  m.gz = m.agz = (float)(res[2] - 1u);
+  m.bmin = cvr::V3{v.box_min[0], v.box_min[1], v.box_min[2]};
+  m.bmax = cvr::V3{v.box_max[0], v.box_max[1], v.box_max[2]};
+  const float ex = v.box_max[0] - v.box_min[0], ey = v.box_max[1] - v.box_min[1], ez = v.box_max[2] - v.box_min[2];
+  m.shift = cvr::V3{v.box_min[0] / ex, v.box_min[1] / ey, v.box_min[2] / ez};
+  m.scale = v.scale;
+  m.inv_sigma = 1.0f / (v.scale * max_density);
+  m.g = v.g;
+  m.ax = v.roughness[0];
+  m.ay = v.roughness[1];
+  m.eta = v.eta;
+  m.inv_eta = 1.0f / v.eta;
+}
+
+// bytes per density voxel / cell / albedo voxel of a storage format
+struct FormatBytes {
+  size_t d, c, a;
+};
+FormatBytes format_bytes(uint32_t fmt) {
+  return fmt ? FormatBytes{2, 16, 8} : FormatBytes{sizeof(float), 2 * sizeof(float4), sizeof(float4)};
+}
+// brick bounds are built (else every brick is unbounded and a sparse medium has no mask)
+bool bounded(const cvr_ctx* c, float scale, float max_density) {
+  const float sigma = scale * max_density;
+  return c->bound_shift && sigma > 0.0f && std::isfinite(sigma) && scale > 0.0f;
+}
+void set_minfo(cvr_ctx* c, uint32_t fmt, float max_density, size_t density, size_t cells, size_t albedo, size_t bounds) {
+  c->minfo = {};
+  c->minfo.format = (int32_t)fmt;
+  c->minfo.max_density_eff = max_density;
+  c->minfo.density_bytes = density;
+  c->minfo.cells_bytes = cells;
+  c->minfo.albedo_bytes = albedo;
+  c->minfo.bounds_bytes = bounds;
+  c->minfo.total_bytes = density + cells + albedo + bounds;
+}
+
+// ------------------------------------------------------------------- dense ----
+// The shape of a dense grid, judged from the numbers alone (before any array is looked at)
+int dense_shape_check(cvr_ctx* c, const uint32_t res[3], uint32_t fmt) {
+  if (res[0] == 0 || res[1] == 0 || res[2] == 0) return set_err(&c->err, CVR_ERR_INVALID, "empty grid");
+  const size_t n = (size_t)res[0] * res[1] * res[2];
+  if (n > 0xFFFFFFFFull) return set_err(&c->err, CVR_ERR_INVALID, "grid exceeds 2^32 voxels");
+  // the kernels index cells and bricks with 24-bit multiplies
+  if ((uint64_t)res[1] * res[2] >= (1ull << 24) || (uint64_t)res[0] * res[1] >= (1ull << 24))
+    return set_err(&c->err, CVR_ERR_UNSUPPORTED, "dense grid with y*z or x*y >= 2^24: use cvr_set_medium_sparse");
+  // an fp32 cell is two float4: dense_cell doubles the u32 cell index (the half format's cell is one)
+  if (!fmt && c->use_cells && n >= (1ull << 31))
+    return set_err(&c->err, CVR_ERR_UNSUPPORTED,
+                   "dense fp32 grid of %zu voxels (>= 2^31) with density cells: use CVR_OPT_MEDIUM_FORMAT 1, "
+                   "CVR_OPT_CELLS 0 or cvr_set_medium_sparse",
+                   n);
+  return CVR_OK;
+}
+
+// The context's density and albedo grids for n voxels of format fmt: the previous dense medium's
+// when both match (the grids' bytes depend on the format too), else new ones.  The previous
+// medium is gone from here on.
+int dense_grids(cvr_ctx* c, size_t n, uint32_t fmt) {
+  const FormatBytes B = format_bytes(fmt);
+  free_sparse(c);
+  c->have_medium = false;
+  if (n != c->n_voxels || !c->d_density || c->grids_format != fmt) {
+    drop_dense(c);
+    HIP_TRY(c, hipMalloc(&c->d_density, n * B.d));
+    HIP_TRY(c, hipMalloc(&c->d_albedo, n * B.a));
+    c->n_voxels = n;
+    c->grids_format = fmt;
+  }
+  return CVR_OK;
+}
+
+// The dense medium from its filled grids on: cells, brick bounds, MediumParams, cvr_medium_info.
+// uniform_rgb: null, or the unrounded rgb that every voxel's equals (format 1: after rounding).
+int finish_dense(cvr_ctx* c, const MediumView& v, uint32_t fmt, float max_density, const float* uniform_rgb,
+                 DevmedTimer& tm) {
+  const uint32_t* res = v.res;
+  const size_t n = (size_t)res[0] * res[1] * res[2];
+  const FormatBytes B = format_bytes(fmt);
+  if (c->d_cells) (void)hipFree(c->d_cells);
+  c->d_cells = nullptr;
+  tm.begin();
+  if (c->use_cells) {
+    HIP_TRY(c, hipMalloc(&c->d_cells, n * B.c));
+    HIP_TRY(c, cvr::launch_build_cells(c->d_density, res[0], res[1], res[2], c->d_cells, c->stream, fmt));
+  }
+  if (c->d_bounds) (void)hipFree(c->d_bounds);
+  c->d_bounds = nullptr;
+  size_t bounds_bytes = 0;
+  uint32_t bnx = 0, bny = 0, bsentinel = 0;
+  if (bounded(c, v.scale, max_density)) {
+    const uint32_t S = 1u << c->bound_shift;
+    bnx = (res[0] + S - 1) / S;
+    bny = (res[1] + S - 1) / S;
+    const size_t nb = (size_t)bnx * bny * ((res[2] + S - 1) / S);
+    bsentinel = (uint32_t)nb;  // the no-bound entry past the last brick (k_build_bounds writes it)
+    HIP_TRY(c, hipMalloc(&c->d_bounds, nb + 1));
+    bounds_bytes = nb + 1;
+    HIP_TRY(c, cvr::launch_build_bounds(c->d_density, res[0], res[1], res[2], c->bound_shift, max_density,
+                                        c->d_bounds, c->stream, fmt));
+  }
+  tm.end(5);
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  cvr::MediumParams& m = c->m;
+  m = cvr::MediumParams{};
+  m.bounds = c->d_bounds;
+  m.bshift = c->bound_shift;
+  m.bnx = bnx;
+  m.bny = bny;
+  m.bnxy = bnx * bny;
+  m.bsentinel = bsentinel;
+  m.cells = c->d_cells;
+  m.density = c->d_density;
+  m.albedo = c->d_albedo;
+  fill_medium_common(m, v, max_density);
+  m.format = fmt;
+  if (uniform_rgb) {
+    m.albedo_uniform = 1u;
+    m.albedo_bg = fmt ? cvr::V3{half_round1(uniform_rgb[0]), half_round1(uniform_rgb[1]), half_round1(uniform_rgb[2])}
+                      : cvr::V3{uniform_rgb[0], uniform_rgb[1], uniform_rgb[2]};
+  }
+  set_minfo(c, fmt, max_density, n * B.d, c->d_cells ? n * B.c : 0, n * B.a, bounds_bytes);
+  c->have_medium = true;
+  return CVR_OK;
+}
+
+// ------------------------------------------------------------------ sparse ----
+// Leaf and brick grids of a sparse medium of resolution res
+struct SparseGeom {
+  uint32_t ln[3];  // ceil(res / 8)
+  size_t nleaf;
+  uint32_t bshift, bnx, bny, bnz;
+  size_t nb;
+};
+// The shape of a sparse grid, judged from the numbers alone; fills *g
+int sparse_shape_check(cvr_ctx* c, const uint32_t res[3], SparseGeom* g) {
+  if (res[0] == 0 || res[1] == 0 || res[2] == 0) return set_err(&c->err, CVR_ERR_INVALID, "empty grid");
+  for (int k = 0; k < 3; ++k) g->ln[k] = (res[k] + 7u) / 8u;
+  g->nleaf = (size_t)g->ln[0] * g->ln[1] * g->ln[2];
+  if (g->nleaf > 0xFFFFFFFFull) return set_err(&c->err, CVR_ERR_INVALID, "leaf table exceeds 2^32 entries");
+  // bricks of 2^bshift <= 8 cells (within one leaf); bounds off -> q = 255.
+  // Default 8^3 cells per brick: one brick word per leaf's cells (C5: 33.6 MB
+  // of words instead of 268 MB at 4^3, so they stay in L2 / Infinity Cache;
+  // 12% faster at an unchanged fetch rate, clouds being empty or dense).
+  g->bshift = !c->bound_shift_set ? 3u : c->bound_shift == 0 ? 2u : std::min(c->bound_shift, 3u);
+  const uint32_t S = 1u << g->bshift;
+  g->bnx = (res[0] + S - 1) / S;
+  g->bny = (res[1] + S - 1) / S;
+  g->bnz = (res[2] + S - 1) / S;
+  g->nb = (size_t)g->bnx * g->bny * g->bnz;
+  // the kernels index brick words and leaves with 24-bit multiplies, bz * (bnx bny) + by * bnx + bx
+  // and (lz * lny + ly) * lnx + lx, and a u32 sum (refused before anything is read or the previous
+  // medium is dropped)
+  if ((uint64_t)g->bnx * g->bny >= (1ull << 24) || g->bnz > (1u << 24) || g->nb >= 0xFFFFFFFFull)
+    return set_err(&c->err, CVR_ERR_UNSUPPORTED,
+                   "sparse grid of %ux%ux%u bricks: x*y >= 2^24, z > 2^24 or %zu bricks >= 2^32 - 1 (a larger "
+                   "CVR_OPT_BOUNDS brick, up to 8 cells, has fewer)",
+                   g->bnx, g->bny, g->bnz, g->nb);
+  return CVR_OK;
+}
+
+// Empty-region mask (MediumParams::emask): the smallest super-brick of 2^es cells per axis whose
+// grid, each axis padded to a power of two (2^lx, 2^ly, ...), fits the 32 kEmaskWords bits.
+struct EmaskGeom {
+  uint32_t es, lx, ly;
+};
+EmaskGeom emask_geometry(const uint32_t ln[3]) {
+  auto log2up = [](uint32_t v) {
+    uint32_t l = 0;
+    while ((1u << l) < v) ++l;
+    return l;
+  };
+  uint32_t es = 3, lx = log2up(ln[0]), ly = log2up(ln[1]), lz = log2up(ln[2]);
+  while (lx + ly + lz > log2up(32u * cvr::kEmaskWords)) {
+    ++es;
+    lx -= lx > 0;
+    ly -= ly > 0;
+    lz -= lz > 0;
+  }
+  return {es, lx, ly};
+}
+
+// What finish_sparse builds from.  d_table is the leaf table (slot or CVR_NO_LEAF per leaf, the
+// slots in any order), a DevTemps allocation of g.nleaf words that the context adopts; d_flags
+// (g.nleaf words), d_sums (flag_scan_tiles(g.nleaf) words) and d_total (one word) are scratch.
+struct SparseBuild {
+  MediumView v;
+  SparseGeom g;
+  uint32_t fmt;
+  float max_density;
+  const float* bg;   // background albedo, unrounded
+  uint32_t n_leaves;  // slots of the pools
+  bool albedo_pool;
+  uint32_t *d_table, *d_flags, *d_sums, *d_total;
+};
+
+// The sparse medium from a leaf table in device memory on.  A leaf's cells read the corners in it
+// and its forward neighbours, so it has a cell leaf iff one of those 8 leaves exists; slot 0 is the
+// zero leaf.  refuse_overflow() (format 1 only) returns the refusal of values that round to
+// infinity, or CVR_OK; it runs after the cell-leaf count's refusal, which keeps the previous
+// medium, and leaves the context without one.  fill_pools() fills c->d_leaf_density and, if
+// allocated, c->d_leaf_albedo.
+template <class Refuse, class Fill>
+int finish_sparse(cvr_ctx* c, const SparseBuild& b, DevTemps& tmp, DevmedTimer& tm, Refuse refuse_overflow,
+                  Fill fill_pools) {
+  const SparseGeom& g = b.g;
+  const FormatBytes B = format_bytes(b.fmt);
+  hipStream_t s = c->stream;
+  tm.begin();
+  HIP_TRY(c, cvr::launch_cell_leaf_flags(b.d_table, g.ln, b.d_flags, s));
+  HIP_TRY(c, cvr::launch_flag_scan(b.d_flags, g.nleaf, b.d_sums, b.d_total, s));
+  tm.end(3);
+  HIP_TRY(c, hipStreamSynchronize(s));
+  uint32_t total = 0;
+  HIP_TRY(c, hipMemcpy(&total, b.d_total, sizeof(total), hipMemcpyDeviceToHost));
+  const size_t ncl = (size_t)total + 1;  // slot 0: the zero leaf
+  if (ncl > (1u << 24))
+    return set_err(&c->err, CVR_ERR_UNSUPPORTED, "sparse medium needs %zu cell leaves (> 2^24)", ncl);
+  int r = b.fmt ? refuse_overflow() : CVR_OK;
+  if (r) {
+    c->have_medium = false;
+    return r;
+  }
+  // drop the previous medium (dense or sparse)
+  drop_dense(c);
+  c->have_medium = false;
+  free_sparse(c);
+  tmp.keep(b.d_table);
+  c->d_leaves = b.d_table;
+  const size_t np = (size_t)b.n_leaves * 512;
+  HIP_TRY(c, hipMalloc(&c->d_leaf_density, (np ? np : 1) * B.d));
+  if (b.albedo_pool && np) HIP_TRY(c, hipMalloc(&c->d_leaf_albedo, np * B.a));
+  tm.begin();
+  if ((r = fill_pools())) return r;
+  tm.end(4);
+  cvr::MediumParams& m = c->m;
+  m = cvr::MediumParams{};
+  fill_medium_common(m, b.v, b.max_density);
+  m.format = b.fmt;
+  m.leaves = c->d_leaves;
+  m.leaf_density = c->d_leaf_density;
+  m.leaf_albedo = c->d_leaf_albedo;
+  m.lnx = g.ln[0];
+  m.lny = g.ln[1];
+  m.albedo_bg = b.fmt ? cvr::V3{half_round1(b.bg[0]), half_round1(b.bg[1]), half_round1(b.bg[2])}
+                      : cvr::V3{b.bg[0], b.bg[1], b.bg[2]};
+  const int unbounded = !bounded(c, b.v.scale, b.max_density);
+  m.bshift = g.bshift;
+  m.bnx = g.bnx;
+  m.bny = g.bny;
+  m.bnxy = g.bnx * g.bny;
+  m.bsentinel = (uint32_t)g.nb;  // the no-bound word past the last brick (k_build_sparse_bounds writes it)
+  HIP_TRY(c, hipMalloc(&c->d_sbounds, (g.nb + 1) * sizeof(uint32_t)));
+  if (c->use_cells) HIP_TRY(c, hipMalloc(&c->d_cells, ncl * 512 * B.c));
+  // the mask: bit set iff a leaf of the super-brick has a cell leaf.  Clear super-bricks' brick
+  // words are 0 only when bounded.
+  const EmaskGeom e = emask_geometry(g.ln);
+  if (!unbounded) {
+    HIP_TRY(c, hipMalloc(&c->d_emask, cvr::kEmaskWords * sizeof(uint32_t)));
+    HIP_TRY(c, hipMemsetAsync(c->d_emask, 0, cvr::kEmaskWords * sizeof(uint32_t), s));
+    m.eshift = e.es;
+    m.eshy = e.lx;
+    m.eshz = e.lx + e.ly;
+    m.emask = c->d_emask;
+  }
+  uint32_t *d_slot = nullptr, *d_coords = nullptr;
+  HIP_TRY(c, tmp.alloc((void**)&d_slot, g.nleaf * sizeof(uint32_t)));
+  HIP_TRY(c, tmp.alloc((void**)&d_coords, 3 * ncl * sizeof(uint32_t)));
+  tm.begin();
+  HIP_TRY(c, cvr::launch_scatter_cell_leaves(b.d_flags, g.nleaf, b.d_sums, g.ln, d_slot, d_coords, c->d_emask,
+                                             e.es - 3u, e.lx, e.lx + e.ly, s));
+  tm.end(3);
+  tm.begin();
+  HIP_TRY(c, cvr::launch_build_sparse(m, d_coords, c->use_cells ? ncl : 0, d_slot, g.bnz, b.max_density, unbounded,
+                                      c->d_cells, c->d_sbounds, s));
+  tm.end(5);
+  HIP_TRY(c, hipStreamSynchronize(s));
+  m.cells = c->d_cells;
+  m.sbounds = c->d_sbounds;
+  c->n_cell_leaves = ncl;
+  set_minfo(c, b.fmt, b.max_density, (np ? np : 1) * B.d, c->d_cells ? ncl * 512 * B.c : 0,
+            c->d_leaf_albedo ? np * B.a : 0,
+            (g.nb + 1 + g.nleaf + (c->d_emask ? cvr::kEmaskWords : 0)) * sizeof(uint32_t));
+  c->have_medium = true;
+  return CVR_OK;
+}
+
+// The scratch of finish_sparse's scan, but for the total's word
+int alloc_flag_scan(cvr_ctx* c, DevTemps& tmp, SparseBuild* b) {
+  HIP_TRY(c, tmp.alloc((void**)&b->d_flags, b->g.nleaf * sizeof(uint32_t)));
+  HIP_TRY(c, tmp.alloc((void**)&b->d_sums, cvr::flag_scan_tiles(b->g.nleaf) * sizeof(uint32_t)));
+  HIP_TRY(c, tmp.alloc((void**)&b->d_table, b->g.nleaf * sizeof(uint32_t)));
+  return CVR_OK;
+}
+
+// The sparse half of cvr_set_medium_device: the leaf rule on the device, then finish_sparse.
+// `bg`: voxel 0's albedo, or the constant.
+int devmed_sparse(cvr_ctx* c, const cvr_device_medium_desc* d, SparseBuild& b, const cvr::MedScan& scan,
+                  const float bg[4], cvr::MedScan* d_scan, DevTemps& tmp, DevmedTimer& tm) {
+  const uint32_t *res = d->res, *ln = b.g.ln;
+  const size_t nleaf = b.g.nleaf;
+  const uint32_t fmt = b.fmt;
+  // the leaf albedo pool is kept iff some voxel's 16 bytes differ from the background; if none
+  // does, no leaf exists through its albedo either and the albedo is not read again
+  b.albedo_pool = !(d->flags & CVR_DEVMED_CONST_ALBEDO) && (scan.albedo_flags & 2u);
+  const float* albedo = b.albedo_pool ? d->d_albedo : nullptr;
+  hipStream_t s = c->stream;
+  int r = alloc_flag_scan(c, tmp, &b);
+  if (r) return r;
+  b.d_total = &d_scan->total[1];
+  b.bg = bg;
+  // leaves: flags -> scan -> table and slots
+  tm.begin();
+  HIP_TRY(c, cvr::launch_leaf_flags(d->d_density, albedo, res, ln, b.d_flags, s));
+  tm.end(2);
+  tm.begin();
+  HIP_TRY(c, cvr::launch_flag_scan(b.d_flags, nleaf, b.d_sums, &d_scan->total[0], s));
+  tm.end(3);
+  HIP_TRY(c, hipStreamSynchronize(s));
+  HIP_TRY(c, hipMemcpy(&b.n_leaves, &d_scan->total[0], sizeof(uint32_t), hipMemcpyDeviceToHost));
+  const uint32_t n_leaves = b.n_leaves;
+  uint32_t* d_slot_leaf = nullptr;
+  HIP_TRY(c, tmp.alloc((void**)&d_slot_leaf, (size_t)n_leaves * sizeof(uint32_t)));
+  tm.begin();
+  HIP_TRY(c, cvr::launch_scatter_leaves(b.d_flags, nleaf, b.d_sums, b.d_table, d_slot_leaf, s));
+  tm.end(3);
+  auto refuse_overflow = [&]() -> int {
+    // the host call names the pools' first overflowing index: when the scans of the grid saw an
+    // overflow, the gather runs once without storing to find that index
+    size_t at = 0;
+    const char* what = nullptr;
+    float value = 0.0f;
+    if (scan.ovf_density != ~0ull || scan.ovf_albedo != ~0ull) {
+      cvr::MedScan chk = scan;
+      chk.ovf_density = chk.ovf_albedo = ~0ull;
+      HIP_TRY(c, hipMemcpy(d_scan, &chk, sizeof(chk), hipMemcpyHostToDevice));
+      HIP_TRY(c, cvr::launch_gather_leaves(d->d_density, albedo, res, ln, d_slot_leaf, n_leaves, bg, fmt, nullptr,
+                                           nullptr, d_scan, s));
+      HIP_TRY(c, hipStreamSynchronize(s));
+      HIP_TRY(c, hipMemcpy(&chk, d_scan, sizeof(chk), hipMemcpyDeviceToHost));
+      const bool in_density = chk.ovf_density != ~0ull;
+      if (in_density || chk.ovf_albedo != ~0ull) {
+        what = in_density ? "leaf density" : "leaf albedo";
+        at = (size_t)(in_density ? chk.ovf_density : chk.ovf_albedo);
+        // the value, for the message: the pool voxel's grid voxel, or the background's channel
+        const size_t p = in_density ? at : at / 4;
+        uint32_t leaf = 0;
+        HIP_TRY(c, hipMemcpy(&leaf, d_slot_leaf + (p >> 9), sizeof(leaf), hipMemcpyDeviceToHost));
+        const uint32_t local = (uint32_t)(p & 511u);
+        const uint32_t x = (leaf % ln[0]) * 8u + (local & 7u), y = ((leaf / ln[0]) % ln[1]) * 8u + ((local >> 3) & 7u),
+                       z = (leaf / (ln[0] * ln[1])) * 8u + (local >> 6);
+        const size_t i = ((size_t)z * res[1] + y) * res[0] + x;
+        if (x < res[0] && y < res[1] && z < res[2])
+          HIP_TRY(c, hipMemcpy(&value, in_density ? d->d_density + i : d->d_albedo + 4 * i + at % 4, sizeof(float),
+                               hipMemcpyDeviceToHost));
+        else
+          value = in_density ? 0.0f : bg[at % 4];
+      }
+    }
+    for (size_t k = 0; k < 3 && !what; ++k)
+      if (overflows_half(bg[k])) what = "albedo_background", at = k, value = bg[k];
+    if (!what) return CVR_OK;
+    return set_err(&c->err, CVR_ERR_INVALID, "medium format half: %s value %g at index %zu rounds to infinity", what,
+                   (double)value, at);
+  };
+  auto gather = [&]() -> int {
+    HIP_TRY(c, cvr::launch_gather_leaves(d->d_density, c->d_leaf_albedo ? albedo : nullptr, res, ln, d_slot_leaf,
+                                         n_leaves, bg, fmt, c->d_leaf_density, c->d_leaf_albedo, nullptr, s));
+    return CVR_OK;
+  };
+  return finish_sparse(c, b, tmp, tm, refuse_overflow, gather);
+}
+}  // namespace
+
+extern "C" {
+
+int cvr_set_medium(cvr_ctx* c, const cvr_medium_desc* md) {
+  if (!c || !md) return set_err(c ? &c->err : nullptr, CVR_ERR_INVALID, "NULL argument");
+  CVR_NOT_IN_SESSION(c, "cvr_set_medium");
+  // (the shape is judged first, from the numbers alone, then the arrays)
+  const uint32_t fmt = (uint32_t)c->medium_format;
+  int r = dense_shape_check(c, md->res, fmt);
+  if (r) return r;
+  const size_t n = (size_t)md->res[0] * md->res[1] * md->res[2];
+  if (!md->density || !md->albedo) return set_err(&c->err, CVR_ERR_INVALID, "density/albedo is NULL");
+  if (fmt) {
+    size_t at = 0;
+    const bool bad_d = half_overflows(md->density, n, 1, 1, &at);
+    const bool bad_a = !bad_d && half_overflows(md->albedo, n, 4, 3, &at);
+    if (bad_d || bad_a) {
+      c->have_medium = false;
+      return set_err(&c->err, CVR_ERR_INVALID, "medium format half: %s value %g at index %zu rounds to infinity",
+                     bad_d ? "density" : "albedo", (double)(bad_d ? md->density : md->albedo)[at], at);
+    }
+  }
+  const float max_density = fmt ? half_majorant(md->max_density) : md->max_density;
+  if ((r = ensure_device(c))) return r;
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  DevmedTimer tm(c);
+  if ((r = dense_grids(c, n, fmt))) return r;
+  if (fmt) {
+    // fp32 staging -> rounded half grids (converted on the device); the staging is freed before
+    // the cells and bounds are built, and in any case before this call returns
+    float* stage = nullptr;
+    HIP_TRY(c, hipMalloc(&stage, n * sizeof(float4)));
+    hipError_t e = hipMemcpy(stage, md->density, n * sizeof(float), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = cvr::launch_to_half(stage, c->d_density, n, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e == hipSuccess) e = hipMemcpy(stage, md->albedo, n * sizeof(float4), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = cvr::launch_to_half(stage, c->d_albedo, 4 * n, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    (void)hipFree(stage);
+    if (e != hipSuccess) return set_err(&c->err, CVR_ERR_HIP, "half medium upload: %s", hipGetErrorString(e));
+  } else {
+    HIP_TRY(c, hipMemcpy(c->d_density, md->density, n * sizeof(float), hipMemcpyHostToDevice));
+    HIP_TRY(c, hipMemcpy(c->d_albedo, md->albedo, n * sizeof(float4), hipMemcpyHostToDevice));
+  }
+  bool same = c->uniform_albedo;
+  if (same) {
+    // every voxel's rgb bit-identical to the first (the XML smoke scene's constant albedo);
+    // format 1: the rounded rgb (voxels that differ may round to the same halves)
+    float first[3] = {md->albedo[0], md->albedo[1], md->albedo[2]};
+    if (fmt)
+      for (float& v : first) v = half_round1(v);
+    for (size_t i = 1; i < n && same; ++i) {
+      same = memcmp(md->albedo + 4 * i, md->albedo, 3 * sizeof(float)) == 0;
+      if (!same && fmt) {
+        float v[3];
+        for (int k = 0; k < 3; ++k) v[k] = half_round1(md->albedo[4 * i + k]);
+        same = memcmp(v, first, sizeof(v)) == 0;
+      }
+    }
+  }
+  return finish_dense(c, view_of(*md), fmt, max_density, same ? md->albedo : nullptr, tm);
+}
+
+int cvr_set_medium_sparse(cvr_ctx* c, const cvr_sparse_medium_desc* sd) {
+  if (!c || !sd) return set_err(c ? &c->err : nullptr, CVR_ERR_INVALID, "NULL argument");
+  CVR_NOT_IN_SESSION(c, "cvr_set_medium_sparse");
+  // (as in cvr_set_medium, the shape is judged first, from the numbers alone, then the arrays;
+  // an empty grid is sparse_shape_check's to refuse, before leaf_dims)
+  const uint32_t* res = sd->res;
+  for (int k = 0; k < 3 && res[0] && res[1] && res[2]; ++k)
+    if (sd->leaf_dims[k] != (res[k] + 7u) / 8u)
+      return set_err(&c->err, CVR_ERR_INVALID, "leaf_dims[%d] = %u, expected ceil(res/8) = %u", k, sd->leaf_dims[k],
+                     (res[k] + 7u) / 8u);
+  SparseBuild b{};
+  int r = sparse_shape_check(c, res, &b.g);
+  if (r) return r;
+  const size_t nleaf = b.g.nleaf;
+  if (!sd->leaf_table || (sd->n_leaves && !sd->leaf_density))
+    return set_err(&c->err, CVR_ERR_INVALID, "leaf table / density pool is NULL");
+  for (size_t i = 0; i < nleaf; ++i) {
+    const uint32_t v = sd->leaf_table[i];
+    if (v != CVR_NO_LEAF && v >= sd->n_leaves)
+      return set_err(&c->err, CVR_ERR_INVALID, "leaf table entry %u >= n_leaves %u", v, sd->n_leaves);
+  }
+  const uint32_t fmt = (uint32_t)c->medium_format;
+  const size_t np = (size_t)sd->n_leaves * 512;
+  b.v = view_of(*sd);
+  b.fmt = fmt;
+  b.max_density = fmt ? half_majorant(sd->max_density) : sd->max_density;
+  b.bg = sd->albedo_background;
+  b.n_leaves = sd->n_leaves;
+  b.albedo_pool = sd->leaf_albedo != nullptr;
+  if ((r = ensure_device(c))) return r;
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  // the table goes to the device, where the cell leaves are counted, before the values are judged
+  DevTemps tmp;
+  DevmedTimer tm(c);
+  if ((r = alloc_flag_scan(c, tmp, &b))) return r;
+  HIP_TRY(c, tmp.alloc((void**)&b.d_total, sizeof(uint32_t)));
+  HIP_TRY(c, hipMemcpy(b.d_table, sd->leaf_table, nleaf * sizeof(uint32_t), hipMemcpyHostToDevice));
+  auto refuse_overflow = [&]() -> int {
+    size_t at = 0;
+    const char* what = nullptr;
+    const float* arr = nullptr;
+    if (half_overflows(sd->leaf_density, np, 1, 1, &at)) what = "leaf density", arr = sd->leaf_density;
+    else if (sd->leaf_albedo && half_overflows(sd->leaf_albedo, np, 4, 3, &at)) what = "leaf albedo", arr = sd->leaf_albedo;
+    else if (half_overflows(sd->albedo_background, 1, 4, 3, &at)) what = "albedo_background", arr = sd->albedo_background;
+    if (!what) return CVR_OK;
+    return set_err(&c->err, CVR_ERR_INVALID, "medium format half: %s value %g at index %zu rounds to infinity", what,
+                   (double)arr[at], at);
+  };
+  auto upload = [&]() -> int {
+    if (fmt && np) {
+      // fp32 staging -> rounded half pools (converted on the device), freed before the cells are built
+      float* stage = nullptr;
+      HIP_TRY(c, hipMalloc(&stage, np * (c->d_leaf_albedo ? sizeof(float4) : sizeof(float))));
+      hipError_t e = hipMemcpy(stage, sd->leaf_density, np * sizeof(float), hipMemcpyHostToDevice);
+      if (e == hipSuccess) e = cvr::launch_to_half(stage, c->d_leaf_density, np, c->stream);
+      if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+      if (e == hipSuccess && c->d_leaf_albedo) {
+        e = hipMemcpy(stage, sd->leaf_albedo, np * sizeof(float4), hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = cvr::launch_to_half(stage, c->d_leaf_albedo, 4 * np, c->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+      }
+      (void)hipFree(stage);
+      if (e != hipSuccess) return set_err(&c->err, CVR_ERR_HIP, "half medium upload: %s", hipGetErrorString(e));
+    } else if (np) {
+      HIP_TRY(c, hipMemcpy(c->d_leaf_density, sd->leaf_density, np * sizeof(float), hipMemcpyHostToDevice));
+      if (c->d_leaf_albedo)
+        HIP_TRY(c, hipMemcpy(c->d_leaf_albedo, sd->leaf_albedo, np * sizeof(float4), hipMemcpyHostToDevice));
+    }
+    return CVR_OK;
+  };
+  return finish_sparse(c, b, tmp, tm, refuse_overflow, upload);
+}
+
+int cvr_set_medium_device(cvr_ctx* c, const cvr_device_medium_desc* d) {
+  if (!c || !d) return set_err(c ? &c->err : nullptr, CVR_ERR_INVALID, "NULL argument");
+  CVR_NOT_IN_SESSION(c, "cvr_set_medium_device");
+  const uint32_t* res = d->res;
+  const bool sparse = (d->flags & CVR_DEVMED_SPARSE) != 0, konst = (d->flags & CVR_DEVMED_CONST_ALBEDO) != 0;
+  const uint32_t fmt = (uint32_t)c->medium_format;
+  // the host calls' shape guards, from res alone
+  SparseBuild b{};
+  int r = sparse ? sparse_shape_check(c, res, &b.g) : dense_shape_check(c, res, fmt);
+  if (r) return r;
+  const size_t n = (size_t)res[0] * res[1] * res[2];
+  // then the flags and the pointers
+  if (d->flags & ~(uint32_t)(CVR_DEVMED_SPARSE | CVR_DEVMED_CONST_ALBEDO | CVR_DEVMED_MAX_DENSITY))
+    return set_err(&c->err, CVR_ERR_INVALID, "unknown cvr_device_medium_desc flags 0x%x", d->flags);
+  if (!d->d_density || (!konst && !d->d_albedo)) return set_err(&c->err, CVR_ERR_INVALID, "d_density/d_albedo is NULL");
+  if (konst && d->d_albedo)
+    return set_err(&c->err, CVR_ERR_INVALID, "d_albedo must be NULL with CVR_DEVMED_CONST_ALBEDO");
+  if ((r = ensure_device(c))) return r;
+  if (!device_readable(c, d->d_density) || (!konst && !device_readable(c, d->d_albedo)))
+    return set_err(&c->err, CVR_ERR_INVALID, "d_density/d_albedo is not device-accessible memory of device %d",
+                   c->device);
+  if (((uintptr_t)d->d_density & 3u) || ((uintptr_t)d->d_albedo & 15u))
+    return set_err(&c->err, CVR_ERR_INVALID, "d_density must be 4-byte and d_albedo 16-byte aligned");
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  DevTemps tmp;
+  DevmedTimer tm(c);
+  // the value scans: majorant, binary16 overflow, albedo sameness
+  cvr::MedScan scan{~0ull, ~0ull, 0u, 0u, {0u, 0u}};
+  cvr::MedScan* d_scan = nullptr;
+  HIP_TRY(c, tmp.alloc((void**)&d_scan, sizeof(scan)));
+  HIP_TRY(c, hipMemcpy(d_scan, &scan, sizeof(scan), hipMemcpyHostToDevice));
+  float first[4] = {d->const_albedo[0], d->const_albedo[1], d->const_albedo[2], d->const_albedo[3]};
+  if (fmt || (d->flags & CVR_DEVMED_MAX_DENSITY)) {
+    tm.begin();
+    HIP_TRY(c, cvr::launch_scan_density(d->d_density, n, fmt, d_scan, c->stream));
+    tm.end(0);
+  }
+  if (!konst) {
+    if (fmt || sparse || c->uniform_albedo) {
+      tm.begin();
+      HIP_TRY(c, cvr::launch_scan_albedo(d->d_albedo, n, fmt, d_scan, c->stream));
+      tm.end(1);
+    }
+    HIP_TRY(c, hipMemcpyAsync(first, d->d_albedo, sizeof(first), hipMemcpyDeviceToHost, c->stream));
+  }
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  HIP_TRY(c, hipMemcpy(&scan, d_scan, sizeof(scan), hipMemcpyDeviceToHost));
+  float max_density = d->max_density;
+  if (d->flags & CVR_DEVMED_MAX_DENSITY) memcpy(&max_density, &scan.max_bits, sizeof(float));
+  if (fmt) max_density = half_majorant(max_density);
+  if (sparse) {
+    b.v = view_of(*d);
+    b.fmt = fmt;
+    b.max_density = max_density;
+    return devmed_sparse(c, d, b, scan, first, d_scan, tmp, tm);
+  }
+  if (fmt) {
+    // cvr_set_medium's refusal: density before albedo, the smallest index (a constant albedo's
+    // grid overflows first at voxel 0)
+    const bool bad_d = scan.ovf_density != ~0ull;
+    size_t at = (size_t)scan.ovf_density;
+    float value = 0.0f;
+    bool bad_a = false;
+    if (bad_d) {
+      HIP_TRY(c, hipMemcpy(&value, d->d_density + at, sizeof(float), hipMemcpyDeviceToHost));
+    } else if (konst) {
+      for (size_t k = 0; k < 3 && !bad_a; ++k)
+        if (overflows_half(first[k])) bad_a = true, at = k, value = first[k];
+    } else if (scan.ovf_albedo != ~0ull) {
+      bad_a = true;
+      at = (size_t)scan.ovf_albedo;
+      HIP_TRY(c, hipMemcpy(&value, d->d_albedo + at, sizeof(float), hipMemcpyDeviceToHost));
+    }
+    if (bad_d || bad_a) {
+      c->have_medium = false;
+      return set_err(&c->err, CVR_ERR_INVALID, "medium format half: %s value %g at index %zu rounds to infinity",
+                     bad_d ? "density" : "albedo", (double)value, at);
+    }
+  }
+  // the grids copied (format 1: converted, straight from the caller's fp32 arrays) or filled
+  if ((r = dense_grids(c, n, fmt))) return r;
+  tm.begin();
+  if (fmt) {
+    HIP_TRY(c, cvr::launch_to_half(d->d_density, c->d_density, n, c->stream));
+    if (!konst) HIP_TRY(c, cvr::launch_to_half(d->d_albedo, c->d_albedo, 4 * n, c->stream));
+  } else {
+    HIP_TRY(c, hipMemcpyAsync(c->d_density, d->d_density, n * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
+    if (!konst)
+      HIP_TRY(c, hipMemcpyAsync(c->d_albedo, d->d_albedo, n * sizeof(float4), hipMemcpyDeviceToDevice, c->stream));
+  }
+  if (konst) HIP_TRY(c, cvr::launch_fill_albedo(c->d_albedo, n, fmt, d->const_albedo, c->stream));
+  tm.end(4);
+  const bool same = c->uniform_albedo && (konst || !(scan.albedo_flags & 1u));
+  return finish_dense(c, view_of(*d), fmt, max_density, same ? first : nullptr, tm);
+}
+
+int cvr_debug_device_medium_ms(const cvr_ctx* c, double out[6]) {
+  if (!c || !out) return set_err(nullptr, CVR_ERR_INVALID, "NULL argument");
+  for (int i = 0; i < 6; ++i) out[i] = c->devmed_ms[i];
+  return CVR_OK;
+}
+
+int cvr_medium_layout(const cvr_ctx* c, struct cvr_medium_layout* out) {
+  if (!c || !out) return set_err(nullptr, CVR_ERR_INVALID, "NULL argument");
+  if (!c->have_medium) return set_err(nullptr, CVR_ERR_STATE, "no medium");
+  const cvr::MediumParams& m = c->m;
+  struct cvr_medium_layout l {};
+  l.sparse = m.leaves != nullptr;
+  l.albedo_uniform = m.albedo_uniform;
+  if (l.sparse) {
+    // (the leaf pool holds 512 voxels per leaf, one voxel when there is no leaf)
+    l.n_leaves = (uint32_t)(c->minfo.density_bytes / (512u * (m.format ? 2u : 4u)));
+    l.n_cell_leaves = (uint32_t)c->n_cell_leaves;
+  }
+  l.brick_shift = m.bshift;
+  l.mask_shift = m.eshift;
+  if (l.sparse || m.albedo_uniform) {
+    l.albedo_bg[0] = m.albedo_bg.x;
+    l.albedo_bg[1] = m.albedo_bg.y;
+    l.albedo_bg[2] = m.albedo_bg.z;
+  }
+  if (m.emask) {
+    // the medium's own mask (a shared medium: the source context's buffer)
+    if (hipSetDevice(c->device) != hipSuccess ||
+        hipMemcpy(l.mask, m.emask, sizeof(l.mask), hipMemcpyDeviceToHost) != hipSuccess)
+      return set_err(nullptr, CVR_ERR_HIP, "cvr_medium_layout: reading the mask failed");
+  }
+  *out = l;
+  return CVR_OK;
+}
+
+int cvr_share_medium(cvr_ctx* c, const cvr_ctx* src) {
+  if (!c || !src) return set_err(c ? &c->err : nullptr, CVR_ERR_INVALID, "NULL argument");
+  CVR_NOT_IN_SESSION(c, "cvr_share_medium");
+  if (c == src) return CVR_OK;
+  if (!src->have_medium) return set_err(&c->err, CVR_ERR_STATE, "source context has no medium");
+  if (src->device != c->device)
+    return set_err(&c->err, CVR_ERR_INVALID, "source context is on device %d, not %d", src->device, c->device);
+  int r = ensure_device(c);
+  if (r) return r;
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  // drop this context's own medium; the kernels read the source's buffers
+  drop_dense(c);
+  free_sparse(c);
+  c->m = src->m;
+  c->minfo = src->minfo;
+  c->n_cell_leaves = src->n_cell_leaves;
+  c->have_medium = true;
+  c->inited = false;
+  return CVR_OK;
+}
+
+int cvr_medium_info(const cvr_ctx* c, struct cvr_medium_info* out) {
+  if (!c || !out) return set_err(nullptr, CVR_ERR_INVALID, "NULL argument");
+  if (!c->have_medium) return set_err(nullptr, CVR_ERR_STATE, "no medium");
+  *out = c->minfo;
+  return CVR_OK;
+}
+
+int cvr_half_round(const float* in, float* out, size_t n) {
+  if (n && (!in || !out)) return set_err(nullptr, CVR_ERR_INVALID, "NULL argument");
+  for (size_t i = 0; i < n; ++i) out[i] = half_round1(in[i]);
+  return CVR_OK;
+}
+
+}  // extern "C"

@@ -101,6 +101,23 @@ def sparse_grid(name, with_albedo=True):
 
 
 @lru_cache(maxsize=None)
+def unusual_table(seed=31):
+    """A media.Sparse that cvr_set_medium_sparse allows and the leaf rule never makes: a ragged
+    20x12x10 grid (3x2x2 leaves, 7 stored), slots in reverse leaf order, the last two stored
+    entries both naming slot 0; the three leaves at the far (y, z) edge have no cell leaf."""
+    rng = np.random.default_rng(seed)
+    present = np.array([[[1, 0, 1], [0, 1, 1]], [[1, 1, 0], [1, 0, 0]]], bool)  # (z, y, x)
+    n = int(present.sum()) - 1
+    table = np.full(present.shape, NO_LEAF, np.uint32)
+    table[present] = np.maximum(n - 1 - np.arange(n + 1), 0).astype(np.uint32)
+    dens = np.float32(0.05) * rng.random((n, 512), dtype=np.float32)
+    dens[rng.random(dens.shape) < 0.4] = 0.0
+    alb = np.ones((n, 512, 4), np.float32)
+    alb[..., :3] = 0.2 + 0.8 * rng.random((n, 512, 3), dtype=np.float32)
+    return media.Sparse((20, 12, 10), table, dens, alb, (0.7, 0.55, 0.33, 1.0), float(dens.max()))
+
+
+@lru_cache(maxsize=None)
 def centre_voxel():
     """A 5^3 grid of density 1 at scale 4 (free paths of a quarter of the box) whose albedo is
     0.9 but for the centre voxel's 0.2: a medium that a wrongly "uniform" albedo renders otherwise."""

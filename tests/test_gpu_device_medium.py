@@ -1,11 +1,13 @@
 """Media built from device memory (cvr_set_medium_device) against the host uploads.
 
 Each case builds two contexts over the same numpy arrays, one through cvr_set_medium or
-cvr_set_medium_sparse (the unchanged host path) and one through cvr_set_medium_device from torch
+cvr_set_medium_sparse (the host upload) and one through cvr_set_medium_device from torch
 tensors, and asserts the same state: cvr_medium_info, cvr_medium_layout (leaves, cell leaves,
 mask words, uniform albedo), the records of 4096 paths of the production launch bit for bit,
 and the launch's counters with `fetches`.  The records are also compared with the oracle over
-the dense grid, so the pair cannot agree on a wrong medium.  With CVR_DEVMED_SPARSE the host
+the dense grid, so the pair cannot agree on a wrong medium.  The two sparse uploads share the
+cell-leaf and mask kernels, so each one's count, mask shift and mask words are also pinned to
+tests/bounds_model.py (assert_cell_leaves_and_mask).  With CVR_DEVMED_SPARSE the host
 side uploads the leaves that the numpy statement of the leaf rule (tests/devmed.py, checked on
 the CPU in tests/test_device_medium_cpu.py) makes of the grid."""
 import numpy as np
@@ -306,6 +308,29 @@ def test_half_overflow_names_what_the_host_names(cvr, kind):
 
 
 # ------------------------------------------------------------------ sparse --
+def assert_cell_leaves_and_mask(cvr, ctx, table, opts, what):
+    """The context's cell-leaf count, mask shift and 64 mask words against tests/bounds_model.py.
+    Both uploads count the cell leaves and set the mask's bits with the same kernels, so their
+    agreeing proves neither: the model is the independent statement of the rule.  The words are
+    packed as MediumParams says: super-brick (sx, sy, sz) = leaf coordinates >> (es - 3) is bit
+    sz << (lx + ly) | sy << lx | sx, in word bit >> 5, 2^lx and 2^ly the padded super-brick grid."""
+    import bounds_model as bm
+    lay = ctx.medium_layout().as_dict()
+    assert lay["n_cell_leaves"] == int(bm.cell_leaves(table).sum()) + 1, what
+    if dict(opts).get(cvr.OPT_BOUNDS) == 0:  # bounds off: no mask is built
+        assert lay["mask_shift"] == 0 and not any(lay["mask"]), what
+        return
+    # (CVR_OPT_EMPTY_MASK 0 keeps the launches from reading the mask; it is built and reported all the same)
+    es, mask = bm.sparse_mask(table)
+    assert lay["mask_shift"] == es == bm.mask_shift(table.shape), what
+    lx, ly = (max((int(n) - 1).bit_length() - (es - 3), 0) for n in (table.shape[2], table.shape[1]))
+    words = [0] * 64
+    for sz, sy, sx in zip(*np.nonzero(mask)):
+        b = int(sz) << (lx + ly) | int(sy) << lx | int(sx)
+        words[b >> 5] |= 1 << (b & 31)
+    assert lay["mask"] == words, what
+
+
 def sparse_case(cvr, name, with_albedo, fmt, opts, ref=True):
     D, A, md = devmed.sparse_grid(name, with_albedo)
     (host, sp), dev = host_sparse(cvr, D, A, md, fmt, opts), device_sparse(cvr, D, A, md, fmt, opts)
@@ -313,6 +338,8 @@ def sparse_case(cvr, name, with_albedo, fmt, opts, ref=True):
     lay = assert_same_state(host, dev, what, devmed.sparse_reference(name, with_albedo, fmt) if ref else None)
     assert lay["sparse"] == 1 and lay["n_leaves"] == sp.leaf_density.shape[0], what
     assert (dev.medium_info().albedo_bytes > 0) == with_albedo
+    assert_cell_leaves_and_mask(cvr, host, sp.table, opts, what + ": host upload")
+    assert_cell_leaves_and_mask(cvr, dev, sp.table, opts, what + ": device build")
     host.close()
     dev.close()
     return lay, sp
@@ -349,8 +376,59 @@ def test_sparse_const_albedo_and_unbounded(cvr, oracle_mod):
         lay = assert_same_state(host, dev, f"sparse const albedo {opts}", devmed.sparse_reference("sparse_small", False, 0))
         assert lay["albedo_bg"] == [float(np.float32(v)) for v in const[:3]]
         assert any(lay["mask"]) == (not opts)
+        for ctx in (host, dev):
+            assert_cell_leaves_and_mask(cvr, ctx, sp.table, opts, f"sparse const albedo {opts}")
         host.close()
         dev.close()
+
+
+def test_host_upload_of_a_table_the_leaf_rule_never_makes(cvr, oracle_mod):
+    """cvr_set_medium_sparse allows slots in any order and several entries naming one slot; the
+    cell leaves and the mask come from the existence of entries alone.  A ragged 20x12x10 grid
+    (3x2x2 leaves), slots in reverse leaf order, two entries sharing slot 0."""
+    import bounds_model as bm
+    sp = devmed.unusual_table()
+    stored = sp.table[sp.table != devmed.NO_LEAF]
+    assert sp.table.shape == (2, 2, 3) and (np.diff(stored.astype(np.int64)) <= 0).all()
+    assert len(stored) == len(np.unique(stored)) + 1 == sp.leaf_density.shape[0] + 1
+    D, A = devmed.densify(sp)
+    assert D.shape == (10, 12, 20)
+    ref = devmed.oracle_records(D, A, sp.max_density)
+    assert (ref["flags"] & 1).any() and (ref["n_albedo"] > 0).any()  # escapes and real collisions
+    ctx = new_ctx(cvr)
+    desc, keep = media.sparse_desc(cvr, sp.res, sp.table, sp.leaf_density, sp.leaf_albedo, sp.albedo_bg, sp.max_density)
+    ctx.set_medium_sparse(desc)
+    ready(cvr, ctx)
+    assert_records_equal(records(ctx), ref, "unusual table against the oracle")
+    assert ctx.medium_layout().n_leaves == sp.leaf_density.shape[0]
+    assert_cell_leaves_and_mask(cvr, ctx, sp.table, (), "unusual table")
+    assert 1 < ctx.medium_layout().n_cell_leaves - 1 < sp.table.size  # some leaf has no cell leaf
+    ctx.close()
+
+
+def test_host_sparse_refusals_keep_their_order(cvr):
+    """Table entry before half overflow, on a context that holds a format-1 medium: the first
+    keeps that medium, the second leaves the context without one."""
+    sp = media.sparse_small(True)
+    ctx = new_ctx(cvr, 1)
+    desc, keep = media.sparse_desc(cvr, sp.res, sp.table, sp.leaf_density, sp.leaf_albedo, sp.albedo_bg, sp.max_density)
+    ctx.set_medium_sparse(desc)
+    ready(cvr, ctx)
+    before = records(ctx)
+    hot = sp.leaf_density.copy()
+    hot[5, 7] = np.float32(1e6)    # pool index 2567: past the first blocks the overflow search tests whole
+    hot[7, 3] = np.float32(-7e4)   # a later one, not named
+    bad = sp.table.copy()
+    bad[sp.table != devmed.NO_LEAF] = hot.shape[0]  # every stored entry one past the pools
+    desc, keep = media.sparse_desc(cvr, sp.res, bad, hot, sp.leaf_albedo, sp.albedo_bg, sp.max_density)
+    code, text = refusal(cvr, lambda: ctx.set_medium_sparse(desc))
+    assert code == INVALID and f"leaf table entry {hot.shape[0]} >= n_leaves {hot.shape[0]}" in text, text
+    assert records(ctx).tobytes() == before.tobytes()  # the previous medium still renders
+    desc, keep = media.sparse_desc(cvr, sp.res, sp.table, hot, sp.leaf_albedo, sp.albedo_bg, sp.max_density)
+    code, text = refusal(cvr, lambda: ctx.set_medium_sparse(desc))
+    assert code == INVALID and f"leaf density value 1e+06 at index {5 * 512 + 7} rounds to infinity" in text, text
+    assert launch_code(cvr, ctx) == STATE
+    ctx.close()
 
 
 def test_sparse_half_overflow(cvr):
