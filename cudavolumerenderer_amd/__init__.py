@@ -12,6 +12,8 @@ from ._lib import (  # noqa: F401
     OPT_MOMENTS, AdaptiveDesc, AdaptiveResult, AdaptiveSession, block_error,
     DenoiseDesc, denoise_host,
     DeviceMediumDesc, MediumLayout, DEVMED_SPARSE, DEVMED_CONST_ALBEDO, DEVMED_MAX_DENSITY,
+    TransferDesc, ScalarMediumDesc, classify_host, raw_transfer_table,
+    SCALAR_F32, SCALAR_U8, SCALAR_U16, SCALAR_I16, TF_CEIL, TF_DENSITY_U,
     PATH_RECORD_DTYPE, CvrError, Context, MediumDesc, PinnedImage, Scene, Stats, default_camera, load,
     medium_from_arrays, tile_origin, tiling, write_hdr, LIB_PATH,
 )
@@ -23,4 +25,6 @@ __all__ = [
     "OPT_MOMENTS", "AdaptiveDesc", "AdaptiveResult", "AdaptiveSession", "block_error",
     "DenoiseDesc", "denoise_host",
     "DeviceMediumDesc", "MediumLayout", "DEVMED_SPARSE", "DEVMED_CONST_ALBEDO", "DEVMED_MAX_DENSITY",
+    "TransferDesc", "ScalarMediumDesc", "classify_host", "raw_transfer_table",
+    "SCALAR_F32", "SCALAR_U8", "SCALAR_U16", "SCALAR_I16", "TF_CEIL", "TF_DENSITY_U",
 ]

@@ -146,6 +146,27 @@ class DeviceMediumDesc(C.Structure):
                 ("g", C.c_float), ("roughness", C.c_float * 2), ("eta", C.c_float)]
 
 
+SCALAR_F32, SCALAR_U8, SCALAR_U16, SCALAR_I16 = 0, 1, 2, 3
+TF_CEIL, TF_DENSITY_U = 1, 2
+_SCALAR_TYPES = {"float32": SCALAR_F32, "uint8": SCALAR_U8, "uint16": SCALAR_U16, "int16": SCALAR_I16}
+
+
+class TransferDesc(C.Structure):
+    """cvr_transfer_desc: a table of n (r, g, b, density) entries in host memory and the scalar
+    range [lo, hi] it spans."""
+    _fields_ = [("n", C.c_uint32), ("flags", C.c_uint32), ("table", C.c_void_p), ("lo", C.c_float),
+                ("hi", C.c_float)]
+
+
+class ScalarMediumDesc(C.Structure):
+    """cvr_scalar_medium_desc: a scalar field in device memory and its transfer function
+    (cvr_set_medium_scalar)."""
+    _fields_ = [("res", C.c_uint32 * 3), ("flags", C.c_uint32), ("d_scalar", C.c_void_p),
+                ("scalar_type", C.c_uint32), ("reserved", C.c_uint32), ("transfer", TransferDesc),
+                ("box_min", C.c_float * 3), ("box_max", C.c_float * 3), ("scale", C.c_float),
+                ("max_density", C.c_float), ("g", C.c_float), ("roughness", C.c_float * 2), ("eta", C.c_float)]
+
+
 class MediumLayout(C.Structure):
     """cvr_medium_layout: what an upload built (either path)."""
     _fields_ = [("sparse", C.c_uint32), ("albedo_uniform", C.c_uint32), ("n_leaves", C.c_uint32),
@@ -245,6 +266,10 @@ def load() -> C.CDLL:
         "cvr_set_medium_device": (I32, [P, C.POINTER(DeviceMediumDesc)]),
         "cvr_medium_layout": (I32, [P, C.POINTER(MediumLayout)]),
         "cvr_debug_device_medium_ms": (I32, [P, C.POINTER(C.c_double)]),
+        "cvr_classify_host": (I32, [P, U32, C.c_size_t, C.POINTER(TransferDesc), P, P]),
+        "cvr_raw_transfer_table": (I32, [FP]),
+        "cvr_set_medium_scalar": (I32, [P, C.POINTER(ScalarMediumDesc)]),
+        "cvr_set_medium_scene_transfer": (I32, [P, P, C.POINTER(TransferDesc), U32]),
     }
     # an older experiment build (tools' --lib, A/B against a previous commit) may lack newer entry
     # points; the in-tree library must export every one (tests/test_host_abi.py)
@@ -319,6 +344,42 @@ def denoise_host(sum_rgba, m2_rgba, n_samples: Optional[int] = None, block_sampl
     return rgba, var
 
 
+def _transfer_desc(table, lo, hi, ceil, density_u):
+    """(TransferDesc, the array it points into): table is (n, 4) floats (r, g, b, density)."""
+    tab = np.ascontiguousarray(table, dtype=np.float32)
+    if tab.ndim != 2 or tab.shape[1] != 4:
+        raise ValueError(f"table: shape {tab.shape}, expected (n, 4)")
+    t = TransferDesc(tab.shape[0], (TF_CEIL if ceil else 0) | (TF_DENSITY_U if density_u else 0), tab.ctypes.data,
+                     lo, hi)
+    return t, tab
+
+
+def classify_host(scalar, table, lo, hi, ceil=False, density_u=False):
+    """The transfer function's written statement on the CPU (cvr_classify_host; no GPU): a numpy
+    array `scalar` of dtype uint8, uint16, int16 or float32 and a table of (n, 4) floats
+    (r, g, b, density) over the scalar range [lo, hi] -> (density scalar.shape, albedo
+    scalar.shape + (4,)).  ceil: entry ceil(x) instead of linear interpolation; density_u: the
+    density is the normalised scalar, not the table's.  Context.set_medium_scalar computes the same
+    bits on the device."""
+    src = np.ascontiguousarray(scalar)
+    if src.dtype.name not in _SCALAR_TYPES:
+        raise ValueError(f"scalar: dtype {src.dtype}, expected uint8, uint16, int16 or float32")
+    t, _tab = _transfer_desc(table, lo, hi, ceil, density_u)
+    density = np.empty(src.shape, np.float32)
+    albedo = np.empty(src.shape + (4,), np.float32)
+    _check(load().cvr_classify_host(src.ctypes.data, _SCALAR_TYPES[src.dtype.name], src.size, C.byref(t),
+                                    density.ctypes.data, albedo.ctypes.data))
+    return density, albedo
+
+
+def raw_transfer_table() -> np.ndarray:
+    """The reference's Raw transfer table, (100, 4) floats (cvr_raw_transfer_table): the Raw scenes'
+    albedo is classify_host(bytes, table, 0, max byte, ceil=True, density_u=True)."""
+    out = np.empty((100, 4), np.float32)
+    _check(load().cvr_raw_transfer_table(_fp(out)))
+    return out
+
+
 def _device_ptr(a):
     """An int address, or an object with data_ptr() (a torch tensor); None stays None."""
     if a is None:
@@ -326,12 +387,12 @@ def _device_ptr(a):
     return int(a.data_ptr()) if hasattr(a, "data_ptr") else int(a)
 
 
-def _check_device_grid(name, t, shape, device):
-    """ValueError unless the tensor-like `t` (an object with data_ptr()) is a contiguous float32
-    array of `shape` on cuda device `device`; attributes it does not have are not judged."""
+def _check_device_grid(name, t, shape, device, dtypes=("float32",)):
+    """ValueError unless the tensor-like `t` (an object with data_ptr()) is a contiguous array of
+    `shape` and one of `dtypes` on cuda device `device`; attributes it does not have are not judged."""
     dtype = getattr(t, "dtype", None)
-    if dtype is not None and str(dtype).split(".")[-1] != "float32":
-        raise ValueError(f"{name}: dtype {dtype}, expected float32")
+    if dtype is not None and str(dtype).split(".")[-1] not in dtypes:
+        raise ValueError(f"{name}: dtype {dtype}, expected {' or '.join(dtypes)}")
     contiguous = getattr(t, "is_contiguous", None)
     if contiguous is not None and not contiguous():
         raise ValueError(f"{name}: not contiguous")
@@ -594,6 +655,53 @@ class Context:
             torch.cuda.current_stream(self.device).synchronize()
         self._c(load().cvr_set_medium_device(self._h, C.byref(d)))
 
+    def set_medium_scalar(self, scalar, table, *, lo, hi, ceil=False, density_u=False, sparse=False,
+                          max_density=None, scalar_type=None, res=None, box_min=(-0.5,) * 3, box_max=(0.5,) * 3,
+                          scale=100.0, g=0.0, roughness=(0.1, 0.1), eta=None):
+        """The medium from a scalar field in device memory and a transfer table, classified inside
+        the build kernels (cvr_set_medium_scalar): the state set_medium_device leaves on device
+        copies of classify_host(scalar, table, lo, hi, ceil, density_u).  scalar: (z, y, x) uint8,
+        int16, uint16 or float32, an object with data_ptr() (a torch tensor on the context's device,
+        contiguous: checked here, ValueError) or an int device address (then scalar_type, a
+        SCALAR_* value, and res = (x, y, z) are required and nothing is checked here).  table:
+        (n, 4) floats (r, g, b, density) in host memory, n 2..4096.  The other arguments are
+        set_medium_device's.  Synchronous; torch's current stream is synchronised first, the tensor
+        is only read and may be freed afterwards; a new table means a new call."""
+        is_tensor = hasattr(scalar, "data_ptr")
+        if res is None:
+            if not is_tensor:
+                raise ValueError("set_medium_scalar: res is required with an int address")
+            if len(scalar.shape) != 3:
+                raise ValueError(f"scalar: shape {tuple(scalar.shape)}, expected (z, y, x)")
+            nz, ny, nx = (int(v) for v in scalar.shape)
+        else:
+            nx, ny, nz = (int(v) for v in res)
+        if is_tensor:
+            _check_device_grid("scalar", scalar, (nz, ny, nx), self.device, tuple(_SCALAR_TYPES))
+        if scalar_type is None:
+            name = str(getattr(scalar, "dtype", "")).split(".")[-1]
+            if name not in _SCALAR_TYPES:
+                raise ValueError("set_medium_scalar: scalar_type is required with an int address")
+            scalar_type = _SCALAR_TYPES[name]
+        t, _tab = _transfer_desc(table, lo, hi, ceil, density_u)
+        d = ScalarMediumDesc()
+        d.res[:] = (nx, ny, nz)
+        d.flags = (DEVMED_SPARSE if sparse else 0) | (DEVMED_MAX_DENSITY if max_density is None else 0)
+        d.d_scalar = _device_ptr(scalar)
+        d.scalar_type = scalar_type
+        d.transfer = t
+        d.box_min[:] = box_min
+        d.box_max[:] = box_max
+        d.scale = scale
+        d.max_density = 0.0 if max_density is None else max_density
+        d.g = g
+        d.roughness[:] = roughness
+        d.eta = np.float32(np.float32(1.05) / np.float32(1.01)) if eta is None else eta
+        if is_tensor and type(scalar).__module__.split(".")[0] == "torch":
+            import torch
+            torch.cuda.current_stream(self.device).synchronize()
+        self._c(load().cvr_set_medium_scalar(self._h, C.byref(d)))
+
     def medium_layout(self) -> MediumLayout:
         """What the upload built (cvr_medium_layout): sparse or dense, uniform albedo and its value,
         leaves, cell leaves, brick and mask shifts and the empty-region mask's 64 words."""
@@ -602,7 +710,7 @@ class Context:
         return ml
 
     def device_medium_ms(self):
-        """Device ms of the last set_medium_device by group, with OPT_TIMING 1
+        """Device ms of the last set_medium_device or set_medium_scalar by group, with OPT_TIMING 1
         (cvr_debug_device_medium_ms): density scan, albedo scan, leaf flags, scans and scatters,
         copy / gather, cells + bounds + brick words."""
         out = (C.c_double * 6)()

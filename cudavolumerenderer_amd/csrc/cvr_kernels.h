@@ -118,6 +118,7 @@ hipError_t launch_to_half(const float* src, void* dst, size_t n, hipStream_t s);
 // Media built from device memory (cvr_set_medium_device; cvr_medium_build.hip).  Every array below
 // is device memory; the launches are asynchronous on s and none waits on another workgroup.
 // What the value scans find, in device memory; the host sets ovf_* to ~0 and the rest to 0 first.
+struct VoxelSource;  // below: the caller's arrays, or a scalar field and a transfer table
 struct MedScan {
   unsigned long long ovf_density;  // smallest index whose finite value rounds to +-inf in binary16 (format 1)
   unsigned long long ovf_albedo;   // the same over the albedo's r, g, b (index 4 voxel + channel)
@@ -131,8 +132,10 @@ hipError_t launch_scan_albedo(const float* albedo, size_t n, uint32_t format, Me
 // n albedo voxels of the context's grid (float4, format 1: 4 halves) set to `value`
 hipError_t launch_fill_albedo(void* albedo, size_t n, uint32_t format, const float value[4], hipStream_t s);
 // The leaf rule of cvr.h: flags[leaf] = the leaf exists (albedo null: by density alone); ln = ceil(res / 8).
-hipError_t launch_leaf_flags(const float* density, const float* albedo, const uint32_t res[3], const uint32_t ln[3],
-                             uint32_t* flags, hipStream_t s);
+// A classified source is launched with_albedo and also finds, of the classified values, what the
+// two scans above find (scan; format as theirs); the arrays' source ignores both.
+hipError_t launch_leaf_flags(const VoxelSource& src, bool with_albedo, const uint32_t res[3], const uint32_t ln[3],
+                             uint32_t* flags, uint32_t format, MedScan* scan, hipStream_t s);
 // flags[leaf] = the leaf or one of its 7 forward neighbours is in `table`
 hipError_t launch_cell_leaf_flags(const uint32_t* table, const uint32_t ln[3], uint32_t* flags, hipStream_t s);
 // Exclusive scan of n 0/1 flags, first two launches: sums (flag_scan_tiles(n) words) receives the
@@ -147,12 +150,68 @@ hipError_t launch_scatter_leaves(const uint32_t* flags, size_t n, const uint32_t
 hipError_t launch_scatter_cell_leaves(const uint32_t* flags, size_t n, const uint32_t* sums, const uint32_t ln[3],
                                       uint32_t* cell_slot, uint32_t* coords, uint32_t* emask, uint32_t k_shift,
                                       uint32_t shy, uint32_t shz, hipStream_t s);
-// The stored leaves' pools from the grid (albedo null: none), out-of-grid voxels (0, bg), format 1
+// The stored leaves' pools from the grid (with_albedo false: no albedo), out-of-grid voxels (0, bg), format 1
 // converted to binary16.  check non-null: nothing is stored; check->ovf_* receive the smallest pool
 // index that overflows binary16.
-hipError_t launch_gather_leaves(const float* density, const float* albedo, const uint32_t res[3], const uint32_t ln[3],
+hipError_t launch_gather_leaves(const VoxelSource& src, bool with_albedo, const uint32_t res[3], const uint32_t ln[3],
                                 const uint32_t* slot_leaf, size_t n_leaves, const float bg[4], uint32_t format,
                                 void* leaf_density, void* leaf_albedo, MedScan* check, hipStream_t s);
+// Transfer functions (cvr_set_medium_scalar, cvr_classify_host).  The per-voxel classification
+// cvr.h states: the one definition, compiled for the host and for the build kernels.  fp32 only,
+// every operation in the written order (-ffp-contract=off, correctly rounded /), so both sides
+// return the same bits.  table: n entries (r, g, b, density).  Returns (r, g, b, density): the
+// voxel's albedo is (r, g, b, 1).
+struct TransferParams {
+  uint32_t n, flags;  // cvr_transfer_desc's: flags bit 0 CVR_TF_CEIL, bit 1 CVR_TF_DENSITY_U
+  float lo, hi;
+};
+__host__ __device__ inline float4 transfer_classify(float s, const float4* table, const TransferParams& p) {
+  const float t = (s - p.lo) / (p.hi - p.lo);
+  float u = t > 0.0f ? t : 0.0f;  // a NaN compares false: 0
+  u = u < 1.0f ? u : 1.0f;
+  const float x = u * (float)(p.n - 1u);
+  float4 e;
+  if (p.flags & 1u) {
+    const uint32_t c = (uint32_t)__builtin_ceilf(x), i = c < p.n - 1u ? c : p.n - 1u;
+    e = table[i];
+  } else {
+    const uint32_t c = (uint32_t)__builtin_floorf(x), i = c < p.n - 2u ? c : p.n - 2u;
+    const float f = x - (float)i;
+    const float4 a = table[i], b = table[i + 1u];
+    e.x = a.x + f * (b.x - a.x);
+    e.y = a.y + f * (b.y - a.y);
+    e.z = a.z + f * (b.z - a.z);
+    e.w = a.w + f * (b.w - a.w);
+  }
+  if (p.flags & 2u) e.w = u;
+  return e;
+}
+// One scalar voxel as the float the classification starts from (exact for the integer types)
+__host__ __device__ inline float scalar_voxel(const void* scalar, uint32_t type, size_t i) {
+  switch (type) {
+    case 1: return (float)static_cast<const uint8_t*>(scalar)[i];
+    case 2: return (float)static_cast<const uint16_t*>(scalar)[i];
+    case 3: return (float)static_cast<const int16_t*>(scalar)[i];
+    default: return static_cast<const float*>(scalar)[i];
+  }
+}
+// Where the build stages take a voxel's values from: the caller's two arrays (scalar null;
+// albedo null: none), or a scalar field of type scalar_type (cvr.h: CVR_SCALAR_*) classified
+// through a table in device memory.
+struct VoxelSource {
+  const float* density = nullptr;
+  const float* albedo = nullptr;
+  const void* scalar = nullptr;
+  uint32_t scalar_type = 0;
+  const float4* table = nullptr;
+  TransferParams tf{};
+};
+// Classified source, dense: one pass over the scalar field that finds what launch_scan_density and
+// launch_scan_albedo find together, and one that stores every voxel's density and albedo
+// (format 1: binary16) into the context's grids.
+hipError_t launch_scan_classified(const VoxelSource& src, size_t n, uint32_t format, MedScan* out, hipStream_t s);
+hipError_t launch_store_classified(const VoxelSource& src, size_t n, uint32_t format, void* density, void* albedo,
+                                   hipStream_t s);
 // cvr_debug_fastdiv (tests): q[i] = fastdiv(u[i], f) on the device, u and q device arrays.
 hipError_t launch_debug_fastdiv(FastDiv f, const uint32_t* u, uint32_t* q, size_t n, hipStream_t s);
 hipError_t launch_tile_to_image(const float4* tile, uint32_t tw, uint32_t th, float4* image, uint32_t iw,

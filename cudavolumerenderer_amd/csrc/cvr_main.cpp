@@ -41,6 +41,7 @@ struct Options {
   std::string output, synthetic, rng_binding = "path", world_to_aabb = "reference", mk_compaction = "fixed";
   std::string devices;  // --devices: a count or a comma list of device ids
   std::string medium_format = "float";  // --medium-format
+  std::string transfer_file, transfer_mode = "linear";  // --transfer, --transfer-mode
   bool pfm = false;
   bool adaptive = false;  // --noise-target given
   float noise_target = 0.0f;
@@ -82,6 +83,11 @@ void usage() {
       "  --medium-format float|half (=float)  storage precision of density, density cells and albedo on\n"
       "                                     the device: half rounds every voxel to IEEE binary16 and halves\n"
       "                                     their bytes (wave-pool scheduler; see CVR_OPT_MEDIUM_FORMAT)\n"
+      "  --transfer FILE                    Raw scenes (and --synthetic bucky): classify the scene's bytes on\n"
+      "                                     the device through the transfer function in FILE, 2..4096 lines\n"
+      "                                     of 'r g b density' spanning byte 0 .. the largest byte, in place of\n"
+      "                                     the reference's built-in table (cvr_set_medium_scalar)\n"
+      "  --transfer-mode linear|ceil (=linear)  interpolate between table entries, or take entry ceil(x)\n"
       "  --pfm                              also write the float image as <output>.pfm\n"
       "  --noise-target F                   adaptive render: sample every 8x8-pixel block until its relative\n"
       "                                     standard error (cvr_block_error, floor 0.01) is at most F, with\n"
@@ -144,6 +150,8 @@ int parse(int argc, char** argv, Options& o) {
     else if (a == "--device") o.device = (unsigned)strtoul(need("device").c_str(), nullptr, 10);
     else if (a == "--devices") o.devices = need("devices");
     else if (a == "--medium-format") o.medium_format = need("medium-format");
+    else if (a == "--transfer") o.transfer_file = need("transfer");
+    else if (a == "--transfer-mode") o.transfer_mode = need("transfer-mode");
     else if (a == "--pfm") o.pfm = true;
     else if (a == "--noise-target") {
       o.noise_target = strtof(need("noise-target").c_str(), nullptr);
@@ -234,6 +242,40 @@ int scene_type_id(const std::string& t) {
   return -1;
 }
 
+// --transfer FILE: lines of 'r g b density' (blank lines and lines starting with # are skipped)
+// into table; false with a message when the file cannot be read, a line does not hold four
+// numbers, or there are not 2..4096 entries.
+bool read_transfer(const std::string& path, std::vector<float>& table) {
+  FILE* fp = fopen(path.c_str(), "r");
+  if (!fp) {
+    fprintf(stderr, "[ConfigParser] Error: --transfer: cannot read '%s'\n", path.c_str());
+    return false;
+  }
+  char line[512];
+  unsigned lineno = 0;
+  bool ok = true;
+  while (ok && fgets(line, sizeof(line), fp)) {
+    ++lineno;
+    const char* p = line;
+    while (*p == ' ' || *p == '\t') ++p;
+    if (*p == '#' || *p == '\n' || *p == '\r' || *p == 0) continue;
+    float v[4];
+    char extra;
+    if (sscanf(p, "%f %f %f %f %c", &v[0], &v[1], &v[2], &v[3], &extra) != 4) {
+      fprintf(stderr, "[ConfigParser] Error: --transfer: line %u of '%s' is not 'r g b density'\n", lineno, path.c_str());
+      ok = false;
+    }
+    table.insert(table.end(), v, v + 4);
+  }
+  fclose(fp);
+  if (ok && (table.size() < 8 || table.size() > 4 * 4096)) {
+    fprintf(stderr, "[ConfigParser] Error: --transfer: '%s' holds %zu entries, a table has 2..4096\n", path.c_str(),
+            table.size() / 4);
+    ok = false;
+  }
+  return ok;
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
@@ -277,6 +319,26 @@ int main(int argc, char** argv) {
   if (r != CVR_OK) {
     fprintf(stderr, "Error: could not load scene (%d): %s\n", r, cvr_last_error(nullptr));
     return 1;
+  }
+  // --transfer: the table, and a scene that has one byte per voxel to classify
+  std::vector<float> transfer_table;
+  cvr_transfer_desc transfer{};
+  if (o.transfer_mode != "linear" && o.transfer_mode != "ceil") {
+    fprintf(stderr, "[ConfigParser] Error: --transfer-mode must be linear or ceil\n");
+    return 2;
+  }
+  if (!o.transfer_file.empty()) {
+    const uint8_t* raw = nullptr;
+    size_t n_raw = 0;
+    if (cvr_scene_raw_bytes(scene, &raw, &n_raw) != CVR_OK || !n_raw) {
+      fprintf(stderr, "[ConfigParser] Error: --transfer applies to Raw scenes only (and --synthetic bucky): this "
+                      "scene has no scalar bytes to classify\n");
+      return 2;
+    }
+    if (!read_transfer(o.transfer_file, transfer_table)) return 2;
+    transfer.n = (uint32_t)(transfer_table.size() / 4);
+    transfer.flags = o.transfer_mode == "ceil" ? CVR_TF_CEIL : 0;
+    transfer.table = transfer_table.data();
   }
   printf("[ConfigParser] kernel set to %s.\n[ConfigParser] iterations set to %u.\n", o.kernel.c_str(), o.iterations);
   if (o.interactive) printf("[ConfigParser] interactive viewer not available in this build; rendering headless.\n");
@@ -333,6 +395,8 @@ int main(int argc, char** argv) {
     if (!rc && o.medium_format == "half") rc = cvr_set_option(ctx, CVR_OPT_MEDIUM_FORMAT, CVR_FORMAT_F16);
     if (!rc && share) {
       rc = cvr_share_medium(ctx, share);
+    } else if (!rc && transfer.n) {
+      rc = cvr_set_medium_scene_transfer(ctx, scene, &transfer, sparse ? CVR_DEVMED_SPARSE : 0);
     } else if (!rc) {
       if (!sparse && (rc = cvr_set_medium(ctx, &md)) == CVR_ERR_UNSUPPORTED) {
         printf("[Scene] dense grid rejected (%s); using the sparse leaf upload\n", cvr_last_error(ctx));

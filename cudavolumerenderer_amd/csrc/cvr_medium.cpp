@@ -1,5 +1,7 @@
 // cvr_medium.cpp - the medium of a context: the host uploads (dense, sparse) and the build from
-// device memory through one set of stages, and what the context tells of the result.
+// device memory (two arrays, or a scalar field and a transfer function: build_from_device)
+// through one set of stages, the transfer function's host statement, and what the context tells
+// of the result.
 //
 // Each rule is stated once: the shape guards (dense_shape_check, sparse_shape_check), the dense
 // build from the grids on (finish_dense), the sparse build from a leaf table in device memory on
@@ -475,17 +477,51 @@ int alloc_flag_scan(cvr_ctx* c, DevTemps& tmp, SparseBuild* b) {
   return CVR_OK;
 }
 
-// The sparse half of cvr_set_medium_device: the leaf rule on the device, then finish_sparse.
-// `bg`: voxel 0's albedo, or the constant.
-int devmed_sparse(cvr_ctx* c, const cvr_device_medium_desc* d, SparseBuild& b, const cvr::MedScan& scan,
+// One voxel's values as a source gives them, for the refusals' messages and the background:
+// out = (albedo r, g, b, w, density).  The arrays' source reads them; a classified source reads
+// the scalar and classifies it here, which gives the bits the kernels compute.
+int source_voxel(cvr_ctx* c, const cvr::VoxelSource& src, const float* host_table, size_t i, bool with_albedo,
+                 float out[5]) {
+  if (!src.scalar) {
+    HIP_TRY(c, hipMemcpy(&out[4], src.density + i, sizeof(float), hipMemcpyDeviceToHost));
+    if (with_albedo) HIP_TRY(c, hipMemcpy(out, src.albedo + 4 * i, 4 * sizeof(float), hipMemcpyDeviceToHost));
+    return CVR_OK;
+  }
+  const size_t size = src.scalar_type == CVR_SCALAR_U8 ? 1 : src.scalar_type == CVR_SCALAR_F32 ? 4 : 2;
+  alignas(4) unsigned char raw[4];
+  HIP_TRY(c, hipMemcpy(raw, static_cast<const unsigned char*>(src.scalar) + i * size, size, hipMemcpyDeviceToHost));
+  const float4 e = cvr::transfer_classify(cvr::scalar_voxel(raw, src.scalar_type, 0),
+                                          reinterpret_cast<const float4*>(host_table), src.tf);
+  out[0] = e.x, out[1] = e.y, out[2] = e.z, out[3] = 1.0f, out[4] = e.w;
+  return CVR_OK;
+}
+
+// What the descriptors of the two device calls say besides the source
+struct DeviceBuild {
+  MediumView v;
+  uint32_t flags;            // CVR_DEVMED_*
+  const float* const_albedo;  // with CVR_DEVMED_CONST_ALBEDO
+  float max_density;          // without CVR_DEVMED_MAX_DENSITY
+  const float* host_table;    // a classified source's table, in host memory
+};
+float majorant_of(const DeviceBuild& d, const cvr::MedScan& scan, uint32_t fmt) {
+  float max_density = d.max_density;
+  if (d.flags & CVR_DEVMED_MAX_DENSITY) memcpy(&max_density, &scan.max_bits, sizeof(float));
+  return fmt ? half_majorant(max_density) : max_density;
+}
+
+// The sparse half of the device calls: the leaf rule on the device, then finish_sparse.
+// `bg`: voxel 0's albedo, or the constant.  scan: the value scans' results (a classified source:
+// not yet run; the leaf flags' pass finds them).
+int devmed_sparse(cvr_ctx* c, const DeviceBuild& d, const cvr::VoxelSource& src, SparseBuild& b, cvr::MedScan scan,
                   const float bg[4], cvr::MedScan* d_scan, DevTemps& tmp, DevmedTimer& tm) {
-  const uint32_t *res = d->res, *ln = b.g.ln;
+  const uint32_t *res = d.v.res, *ln = b.g.ln;
   const size_t nleaf = b.g.nleaf;
   const uint32_t fmt = b.fmt;
+  const bool classified = src.scalar != nullptr, konst = (d.flags & CVR_DEVMED_CONST_ALBEDO) != 0;
   // the leaf albedo pool is kept iff some voxel's 16 bytes differ from the background; if none
   // does, no leaf exists through its albedo either and the albedo is not read again
-  b.albedo_pool = !(d->flags & CVR_DEVMED_CONST_ALBEDO) && (scan.albedo_flags & 2u);
-  const float* albedo = b.albedo_pool ? d->d_albedo : nullptr;
+  b.albedo_pool = !konst && (scan.albedo_flags & 2u);
   hipStream_t s = c->stream;
   int r = alloc_flag_scan(c, tmp, &b);
   if (r) return r;
@@ -493,13 +529,21 @@ int devmed_sparse(cvr_ctx* c, const cvr_device_medium_desc* d, SparseBuild& b, c
   b.bg = bg;
   // leaves: flags -> scan -> table and slots
   tm.begin();
-  HIP_TRY(c, cvr::launch_leaf_flags(d->d_density, albedo, res, ln, b.d_flags, s));
+  HIP_TRY(c, cvr::launch_leaf_flags(src, classified || b.albedo_pool, res, ln, b.d_flags, fmt, d_scan, s));
   tm.end(2);
   tm.begin();
   HIP_TRY(c, cvr::launch_flag_scan(b.d_flags, nleaf, b.d_sums, &d_scan->total[0], s));
   tm.end(3);
   HIP_TRY(c, hipStreamSynchronize(s));
-  HIP_TRY(c, hipMemcpy(&b.n_leaves, &d_scan->total[0], sizeof(uint32_t), hipMemcpyDeviceToHost));
+  if (classified) {
+    HIP_TRY(c, hipMemcpy(&scan, d_scan, sizeof(scan), hipMemcpyDeviceToHost));
+    b.albedo_pool = (scan.albedo_flags & 2u) != 0;
+    b.max_density = majorant_of(d, scan, fmt);
+    b.n_leaves = scan.total[0];
+  } else {
+    HIP_TRY(c, hipMemcpy(&b.n_leaves, &d_scan->total[0], sizeof(uint32_t), hipMemcpyDeviceToHost));
+  }
+  const bool with_albedo = b.albedo_pool;
   const uint32_t n_leaves = b.n_leaves;
   uint32_t* d_slot_leaf = nullptr;
   HIP_TRY(c, tmp.alloc((void**)&d_slot_leaf, (size_t)n_leaves * sizeof(uint32_t)));
@@ -516,8 +560,8 @@ int devmed_sparse(cvr_ctx* c, const cvr_device_medium_desc* d, SparseBuild& b, c
       cvr::MedScan chk = scan;
       chk.ovf_density = chk.ovf_albedo = ~0ull;
       HIP_TRY(c, hipMemcpy(d_scan, &chk, sizeof(chk), hipMemcpyHostToDevice));
-      HIP_TRY(c, cvr::launch_gather_leaves(d->d_density, albedo, res, ln, d_slot_leaf, n_leaves, bg, fmt, nullptr,
-                                           nullptr, d_scan, s));
+      HIP_TRY(c, cvr::launch_gather_leaves(src, with_albedo, res, ln, d_slot_leaf, n_leaves, bg, fmt, nullptr, nullptr,
+                                           d_scan, s));
       HIP_TRY(c, hipStreamSynchronize(s));
       HIP_TRY(c, hipMemcpy(&chk, d_scan, sizeof(chk), hipMemcpyDeviceToHost));
       const bool in_density = chk.ovf_density != ~0ull;
@@ -532,11 +576,13 @@ int devmed_sparse(cvr_ctx* c, const cvr_device_medium_desc* d, SparseBuild& b, c
         const uint32_t x = (leaf % ln[0]) * 8u + (local & 7u), y = ((leaf / ln[0]) % ln[1]) * 8u + ((local >> 3) & 7u),
                        z = (leaf / (ln[0] * ln[1])) * 8u + (local >> 6);
         const size_t i = ((size_t)z * res[1] + y) * res[0] + x;
-        if (x < res[0] && y < res[1] && z < res[2])
-          HIP_TRY(c, hipMemcpy(&value, in_density ? d->d_density + i : d->d_albedo + 4 * i + at % 4, sizeof(float),
-                               hipMemcpyDeviceToHost));
-        else
+        if (x < res[0] && y < res[1] && z < res[2]) {
+          float v[5];
+          if ((r = source_voxel(c, src, d.host_table, i, !in_density, v))) return r;
+          value = in_density ? v[4] : v[at % 4];
+        } else {
           value = in_density ? 0.0f : bg[at % 4];
+        }
       }
     }
     for (size_t k = 0; k < 3 && !what; ++k)
@@ -546,11 +592,121 @@ int devmed_sparse(cvr_ctx* c, const cvr_device_medium_desc* d, SparseBuild& b, c
                    (double)value, at);
   };
   auto gather = [&]() -> int {
-    HIP_TRY(c, cvr::launch_gather_leaves(d->d_density, c->d_leaf_albedo ? albedo : nullptr, res, ln, d_slot_leaf,
-                                         n_leaves, bg, fmt, c->d_leaf_density, c->d_leaf_albedo, nullptr, s));
+    HIP_TRY(c, cvr::launch_gather_leaves(src, with_albedo && c->d_leaf_albedo, res, ln, d_slot_leaf, n_leaves, bg, fmt,
+                                         c->d_leaf_density, c->d_leaf_albedo, nullptr, s));
     return CVR_OK;
   };
   return finish_sparse(c, b, tmp, tm, refuse_overflow, gather);
+}
+
+// n outside 2..4096, unknown flags, a NULL table, lo / hi not finite or hi <= lo, in cvr.h's order
+// for cvr_set_medium_scalar (which looks at d_scalar between the table and lo / hi: after_table)
+template <class F>
+int transfer_check(std::string* err, const cvr_transfer_desc* t, F after_table) {
+  if (t->flags & ~(uint32_t)(CVR_TF_CEIL | CVR_TF_DENSITY_U))
+    return set_err(err, CVR_ERR_INVALID, "unknown cvr_transfer_desc flags 0x%x", t->flags);
+  if (t->n < 2u || t->n > 4096u)
+    return set_err(err, CVR_ERR_INVALID, "transfer table of %u entries (2..4096)", t->n);
+  if (!t->table) return set_err(err, CVR_ERR_INVALID, "transfer table is NULL");
+  if (int r = after_table()) return r;
+  if (!std::isfinite(t->lo) || !std::isfinite(t->hi) || !(t->hi > t->lo))
+    return set_err(err, CVR_ERR_INVALID, "transfer range lo %g, hi %g: both finite and hi > lo", (double)t->lo,
+                   (double)t->hi);
+  return CVR_OK;
+}
+
+// Both device calls from their checked arguments on: one sequence of stages for either source.
+// b.g is filled for a sparse build; tmp may already hold the call's allocations (the table).
+int build_from_device(cvr_ctx* c, const DeviceBuild& d, const cvr::VoxelSource& src, SparseBuild& b, DevTemps& tmp) {
+  const uint32_t* res = d.v.res;
+  const bool sparse = (d.flags & CVR_DEVMED_SPARSE) != 0, konst = (d.flags & CVR_DEVMED_CONST_ALBEDO) != 0;
+  const bool classified = src.scalar != nullptr;
+  const uint32_t fmt = (uint32_t)c->medium_format;
+  const size_t n = (size_t)res[0] * res[1] * res[2];
+  int r;
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  DevmedTimer tm(c);
+  // the value scans: majorant, binary16 overflow, albedo sameness
+  cvr::MedScan scan{~0ull, ~0ull, 0u, 0u, {0u, 0u}};
+  cvr::MedScan* d_scan = nullptr;
+  HIP_TRY(c, tmp.alloc((void**)&d_scan, sizeof(scan)));
+  HIP_TRY(c, hipMemcpy(d_scan, &scan, sizeof(scan), hipMemcpyHostToDevice));
+  float first[5] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+  if (konst) memcpy(first, d.const_albedo, 4 * sizeof(float));
+  const bool scan_density = fmt || (d.flags & CVR_DEVMED_MAX_DENSITY),
+             scan_albedo = !konst && (fmt || sparse || c->uniform_albedo);
+  if (classified) {
+    // one pass finds both scans' results; a sparse build finds them in its leaf flags' pass
+    if (!sparse && (scan_density || scan_albedo)) {
+      tm.begin();
+      HIP_TRY(c, cvr::launch_scan_classified(src, n, fmt, d_scan, c->stream));
+      tm.end(0);
+    }
+  } else {
+    if (scan_density) {
+      tm.begin();
+      HIP_TRY(c, cvr::launch_scan_density(src.density, n, fmt, d_scan, c->stream));
+      tm.end(0);
+    }
+    if (scan_albedo) {
+      tm.begin();
+      HIP_TRY(c, cvr::launch_scan_albedo(src.albedo, n, fmt, d_scan, c->stream));
+      tm.end(1);
+    }
+  }
+  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  if (!konst && (r = source_voxel(c, src, d.host_table, 0, true, first))) return r;
+  HIP_TRY(c, hipMemcpy(&scan, d_scan, sizeof(scan), hipMemcpyDeviceToHost));
+  const float max_density = majorant_of(d, scan, fmt);
+  if (sparse) {
+    b.v = d.v;
+    b.fmt = fmt;
+    b.max_density = max_density;
+    return devmed_sparse(c, d, src, b, scan, first, d_scan, tmp, tm);
+  }
+  if (fmt) {
+    // cvr_set_medium's refusal: density before albedo, the smallest index (a constant albedo's
+    // grid overflows first at voxel 0)
+    const bool bad_d = scan.ovf_density != ~0ull;
+    size_t at = (size_t)scan.ovf_density;
+    float value = 0.0f;
+    bool bad_a = false;
+    float v[5];
+    if (bad_d) {
+      if ((r = source_voxel(c, src, d.host_table, at, false, v))) return r;
+      value = v[4];
+    } else if (konst) {
+      for (size_t k = 0; k < 3 && !bad_a; ++k)
+        if (overflows_half(first[k])) bad_a = true, at = k, value = first[k];
+    } else if (scan.ovf_albedo != ~0ull) {
+      bad_a = true;
+      at = (size_t)scan.ovf_albedo;
+      if ((r = source_voxel(c, src, d.host_table, at / 4, true, v))) return r;
+      value = v[at % 4];
+    }
+    if (bad_d || bad_a) {
+      c->have_medium = false;
+      return set_err(&c->err, CVR_ERR_INVALID, "medium format half: %s value %g at index %zu rounds to infinity",
+                     bad_d ? "density" : "albedo", (double)value, at);
+    }
+  }
+  // the grids copied (format 1: converted, straight from the caller's fp32 arrays), classified or filled
+  if ((r = dense_grids(c, n, fmt))) return r;
+  tm.begin();
+  if (classified) {
+    HIP_TRY(c, cvr::launch_store_classified(src, n, fmt, c->d_density, c->d_albedo, c->stream));
+  } else if (fmt) {
+    HIP_TRY(c, cvr::launch_to_half(src.density, c->d_density, n, c->stream));
+    if (!konst) HIP_TRY(c, cvr::launch_to_half(src.albedo, c->d_albedo, 4 * n, c->stream));
+  } else {
+    HIP_TRY(c, hipMemcpyAsync(c->d_density, src.density, n * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
+    if (!konst)
+      HIP_TRY(c, hipMemcpyAsync(c->d_albedo, src.albedo, n * sizeof(float4), hipMemcpyDeviceToDevice, c->stream));
+  }
+  if (konst) HIP_TRY(c, cvr::launch_fill_albedo(c->d_albedo, n, fmt, d.const_albedo, c->stream));
+  tm.end(4);
+  const bool same = c->uniform_albedo && (konst || !(scan.albedo_flags & 1u));
+  return finish_dense(c, d.v, fmt, max_density, same ? first : nullptr, tm);
 }
 }  // namespace
 
@@ -694,12 +850,10 @@ int cvr_set_medium_device(cvr_ctx* c, const cvr_device_medium_desc* d) {
   CVR_NOT_IN_SESSION(c, "cvr_set_medium_device");
   const uint32_t* res = d->res;
   const bool sparse = (d->flags & CVR_DEVMED_SPARSE) != 0, konst = (d->flags & CVR_DEVMED_CONST_ALBEDO) != 0;
-  const uint32_t fmt = (uint32_t)c->medium_format;
   // the host calls' shape guards, from res alone
   SparseBuild b{};
-  int r = sparse ? sparse_shape_check(c, res, &b.g) : dense_shape_check(c, res, fmt);
+  int r = sparse ? sparse_shape_check(c, res, &b.g) : dense_shape_check(c, res, (uint32_t)c->medium_format);
   if (r) return r;
-  const size_t n = (size_t)res[0] * res[1] * res[2];
   // then the flags and the pointers
   if (d->flags & ~(uint32_t)(CVR_DEVMED_SPARSE | CVR_DEVMED_CONST_ALBEDO | CVR_DEVMED_MAX_DENSITY))
     return set_err(&c->err, CVR_ERR_INVALID, "unknown cvr_device_medium_desc flags 0x%x", d->flags);
@@ -712,77 +866,97 @@ int cvr_set_medium_device(cvr_ctx* c, const cvr_device_medium_desc* d) {
                    c->device);
   if (((uintptr_t)d->d_density & 3u) || ((uintptr_t)d->d_albedo & 15u))
     return set_err(&c->err, CVR_ERR_INVALID, "d_density must be 4-byte and d_albedo 16-byte aligned");
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
+  cvr::VoxelSource src;
+  src.density = d->d_density;
+  src.albedo = d->d_albedo;
   DevTemps tmp;
-  DevmedTimer tm(c);
-  // the value scans: majorant, binary16 overflow, albedo sameness
-  cvr::MedScan scan{~0ull, ~0ull, 0u, 0u, {0u, 0u}};
-  cvr::MedScan* d_scan = nullptr;
-  HIP_TRY(c, tmp.alloc((void**)&d_scan, sizeof(scan)));
-  HIP_TRY(c, hipMemcpy(d_scan, &scan, sizeof(scan), hipMemcpyHostToDevice));
-  float first[4] = {d->const_albedo[0], d->const_albedo[1], d->const_albedo[2], d->const_albedo[3]};
-  if (fmt || (d->flags & CVR_DEVMED_MAX_DENSITY)) {
-    tm.begin();
-    HIP_TRY(c, cvr::launch_scan_density(d->d_density, n, fmt, d_scan, c->stream));
-    tm.end(0);
+  return build_from_device(c, {view_of(*d), d->flags, d->const_albedo, d->max_density, nullptr}, src, b, tmp);
+}
+
+int cvr_classify_host(const void* scalar, uint32_t scalar_type, size_t n_voxels, const cvr_transfer_desc* t,
+                      float* density, float* albedo) {
+  if (!t || (n_voxels && !scalar)) return set_err(nullptr, CVR_ERR_INVALID, "NULL argument");
+  if (scalar_type > CVR_SCALAR_I16) return set_err(nullptr, CVR_ERR_INVALID, "unknown scalar_type %u", scalar_type);
+  if (int r = transfer_check(nullptr, t, [] { return CVR_OK; })) return r;
+  const cvr::TransferParams p{t->n, t->flags, t->lo, t->hi};
+  // (the table as float4: copied, the caller's need not be 16-byte aligned)
+  std::vector<float4> table(t->n);
+  memcpy(table.data(), t->table, (size_t)t->n * sizeof(float4));
+  for (size_t i = 0; i < n_voxels; ++i) {
+    const float4 e = cvr::transfer_classify(cvr::scalar_voxel(scalar, scalar_type, i), table.data(), p);
+    if (density) density[i] = e.w;
+    if (albedo) albedo[4 * i] = e.x, albedo[4 * i + 1] = e.y, albedo[4 * i + 2] = e.z, albedo[4 * i + 3] = 1.0f;
   }
-  if (!konst) {
-    if (fmt || sparse || c->uniform_albedo) {
-      tm.begin();
-      HIP_TRY(c, cvr::launch_scan_albedo(d->d_albedo, n, fmt, d_scan, c->stream));
-      tm.end(1);
-    }
-    HIP_TRY(c, hipMemcpyAsync(first, d->d_albedo, sizeof(first), hipMemcpyDeviceToHost, c->stream));
-  }
-  HIP_TRY(c, hipStreamSynchronize(c->stream));
-  HIP_TRY(c, hipMemcpy(&scan, d_scan, sizeof(scan), hipMemcpyDeviceToHost));
-  float max_density = d->max_density;
-  if (d->flags & CVR_DEVMED_MAX_DENSITY) memcpy(&max_density, &scan.max_bits, sizeof(float));
-  if (fmt) max_density = half_majorant(max_density);
-  if (sparse) {
-    b.v = view_of(*d);
-    b.fmt = fmt;
-    b.max_density = max_density;
-    return devmed_sparse(c, d, b, scan, first, d_scan, tmp, tm);
-  }
-  if (fmt) {
-    // cvr_set_medium's refusal: density before albedo, the smallest index (a constant albedo's
-    // grid overflows first at voxel 0)
-    const bool bad_d = scan.ovf_density != ~0ull;
-    size_t at = (size_t)scan.ovf_density;
-    float value = 0.0f;
-    bool bad_a = false;
-    if (bad_d) {
-      HIP_TRY(c, hipMemcpy(&value, d->d_density + at, sizeof(float), hipMemcpyDeviceToHost));
-    } else if (konst) {
-      for (size_t k = 0; k < 3 && !bad_a; ++k)
-        if (overflows_half(first[k])) bad_a = true, at = k, value = first[k];
-    } else if (scan.ovf_albedo != ~0ull) {
-      bad_a = true;
-      at = (size_t)scan.ovf_albedo;
-      HIP_TRY(c, hipMemcpy(&value, d->d_albedo + at, sizeof(float), hipMemcpyDeviceToHost));
-    }
-    if (bad_d || bad_a) {
-      c->have_medium = false;
-      return set_err(&c->err, CVR_ERR_INVALID, "medium format half: %s value %g at index %zu rounds to infinity",
-                     bad_d ? "density" : "albedo", (double)value, at);
-    }
-  }
-  // the grids copied (format 1: converted, straight from the caller's fp32 arrays) or filled
-  if ((r = dense_grids(c, n, fmt))) return r;
-  tm.begin();
-  if (fmt) {
-    HIP_TRY(c, cvr::launch_to_half(d->d_density, c->d_density, n, c->stream));
-    if (!konst) HIP_TRY(c, cvr::launch_to_half(d->d_albedo, c->d_albedo, 4 * n, c->stream));
-  } else {
-    HIP_TRY(c, hipMemcpyAsync(c->d_density, d->d_density, n * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
-    if (!konst)
-      HIP_TRY(c, hipMemcpyAsync(c->d_albedo, d->d_albedo, n * sizeof(float4), hipMemcpyDeviceToDevice, c->stream));
-  }
-  if (konst) HIP_TRY(c, cvr::launch_fill_albedo(c->d_albedo, n, fmt, d->const_albedo, c->stream));
-  tm.end(4);
-  const bool same = c->uniform_albedo && (konst || !(scan.albedo_flags & 1u));
-  return finish_dense(c, view_of(*d), fmt, max_density, same ? first : nullptr, tm);
+  return CVR_OK;
+}
+
+int cvr_set_medium_scalar(cvr_ctx* c, const cvr_scalar_medium_desc* d) {
+  if (!c || !d) return set_err(c ? &c->err : nullptr, CVR_ERR_INVALID, "NULL argument");
+  CVR_NOT_IN_SESSION(c, "cvr_set_medium_scalar");
+  const uint32_t* res = d->res;
+  const bool sparse = (d->flags & CVR_DEVMED_SPARSE) != 0;
+  SparseBuild b{};
+  int r = sparse ? sparse_shape_check(c, res, &b.g) : dense_shape_check(c, res, (uint32_t)c->medium_format);
+  if (r) return r;
+  if (d->flags & ~(uint32_t)(CVR_DEVMED_SPARSE | CVR_DEVMED_MAX_DENSITY))
+    return set_err(&c->err, CVR_ERR_INVALID, "unknown cvr_scalar_medium_desc flags 0x%x", d->flags);
+  if (d->scalar_type > CVR_SCALAR_I16)
+    return set_err(&c->err, CVR_ERR_INVALID, "unknown scalar_type %u", d->scalar_type);
+  const cvr_transfer_desc* t = &d->transfer;
+  r = transfer_check(&c->err, t, [&]() -> int {
+    return d->d_scalar ? CVR_OK : set_err(&c->err, CVR_ERR_INVALID, "d_scalar is NULL");
+  });
+  if (r) return r;
+  if ((r = ensure_device(c))) return r;
+  if (!device_readable(c, d->d_scalar))
+    return set_err(&c->err, CVR_ERR_INVALID, "d_scalar is not device-accessible memory of device %d", c->device);
+  const size_t size = d->scalar_type == CVR_SCALAR_U8 ? 1 : d->scalar_type == CVR_SCALAR_F32 ? 4 : 2;
+  if ((uintptr_t)d->d_scalar & (size - 1))
+    return set_err(&c->err, CVR_ERR_INVALID, "d_scalar must be %zu-byte aligned", size);
+  // the table goes to the device once; the kernels stage it in LDS per workgroup
+  DevTemps tmp;
+  float4* d_table = nullptr;
+  HIP_TRY(c, tmp.alloc((void**)&d_table, (size_t)t->n * sizeof(float4)));
+  HIP_TRY(c, hipMemcpy(d_table, t->table, (size_t)t->n * sizeof(float4), hipMemcpyHostToDevice));
+  std::vector<float4> table(t->n);
+  memcpy(table.data(), t->table, (size_t)t->n * sizeof(float4));
+  cvr::VoxelSource src;
+  src.scalar = d->d_scalar;
+  src.scalar_type = d->scalar_type;
+  src.table = d_table;
+  src.tf = {t->n, t->flags, t->lo, t->hi};
+  return build_from_device(c, {view_of(*d), d->flags, nullptr, d->max_density, &table[0].x}, src, b, tmp);
+}
+
+int cvr_set_medium_scene_transfer(cvr_ctx* c, const cvr_scene* scene, const cvr_transfer_desc* t, uint32_t flags) {
+  if (!c || !scene || !t) return set_err(c ? &c->err : nullptr, CVR_ERR_INVALID, "NULL argument");
+  const uint8_t* bytes = nullptr;
+  size_t n = 0;
+  cvr_medium_desc md{};
+  int r = cvr_scene_raw_bytes(scene, &bytes, &n);
+  if (!r) r = cvr_scene_medium(scene, &md);
+  if (r || !n || n != (size_t)md.res[0] * md.res[1] * md.res[2])
+    return set_err(&c->err, CVR_ERR_INVALID, "the scene has no raw bytes (one per voxel): not a Raw scene");
+  if ((r = ensure_device(c))) return r;
+  DevTemps tmp;
+  void* d_bytes = nullptr;
+  HIP_TRY(c, tmp.alloc(&d_bytes, n));
+  HIP_TRY(c, hipMemcpy(d_bytes, bytes, n, hipMemcpyHostToDevice));
+  cvr_scalar_medium_desc d{};
+  memcpy(d.res, md.res, sizeof(d.res));
+  d.flags = flags | CVR_DEVMED_MAX_DENSITY;
+  d.d_scalar = d_bytes;
+  d.scalar_type = CVR_SCALAR_U8;
+  d.transfer = *t;
+  d.transfer.lo = 0.0f;
+  d.transfer.hi = (float)*std::max_element(bytes, bytes + n);
+  memcpy(d.box_min, md.box_min, sizeof(d.box_min));
+  memcpy(d.box_max, md.box_max, sizeof(d.box_max));
+  d.scale = md.scale;
+  d.g = md.g;
+  d.roughness[0] = md.roughness[0], d.roughness[1] = md.roughness[1];
+  d.eta = md.eta;
+  return cvr_set_medium_scalar(c, &d);
 }
 
 int cvr_debug_device_medium_ms(const cvr_ctx* c, double out[6]) {

@@ -1,6 +1,7 @@
-// cvr_medium_build.hip - the device-side front end of cvr_set_medium_device (gfx950): what the
-// host uploads decide with loops over every voxel or leaf, decided here from the caller's device
-// arrays.  Value scans (majorant, binary16 overflow, uniform albedo), the dense -> 8^3 leaves
+// cvr_medium_build.hip - the device-side front end of cvr_set_medium_device and
+// cvr_set_medium_scalar (gfx950): what the host uploads decide with loops over every voxel or
+// leaf, decided here from a voxel source in device memory, the caller's two arrays or a scalar
+// field classified through a transfer table staged in LDS.  Value scans (majorant, binary16 overflow, uniform albedo), the dense -> 8^3 leaves
 // rule of cvr.h (leaf flags, exclusive scan, gather), the cell-leaf table and the empty-region
 // mask.  The cells, bounds and brick words are then built by cvr_kernels.hip's kernels, unchanged.
 //
@@ -9,6 +10,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <type_traits>
 
 #include "cvr_kernels.h"
 
@@ -51,6 +53,45 @@ __device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
   return v;
 }
 
+// ---------------------------------------------------------- voxel sources ---
+// Where a kernel takes a voxel's density and albedo from.  The caller's two arrays:
+struct ArraySrc {
+  using Scalar = void;
+  const float* __restrict__ D;
+  const float4* __restrict__ A;  // null: no albedo
+  __device__ void stage() {}
+  __device__ bool has_albedo() const { return A != nullptr; }
+  __device__ void voxel(size_t i, float& d, float4& a) const {
+    d = D[i];
+    if (A) a = A[i];
+  }
+};
+// A scalar field of type T classified through the transfer table (cvr.h; transfer_classify is the
+// statement).  stage() copies the table into the workgroup's dynamic LDS, n x 16 bytes, once;
+// every work-item of the workgroup calls it before the first voxel().
+template <class T>
+struct ScalarSrc {
+  using Scalar = T;
+  const T* __restrict__ S;
+  const float4* __restrict__ table;
+  TransferParams p;
+  uint32_t albedo;  // 0: the colours are not looked at (has_albedo() false)
+  const float4* lds;
+  __device__ void stage() {
+    extern __shared__ float4 s_table[];
+    for (uint32_t k = threadIdx.x; k < p.n; k += blockDim.x) s_table[k] = table[k];
+    __syncthreads();
+    lds = s_table;
+  }
+  __device__ bool has_albedo() const { return albedo != 0u; }
+  __device__ void classified(float s, float& d, float4& a) const {
+    const float4 e = transfer_classify(s, lds, p);
+    d = e.w;
+    a = make_float4(e.x, e.y, e.z, 1.0f);
+  }
+  __device__ void voxel(size_t i, float& d, float4& a) const { classified((float)S[i], d, a); }
+};
+
 // ----------------------------------------------------------- value scans ---
 // Streaming reads: consecutive lanes read consecutive 16 bytes (1 KiB per wave and load), a wave
 // reduction, then at most one atomic of each kind per workgroup, and none when the result already
@@ -58,61 +99,48 @@ __device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
 // atomic that changes nothing).  Atomics on one word are serialised at the memory side: with 8192
 // workgroups each issuing theirs, C2's 60 MB density scan took 0.095 ms; with 2048 workgroups and
 // the reads first, 0.026 ms (profiles/device_medium/README.md).
-__global__ __launch_bounds__(256) void k_scan_density(const float* __restrict__ D, size_t n, uint32_t format,
-                                                      MedScan* __restrict__ out) {
+
+// What a work-item has seen of the densities; commit() reduces the workgroup's (s_mx, s_ov: 4
+// entries of LDS each) into out.
+struct DensityScan {
   float mx = 0.0f;  // max(0, every non-NaN voxel): a NaN or -0 never compares greater
   unsigned long long ov = kNoIndex;
-  auto take = [&](float v, size_t i) {
+  __device__ __forceinline__ void take(float v, size_t i, uint32_t format) {
     mx = v > mx ? v : mx;
     if (format && half_overflow(v) && i < ov) ov = i;
-  };
-  // 16 bytes per lane where the array's alignment allows it, the last n % 4 voxels one by one
-  const size_t n4 = ((uintptr_t)D & 15u) ? 0 : n / 4;
-  const float4* __restrict__ D4 = reinterpret_cast<const float4*>(D);
-#pragma unroll 2
-  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (size_t)gridDim.x * 256) {
-    const float4 v = D4[i];
-    take(v.x, 4 * i);
-    take(v.y, 4 * i + 1);
-    take(v.z, 4 * i + 2);
-    take(v.w, 4 * i + 3);
   }
-  for (size_t i = 4 * n4 + (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) take(D[i], i);
-  mx = wave_max(mx);
-  ov = wave_min(ov);
-  __shared__ float s_mx[4];
-  __shared__ unsigned long long s_ov[4];
-  const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
-  if (lane == 0) {
-    s_mx[w] = mx;
-    s_ov[w] = ov;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    for (uint32_t k = 1; k < 4; ++k) {
-      mx = s_mx[k] > mx ? s_mx[k] : mx;
-      ov = s_ov[k] < ov ? s_ov[k] : ov;
+  __device__ __forceinline__ void commit(float* s_mx, unsigned long long* s_ov, MedScan* __restrict__ out) {
+    mx = wave_max(mx);
+    ov = wave_min(ov);
+    const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
+    if (lane == 0) {
+      s_mx[w] = mx;
+      s_ov[w] = ov;
     }
-    // mx >= +0, so its bits order as the values do
-    if (__float_as_uint(mx) > __atomic_load_n(&out->max_bits, __ATOMIC_RELAXED))
-      atomicMax(&out->max_bits, __float_as_uint(mx));
-    if (ov < __atomic_load_n(&out->ovf_density, __ATOMIC_RELAXED)) atomicMin(&out->ovf_density, ov);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      for (uint32_t k = 1; k < 4; ++k) {
+        mx = s_mx[k] > mx ? s_mx[k] : mx;
+        ov = s_ov[k] < ov ? s_ov[k] : ov;
+      }
+      // mx >= +0, so its bits order as the values do
+      if (__float_as_uint(mx) > __atomic_load_n(&out->max_bits, __ATOMIC_RELAXED))
+        atomicMax(&out->max_bits, __float_as_uint(mx));
+      if (ov < __atomic_load_n(&out->ovf_density, __ATOMIC_RELAXED)) atomicMin(&out->ovf_density, ov);
+    }
   }
-}
-
-// albedo_flags bit 0: some voxel's rgb differs from voxel 0's (format 1: the rounded halves; bits
-// are compared, w is ignored); bit 1: some voxel's 16 bytes differ from voxel 0's (the leaf rule).
-__global__ __launch_bounds__(256) void k_scan_albedo(const float4* __restrict__ A, size_t n, uint32_t format,
-                                                     MedScan* __restrict__ out) {
-  const float4 f = A[0];
-  const uint32_t f0 = __float_as_uint(f.x), f1 = __float_as_uint(f.y), f2 = __float_as_uint(f.z),
-                 f3 = __float_as_uint(f.w);
-  const uint32_t h0 = half_bits(f.x), h1 = half_bits(f.y), h2 = half_bits(f.z);
+};
+// The same of the albedos, against voxel 0's.  albedo_flags bit 0: some voxel's rgb differs from
+// voxel 0's (format 1: the rounded halves; bits are compared, w is ignored); bit 1: some voxel's
+// 16 bytes differ from voxel 0's (the leaf rule).
+struct AlbedoScan {
+  uint32_t f0, f1, f2, f3, h0, h1, h2;
   uint32_t flags = 0;
   unsigned long long ov = kNoIndex;
-#pragma unroll 2
-  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
-    const float4 a = A[i];
+  __device__ __forceinline__ explicit AlbedoScan(const float4 f)
+      : f0(__float_as_uint(f.x)), f1(__float_as_uint(f.y)), f2(__float_as_uint(f.z)), f3(__float_as_uint(f.w)),
+        h0(half_bits(f.x)), h1(half_bits(f.y)), h2(half_bits(f.z)) {}
+  __device__ __forceinline__ void take(const float4 a, size_t i, uint32_t format) {
     const bool rgb = __float_as_uint(a.x) != f0 || __float_as_uint(a.y) != f1 || __float_as_uint(a.z) != f2;
     if (rgb || __float_as_uint(a.w) != f3) flags |= 2u;
     if (format) {
@@ -124,24 +152,135 @@ __global__ __launch_bounds__(256) void k_scan_albedo(const float4* __restrict__ 
       flags |= 1u;
     }
   }
-  flags = wave_or(flags);
-  ov = wave_min(ov);
+  __device__ __forceinline__ void commit(uint32_t* s_fl, unsigned long long* s_ov, MedScan* __restrict__ out) {
+    flags = wave_or(flags);
+    ov = wave_min(ov);
+    const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
+    if (lane == 0) {
+      s_fl[w] = flags;
+      s_ov[w] = ov;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      for (uint32_t k = 1; k < 4; ++k) {
+        flags |= s_fl[k];
+        ov = s_ov[k] < ov ? s_ov[k] : ov;
+      }
+      if (flags & ~__atomic_load_n(&out->albedo_flags, __ATOMIC_RELAXED)) atomicOr(&out->albedo_flags, flags);
+      if (ov < __atomic_load_n(&out->ovf_albedo, __ATOMIC_RELAXED)) atomicMin(&out->ovf_albedo, ov);
+    }
+  }
+};
+
+__global__ __launch_bounds__(256) void k_scan_density(const float* __restrict__ D, size_t n, uint32_t format,
+                                                      MedScan* __restrict__ out) {
+  DensityScan ds;
+  // 16 bytes per lane where the array's alignment allows it, the last n % 4 voxels one by one
+  const size_t n4 = ((uintptr_t)D & 15u) ? 0 : n / 4;
+  const float4* __restrict__ D4 = reinterpret_cast<const float4*>(D);
+#pragma unroll 2
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (size_t)gridDim.x * 256) {
+    const float4 v = D4[i];
+    ds.take(v.x, 4 * i, format);
+    ds.take(v.y, 4 * i + 1, format);
+    ds.take(v.z, 4 * i + 2, format);
+    ds.take(v.w, 4 * i + 3, format);
+  }
+  for (size_t i = 4 * n4 + (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256)
+    ds.take(D[i], i, format);
+  __shared__ float s_mx[4];
+  __shared__ unsigned long long s_ov[4];
+  ds.commit(s_mx, s_ov, out);
+}
+
+__global__ __launch_bounds__(256) void k_scan_albedo(const float4* __restrict__ A, size_t n, uint32_t format,
+                                                     MedScan* __restrict__ out) {
+  AlbedoScan as(A[0]);
+#pragma unroll 2
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) as.take(A[i], i, format);
   __shared__ uint32_t s_fl[4];
   __shared__ unsigned long long s_ov[4];
-  const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
-  if (lane == 0) {
-    s_fl[w] = flags;
-    s_ov[w] = ov;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    for (uint32_t k = 1; k < 4; ++k) {
-      flags |= s_fl[k];
-      ov = s_ov[k] < ov ? s_ov[k] : ov;
+  as.commit(s_fl, s_ov, out);
+}
+
+// Both scans' workgroup reductions with the table's LDS as their scratch, after the workgroup's
+// last voxel (the launches allocate at least 8 entries).
+__device__ __forceinline__ void commit_in_table_lds(DensityScan& ds, AlbedoScan& as, MedScan* __restrict__ out) {
+  extern __shared__ float4 s_table[];
+  __syncthreads();  // the table is read no more
+  unsigned long long* s_ov = reinterpret_cast<unsigned long long*>(s_table);
+  float* s_mx = reinterpret_cast<float*>(s_ov + 8);
+  ds.commit(s_mx, s_ov, out);
+  as.commit(reinterpret_cast<uint32_t*>(s_mx + 4), s_ov + 4, out);
+}
+
+// The classified source's two dense passes over the scalar field.  kStore false: the scan, which
+// finds what k_scan_density and k_scan_albedo find, of the classified values, together.  kStore
+// true: every voxel's density and albedo into the context's grids (format 1: as binary16).
+// Integer scalars are loaded 16 bytes per lane: the field is cut into a head up to the first
+// 16-byte boundary, whole 16-byte groups, and a tail; a wave loads 64 groups (1 KiB) and hands the
+// voxels round with lane shuffles so that in each of its V steps lane l has voxel 64 k + l of the
+// wave's run, and the stores of a step are consecutive.  Head and tail (a float field: every
+// voxel) are taken one voxel per lane.  The workgroup reduction's scratch is the table's LDS, after
+// the last voxel (at least 8 entries are allocated).
+template <class T, bool kStore>
+__global__ __launch_bounds__(256) void k_classified(ScalarSrc<T> src, size_t n, uint32_t format,
+                                                    void* __restrict__ density, void* __restrict__ albedo,
+                                                    MedScan* __restrict__ out) {
+  src.stage();
+  float d0;
+  float4 a0;
+  src.voxel(0, d0, a0);
+  DensityScan ds;
+  AlbedoScan as(a0);
+  auto take = [&](size_t i, float s) {
+    float d;
+    float4 a;
+    src.classified(s, d, a);
+    if (!kStore) {
+      ds.take(d, i, format);
+      as.take(a, i, format);
+    } else if (format) {
+      uint2 h;
+      h.x = half_bits(a.x) | half_bits(a.y) << 16;
+      h.y = half_bits(a.z) | half_bits(a.w) << 16;
+      reinterpret_cast<_Float16*>(density)[i] = (_Float16)d;
+      reinterpret_cast<uint2*>(albedo)[i] = h;
+    } else {
+      reinterpret_cast<float*>(density)[i] = d;
+      reinterpret_cast<float4*>(albedo)[i] = a;
     }
-    if (flags & ~__atomic_load_n(&out->albedo_flags, __ATOMIC_RELAXED)) atomicOr(&out->albedo_flags, flags);
-    if (ov < __atomic_load_n(&out->ovf_albedo, __ATOMIC_RELAXED)) atomicMin(&out->ovf_albedo, ov);
+  };
+  constexpr uint32_t kSize = (uint32_t)sizeof(T), V = kSize < 4u ? 16u / kSize : 1u;
+  size_t head = 0, body_end = 0;
+  if constexpr (V > 1u) {
+    head = ((16u - (uint32_t)((uintptr_t)src.S & 15u)) & 15u) / kSize;
+    head = head < n ? head : n;
+    const size_t groups = (n - head) / V;
+    body_end = head + groups * V;
+    const uint4* __restrict__ S16 = reinterpret_cast<const uint4*>(src.S + head);
+    const uint32_t lane = threadIdx.x & 63u;
+    const size_t wave = ((size_t)blockIdx.x * 256 + threadIdx.x) >> 6, nwaves = (size_t)gridDim.x * 4;
+    // (the bounds are the wave's: every lane takes part in the shuffles)
+    for (size_t g0 = wave * 64; g0 < groups; g0 += nwaves * 64) {
+      const uint4 q = g0 + lane < groups ? S16[g0 + lane] : make_uint4(0u, 0u, 0u, 0u);
+#pragma unroll
+      for (uint32_t k = 0; k < V; ++k) {
+        const uint32_t j = k * 64u + lane, from = j / V, byte = (j % V) * kSize;
+        const uint32_t w0 = __shfl(q.x, from), w1 = __shfl(q.y, from), w2 = __shfl(q.z, from), w3 = __shfl(q.w, from);
+        const uint32_t w = byte < 4u ? w0 : byte < 8u ? w1 : byte < 12u ? w2 : w3;
+        const T v = (T)(w >> ((byte & 3u) * 8u));
+        const size_t i = head + g0 * V + j;
+        if (i < body_end) take(i, (float)v);
+      }
+    }
   }
+  const size_t rest = head + (n - body_end);
+  for (size_t e = (size_t)blockIdx.x * 256 + threadIdx.x; e < rest; e += (size_t)gridDim.x * 256) {
+    const size_t i = e < head ? e : body_end + (e - head);
+    take(i, (float)src.S[i]);
+  }
+  if (!kStore) commit_in_table_lds(ds, as, out);
 }
 
 // The context's albedo grid filled with one value (CVR_DEVMED_CONST_ALBEDO, dense).
@@ -162,16 +301,27 @@ __global__ __launch_bounds__(256) void k_fill_albedo(void* __restrict__ dst, siz
 // albedo bytes other than voxel 0's.  One workgroup takes 32 leaves of one (lz, ly) row: its
 // work-items are 256 consecutive x, so a wave reads 64-voxel x-runs of each of the row's 64
 // (z, y) lines, not one leaf's 8-voxel rows; the 8 lanes of a leaf then OR their findings.
-__global__ __launch_bounds__(256) void k_leaf_flags(const float* __restrict__ D, const float4* __restrict__ A,
-                                                    uint32_t nx, uint32_t ny, uint32_t nz, uint32_t lnx, uint32_t lny,
-                                                    uint32_t lnz, uint32_t* __restrict__ flags) {
+// A classified source reads one scalar per lane and row here (a wave's run is 64 to 256 bytes),
+// always looks at the colours, and finds the value scans' results on the way (scan), so that a
+// sparse build reads the field once here and once in the gather.
+template <class Src>
+__global__ __launch_bounds__(256) void k_leaf_flags(Src src, uint32_t nx, uint32_t ny, uint32_t nz, uint32_t lnx,
+                                                    uint32_t lny, uint32_t lnz, uint32_t* __restrict__ flags,
+                                                    uint32_t format, MedScan* __restrict__ scan) {
+  constexpr bool kScan = !std::is_void_v<typename Src::Scalar>;
+  src.stage();
   const uint32_t nxc = (lnx + 31u) / 32u;
   const size_t ntasks = (size_t)nxc * lny * lnz;
+  const bool with_albedo = src.has_albedo();
   uint32_t b0 = 0, b1 = 0, b2 = 0, b3 = 0;
-  if (A) {
-    const float4 f = A[0];
+  if (with_albedo) {
+    float d;
+    float4 f;
+    src.voxel(0, d, f);
     b0 = __float_as_uint(f.x), b1 = __float_as_uint(f.y), b2 = __float_as_uint(f.z), b3 = __float_as_uint(f.w);
   }
+  DensityScan ds;
+  AlbedoScan as(make_float4(__uint_as_float(b0), __uint_as_float(b1), __uint_as_float(b2), __uint_as_float(b3)));
   for (size_t t = blockIdx.x; t < ntasks; t += gridDim.x) {
     const uint32_t xc = (uint32_t)(t % nxc), ly = (uint32_t)((t / nxc) % lny), lz = (uint32_t)(t / ((size_t)nxc * lny));
     const uint32_t x = xc * 256u + threadIdx.x;
@@ -182,12 +332,17 @@ __global__ __launch_bounds__(256) void k_leaf_flags(const float* __restrict__ D,
         const uint32_t y = ly * 8u + (r & 7u), z = lz * 8u + (r >> 3);
         if (y < ny && z < nz) {
           const size_t i = ((size_t)z * ny + y) * nx + x;
-          any |= D[i] != 0.0f;
-          if (A) {
-            const float4 a = A[i];
+          float d;
+          float4 a;
+          src.voxel(i, d, a);
+          if (kScan) {
+            ds.take(d, i, format);
+            as.take(a, i, format);
+          }
+          any |= d != 0.0f;
+          if (with_albedo)
             any |= __float_as_uint(a.x) != b0 || __float_as_uint(a.y) != b1 || __float_as_uint(a.z) != b2 ||
                    __float_as_uint(a.w) != b3;
-          }
         }
       }
     }
@@ -198,6 +353,7 @@ __global__ __launch_bounds__(256) void k_leaf_flags(const float* __restrict__ D,
     const uint32_t lx = x >> 3;
     if ((x & 7u) == 0 && lx < lnx) flags[((size_t)lz * lny + ly) * lnx + lx] = any;
   }
+  if constexpr (kScan) commit_in_table_lds(ds, as, scan);
 }
 
 // flags[leaf] = 1 iff the leaf or one of its 7 forward neighbours exists (it needs a cell leaf)
@@ -347,20 +503,22 @@ __global__ __launch_bounds__(256) void k_scatter_cell_leaves(const uint32_t* __r
 // grid's voxel, or (0, background) outside the grid; format 1 converts to binary16 here.
 // kStore false: nothing is written; the smallest pool index (albedo: 4 p + channel) whose value
 // overflows binary16 goes to out, the index cvr_set_medium_sparse would name.
-template <bool kStore>
-__global__ __launch_bounds__(256) void k_gather_leaves(const float* __restrict__ D, const float4* __restrict__ A,
-                                                       uint32_t nx, uint32_t ny, uint32_t nz, uint32_t lnx,
+template <class Src, bool kStore>
+__global__ __launch_bounds__(256) void k_gather_leaves(Src src, uint32_t nx, uint32_t ny, uint32_t nz, uint32_t lnx,
                                                        uint32_t lny, const uint32_t* __restrict__ slot_leaf,
                                                        size_t n_pool, float4 bg, uint32_t format,
                                                        void* __restrict__ leaf_density, void* __restrict__ leaf_albedo,
                                                        MedScan* __restrict__ out) {
+  src.stage();
+  const bool with_albedo = src.has_albedo();
   for (size_t p = (size_t)blockIdx.x * 256 + threadIdx.x; p < n_pool; p += (size_t)gridDim.x * 256) {
     const uint32_t leaf = slot_leaf[p >> 9], local = (uint32_t)p & 511u;
     const uint32_t lx = leaf % lnx, ly = (leaf / lnx) % lny, lz = leaf / (lnx * lny);
     const uint32_t x = lx * 8u + (local & 7u), y = ly * 8u + ((local >> 3) & 7u), z = lz * 8u + (local >> 6);
     const bool in = x < nx && y < ny && z < nz;
-    const size_t i = in ? ((size_t)z * ny + y) * nx + x : 0;
-    const float d = in ? D[i] : 0.0f;
+    float d = 0.0f;
+    float4 a = bg;
+    if (in) src.voxel(((size_t)z * ny + y) * nx + x, d, a);
     if (kStore) {
       if (format)
         reinterpret_cast<_Float16*>(leaf_density)[p] = (_Float16)d;
@@ -369,8 +527,7 @@ __global__ __launch_bounds__(256) void k_gather_leaves(const float* __restrict__
     } else if (half_overflow(d)) {
       atomicMin(&out->ovf_density, (unsigned long long)p);
     }
-    if (A) {
-      const float4 a = in ? A[i] : bg;
+    if (with_albedo) {
       if (!kStore) {
         const unsigned long long at =
             half_overflow(a.x) ? 4 * p : half_overflow(a.y) ? 4 * p + 1 : half_overflow(a.z) ? 4 * p + 2 : kNoIndex;
@@ -391,6 +548,37 @@ uint32_t stream_grid(size_t n) { return (uint32_t)std::min<size_t>((n + 255) / 2
 // the scans: 8 resident workgroups per CU of 256, each looping
 uint32_t scan_grid(size_t n) { return (uint32_t)std::min<size_t>((n + 255) / 256, 2048); }
 
+// f(src, lds): the source as the kernels take it and the dynamic LDS its table needs
+template <class F>
+void with_source(const VoxelSource& v, bool with_albedo, F f) {
+  // (the classified scan's reduction reuses the table's LDS: at least 8 entries)
+  const size_t lds = (size_t)std::max(v.tf.n, 8u) * sizeof(float4);
+  const uint32_t al = with_albedo ? 1u : 0u;
+  if (!v.scalar)
+    f(ArraySrc{v.density, with_albedo ? reinterpret_cast<const float4*>(v.albedo) : nullptr}, (size_t)0);
+  else if (v.scalar_type == 1u)
+    f(ScalarSrc<uint8_t>{static_cast<const uint8_t*>(v.scalar), v.table, v.tf, al, nullptr}, lds);
+  else if (v.scalar_type == 2u)
+    f(ScalarSrc<uint16_t>{static_cast<const uint16_t*>(v.scalar), v.table, v.tf, al, nullptr}, lds);
+  else if (v.scalar_type == 3u)
+    f(ScalarSrc<int16_t>{static_cast<const int16_t*>(v.scalar), v.table, v.tf, al, nullptr}, lds);
+  else
+    f(ScalarSrc<float>{static_cast<const float*>(v.scalar), v.table, v.tf, al, nullptr}, lds);
+}
+
+template <bool kStore>
+hipError_t launch_classified(const VoxelSource& v, size_t n, uint32_t format, void* density, void* albedo,
+                             MedScan* out, hipStream_t s) {
+  if (!v.scalar) return hipErrorInvalidValue;
+  with_source(v, true, [&](auto src, size_t lds) {
+    using T = typename decltype(src)::Scalar;
+    if constexpr (!std::is_void_v<T>)
+      hipLaunchKernelGGL((k_classified<T, kStore>), dim3(scan_grid(n)), dim3(256), lds, s, src, n, format, density,
+                         albedo, out);
+  });
+  return hipGetLastError();
+}
+
 }  // namespace
 
 hipError_t launch_scan_density(const float* density, size_t n, uint32_t format, MedScan* out, hipStream_t s) {
@@ -410,11 +598,22 @@ hipError_t launch_fill_albedo(void* albedo, size_t n, uint32_t format, const flo
   return hipGetLastError();
 }
 
-hipError_t launch_leaf_flags(const float* density, const float* albedo, const uint32_t res[3], const uint32_t ln[3],
-                             uint32_t* flags, hipStream_t s) {
+hipError_t launch_scan_classified(const VoxelSource& src, size_t n, uint32_t format, MedScan* out, hipStream_t s) {
+  return launch_classified<false>(src, n, format, nullptr, nullptr, out, s);
+}
+
+hipError_t launch_store_classified(const VoxelSource& src, size_t n, uint32_t format, void* density, void* albedo,
+                                   hipStream_t s) {
+  return launch_classified<true>(src, n, format, density, albedo, nullptr, s);
+}
+
+hipError_t launch_leaf_flags(const VoxelSource& v, bool with_albedo, const uint32_t res[3], const uint32_t ln[3],
+                             uint32_t* flags, uint32_t format, MedScan* scan, hipStream_t s) {
   const size_t ntasks = (size_t)((ln[0] + 31u) / 32u) * ln[1] * ln[2];
-  hipLaunchKernelGGL(k_leaf_flags, dim3((uint32_t)std::min<size_t>(ntasks, 1u << 20)), dim3(256), 0, s, density,
-                     reinterpret_cast<const float4*>(albedo), res[0], res[1], res[2], ln[0], ln[1], ln[2], flags);
+  with_source(v, with_albedo, [&](auto src, size_t lds) {
+    hipLaunchKernelGGL(k_leaf_flags<decltype(src)>, dim3((uint32_t)std::min<size_t>(ntasks, 1u << 20)), dim3(256), lds,
+                       s, src, res[0], res[1], res[2], ln[0], ln[1], ln[2], flags, format, scan);
+  });
   return hipGetLastError();
 }
 
@@ -448,19 +647,21 @@ hipError_t launch_scatter_cell_leaves(const uint32_t* flags, size_t n, const uin
   return hipGetLastError();
 }
 
-hipError_t launch_gather_leaves(const float* density, const float* albedo, const uint32_t res[3], const uint32_t ln[3],
+hipError_t launch_gather_leaves(const VoxelSource& v, bool with_albedo, const uint32_t res[3], const uint32_t ln[3],
                                 const uint32_t* slot_leaf, size_t n_leaves, const float bg[4], uint32_t format,
                                 void* leaf_density, void* leaf_albedo, MedScan* check, hipStream_t s) {
   const size_t np = n_leaves * 512;
   if (np == 0) return hipSuccess;
   const float4 b = make_float4(bg[0], bg[1], bg[2], bg[3]);
-  const float4* A = reinterpret_cast<const float4*>(albedo);
-  if (check)
-    hipLaunchKernelGGL(k_gather_leaves<false>, dim3(stream_grid(np)), dim3(256), 0, s, density, A, res[0], res[1],
-                       res[2], ln[0], ln[1], slot_leaf, np, b, format, nullptr, nullptr, check);
-  else
-    hipLaunchKernelGGL(k_gather_leaves<true>, dim3(stream_grid(np)), dim3(256), 0, s, density, A, res[0], res[1],
-                       res[2], ln[0], ln[1], slot_leaf, np, b, format, leaf_density, leaf_albedo, nullptr);
+  with_source(v, with_albedo, [&](auto src, size_t lds) {
+    using Src = decltype(src);
+    if (check)
+      hipLaunchKernelGGL((k_gather_leaves<Src, false>), dim3(stream_grid(np)), dim3(256), lds, s, src, res[0], res[1],
+                         res[2], ln[0], ln[1], slot_leaf, np, b, format, nullptr, nullptr, check);
+    else
+      hipLaunchKernelGGL((k_gather_leaves<Src, true>), dim3(stream_grid(np)), dim3(256), lds, s, src, res[0], res[1],
+                         res[2], ln[0], ln[1], slot_leaf, np, b, format, leaf_density, leaf_albedo, nullptr);
+  });
   return hipGetLastError();
 }
 

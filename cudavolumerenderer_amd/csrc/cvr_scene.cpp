@@ -31,11 +31,20 @@ static void tf_ramp(std::vector<float>& tf, const float (&a)[3], const float (&b
   }
 }
 
+// The one Raw table: 100 entries (r, g, b, 1); cvr_raw_transfer_table hands it out
+static const std::vector<float>& raw_transfer_table() {
+  static const std::vector<float> table = [] {
+    static const float green[3] = {0.02f, 0.2f, 0.02f}, red[3] = {1.F, 0.02f, 0.02f}, blue[3] = {0.F, 0.02f, 1.F};
+    std::vector<float> tf;
+    tf_ramp(tf, green, red, 20);
+    tf_ramp(tf, red, blue, 80);
+    return tf;
+  }();
+  return table;
+}
+
 static std::vector<float> raw_transfer_albedo(const std::vector<float>& density) {
-  static const float green[3] = {0.02f, 0.2f, 0.02f}, red[3] = {1.F, 0.02f, 0.02f}, blue[3] = {0.F, 0.02f, 1.F};
-  std::vector<float> tf;
-  tf_ramp(tf, green, red, 20);
-  tf_ramp(tf, red, blue, 80);
+  const std::vector<float>& tf = raw_transfer_table();
   const float last = (float)(tf.size() / 4 - 1);
   std::vector<float> albedo(density.size() * 4);
   for (size_t i = 0; i < density.size(); ++i)
@@ -546,6 +555,13 @@ int cvr_scene_is_sparse(const cvr_scene* s) { return s && s->sparse_only ? 1 : 0
 int cvr_scene_camera(const cvr_scene* s, uint32_t w, uint32_t h, float inv_view[12], float r2v[2]) {
   if (!s || !inv_view || !r2v || w == 0 || h == 0) return CVR_ERR_INVALID;
   cvr::camera_for_fov(s->fov_x, w, h, inv_view, r2v);
+  return CVR_OK;
+}
+
+int cvr_raw_transfer_table(float out[400]) {
+  if (!out) return CVR_ERR_INVALID;
+  const std::vector<float>& tf = cvr::raw_transfer_table();
+  memcpy(out, tf.data(), tf.size() * sizeof(float));
   return CVR_OK;
 }
 

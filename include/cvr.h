@@ -30,6 +30,9 @@ extern "C" {
  *              6 + CVR_HAS_DENOISE (no new number, an addition within 6): cvr_denoise_desc, cvr_denoise*
  *              6 + CVR_HAS_DEVICE_MEDIUM (likewise): cvr_device_medium_desc, cvr_set_medium_device,
  *                  cvr_medium_layout
+ *              6 + CVR_HAS_TRANSFER (likewise): cvr_transfer_desc, cvr_scalar_medium_desc,
+ *                  cvr_classify_host, cvr_raw_transfer_table, cvr_set_medium_scalar,
+ *                  cvr_set_medium_scene_transfer
  * CVR_ABI_VERSION is the ABI this header declares: 6, the library's (cvr_abi_version()).  ABI 6 only
  * adds to ABI 5, so a host that must also load an ABI 5 library can hold itself to that surface:
  * with CVR_ABI_TARGET defined as 5 before the include, the ABI 6 functions and structs are not
@@ -714,7 +717,7 @@ typedef struct cvr_device_medium_desc {
 } cvr_device_medium_desc; /* 96 bytes */
 int cvr_set_medium_device(cvr_ctx* ctx, const cvr_device_medium_desc* medium);
 /* Measurement only: with CVR_OPT_TIMING 1, the device milliseconds (HIP events) the last
- * cvr_set_medium_device spent in {density scan, albedo scan, leaf flags, scans and scatters,
+ * cvr_set_medium_device or cvr_set_medium_scalar spent in {density scan, albedo scan, leaf flags, scans and scatters,
  * copy / conversion / gather, cells + bounds + brick words}; zeros otherwise.  Timing adds a host
  * synchronisation per group. */
 int cvr_debug_device_medium_ms(const cvr_ctx* ctx, double out_ms[6]);
@@ -727,6 +730,90 @@ struct cvr_medium_layout {
   uint32_t mask[64];
 };
 int cvr_medium_layout(const cvr_ctx* ctx, struct cvr_medium_layout* out);
+
+/* ---- transfer functions: scalar volumes classified on the device (extension within ABI 6:
+ *      CVR_HAS_TRANSFER) -- */
+/* A scalar field (u8, u16, i16 or f32) and a table of n entries (r, g, b, density) give every
+ * voxel a density and an albedo.  Every operation is fp32 +, -, x, /, floorf, ceilf and
+ * comparisons in the order written here, no fused multiply-add, so the build kernels and
+ * cvr_classify_host return the same bits (one definition compiles for both, cvr_kernels.h).
+ * Per voxel:
+ *   s = the voxel converted to float (exact for the integer types);
+ *   t = (s - lo) / (hi - lo);
+ *   u = t > 0 ? t : 0, then u = u < 1 ? u : 1 (a NaN scalar so gives 0);
+ *   x = u * (float)(n - 1);
+ *   with CVR_TF_CEIL:  i = min((uint)ceilf(x), n - 1), e = entry i;
+ *   otherwise:         i = min((uint)floorf(x), n - 2), f = x - (float)i,
+ *                      e_c = a_c + f * (b_c - a_c) per component c of r, g, b, density, a = entry i,
+ *                      b = entry i + 1 (one subtract, one multiply, one add, in that order);
+ *   albedo = (e_r, e_g, e_b, 1.0f);
+ *   density = u with CVR_TF_DENSITY_U, else e's density.
+ * The reference's Raw scenes (RawSceneBuilder.h:95-140) are cvr_raw_transfer_table() with
+ * CVR_TF_CEIL | CVR_TF_DENSITY_U, lo 0 and hi the largest byte.
+ * A descriptor is refused (CVR_ERR_INVALID) for n outside 2..4096, unknown flags, a NULL table,
+ * lo or hi not finite, or hi <= lo. */
+#define CVR_HAS_TRANSFER 1
+enum { CVR_SCALAR_F32 = 0, CVR_SCALAR_U8 = 1, CVR_SCALAR_U16 = 2, CVR_SCALAR_I16 = 3 };
+enum { CVR_TF_CEIL = 1,        /* entry ceil(x) instead of linear interpolation (the Raw scenes' rule) */
+       CVR_TF_DENSITY_U = 2 }; /* density = u, the normalised scalar, not the table's w */
+typedef struct cvr_transfer_desc {
+  uint32_t n;         /* table entries, 2..4096 */
+  uint32_t flags;
+  const float* table; /* HOST, n * 4 floats: (r, g, b, density) */
+  float lo, hi;       /* finite, hi > lo */
+} cvr_transfer_desc; /* 24 bytes */
+/* Host only, no GPU: the statement above over n_voxels voxels of `scalar` (host memory of type
+ * scalar_type).  density (n_voxels floats) and albedo (4 * n_voxels floats) may each be NULL. */
+int cvr_classify_host(const void* scalar, uint32_t scalar_type, size_t n_voxels, const cvr_transfer_desc* transfer,
+                      float* density, float* albedo);
+/* Host only: the reference's 100-entry Raw table, green -> red over 20 entries, then red -> blue
+ * over 80, each with density 1 (Raw scenes take their density from u); the one table the Raw
+ * loader classifies with. */
+int cvr_raw_transfer_table(float out[400]);
+/* The medium from a scalar field in device memory and a table: density and albedo are computed
+ * per voxel inside the build kernels and written straight into the context's storage, fp32 or
+ * binary16; no dense array of the classified medium exists outside the context.
+ * The context ends in the state cvr_set_medium_device leaves on device copies of the arrays
+ * cvr_classify_host makes of the same scalar field and table, with the same flags, box and
+ * parameters, and so, through that call's contract, in the state the host uploads leave: equal
+ * cvr_medium_info and cvr_medium_layout, the same paths bit for bit, in both medium formats, dense
+ * and sparse.  Everything that call derives from values is derived from the classified values:
+ * the majorant (CVR_DEVMED_MAX_DENSITY), the binary16 overflow refusal with its code and message
+ * (density before albedo, the smallest index; the context is left without a medium), uniform-albedo
+ * detection, the leaf rule with voxel (0,0,0)'s classified albedo as background, and dropping the
+ * leaf albedo pool.
+ * flags: CVR_DEVMED_SPARSE and / or CVR_DEVMED_MAX_DENSITY.  d_scalar: res product elements, x
+ * fastest, aligned to its element size only.
+ * Refusals, in this order: the host call's shape guards, from res alone and before any pointer is
+ * looked at; unknown flags (CVR_DEVMED_CONST_ALBEDO is one here) or scalar_type; n outside
+ * 2..4096; a NULL table or d_scalar; lo / hi not finite or hi <= lo; a d_scalar that is not
+ * device-accessible memory of the context's device or is misaligned for its type.  All are
+ * CVR_ERR_INVALID with the previous medium kept.  Inside an adaptive session: CVR_ERR_STATE.
+ * Synchronous on the context's stream; the scalar field is only read (dense: at most twice, one
+ * scan and one store; sparse: once for the leaf flags, a pass that also finds the scans' results,
+ * and once in the gather; a binary16 overflow reads the stored leaves' voxels once more to name
+ * its index) and may be freed afterwards;
+ * the context does not keep it: changing the table means calling again with the same field.
+ * cvr_debug_device_medium_ms reports this call's groups too (the one scan under "density scan",
+ * the store under "copy / conversion / gather"). */
+typedef struct cvr_scalar_medium_desc {
+  uint32_t res[3];
+  uint32_t flags;
+  const void* d_scalar; /* device, res product elements of scalar_type, x fastest, contiguous */
+  uint32_t scalar_type; /* CVR_SCALAR_* */
+  uint32_t reserved;    /* 0 */
+  cvr_transfer_desc transfer;
+  float box_min[3], box_max[3];
+  float scale, max_density, g, roughness[2], eta;
+} cvr_scalar_medium_desc; /* 104 bytes */
+int cvr_set_medium_scalar(cvr_ctx* ctx, const cvr_scalar_medium_desc* medium);
+/* cvr_set_medium_scalar on a Raw scene's bytes (cvr_scene_raw_bytes, one byte per voxel): they
+ * are uploaded to a temporary device buffer, classified as CVR_SCALAR_U8 with lo 0 and hi the
+ * largest byte (transfer's lo and hi are ignored), and the buffer is freed.  The box, scale and
+ * BSDF parameters are the scene's; max_density is found on the device (flags: CVR_DEVMED_SPARSE
+ * or 0).  A scene without raw bytes: CVR_ERR_INVALID. */
+int cvr_set_medium_scene_transfer(cvr_ctx* ctx, const cvr_scene* scene, const cvr_transfer_desc* transfer,
+                                  uint32_t flags);
 #endif /* CVR_ABI_VERSION >= 6 */
 
 /* Pinned, device-mapped host memory for cvr_render_share_to_host /
