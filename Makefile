@@ -12,8 +12,8 @@ HIPFLAGS := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -ffp-contract=off \
             -fhip-fp32-correctly-rounded-divide-sqrt -Iinclude -I$(CSRC) -Wall
 OBJDIR ?= build/obj
 SRCS_HIP := $(CSRC)/cvr_kernels.hip $(CSRC)/cvr_persistent.hip $(CSRC)/cvr_pool.hip $(CSRC)/cvr_wpool.hip $(CSRC)/cvr_wavefront.hip \
-            $(CSRC)/cvr_denoise.hip $(CSRC)/cvr_medium_build.hip
-SRCS_CPP := $(CSRC)/cvr_api.cpp $(CSRC)/cvr_medium.cpp $(CSRC)/cvr_scene.cpp $(CSRC)/cvr_vdb.cpp $(CSRC)/cvr_mhd.cpp $(CSRC)/cvr_xml.cpp
+            $(CSRC)/cvr_denoise.hip $(CSRC)/cvr_medium_build.hip $(CSRC)/cvr_env.hip
+SRCS_CPP := $(CSRC)/cvr_api.cpp $(CSRC)/cvr_medium.cpp $(CSRC)/cvr_environment.cpp $(CSRC)/cvr_image_io.cpp $(CSRC)/cvr_scene.cpp $(CSRC)/cvr_vdb.cpp $(CSRC)/cvr_mhd.cpp $(CSRC)/cvr_xml.cpp
 OBJS := $(patsubst $(CSRC)/%.hip,$(OBJDIR)/%.o,$(SRCS_HIP)) $(patsubst $(CSRC)/%.cpp,$(OBJDIR)/%.o,$(SRCS_CPP))
 HDRS := include/cvr.h include/cvr_detmath.h $(wildcard $(CSRC)/*.h)
 # Per-file flags, HIPFLAGS_<file name without .hip>; every rule that compiles a .hip file goes through
@@ -27,7 +27,7 @@ HDRS := include/cvr.h include/cvr_detmath.h $(wildcard $(CSRC)/*.h)
 HIPFLAGS_cvr_wpool := -fno-slp-vectorize
 hipflags = $(HIPFLAGS) $(HIPFLAGS_$(basename $(notdir $(1)))) $(DEFS)
 
-all: $(PKG)/libcvr.so $(PKG)/cvr build/launcher_order build/wpool_select oracle
+all: $(PKG)/libcvr.so $(PKG)/cvr build/launcher_order build/wpool_select build/wpool_select_env oracle
 
 $(OBJDIR)/%.o: $(CSRC)/%.hip $(HDRS)
 	@mkdir -p $(OBJDIR)
@@ -53,6 +53,10 @@ build/launcher_order: tests/cpp/launcher_order.cpp include/cvr_launcher.hpp incl
 # Host-only C++ test: the wave pool's instance selection over its whole request space
 # (tests/test_wpool_select.py); no HIP.
 build/wpool_select: tests/cpp/wpool_select.cpp $(CSRC)/cvr_wpool_select.h
+	@mkdir -p build
+	g++ -O2 -std=c++17 -Wall -Wextra -I$(CSRC) -o $@ $<
+# The same over the environment half of the space (tests/test_wpool_select_env.py)
+build/wpool_select_env: tests/cpp/wpool_select_env.cpp $(CSRC)/cvr_wpool_select.h
 	@mkdir -p build
 	g++ -O2 -std=c++17 -Wall -Wextra -I$(CSRC) -o $@ $<
 

@@ -14,6 +14,8 @@ from ._lib import (  # noqa: F401
     DeviceMediumDesc, MediumLayout, DEVMED_SPARSE, DEVMED_CONST_ALBEDO, DEVMED_MAX_DENSITY,
     TransferDesc, ScalarMediumDesc, classify_host, raw_transfer_table,
     SCALAR_F32, SCALAR_U8, SCALAR_U16, SCALAR_I16, TF_CEIL, TF_DENSITY_U,
+    EnvironmentDesc, EnvironmentInfo, ENV_HOST, ENV_DEVICE, ENV_RECORD_DTYPE, environment_eval_host,
+    environment_eval_host_fn, read_image, rotation_y,
     PATH_RECORD_DTYPE, CvrError, Context, MediumDesc, PinnedImage, Scene, Stats, default_camera, load,
     medium_from_arrays, tile_origin, tiling, write_hdr, LIB_PATH,
 )
@@ -27,4 +29,6 @@ __all__ = [
     "DeviceMediumDesc", "MediumLayout", "DEVMED_SPARSE", "DEVMED_CONST_ALBEDO", "DEVMED_MAX_DENSITY",
     "TransferDesc", "ScalarMediumDesc", "classify_host", "raw_transfer_table",
     "SCALAR_F32", "SCALAR_U8", "SCALAR_U16", "SCALAR_I16", "TF_CEIL", "TF_DENSITY_U",
+    "EnvironmentDesc", "EnvironmentInfo", "ENV_HOST", "ENV_DEVICE", "ENV_RECORD_DTYPE", "environment_eval_host",
+    "environment_eval_host_fn", "read_image", "rotation_y",
 ]

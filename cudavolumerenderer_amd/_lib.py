@@ -8,6 +8,7 @@ raises.
 from __future__ import annotations
 
 import ctypes as C
+import math
 import os
 from typing import Optional, Sequence
 
@@ -178,6 +179,36 @@ class MediumLayout(C.Structure):
                 for k, _ in self._fields_}
 
 
+ENV_HOST, ENV_DEVICE = 0, 1
+
+
+class EnvironmentDesc(C.Structure):
+    """cvr_environment_desc: a latitude-longitude map of width x height texels of 3 or 4 floats in
+    host or device memory, its scale and its world-to-environment rotation (all zero: identity)."""
+    _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("channels", C.c_uint32),
+                ("location", C.c_uint32), ("pixels", C.c_void_p), ("scale", C.c_float),
+                ("rotation", C.c_float * 9)]
+
+
+class EnvironmentInfo(C.Structure):
+    """cvr_environment_info: the stored map's size (0 x 0: none), device bytes and largest component."""
+    _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("bytes", C.c_uint64),
+                ("max_component", C.c_float), ("reserved", C.c_uint32)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
+
+
+class EnvRecord(C.Structure):
+    _fields_ = [("image_id", C.c_uint32), ("flags", C.c_uint32), ("n_segments", C.c_uint32),
+                ("T", C.c_float * 3), ("d", C.c_float * 3), ("C", C.c_float * 3)]
+
+
+ENV_RECORD_DTYPE = np.dtype([("image_id", "<u4"), ("flags", "<u4"), ("n_segments", "<u4"), ("T", "<f4", (3,)),
+                             ("d", "<f4", (3,)), ("C", "<f4", (3,))])
+assert ENV_RECORD_DTYPE.itemsize == C.sizeof(EnvRecord) == 48
+TEXEL_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_float))
+
 _lib = None
 
 
@@ -270,6 +301,15 @@ def load() -> C.CDLL:
         "cvr_raw_transfer_table": (I32, [FP]),
         "cvr_set_medium_scalar": (I32, [P, C.POINTER(ScalarMediumDesc)]),
         "cvr_set_medium_scene_transfer": (I32, [P, P, C.POINTER(TransferDesc), U32]),
+        "cvr_set_environment": (I32, [P, C.POINTER(EnvironmentDesc)]),
+        "cvr_clear_environment": (I32, [P]),
+        "cvr_environment_info": (I32, [P, C.POINTER(EnvironmentInfo)]),
+        "cvr_environment_eval_host": (I32, [C.POINTER(EnvironmentDesc), FP, C.c_size_t, FP]),
+        "cvr_environment_eval_host_fn": (I32, [U32, U32, FP, TEXEL_FN, P, FP, C.c_size_t, FP]),
+        "cvr_environment_eval": (I32, [P, FP, C.c_size_t, FP]),
+        "cvr_trace_env": (I32, [P, U32, U32, C.POINTER(EnvRecord)]),
+        "cvr_read_image": (I32, [C.c_char_p, C.POINTER(U32), C.POINTER(U32), C.POINTER(FP)]),
+        "cvr_free_image": (None, [FP]),
     }
     # an older experiment build (tools' --lib, A/B against a previous commit) may lack newer entry
     # points; the in-tree library must export every one (tests/test_host_abi.py)
@@ -378,6 +418,73 @@ def raw_transfer_table() -> np.ndarray:
     out = np.empty((100, 4), np.float32)
     _check(load().cvr_raw_transfer_table(_fp(out)))
     return out
+
+
+def _rotation9(rotation):
+    """9 floats, row-major world-to-environment; None: zeros, which the library reads as identity."""
+    if rotation is None:
+        return np.zeros(9, np.float32)
+    r = np.ascontiguousarray(rotation, dtype=np.float32).reshape(-1)
+    if r.size != 9:
+        raise ValueError(f"rotation: {r.size} floats, expected 9 (3 x 3, row-major)")
+    return r
+
+
+def rotation_y(degrees: float) -> np.ndarray:
+    """The world-to-environment rotation that turns the map by `degrees` about +Y (the CLI's
+    --env-rotate-y): (3, 3) float32, computed in fp64 and rounded once."""
+    a = float(degrees) * (math.pi / 180.0)
+    c, s = math.cos(a), math.sin(a)
+    return np.array([[c, 0.0, -s], [0.0, 1.0, 0.0], [s, 0.0, c]], np.float64).astype(np.float32)
+
+
+def _dirs3(dirs):
+    d = np.ascontiguousarray(dirs, dtype=np.float32)
+    if d.ndim != 2 or d.shape[1] != 3:
+        raise ValueError(f"dirs: shape {d.shape}, expected (n, 3)")
+    return d
+
+
+def environment_eval_host(image, dirs, scale: float = 1.0, rotation=None) -> np.ndarray:
+    """The environment lookup's written statement on the CPU (cvr_environment_eval_host; no GPU):
+    image (H, W, 3|4) float32, row 0 the top; dirs (n, 3) -> (n, 3) radiance.
+    Context.environment_eval and the render kernels compute the same bits."""
+    img = np.ascontiguousarray(image, dtype=np.float32)
+    if img.ndim != 3:
+        raise ValueError(f"image: shape {img.shape}, expected (H, W, 3|4)")
+    d = _dirs3(dirs)
+    desc = EnvironmentDesc(img.shape[1], img.shape[0], img.shape[2], ENV_HOST, img.ctypes.data, scale)
+    desc.rotation[:] = _rotation9(rotation).tolist()
+    out = np.empty_like(d)
+    _check(load().cvr_environment_eval_host(C.byref(desc), _fp(d), d.shape[0], _fp(out)))
+    return out
+
+
+def environment_eval_host_fn(width: int, height: int, texel, dirs, rotation=None) -> np.ndarray:
+    """The same statement with the stored texels behind a callback, texel(x, y) -> (r, g, b), for
+    maps too large to hold on the host (cvr_environment_eval_host_fn; no scale is applied)."""
+    d = _dirs3(dirs)
+
+    def cb(_user, x, y, rgba):
+        v = texel(x, y)
+        rgba[0], rgba[1], rgba[2] = float(v[0]), float(v[1]), float(v[2])
+
+    r = None if rotation is None else _rotation9(rotation)
+    out = np.empty_like(d)
+    _check(load().cvr_environment_eval_host_fn(width, height, None if r is None else _fp(r), TEXEL_FN(cb), None,
+                                               _fp(d), d.shape[0], _fp(out)))
+    return out
+
+
+def read_image(path: str) -> np.ndarray:
+    """A Radiance .hdr or colour .pfm file as (H, W, 3) float32, row 0 the top (cvr_read_image)."""
+    w, h = C.c_uint32(), C.c_uint32()
+    p = C.POINTER(C.c_float)()
+    _check(load().cvr_read_image(os.fsencode(path), C.byref(w), C.byref(h), C.byref(p)))
+    try:
+        return np.ctypeslib.as_array(p, shape=(h.value, w.value, 3)).copy()
+    finally:
+        load().cvr_free_image(p)
 
 
 def _device_ptr(a):
@@ -701,6 +808,60 @@ class Context:
             import torch
             torch.cuda.current_stream(self.device).synchronize()
         self._c(load().cvr_set_medium_scalar(self._h, C.byref(d)))
+
+    def set_environment(self, image, scale: float = 1.0, rotation=None):
+        """Light the scene with a latitude-longitude map (cvr_set_environment): an escaping path adds
+        its throughput times the map's radiance in its direction.  image: a numpy (H, W, 3|4)
+        float32 array (row 0 the top), or an object with data_ptr() of that shape (a torch tensor on
+        the context's device, contiguous: checked here, ValueError), which is converted on the
+        device with no host copy.  scale multiplies every component; rotation: 9 floats, row-major
+        world-to-environment (None: identity).  The context keeps its own copy."""
+        d = EnvironmentDesc()
+        if hasattr(image, "data_ptr"):
+            shape = tuple(int(v) for v in image.shape)
+            if len(shape) != 3:
+                raise ValueError(f"image: shape {shape}, expected (H, W, 3|4)")
+            _check_device_grid("image", image, shape, self.device)
+            keep, d.location, d.pixels = image, ENV_DEVICE, _device_ptr(image)
+            if type(image).__module__.split(".")[0] == "torch":
+                import torch
+                torch.cuda.current_stream(self.device).synchronize()
+        else:
+            keep = np.ascontiguousarray(image, dtype=np.float32)
+            shape = keep.shape
+            if keep.ndim != 3:
+                raise ValueError(f"image: shape {shape}, expected (H, W, 3|4)")
+            d.location, d.pixels = ENV_HOST, keep.ctypes.data
+        d.height, d.width, d.channels = shape
+        d.scale = scale
+        d.rotation[:] = _rotation9(rotation).tolist()
+        self._c(load().cvr_set_environment(self._h, C.byref(d)))
+        del keep
+
+    def clear_environment(self):
+        """Back to the constant environment of radiance 1 (cvr_clear_environment)."""
+        self._c(load().cvr_clear_environment(self._h))
+
+    def environment_info(self) -> EnvironmentInfo:
+        """The stored map's width, height, device bytes and largest component (0 x 0: none)."""
+        out = EnvironmentInfo()
+        self._c(load().cvr_environment_info(self._h, C.byref(out)))
+        return out
+
+    def environment_eval(self, dirs) -> np.ndarray:
+        """The device's lookup of the context's environment for dirs (n, 3) -> (n, 3)
+        (cvr_environment_eval): the same bits as environment_eval_host."""
+        d = _dirs3(dirs)
+        out = np.empty_like(d)
+        self._c(load().cvr_environment_eval(self._h, _fp(d), d.shape[0], _fp(out)))
+        return out
+
+    def trace_env(self, first: int, count: int) -> np.ndarray:
+        """trace_paths' walk with the environment applied (cvr_trace_env): records of image_id, flags,
+        n_segments, T (before the environment), d (at escape) and C = T * L(d)."""
+        out = np.zeros(count, ENV_RECORD_DTYPE)
+        self._c(load().cvr_trace_env(self._h, first, count, out.ctypes.data_as(C.POINTER(EnvRecord))))
+        return out
 
     def medium_layout(self) -> MediumLayout:
         """What the upload built (cvr_medium_layout): sparse or dense, uniform albedo and its value,

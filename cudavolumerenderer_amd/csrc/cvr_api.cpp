@@ -113,7 +113,7 @@ cvr::WpoolRequest wpool_request(const cvr_ctx* c, bool record, bool flush) {
   const bool sparse = c->m.leaves != nullptr;
   return {scatter_eps_for(c), wpool_waves_for(c), sparse, !sparse && c->m.cells && c->m.bounds,
           c->m.albedo_uniform != 0u, c->m.format != 0u, c->kernel == CVR_KERNEL_NAIVE_MK, c->count_words != 0,
-          c->moments != 0, record, flush};
+          c->moments != 0, record, flush, c->have_env};
 }
 // The generic instance of a layout at the context's budget (never refused): do_init's grids, every such instance's wpg.
 cvr::WpoolInstance wpool_generic(const cvr_ctx* c, bool sparse) {
@@ -131,18 +131,19 @@ bool mk_on_wpool(const cvr_ctx* c) {
          cvr::wpool_select({true, wpool_waves_for(c), false, false, false, false, /*naive_mk*/ true}, &k);
 }
 
-// What the context has that the half-format (kForHalf) or the moments instances (kForMoments: generic dense / fp32
-// sparse layout) do not run with: the first entry of the feature's that holds, or null.
-enum : unsigned { kForHalf = 1, kForMoments = 2, kForBoth = 3 };
+// What the context has that the half-format (kForHalf), the moments instances (kForMoments: generic dense / fp32
+// sparse layout) or the environment instances (kForEnv) do not run with: the first entry of the feature's that
+// holds, or null.
+enum : unsigned { kForHalf = 1, kForMoments = 2, kForEnv = 4, kForAll = 7 };
 const char* wpool_refusal(const cvr_ctx* c, unsigned feature) {
   const struct { unsigned features; bool holds; const char* text; } list[] = {
       {kForMoments, c->external_out, "a caller's output buffer (cvr_set_output)"},
-      {kForMoments, c->kernel == CVR_KERNEL_NAIVE_MK, "kernel id naiveMK"},
-      {kForBoth, c->rng_binding != 0, "CVR_OPT_RNG_BINDING 1"},
-      {kForBoth, scheduler_for(c) != 3, "a scheduler other than the wave pool (CVR_OPT_SCHEDULER 3)"},
-      {kForBoth, wpool_waves_for(c) != cvr::kWpoolWaves, "CVR_OPT_WAVES other than 5"},
-      {kForBoth, c->mk_compaction != 0, "CVR_OPT_MK_COMPACTION 1"},
-      {kForBoth, c->count_words != 0, "CVR_OPT_COUNT_WORDS 1"},
+      {kForMoments | kForEnv, c->kernel == CVR_KERNEL_NAIVE_MK, "kernel id naiveMK"},
+      {kForAll, c->rng_binding != 0, "CVR_OPT_RNG_BINDING 1"},
+      {kForAll, scheduler_for(c) != 3, "a scheduler other than the wave pool (CVR_OPT_SCHEDULER 3)"},
+      {kForAll, wpool_waves_for(c) != cvr::kWpoolWaves, "CVR_OPT_WAVES other than 5"},
+      {kForAll, c->mk_compaction != 0, "CVR_OPT_MK_COMPACTION 1"},
+      {kForAll, c->count_words != 0, "CVR_OPT_COUNT_WORDS 1"},
       {kForMoments, c->m.leaves && c->m.format != 0u, "a sparse half medium"},
   };
   for (const auto& e : list)
@@ -634,6 +635,7 @@ int cvr_destroy(cvr_ctx* c) {
   if (c->stream) (void)hipStreamSynchronize(c->stream);
   cvr::drop_dense(c);
   cvr::free_sparse(c);
+  cvr::free_environment(c);
   if (c->d_out_owned) (void)hipFree(c->d_out_owned);
   if (c->d_work) (void)hipFree(c->d_work);
   if (c->d_pool_T) (void)hipFree(c->d_pool_T);
@@ -1075,6 +1077,14 @@ int cvr_launch_render(cvr_ctx* c) {
     if (c->out_owned_px < 2 * (size_t)c->tile_w * c->tile_h || c->d_out != c->d_out_owned)
       return set_err(&c->err, CVR_ERR_STATE, "the framebuffer holds no moments (cvr_set_resolution)");
   }
+  if (c->have_env) {
+    // an environment map: the wave pool's environment instances only
+    const char* why = wpool_refusal(c, kForEnv);
+    if (!why && c->d_rec_active) why = "cvr_trace_launch";
+    if (!why && c->frame_done_active) why = "cvr_render_frame's in-launch output";
+    if (why)
+      return set_err(&c->err, CVR_ERR_UNSUPPORTED, "an environment map (cvr_set_environment) does not run with %s", why);
+  }
   // a range as the caller gave it (count UINT64_MAX: to the end) names u32 path ids; past the
   // tile's n_paths it is clipped, past 2^32 - 1 it is a mistake
   if (c->range_count != UINT64_MAX &&
@@ -1176,7 +1186,8 @@ int cvr_launch_render(cvr_ctx* c) {
       c->pool_T_n = need;
     }
     L.pool_T = c->d_pool_T;
-    L.rec = c->d_rec_active;
+    // (an environment instance has no records: the field carries the map's header instead)
+    L.rec = c->have_env ? static_cast<void*>(c->d_env_hdr) : c->d_rec_active;
     if (c->frame_done_active) {
       // in-launch output: the first kFrameFlushers workgroups flush, the rest render
       if (L.rec || L.order != 1 || grid <= 4 * cvr::kFrameFlushers)
@@ -1365,6 +1376,9 @@ int cvr_trace_launch(cvr_ctx* c, cvr_path_record* out, uint64_t n_out) {
   CVR_NOT_IN_SESSION(c, "cvr_trace_launch");
   if (c->moments && !c->ad.internal)
     return set_err(&c->err, CVR_ERR_UNSUPPORTED, "second moments (CVR_OPT_MOMENTS 1) do not run with cvr_trace_launch");
+  if (c->have_env)
+    return set_err(&c->err, CVR_ERR_UNSUPPORTED,
+                   "an environment map (cvr_set_environment) does not run with cvr_trace_launch");
   int r = check_ready(c);
   if (r) return r;
   if ((r = do_init(c))) return r;
@@ -1432,6 +1446,28 @@ int cvr_trace_paths(cvr_ctx* c, uint32_t first, uint32_t count, cvr_path_record*
   if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
   if (e == hipSuccess)
     e = hipMemcpy(out, d_rec, (size_t)count * sizeof(cvr::PathRecord), hipMemcpyDeviceToHost);
+  (void)hipFree(d_rec);
+  if (e != hipSuccess) return set_err(&c->err, CVR_ERR_HIP, "trace: %s", hipGetErrorString(e));
+  return CVR_OK;
+}
+
+int cvr_trace_env(cvr_ctx* c, uint32_t first, uint32_t count, cvr_env_record* out) {
+  static_assert(sizeof(cvr_env_record) == sizeof(cvr::EnvRecord) && sizeof(cvr_env_record) == 48, "record layouts");
+  if (!c || !out) return set_err(c ? &c->err : nullptr, CVR_ERR_INVALID, "NULL argument");
+  CVR_NOT_IN_SESSION(c, "cvr_trace_env");
+  int r = check_ready(c);
+  if (r) return r;
+  if (!c->have_env) return set_err(&c->err, CVR_ERR_STATE, "no environment (cvr_set_environment)");
+  if (c->kernel == CVR_KERNEL_NAIVE_MK)
+    return set_err(&c->err, CVR_ERR_UNSUPPORTED, "an environment map (cvr_set_environment) does not run with kernel id naiveMK");
+  if (count == 0) return CVR_OK;
+  cvr::LaunchParams L{};
+  fill_launch(c, L, first, count, /*sharded=*/false);
+  cvr::EnvRecord* d_rec = nullptr;
+  HIP_TRY(c, hipMalloc(&d_rec, (size_t)count * sizeof(cvr::EnvRecord)));
+  hipError_t e = cvr::launch_trace_env(launch_medium(c), L, scatter_eps_for(c), c->d_env_hdr, d_rec, c->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+  if (e == hipSuccess) e = hipMemcpy(out, d_rec, (size_t)count * sizeof(cvr::EnvRecord), hipMemcpyDeviceToHost);
   (void)hipFree(d_rec);
   if (e != hipSuccess) return set_err(&c->err, CVR_ERR_HIP, "trace: %s", hipGetErrorString(e));
   return CVR_OK;
@@ -1754,6 +1790,7 @@ int cvr_render_frame(cvr_ctx* c, float* host_image, size_t host_floats, uint32_t
                       c->rng_binding == 0;
   const uint32_t brows = (L0.order == 1 && queued && c->shard_world == 1) ? H / 8u : 0u;
   if (parts == 0) parts = 1;
+  if (c->have_env) parts = 1;  // the environment is the context's own: no helper contexts (and no in-launch output)
   parts = std::min<uint32_t>(parts, 3u);
   if (brows < parts) parts = brows ? brows : 1u;
   // band k takes (parts - k) shares of the block rows: the last band, whose copy

@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "cvr.h"
+#include "cvr_env.h"
 #include "cvr_kernels.h"
 
 struct cvr_ctx {
@@ -174,6 +175,12 @@ struct cvr_ctx {
   // cvr_denoise*: the two scratch images the passes alternate between (dn_px pixels each)
   float4* d_dn = nullptr;
   size_t dn_px = 0;
+  // cvr_set_environment: the context's own stored texels, the header as the kernels read it
+  // (device memory, 64 bytes: LaunchParams::rec of the kMedEnv instances) and its host copy
+  bool have_env = false;
+  cvr::EnvParams env{};
+  cvr::EnvParams* d_env_hdr = nullptr;
+  float env_max = 0.0f;  // the largest stored component
 };
 
 namespace cvr {
@@ -183,6 +190,10 @@ int ensure_device(cvr_ctx* c);
 // The context's own medium buffers, freed and reset: the sparse medium's five, the dense medium's four grids.
 void free_sparse(cvr_ctx* c);
 void drop_dense(cvr_ctx* c);
+// p is memory the context's device can read, by what the runtime knows of it
+bool device_readable(const cvr_ctx* c, const void* p);
+// The context's environment map and its device header, freed and reset (cvr_environment.cpp)
+void free_environment(cvr_ctx* c);
 // f32 -> binary16 -> f32, round to nearest even, subnormals kept (CVR_OPT_MEDIUM_FORMAT 1)
 float half_round1(float f);
 // first finite value of v[0..n) (of every `stride`-th group's first `take` values) that rounds to +-inf

@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "cvr_env.h"
 #include "cvr_walk.h"
 #include "cvr_wpool_select.h"
 
@@ -51,6 +52,14 @@ hipError_t launch_persistent(const MediumParams& m, const LaunchParams& L, bool 
 hipError_t persistent_occupancy(bool scatter_eps, int waves, int* blocks_per_cu);
 hipError_t launch_trace(const MediumParams& m, const LaunchParams& L, bool scatter_eps, PathRecord* rec,
                         hipStream_t s);
+// cvr_trace_env: launch_trace's walk with the environment applied at the escape; layout identical to
+// cvr_env_record (include/cvr.h).  env: the map's header in device memory.
+struct EnvRecord {
+  uint32_t image_id, flags, n_segments;
+  float T[3], d[3], C[3];
+};
+hipError_t launch_trace_env(const MediumParams& m, const LaunchParams& L, bool scatter_eps, const EnvParams* env,
+                            EnvRecord* rec, hipStream_t s);
 hipError_t launch_pool(const MediumParams& m, const LaunchParams& L, bool scatter_eps, uint32_t grid, hipStream_t s);
 hipError_t pool_occupancy(bool scatter_eps, int* blocks_per_cu);
 // The wave pool: the instance wpool_select (cvr_wpool_select.h) gives for request q, which the

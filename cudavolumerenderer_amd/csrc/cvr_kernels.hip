@@ -173,35 +173,17 @@ __global__ __launch_bounds__(256) void k_mk_extend(MediumParams m, LaunchParams 
 }
 
 // --------------------------------------------------------------- trace ----
+// One path of the single-kernel walk (NaiveVolPTsk_kernel.cuh:22-84), start to end: ps ends as the
+// path ended (an escaped path's d is its direction at escape), r holds its record but T.
 template <bool kScatterEps>
-__global__ __launch_bounds__(256) void k_trace(MediumParams m, LaunchParams L, PathRecord* rec) {
-  const uint32_t tid = blockIdx.x * blockDim.x + threadIdx.x;
-  if (tid >= L.path_count) return;
-  if (L.naive_mk & 1u) {
-    const MkResult mr = walk_mk(m, L, L.path_first + tid);
-    PathRecord r = {};
-    r.image_id = (L.path_first + tid) % L.tile_px;
-    r.flags = mr.flags;
-    r.T[0] = mr.T.x;
-    r.T[1] = mr.T.y;
-    r.T[2] = mr.T.z;
-    r.n_segments = mr.n_segments;
-    r.n_steps = mr.n_steps;
-    r.n_density = mr.n_density;
-    r.n_albedo = mr.n_albedo;
-    rec[tid] = r;
-    if (mr.n_fetch) atomicAdd(L.stats + STAT_FETCH, (unsigned long long)mr.n_fetch);
-    return;
-  }
-  PathState ps;
-  path_begin(L, L.path_first + tid, ps);
+__device__ __forceinline__ void walk_sk(const MediumParams& m, const LaunchParams& L, uint32_t path_id, PathState& ps,
+                                        PathRecord& r, uint32_t& n_fetch) {
+  path_begin(L, path_id, ps);
   Isect is;
   is.dist = 0.0f;
   is.normal = mk3(0, 0, 0);
   is.inside = false;
-  PathRecord r = {};
   r.image_id = ps.image_id;
-  uint32_t n_fetch = 0;
   for (;;) {
     if (L.max_segments && r.n_segments >= L.max_segments) {
       r.flags |= 2u;
@@ -229,11 +211,69 @@ __global__ __launch_bounds__(256) void k_trace(MediumParams m, LaunchParams L, P
     }
     if (!roulette(ps)) break;
   }
+}
+
+template <bool kScatterEps>
+__global__ __launch_bounds__(256) void k_trace(MediumParams m, LaunchParams L, PathRecord* rec) {
+  const uint32_t tid = blockIdx.x * blockDim.x + threadIdx.x;
+  if (tid >= L.path_count) return;
+  if (L.naive_mk & 1u) {
+    const MkResult mr = walk_mk(m, L, L.path_first + tid);
+    PathRecord r = {};
+    r.image_id = (L.path_first + tid) % L.tile_px;
+    r.flags = mr.flags;
+    r.T[0] = mr.T.x;
+    r.T[1] = mr.T.y;
+    r.T[2] = mr.T.z;
+    r.n_segments = mr.n_segments;
+    r.n_steps = mr.n_steps;
+    r.n_density = mr.n_density;
+    r.n_albedo = mr.n_albedo;
+    rec[tid] = r;
+    if (mr.n_fetch) atomicAdd(L.stats + STAT_FETCH, (unsigned long long)mr.n_fetch);
+    return;
+  }
+  PathState ps;
+  PathRecord r = {};
+  uint32_t n_fetch = 0;
+  walk_sk<kScatterEps>(m, L, L.path_first + tid, ps, r, n_fetch);
   r.T[0] = ps.T.x;
   r.T[1] = ps.T.y;
   r.T[2] = ps.T.z;
   rec[tid] = r;
   if (n_fetch) atomicAdd(L.stats + STAT_FETCH, (unsigned long long)n_fetch);
+}
+
+// cvr_trace_env: the same walk, its record the path's end with the environment applied (EnvRecord =
+// cvr_env_record: T before the environment, d at escape, C = T (.) L(d); d and C zero otherwise).
+template <bool kScatterEps>
+__global__ __launch_bounds__(256) void k_trace_env(MediumParams m, LaunchParams L, const EnvParams* __restrict__ Ep,
+                                                   EnvRecord* __restrict__ rec) {
+  const uint32_t tid = blockIdx.x * blockDim.x + threadIdx.x;
+  if (tid >= L.path_count) return;
+  PathState ps;
+  PathRecord r = {};
+  uint32_t n_fetch = 0;
+  walk_sk<kScatterEps>(m, L, L.path_first + tid, ps, r, n_fetch);
+  EnvRecord o = {};
+  o.image_id = r.image_id;
+  o.flags = r.flags;
+  o.n_segments = r.n_segments;
+  o.T[0] = ps.T.x;
+  o.T[1] = ps.T.y;
+  o.T[2] = ps.T.z;
+  if (r.flags & 1u) {
+    const EnvParams E = *Ep;
+    float rgb[3];
+    env_lookup(E, ps.d.x, ps.d.y, ps.d.z, rgb);
+    o.d[0] = ps.d.x;
+    o.d[1] = ps.d.y;
+    o.d[2] = ps.d.z;
+    o.C[0] = ps.T.x * rgb[0];
+    o.C[1] = ps.T.y * rgb[1];
+    o.C[2] = ps.T.z * rgb[2];
+  }
+  rec[tid] = o;
 }
 
 // ------------------------------------------- thread-bound regenerationSK ---
@@ -967,6 +1007,17 @@ hipError_t launch_trace(const MediumParams& m, const LaunchParams& L, bool scatt
     hipLaunchKernelGGL(k_trace<true>, dim3(grid), dim3(256), 0, s, m, L, rec);
   else
     hipLaunchKernelGGL(k_trace<false>, dim3(grid), dim3(256), 0, s, m, L, rec);
+  return hipGetLastError();
+}
+
+hipError_t launch_trace_env(const MediumParams& m, const LaunchParams& L, bool scatter_eps, const EnvParams* env,
+                            EnvRecord* rec, hipStream_t s) {
+  if (L.path_count == 0) return hipSuccess;
+  const uint32_t grid = (L.path_count + 255u) / 256u;
+  if (scatter_eps)
+    hipLaunchKernelGGL(k_trace_env<true>, dim3(grid), dim3(256), 0, s, m, L, env, rec);
+  else
+    hipLaunchKernelGGL(k_trace_env<false>, dim3(grid), dim3(256), 0, s, m, L, env, rec);
   return hipGetLastError();
 }
 

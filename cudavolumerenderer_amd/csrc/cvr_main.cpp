@@ -42,6 +42,9 @@ struct Options {
   std::string devices;  // --devices: a count or a comma list of device ids
   std::string medium_format = "float";  // --medium-format
   std::string transfer_file, transfer_mode = "linear";  // --transfer, --transfer-mode
+  std::string envmap;  // --envmap FILE
+  float env_scale = 1.0f;
+  double env_rotate_y = 0.0;  // degrees
   bool pfm = false;
   bool adaptive = false;  // --noise-target given
   float noise_target = 0.0f;
@@ -88,6 +91,11 @@ void usage() {
       "                                     of 'r g b density' spanning byte 0 .. the largest byte, in place of\n"
       "                                     the reference's built-in table (cvr_set_medium_scalar)\n"
       "  --transfer-mode linear|ceil (=linear)  interpolate between table entries, or take entry ceil(x)\n"
+      "  --envmap FILE(.hdr|.pfm)           light the scene with a latitude-longitude environment map in place\n"
+      "                                     of the constant white one (cvr_set_environment; every device's\n"
+      "                                     context keeps a copy; not with naiveMK or --rng-binding thread)\n"
+      "  --env-scale F (=1)                 multiply the map's radiance by F (finite, >= 0)\n"
+      "  --env-rotate-y DEG (=0)            turn the map by DEG degrees about the +Y axis\n"
       "  --pfm                              also write the float image as <output>.pfm\n"
       "  --noise-target F                   adaptive render: sample every 8x8-pixel block until its relative\n"
       "                                     standard error (cvr_block_error, floor 0.01) is at most F, with\n"
@@ -152,6 +160,9 @@ int parse(int argc, char** argv, Options& o) {
     else if (a == "--medium-format") o.medium_format = need("medium-format");
     else if (a == "--transfer") o.transfer_file = need("transfer");
     else if (a == "--transfer-mode") o.transfer_mode = need("transfer-mode");
+    else if (a == "--envmap") o.envmap = need("envmap");
+    else if (a == "--env-scale") o.env_scale = strtof(need("env-scale").c_str(), nullptr);
+    else if (a == "--env-rotate-y") o.env_rotate_y = strtod(need("env-rotate-y").c_str(), nullptr);
     else if (a == "--pfm") o.pfm = true;
     else if (a == "--noise-target") {
       o.noise_target = strtof(need("noise-target").c_str(), nullptr);
@@ -340,6 +351,28 @@ int main(int argc, char** argv) {
     transfer.flags = o.transfer_mode == "ceil" ? CVR_TF_CEIL : 0;
     transfer.table = transfer_table.data();
   }
+  // --envmap: the file's texels and the descriptor every context takes its copy from
+  float* env_rgb = nullptr;
+  cvr_environment_desc env{};
+  if (!o.envmap.empty()) {
+    if ((r = cvr_read_image(o.envmap.c_str(), &env.width, &env.height, &env_rgb)) != CVR_OK) {
+      fprintf(stderr, "[ConfigParser] Error: --envmap: cannot read '%s' as a Radiance .hdr or a colour .pfm (%d)\n",
+              o.envmap.c_str(), r);
+      return 2;
+    }
+    env.channels = 3;
+    env.location = CVR_ENV_HOST;
+    env.pixels = env_rgb;
+    env.scale = o.env_scale;
+    if (o.env_rotate_y != 0.0) {  // world-to-environment: the map turns by +DEG about +Y
+      const double a = o.env_rotate_y * (3.14159265358979323846 / 180.0);
+      const float cs = (float)std::cos(a), sn = (float)std::sin(a);
+      const float R[9] = {cs, 0.0f, -sn, 0.0f, 1.0f, 0.0f, sn, 0.0f, cs};
+      memcpy(env.rotation, R, sizeof(R));
+    }
+    printf("[ConfigParser] environment map %s: %ux%u, scale %g, rotated %g degrees about +Y.\n", o.envmap.c_str(),
+           env.width, env.height, (double)env.scale, o.env_rotate_y);
+  }
   printf("[ConfigParser] kernel set to %s.\n[ConfigParser] iterations set to %u.\n", o.kernel.c_str(), o.iterations);
   if (o.interactive) printf("[ConfigParser] interactive viewer not available in this build; rendering headless.\n");
   if (o.output.empty())  // Config::operator<< (Config.h:237-248)
@@ -405,6 +438,7 @@ int main(int argc, char** argv) {
       if (!rc && sparse) rc = cvr_set_medium_sparse(ctx, &sd);
     }
     if (!rc) rc = cvr_set_camera(ctx, inv_view, r2v, full_res);
+    if (!rc && env_rgb) rc = cvr_set_environment(ctx, &env);
     if (!rc) rc = cvr_init(ctx);
     if (rc) {
       fprintf(stderr, "Error: %s\n", cvr_last_error(ctx));
@@ -618,6 +652,7 @@ int main(int argc, char** argv) {
     }
   }
   if (himg) cvr_host_free(himg);
+  cvr_free_image(env_rgb);
   if (o.trials > 1) {
     mean /= (double)times.size();
     double var = 0;

@@ -97,6 +97,17 @@ void drop_dense(cvr_ctx* c) {
   c->d_bounds = nullptr;
   c->n_voxels = 0;
 }
+// p is memory the context's device can read, by what the runtime knows of it: device memory of
+// that device, managed memory, or mapped host memory (an address HIP does not know is refused)
+bool device_readable(const cvr_ctx* c, const void* p) {
+  hipPointerAttribute_t at{};
+  if (hipPointerGetAttributes(&at, p) != hipSuccess) {
+    (void)hipGetLastError();
+    return false;
+  }
+  if (at.type == hipMemoryTypeDevice) return at.device == c->device;
+  return (at.type == hipMemoryTypeManaged || at.type == hipMemoryTypeHost) && at.devicePointer != nullptr;
+}
 }  // namespace cvr
 
 using cvr::drop_dense;
@@ -143,17 +154,7 @@ struct DevmedTimer {
       c->devmed_ms[i] += ms;
   }
 };
-// p is memory the context's device can read, by what the runtime knows of it: device memory of
-// that device, managed memory, or mapped host memory (an address HIP does not know is refused)
-bool device_readable(const cvr_ctx* c, const void* p) {
-  hipPointerAttribute_t at{};
-  if (hipPointerGetAttributes(&at, p) != hipSuccess) {
-    (void)hipGetLastError();
-    return false;
-  }
-  if (at.type == hipMemoryTypeDevice) return at.device == c->device;
-  return (at.type == hipMemoryTypeManaged || at.type == hipMemoryTypeHost) && at.devicePointer != nullptr;
-}
+using cvr::device_readable;
 using cvr::overflows_half;
 
 // What the three descriptors say of the medium besides its arrays

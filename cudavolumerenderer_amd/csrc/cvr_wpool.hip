@@ -25,6 +25,7 @@
 // need no atomics and no barriers: their counters are wave-uniform scalars.
 #include <hip/hip_runtime.h>
 
+#include "cvr_env.h"
 #include "cvr_kernels.h"
 #include "cvr_walk.h"
 
@@ -489,7 +490,7 @@ __device__ void frame_flusher(const LaunchParams& L, uint32_t f, uint32_t lane) 
 
 // k_wpool's instances (kMed* layouts and bits: cvr_wpool_select.h).  kMedDenseFull is the defaults' layout, its
 // null checks fold away (C2 -0.6%, C3 -1.8%); kMedDenseFullUniform pins the uniform albedo, whose check would cost
-// the non-uniform instance 1.5% on C2.  Only the kFlush, kRecord, kMedCount, kMedMoments instances carry that code.
+// the non-uniform instance 1.5% on C2.  Only the kFlush, kRecord, kMedCount, kMedMoments, kMedEnv instances carry that code.
 #if CVR_WPOOL_TAILSTAMP
 constexpr uint32_t kTailWaves = 16384;
 __device__ unsigned long long g_tail[8 * kTailWaves];
@@ -510,12 +511,37 @@ __device__ __forceinline__ void splat_moments(const LaunchParams& L, const PathS
   if (zz != 0.0f) __hip_atomic_fetch_add(px + 2, zz, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   __hip_atomic_fetch_add(px + 3, 1.0f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
+// kMedEnv: an escaping path's T becomes T (.) L(d), the environment's radiance in its direction
+// (cvr_env.h), before the splats.  The map's header (EnvParams, 64 bytes of device memory) is reached
+// through LaunchParams::rec, which an instance without records never reads, so that every other
+// instance keeps its parameters as they are; it is loaded with scalar loads from a wave-uniform address.
+__device__ __forceinline__ void env_shade(const LaunchParams& L, PathState& ps) {
+  typedef __attribute__((address_space(4))) const uint32_t* CWords;
+  const uint64_t a = reinterpret_cast<uint64_t>(fresh(L).rec);
+  // (the builtin returns int: through uint32_t, or the low half's bit 31 is sign-extended over the high half)
+  const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)a);
+  const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)(a >> 32));
+  const uint64_t ua = (uint64_t)lo | (uint64_t)hi << 32;
+  CWords hw = reinterpret_cast<CWords>(ua);
+  EnvParams E;
+  E.texels = reinterpret_cast<const float4*>((uint64_t)hw[0] | (uint64_t)hw[1] << 32);
+  E.w = hw[2];
+  E.h = hw[3];
+#pragma unroll
+  for (int i = 0; i < 9; ++i) E.R[i] = __uint_as_float(hw[4 + i]);
+  float rgb[3];
+  env_lookup(E, ps.d.x, ps.d.y, ps.d.z, rgb);
+  ps.T = mk3(ps.T.x * rgb[0], ps.T.y * rgb[1], ps.T.z * rgb[2]);
+}
 template <bool kScatterEps, int kWaves, int kMedMk, bool kRecord, bool kFlush>
 __global__ __launch_bounds__(64 * wpg_of(kMedMk, kWaves), kWaves) void k_wpool(MediumParams mk, LaunchParams Lk) {
   constexpr bool kMK = (kMedMk & kMedMK) != 0;
   constexpr bool kCountWords = (kMedMk & kMedCount) != 0;
   constexpr bool kMoments = (kMedMk & kMedMoments) != 0;
+  constexpr bool kEnv = (kMedMk & kMedEnv) != 0;
   constexpr int kMed = kMedMk & 3;
+  static_assert(!kEnv || (kWaves == kWpoolWaves && !kMK && !kRecord && !kFlush && !kCountWords),
+                "environment: the default budget, no naiveMK walk, records, in-launch output or word counts");
   static_assert(!kMoments || (!kMK && !kRecord && !kFlush && !kCountWords && !(kMedMk & kMedHalf)),
                 "moments: no naiveMK walk, records, in-launch output, word counts or pinned half format");
   static_assert(!kMK || (kScatterEps && !kRecord && !kFlush), "naiveMK: scatter -eps, no records / in-launch output");
@@ -1060,6 +1086,9 @@ __global__ __launch_bounds__(64 * wpg_of(kMedMk, kWaves), kWaves) void k_wpool(M
       // packed fp32 it fits in 96 VGPRs, and the synchronous render gains 0.26 % from it, inside the
       // run-to-run spread: profiles/round7/README.md)
       // (the moments instance too: a sum of squares cannot be combined through a sum)
+      if constexpr (kEnv) {  // the escapes' contributions C = T (.) L(d): what both splats below add
+        if (escaped) env_shade(L, ps);
+      }
       splat_wave<!kFlush && !kMoments>(S, L, ps, escaped, s, lane);
       if constexpr (kMoments) {
         if (escaped) splat_moments(L, ps);
@@ -1195,6 +1224,11 @@ constexpr WpoolRow kWpoolTable[] = {
     // second moments, word counts
     CVR_WP_ROWS(5, kMedDense | kMedMoments, false, false), CVR_WP_ROWS(5, kMedSparse | kMedMoments, false, false),
     CVR_WP_ROWS(5, kMedSparse | kMedCount, false, false),
+    // an environment map: the generic layouts, without and with the second moments
+    CVR_WP_ROWS(5, kMedDense | kMedEnv, false, false), CVR_WP_ROWS(5, kMedSparse | kMedEnv, false, false),
+    CVR_WP_ROWS(5, kMedSparse | kMedHalf | kMedEnv, false, false),
+    CVR_WP_ROWS(5, kMedDense | kMedEnv | kMedMoments, false, false),
+    CVR_WP_ROWS(5, kMedSparse | kMedEnv | kMedMoments, false, false),
     // naiveMK's walk: scatter -eps
     CVR_WP_ROWMK(kMedDense), CVR_WP_ROWMK(kMedSparse), CVR_WP_ROWMK(kMedDenseFull), CVR_WP_ROWMK(kMedDenseFullUniform),
     CVR_WP_ROWMK(kMedSparse | kMedHalf), CVR_WP_ROWMK(kMedDenseFull | kMedHalf),
@@ -1210,11 +1244,12 @@ constexpr const WpoolRow* wpool_row(const WpoolInstance& k) {
     if (r.id == k) return &r;
   return nullptr;
 }
-// Over the whole request space: every instance selected is a row, and every row is selected.
+// Over the whole request space, with and without an environment: every instance selected is a row, and every
+// row is selected.
 constexpr bool wpool_table_is_the_selection() {
   bool hit[kWpoolRows] = {};
   WpoolInstance k{};
-  for (int i = 0; i < kWpoolRequests; ++i)
+  for (int i = 0; i < kWpoolRequestsAll; ++i)
     if (wpool_select(wpool_request_at(i), &k)) {
       const WpoolRow* r = wpool_row(k);
       if (!r) return false;
@@ -1224,7 +1259,7 @@ constexpr bool wpool_table_is_the_selection() {
     if (!h) return false;
   return true;
 }
-static_assert(kWpoolRows == 57 && wpool_table_is_the_selection(), "the instance table and wpool_select disagree");
+static_assert(kWpoolRows == 67 && wpool_table_is_the_selection(), "the instance table and wpool_select disagree");
 
 hipError_t launch_wpool(const MediumParams& m, const LaunchParams& L, const WpoolRequest& q, uint32_t grid,
                         hipStream_t s) {

@@ -33,6 +33,9 @@ extern "C" {
  *              6 + CVR_HAS_TRANSFER (likewise): cvr_transfer_desc, cvr_scalar_medium_desc,
  *                  cvr_classify_host, cvr_raw_transfer_table, cvr_set_medium_scalar,
  *                  cvr_set_medium_scene_transfer
+ *              6 + CVR_HAS_ENVMAP (likewise): cvr_environment_desc, cvr_set_environment,
+ *                  cvr_clear_environment, cvr_environment_info, cvr_environment_eval*, cvr_trace_env,
+ *                  cvr_read_image, cvr_free_image
  * CVR_ABI_VERSION is the ABI this header declares: 6, the library's (cvr_abi_version()).  ABI 6 only
  * adds to ABI 5, so a host that must also load an ABI 5 library can hold itself to that surface:
  * with CVR_ABI_TARGET defined as 5 before the include, the ABI 6 functions and structs are not
@@ -814,6 +817,111 @@ int cvr_set_medium_scalar(cvr_ctx* ctx, const cvr_scalar_medium_desc* medium);
  * or 0).  A scene without raw bytes: CVR_ERR_INVALID. */
 int cvr_set_medium_scene_transfer(cvr_ctx* ctx, const cvr_scene* scene, const cvr_transfer_desc* transfer,
                                   uint32_t flags);
+
+/* ---- environment-map lighting (extension within ABI 6: CVR_HAS_ENVMAP) -- */
+/* Without an environment every path that leaves the box adds its throughput T: a constant white
+ * environment of radiance 1 (the reference's only light).  With one, an escaping path adds
+ * C = T (.) L(d), L the radiance of a latitude-longitude map in its direction d at escape.
+ * The lookup is fp32 only, every operation in the order written here, the fused ones explicit
+ * (det_fmaf; cvr_detmath.h), so the kernels and cvr_environment_eval_host return the same bits
+ * (one definition compiles for both, cvr_env.h).  For a direction d (unit or not), the row-major
+ * world-to-environment rotation R[9] and W x H stored texels (row 0 is the top, +Y is up, -Z is
+ * the centre column: Mitsuba's envmap convention):
+ *   e_x = (R0 d.x + R1 d.y) + R2 d.z        (likewise e_y from R3..5, e_z from R6..8)
+ *   u = det_fmaf(det_atan2f(e_x, -e_z), 0.15915494309189535f, 0.5f)
+ *   v = det_acosf(det_fminf(det_fmaxf(e_y, -1), 1)) * 0.3183098861837907f
+ *   u = det_fminf(det_fmaxf(u, 0), 1), v likewise                  (a NaN becomes 0)
+ *   x = det_fmaf(u, (float)W, -0.5f), y = det_fmaf(v, (float)H, -0.5f)
+ *   x0 = det_floor_i32(x), fx = x - (float)x0;  y0, fy likewise
+ *   xa = x0 < 0 ? W-1 : x0,  xb = x0+1 >= W ? 0 : x0+1           (u wraps)
+ *   ya = y0 < 0 ? 0 : y0,    yb = y0+1 >= H ? H-1 : y0+1         (v clamps)
+ *   per channel, A, B = row ya at xa, xb and C, D = row yb at xa, xb:
+ *     t = det_fmaf(fx, B - A, A), b = det_fmaf(fx, D - C, C), L = det_fmaf(fy, b - t, t)
+ * So no index leaves the image, a constant map returns exactly its constant, the seam
+ * d = (+-0, 0, 1) reads columns W-1 and 0, and the poles read rows 0 and H-1 alone.
+ * Stored texels are (fl(scale r), fl(scale g), fl(scale b), 0): 16 bytes, one load per tap.
+ *
+ * cvr_set_environment: the context keeps its own copy (W * H * 16 device bytes); the caller's
+ * array is only read and may be freed afterwards.  From CVR_ENV_DEVICE memory (a torch tensor) no
+ * array crosses to the host: one kernel converts the 3- or 4-channel input and in the same pass
+ * finds the largest stored component and the smallest index of an invalid one; a host array is
+ * staged on the device and takes the same kernel.  Synchronous on the context's stream.
+ * Refusals, in this order, the previous environment (or none) kept in each case:
+ *   inside an adaptive session: CVR_ERR_STATE;
+ *   width outside 2..16384, height outside 2..8192, channels other than 3 or 4, an unknown
+ *   location, a NULL pixels pointer, a scale that is negative or not finite, a rotation entry
+ *   that is not finite: CVR_ERR_INVALID;
+ *   CVR_ENV_DEVICE pixels that are not device-accessible memory of the context's device, or
+ *   4-channel ones that are not 16-byte aligned: CVR_ERR_INVALID;
+ *   a stored component that is negative or not finite (after scaling): CVR_ERR_INVALID, the
+ *   message names the smallest index (texel * channels + channel) of one.  (The framebuffer's
+ *   sums are then never -0 and all contributions have one sign.)
+ * cvr_clear_environment: back to radiance 1, with the launches and kernel instances of a
+ * context that never had an environment.
+ * With an environment a launch runs on the wave-pool scheduler at 5 waves per SIMD with its
+ * generic dense instance or a sparse one (fp32 or half), without or with CVR_OPT_MOMENTS (the
+ * moments are then sums of fl(C C), the count is unchanged): cvr_launch_render, cvr_render_frame
+ * (always its normalise-and-copy path in one part: cvr_frame_flush_info reports 0 blocks),
+ * cvr_render_image / _tiles / _share_to_host, block shards, path ranges, a caller's output buffer,
+ * the adaptive session and cvr_denoise.  CVR_ERR_UNSUPPORTED, the message naming the obstacle:
+ * kernel id naiveMK, another CVR_OPT_SCHEDULER or CVR_OPT_WAVES value, CVR_OPT_RNG_BINDING 1,
+ * CVR_OPT_COUNT_WORDS 1, CVR_OPT_MK_COMPACTION 1, cvr_trace_launch, and second moments on a sparse
+ * half medium.
+ * Not supported: next-event estimation or importance sampling of the map (a small bright sun is
+ * noisy), the XML scenes' envmap emitter, sharing one environment between contexts (each keeps a
+ * copy; cvr_render_frame's helper contexts are not used with one), naiveMK. */
+#define CVR_HAS_ENVMAP 1
+enum { CVR_ENV_HOST = 0, CVR_ENV_DEVICE = 1 }; /* cvr_environment_desc.location */
+typedef struct cvr_environment_desc {
+  uint32_t width, height; /* 2..16384, 2..8192 */
+  uint32_t channels;      /* floats per texel: 3, or 4 (the fourth is ignored) */
+  uint32_t location;      /* CVR_ENV_HOST / CVR_ENV_DEVICE: where pixels lives */
+  const float* pixels;    /* width * height * channels floats, row 0 the top, contiguous */
+  float scale;            /* finite, >= 0: every component is multiplied by it when stored */
+  float rotation[9];      /* row-major world-to-environment; all zero: the identity */
+} cvr_environment_desc;   /* 64 bytes */
+struct cvr_environment_info {
+  uint32_t width, height; /* 0, 0: no environment */
+  uint64_t bytes;         /* device bytes of the stored texels */
+  float max_component;    /* the largest stored component */
+  uint32_t reserved;
+};
+int cvr_set_environment(cvr_ctx* ctx, const cvr_environment_desc* desc);
+int cvr_clear_environment(cvr_ctx* ctx);
+int cvr_environment_info(const cvr_ctx* ctx, struct cvr_environment_info* out);
+/* Host only, no GPU: the statement above for n directions (dirs: 3 n floats) of a
+ * CVR_ENV_HOST descriptor, into out_rgb (3 n floats).  The descriptor is checked as
+ * cvr_set_environment checks it, its texel values excepted. */
+int cvr_environment_eval_host(const cvr_environment_desc* desc, const float* dirs, size_t n, float* out_rgb);
+/* The same with the stored texel (x, y) taken from a callback instead of an array (rgba[0..2]
+ * are used as they are: no scale), for maps too large to hold on the host.  rotation: 9 floats
+ * or NULL (the identity). */
+typedef void (*cvr_texel_fn)(void* user, uint32_t x, uint32_t y, float rgba[4]);
+int cvr_environment_eval_host_fn(uint32_t width, uint32_t height, const float* rotation, cvr_texel_fn texel,
+                                 void* user, const float* dirs, size_t n, float* out_rgb);
+/* The device's lookup of the context's environment for n arbitrary directions (host arrays),
+ * by a small kernel: the parity hook that is independent of the walk.  Synchronous.
+ * CVR_ERR_STATE: no environment. */
+int cvr_environment_eval(cvr_ctx* ctx, const float* host_dirs, size_t n, float* host_out_rgb);
+/* cvr_trace_paths' one-path-per-work-item walk with the environment applied: T is the
+ * throughput before the environment (cvr_path_record's T), d the direction at escape and
+ * C = T (.) L(d) the contribution; d and C are zero for a path that does not escape.  Kernel id
+ * naiveMK: CVR_ERR_UNSUPPORTED; no environment: CVR_ERR_STATE. */
+typedef struct cvr_env_record {
+  uint32_t image_id;
+  uint32_t flags; /* bit0 escaped, bit1 truncated */
+  uint32_t n_segments;
+  float T[3], d[3], C[3];
+} cvr_env_record; /* 48 bytes */
+int cvr_trace_env(cvr_ctx* ctx, uint32_t first, uint32_t count, cvr_env_record* host_out);
+/* Host only: read a Radiance .hdr (32-bit_rle_rgbe, "-Y h +X w" only; flat scanlines as
+ * cvr_write_hdr writes them, or new-style run-length encoded ones) or a colour .pfm ("PF",
+ * either byte order, rows bottom-up in the file) into a malloc'ed array of width * height * 3
+ * floats, row 0 the top; the format is taken from the file's first bytes.  Release it with
+ * cvr_free_image.  A file that cannot be opened, is truncated or malformed, has a zero
+ * dimension or (.hdr) a run that passes its scanline: CVR_ERR_IO. */
+int cvr_read_image(const char* path, uint32_t* width, uint32_t* height, float** rgb);
+void cvr_free_image(float* rgb);
 #endif /* CVR_ABI_VERSION >= 6 */
 
 /* Pinned, device-mapped host memory for cvr_render_share_to_host /

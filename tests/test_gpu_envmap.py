@@ -1,0 +1,543 @@
+"""Environment-map lighting on the GPU (cvr_set_environment; include/cvr.h, CVR_HAS_ENVMAP).
+
+Chain of evidence, every link a comparison of bits unless a sum of several paths is involved:
+  1. the device's lookup (cvr_environment_eval) equals the host statement (cvr_environment_eval_host),
+     which tests/test_envmap_cpu.py holds against an fp64 restatement and its stated properties;
+  2. cvr_trace_env's walk equals the unchanged CPU oracle's (image id, flags, T, segments; the
+     direction of a camera ray that misses the box), and its C equals T (.) eval_host(d);
+  3. the production kernel's framebuffer at one sample per pixel equals cvr_trace_env's C per pixel,
+     on every medium layout the environment instances serve, and sums of several samples equal
+     the records' fp64 sums within the summation-order bound of parity_util;
+  4. the same through the second moments, the adaptive session, the denoiser and the other render
+     entry points, and the refusals cvr.h lists.
+Tiles are 16x16 or 32x24 pixels with 1 and 4 samples: every test is a few hundred paths."""
+import os
+import subprocess
+
+import numpy as np
+import pytest
+import torch  # (imported before libcvr is loaded, as tests/test_gpu_denoise.py does)
+
+from envmap_util import ROT, SIZES, random_dirs, special_dirs
+from media import SCALE, dense_arrays, sparse_desc, sparse_small, staircase
+from parity_util import COUNTERS, assert_pixels_close
+
+pytestmark = pytest.mark.gpu
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CLI = os.path.join(ROOT, "cudavolumerenderer_amd", "cvr")
+DEV = "cuda:0"
+TILE = (16, 16)
+SEED = 3
+
+
+def bits(a):
+    return np.ascontiguousarray(a, np.float32).view(np.uint32)
+
+
+def env_image(W, H, seed=0, channels=3):
+    """A positive map with structure in both directions and a bright patch (a 'sun')."""
+    rng = np.random.default_rng(100 + seed + W)
+    yy, xx = np.mgrid[0:H, 0:W]
+    img = np.zeros((H, W, channels), np.float32)
+    for c in range(3):
+        img[..., c] = (0.2 + 0.8 * rng.random((H, W)) + np.sin(2 * np.pi * xx / W + c) ** 2 + yy / H).astype(np.float32)
+    img[H // 3, W // 2, :3] = (40.0, 30.0, 20.0)
+    if channels == 4:
+        img[..., 3] = -7.0  # ignored: never read into the stored texels
+    return img
+
+
+def two_tone(W=16, H=8):
+    img = np.full((H, W, 3), 0.05, np.float32)
+    img[:, : W // 2] = (3.0, 2.0, 1.0)
+    return img
+
+
+# ------------------------------------------------------------------- media --
+def dense_medium(cvr, kind):
+    if kind == "dense_cells":
+        m = staircase()
+        desc, keep = cvr.medium_from_arrays(m.density, m.albedo, m.box_min, m.box_max, m.scale, m.max_density)
+        return desc, keep, (m.density, m.albedo, m.box_min, m.box_max, m.scale, m.max_density)
+    d, a, md = dense_arrays("max")
+    desc, keep = cvr.medium_from_arrays(d, a, scale=SCALE, max_density=md)
+    return desc, keep, (d, a, (-0.5,) * 3, (0.5,) * 3, SCALE, md)
+
+
+MEDIA = {  # name -> (sparse, options)
+    "dense_generic": (False, (("OPT_CELLS", 0),)),
+    "dense_cells": (False, ()),
+    "dense_half": (False, (("OPT_MEDIUM_FORMAT", 1),)),
+    "sparse": (True, ()),
+    "sparse_half": (True, (("OPT_MEDIUM_FORMAT", 1),)),
+}
+
+
+def make_ctx(cvr, medium, kernel="regenerationSK", tile=TILE, opts=(), full=None):
+    """(context with the medium, camera and launch of `tile` set; what keeps its arrays alive)."""
+    sparse, mopts = MEDIA[medium]
+    ctx = cvr.Context(0, kernel)
+    for k, v in tuple(mopts) + tuple(opts):
+        ctx.set_option(getattr(cvr, k), v)
+    if sparse:
+        desc, keep = sparse_desc(cvr, *sparse_small())
+        ctx.set_medium_sparse(desc)
+    else:
+        desc, keep, _ = dense_medium(cvr, medium)
+        ctx.set_medium(desc)
+    full = full or tile
+    iv, r2v = cvr.default_camera(*full)
+    ctx.set_camera(iv, r2v, full)
+    ctx.init()
+    ctx.set_resolution(*tile)
+    ctx.set_offset(0, 0)
+    ctx.set_seed(SEED)
+    return ctx, (desc, keep, iv, r2v)
+
+
+def launch(ctx, iters, tile=TILE):
+    """One launch of `iters` whole samples from SEED into a cleared framebuffer: (sums, stats)."""
+    ctx.set_iterations(iters)
+    ctx.set_seed(SEED)
+    ctx.set_path_range(0, tile[0] * tile[1] * iters)
+    ctx.clear_output()
+    ctx.launch_render()
+    ctx.synchronize()
+    return ctx.copy_output(*tile), ctx.stats()
+
+
+def records(ctx, iters, tile=TILE):
+    ctx.set_iterations(iters)
+    ctx.set_seed(SEED)
+    return ctx.trace_env(0, tile[0] * tile[1] * iters)
+
+
+def record_sums(rec, tile, iters, field="C", square=False):
+    """fp64 per-pixel sums of the records' contributions (square: of their fp32 squares)."""
+    px = tile[0] * tile[1]
+    v = rec[field].astype(np.float32)
+    if square:
+        v = (v * v).astype(np.float32)
+    return v.astype(np.float64).reshape(iters, px, 3).sum(axis=0).reshape(tile[1], tile[0], 3)
+
+
+# ------------------------------------------------------ 1. the lookup alone --
+@pytest.fixture(scope="module")
+def eval_ctx(cvr):
+    ctx = cvr.Context(0, "regenerationSK")
+    yield ctx
+    ctx.close()
+
+
+@pytest.mark.parametrize("size", SIZES)
+def test_eval_equals_the_host_statement(cvr, eval_ctx, size):
+    W, H = size
+    dirs = np.concatenate([special_dirs(), random_dirs(4096, seed=W + H)])
+    for channels in (3, 4):
+        img = env_image(W, H, channels=channels)
+        for rot in (None, ROT):
+            for scale in (1.0, 0.37):
+                want = cvr.environment_eval_host(img, dirs, scale, rot)
+                eval_ctx.set_environment(img, scale, rot)
+                host_up = eval_ctx.environment_eval(dirs)
+                info = eval_ctx.environment_info()
+                assert (info.width, info.height, info.bytes) == (W, H, W * H * 16)
+                assert info.max_component == (np.float32(scale) * img[..., :3]).max()
+                eval_ctx.set_environment(torch.from_numpy(img).to(DEV), scale, rot)
+                dev_up = eval_ctx.environment_eval(dirs)
+                what = f"{W}x{H} channels {channels} scale {scale} {'rotated' if rot is not None else 'identity'}"
+                assert np.isfinite(want).all(), what
+                assert np.array_equal(bits(host_up), bits(want)), what
+                assert np.array_equal(bits(dev_up), bits(want)), what
+    eval_ctx.clear_environment()
+    assert eval_ctx.environment_info().width == 0
+    with pytest.raises(cvr.CvrError) as e:
+        eval_ctx.environment_eval(dirs[:4])
+    assert e.value.code == -3
+
+
+def test_index_width_of_the_largest_map(cvr, eval_ctx):
+    """16384 x 8192 texels are 2^31 bytes stored: the last rows' byte offsets need all 31 bits, and the
+    stored array's float index (4 per texel) passes 2^28.  Texel (x, y) is (x, y, x + y) / 64, exact
+    in fp32 and so recoverable; the host side takes the same formula through
+    cvr_environment_eval_host_fn's callback, not a 2 GB array."""
+    W, H = 16384, 8192
+    x = torch.arange(W, device=DEV, dtype=torch.float32)
+    y = torch.arange(H, device=DEV, dtype=torch.float32)
+    t = torch.empty((H, W, 3), device=DEV, dtype=torch.float32)
+    t[..., 0] = x[None, :] / 64
+    t[..., 1] = y[:, None] / 64
+    t[..., 2] = (x[None, :] + y[:, None]) / 64
+    eval_ctx.set_environment(t)
+    del t
+    info = eval_ctx.environment_info()
+    assert info.bytes == 2 ** 31 and info.max_component == np.float32((W - 1 + H - 1) / 64)
+    dirs = np.array([[0.0, -1.0, 0.0], [1e-30, -1.0, -0.0],            # the bottom pole: row H - 1
+                     [0.0, 0.0, 1.0], [-0.0, 0.0, 1.0],                # the seam: columns W - 1 and 0
+                     [0.0, -0.999, 1.0], [0.3, -0.9, 0.2], [-0.5, -0.7, -0.1],  # low rows: byte offsets above 2^30
+                     [0.1, 0.2, -1.0], [0.9, 0.01, 0.4], [-0.6, 0.8, 0.3]], np.float32)
+    got = eval_ctx.environment_eval(dirs)
+    want = cvr.environment_eval_host_fn(W, H, lambda x, y: (x / 64.0, y / 64.0, (x + y) / 64.0), dirs)
+    assert np.array_equal(bits(got), bits(want)), (got, want)
+    assert got[0, 1] == np.float32((H - 1) / 64) and got[1, 1] == np.float32((H - 1) / 64)
+    assert (got[4:7, 1] * 64 > 0.7 * H).all()  # these did read rows whose byte offsets need all 31 bits
+    eval_ctx.clear_environment()
+
+
+# ------------------------------------------------- 2. the walk is untouched --
+def oracle_of(cvr, oracle_mod, medium):
+    if MEDIA[medium][0]:
+        s = sparse_small()
+        return oracle_mod.Oracle.from_leaves(s.res, s.table, s.leaf_density, s.leaf_albedo, s.albedo_bg, scale=SCALE,
+                                             max_density=s.max_density)
+    _, _, (d, a, bmin, bmax, scale, md) = dense_medium(cvr, medium)
+    return oracle_mod.Oracle(d, a, bmin, bmax, scale, md)
+
+
+@pytest.mark.parametrize("kernel", ["naiveSK", "regenerationSK"])
+@pytest.mark.parametrize("medium", ["dense_cells", "sparse"])
+def test_trace_env_walk_equals_the_oracle(cvr, oracle_mod, medium, kernel):
+    iters = 4
+    n = TILE[0] * TILE[1] * iters
+    ctx, (_, _, iv, r2v) = make_ctx(cvr, medium, kernel)
+    orc = oracle_of(cvr, oracle_mod, medium)
+    L = orc.launch(iv, r2v, TILE, TILE, (0, 0), cvr.KERNELS.index(kernel), SEED)
+    c = orc.trace_paths(L, 0, n)
+    # the camera (the default one: the box fills two thirds of the tile) gives both kinds of escape
+    missed = (c["flags"] & 1 == 1) & (c["n_segments"] == 1)
+    later = (c["flags"] & 1 == 1) & (c["n_segments"] >= 2)
+    assert missed.mean() >= 0.1 and later.mean() >= 0.1, (missed.mean(), later.mean())
+    img = env_image(64, 32)
+    ctx.set_environment(img, 0.37, ROT)
+    g = records(ctx, iters)
+    for f in ("image_id", "flags", "n_segments"):
+        assert np.array_equal(g[f], c[f]), f
+    assert np.array_equal(bits(g["T"]), bits(c["T"]))
+    esc = g["flags"] & 1 == 1
+    assert (g["d"][~esc] == 0).all() and (g["C"][~esc] == 0).all()
+    rays = np.array([oracle_mod.camera_ray(L, int(p))[1] for p in np.nonzero(missed)[0]], np.float32)
+    assert np.array_equal(bits(g["d"][missed]), bits(rays))
+    want = g["T"][esc] * cvr.environment_eval_host(img, g["d"][esc], 0.37, ROT)
+    assert np.array_equal(bits(g["C"][esc]), bits(want))
+    # the plain records are what they were
+    p = ctx.trace_paths(0, n)
+    assert np.array_equal(bits(p["T"]), bits(c["T"])) and np.array_equal(p["n_steps"], c["n_steps"])
+    ctx.close()
+
+
+# ------------------------------------------------ 3. the production kernel --
+@pytest.mark.parametrize("medium", list(MEDIA))
+def test_framebuffer_equals_the_records(cvr, medium):
+    ctx, keep = make_ctx(cvr, medium)
+    plain, st0 = launch(ctx, 1)
+    ctx.set_environment(env_image(64, 32), 1.0, ROT)
+    rec = records(ctx, 1)
+    fb, st1 = launch(ctx, 1)
+    px = TILE[0] * TILE[1]
+    esc = rec["flags"] & 1 == 1
+    assert 0.2 < esc.mean() < 1.0
+    assert np.array_equal(rec["image_id"], np.arange(px))  # one path per pixel, in pixel order
+    assert np.array_equal(bits(fb[..., :3].reshape(px, 3)), bits(rec["C"])), medium
+    assert np.array_equal(fb[..., 3].reshape(px), esc.astype(np.float32))
+    assert not np.array_equal(bits(fb), bits(plain))
+    for k in COUNTERS + ("fetches",):
+        assert getattr(st1, k) == getattr(st0, k), k
+    # four samples: sums of four contributions of one sign
+    rec4 = records(ctx, 4)
+    fb4, _ = launch(ctx, 4)
+    assert_pixels_close(fb4[..., :3].astype(np.float64), record_sums(rec4, TILE, 4), 4, medium)
+    ctx.close()
+
+
+@pytest.mark.parametrize("medium", ["dense_cells", "sparse"])
+def test_constant_maps_tie_to_the_plain_render(cvr, medium):
+    ctx, keep = make_ctx(cvr, medium)
+    plain, _ = launch(ctx, 1)
+    assert plain[..., :3].max() > 0
+    ctx.set_environment(np.ones((2, 2, 3), np.float32))
+    assert np.array_equal(bits(launch(ctx, 1)[0]), bits(plain))
+    ctx.set_environment(np.full((5, 7, 4), 0.5, np.float32), scale=2.0)
+    assert np.array_equal(bits(launch(ctx, 1)[0]), bits(plain))
+    ctx.set_environment(np.full((5, 7, 3), 0.25, np.float32), rotation=ROT)
+    quarter = launch(ctx, 1)[0]
+    assert np.array_equal(bits(quarter[..., :3]), bits(plain[..., :3] * np.float32(0.25)))
+    assert np.array_equal(bits(quarter[..., 3]), bits(plain[..., 3]))
+    ctx.clear_environment()
+    assert np.array_equal(bits(launch(ctx, 1)[0]), bits(plain))
+    ctx.close()
+
+
+# ------------------------------------------------------------- 4. moments --
+@pytest.mark.parametrize("medium", ["dense_cells", "sparse"])
+def test_moments_are_sums_of_squared_contributions(cvr, medium):
+    ctx, keep = make_ctx(cvr, medium, opts=(("OPT_MOMENTS", 1),))
+    ctx.set_environment(env_image(7, 5), 1.0, ROT)
+    px = TILE[0] * TILE[1]
+    rec = records(ctx, 1)
+    launch(ctx, 1)
+    s1, s2 = ctx.copy_moments()
+    c = rec["C"].astype(np.float32)
+    assert np.array_equal(bits(s1[..., :3].reshape(px, 3)), bits(c))
+    assert np.array_equal(bits(s2[..., :3].reshape(px, 3)), bits(c * c))
+    assert np.array_equal(s2[..., 3].reshape(px), (rec["flags"] & 1).astype(np.float32))
+    rec4 = records(ctx, 4)
+    launch(ctx, 4)
+    s1, s2 = ctx.copy_moments()
+    assert_pixels_close(s1[..., :3].astype(np.float64), record_sums(rec4, TILE, 4), 4, medium + " sums")
+    assert_pixels_close(s2[..., :3].astype(np.float64), record_sums(rec4, TILE, 4, square=True), 4, medium + " moments")
+    count = (rec4["flags"] & 1).reshape(4, px).sum(axis=0).reshape(TILE[1], TILE[0])
+    assert np.array_equal(s2[..., 3], count.astype(np.float32))
+    ctx.close()
+
+
+def test_adaptive_session_and_denoiser_under_a_two_tone_map(cvr):
+    """Every block's pixels are its records' sums over the block's own sample count.  The bound:
+    a pixel of a block with s samples is fl(S / s) of a sum S of at most s <= 8 contributions of
+    one sign, so image * s differs from the fp64 sum by the summation-order bound of s terms,
+    2 (s - 1) 2^-24, plus the division's rounding, 2^-24: within parity_util's bound for 9 terms."""
+    mn, mx, step = 2, 8, 2
+    ctx, keep = make_ctx(cvr, "dense_cells")
+    ctx.set_environment(two_tone(), rotation=ROT)
+    px = TILE[0] * TILE[1]
+    rec = records(ctx, mx)
+    c = rec["C"].astype(np.float64).reshape(mx, TILE[1], TILE[0], 3)
+    ctx.set_iterations(mx)
+    ctx.set_seed(SEED)
+    ctx.set_path_range(0, 2 ** 64 - 1)
+    with ctx.adaptive(cvr.AdaptiveDesc(mn, mx, step, 0.25, 0.01)) as a:
+        while not a.step().done:
+            pass
+        img = a.image()
+        err, smp = a.maps()
+        den = a.denoised()
+        s1, s2 = ctx.copy_moments()
+    assert smp.shape == (2, 2) and smp.min() >= mn and smp.max() <= mx and (smp % step == 0).all()
+    for by in range(2):
+        for bx in range(2):
+            s = int(smp[by, bx])
+            blk = (slice(8 * by, 8 * by + 8), slice(8 * bx, 8 * bx + 8))
+            want = c[:s][(slice(None),) + blk].sum(axis=0)
+            assert_pixels_close(img[blk][..., :3].astype(np.float64) * s, want, mx + 1, f"block {bx},{by} ({s} samples)")
+    assert img[..., :3].max() > 0
+    host, _ = cvr.denoise_host(s1, s2, None, smp)
+    assert np.array_equal(bits(den), bits(host))
+    ctx.close()
+
+
+# -------------------------------------------------------- 5. entry points --
+def test_render_frame_copies_and_reports_no_flushed_block(cvr):
+    tile = (32, 24)
+    ctx, keep = make_ctx(cvr, "dense_cells", tile=tile)
+    ctx.set_environment(env_image(64, 32), 0.37)
+    fb, _ = launch(ctx, 1, tile)
+    for parts in (0, 2):
+        ctx.set_seed(SEED)
+        with cvr.PinnedImage(*tile) as pin:
+            ctx.render_frame(pin, parts)
+            got = np.array(pin.array, copy=True)
+        assert np.array_equal(bits(got), bits(fb)), parts
+        assert ctx.frame_flush_info()[0] == 0
+    ctx.close()
+
+
+def test_render_image_tiles_equal_the_per_tile_records(cvr):
+    W = H = 32
+    ctx, (_, _, iv, r2v) = make_ctx(cvr, "dense_cells", full=(W, H))
+    img_env = env_image(64, 32)
+    ctx.set_environment(img_env, 1.0, ROT)
+    ctx.set_seed(SEED)
+    img, st = ctx.render_image(W, H, (2, 2), 1)
+    n = TILE[0] * TILE[1]
+    assert st.paths == 4 * n
+    ctx.set_resolution(*TILE)
+    ctx.set_iterations(1)
+    for k in range(4):
+        ox, oy = 16 * (k % 2), 16 * (k // 2)
+        ctx.set_offset(ox, oy)
+        ctx.set_seed((SEED + k * n) & 0xFFFFFFFF)  # regenerationSK's reset() between tiles
+        rec = ctx.trace_env(0, n)
+        assert np.array_equal(bits(img[oy:oy + 16, ox:ox + 16, :3].reshape(n, 3)), bits(rec["C"])), k
+    ctx.close()
+
+
+def test_shards_ranges_and_a_callers_buffer(cvr):
+    ctx, keep = make_ctx(cvr, "sparse")
+    ctx.set_environment(env_image(7, 5))
+    whole, _ = launch(ctx, 1)
+    px = TILE[0] * TILE[1]
+    parts = []
+    for rank in (0, 1):
+        ctx.set_block_shard(rank, 2)
+        parts.append(launch(ctx, 1)[0])
+    ctx.set_block_shard(0, 1)
+    assert (parts[0][..., 3] * parts[1][..., 3] == 0).all() and parts[0].max() > 0 and parts[1].max() > 0
+    assert np.array_equal(bits(parts[0] + parts[1]), bits(whole))
+    # two path ranges accumulate into the whole
+    ctx.set_iterations(1)
+    ctx.set_seed(SEED)
+    ctx.clear_output()
+    for first, count in ((0, 100), (100, px - 100)):
+        ctx.set_path_range(first, count)
+        ctx.launch_render()
+    ctx.synchronize()
+    assert np.array_equal(bits(ctx.copy_output(*TILE)), bits(whole))
+    # a caller's output buffer
+    buf = torch.zeros((TILE[1], TILE[0], 4), device=DEV, dtype=torch.float32)
+    torch.cuda.synchronize()
+    ctx.set_output(buf.data_ptr())
+    ctx.set_path_range(0, px)
+    ctx.launch_render()
+    ctx.synchronize()
+    assert np.array_equal(bits(buf.cpu().numpy()), bits(whole))
+    ctx.set_output(None)
+    ctx.close()
+
+
+# ------------------------------------------------------------ 6. refusals --
+REFUSED = [  # (kernel id, options, the obstacle named, whether the launch runs once the environment is cleared)
+    ("regenerationSK", (("OPT_SCHEDULER", 0),), "a scheduler other than the wave pool", True),
+    ("regenerationSK", (("OPT_SCHEDULER", 4),), "a scheduler other than the wave pool", True),
+    ("regenerationSK", (("OPT_WAVES", 4),), "CVR_OPT_WAVES other than 5", True),
+    ("regenerationSK", (("OPT_RNG_BINDING", 1),), "CVR_OPT_RNG_BINDING 1", True),
+    ("regenerationSK", (("OPT_COUNT_WORDS", 1),), "CVR_OPT_COUNT_WORDS 1", True),
+    ("naiveMK", (), "kernel id naiveMK", True),
+    # (the reference's compaction may end a launch of its own accord, CVR_ERR_STATE: not launched here)
+    ("naiveMK", (("OPT_MK_COMPACTION", 1),), "kernel id naiveMK", False),
+    ("regenerationSK", (("OPT_MK_COMPACTION", 1),), "CVR_OPT_MK_COMPACTION 1", False),
+]
+
+
+@pytest.mark.parametrize("kernel,opts,text,runs_plain", REFUSED,
+                         ids=[f"{k}-{'-'.join(f'{n}{v}' for n, v in o) or 'plain'}" for k, o, _, _ in REFUSED])
+def test_unsupported_combinations_are_refused(cvr, kernel, opts, text, runs_plain):
+    ctx, keep = make_ctx(cvr, "dense_cells", kernel, opts=opts)
+    ctx.set_environment(two_tone())
+    ctx.set_iterations(1)
+    with pytest.raises(cvr.CvrError) as e:
+        ctx.launch_render()
+    assert e.value.code == -5 and "environment map" in str(e.value) and text in str(e.value), str(e.value)
+    ctx.clear_environment()
+    if runs_plain:
+        ctx.launch_render()  # the obstacle was the environment's alone
+        ctx.synchronize()
+    ctx.close()
+
+
+def test_trace_launch_and_half_moments_are_refused(cvr):
+    ctx, keep = make_ctx(cvr, "sparse")
+    ctx.set_environment(two_tone())
+    ctx.set_iterations(1)
+    ctx.set_path_range(0, 256)
+    with pytest.raises(cvr.CvrError) as e:
+        ctx.trace_launch(256)
+    assert e.value.code == -5 and "environment map" in str(e.value) and "cvr_trace_launch" in str(e.value)
+    ctx.close()
+    ctx, keep = make_ctx(cvr, "sparse_half", opts=(("OPT_MOMENTS", 1),))
+    ctx.set_environment(two_tone())
+    ctx.set_iterations(1)
+    with pytest.raises(cvr.CvrError) as e:
+        ctx.launch_render()
+    assert e.value.code == -5 and "a sparse half medium" in str(e.value)
+    ctx.close()
+    ctx, keep = make_ctx(cvr, "sparse", "naiveMK")
+    ctx.set_environment(two_tone())
+    with pytest.raises(cvr.CvrError) as e:
+        ctx.trace_env(0, 16)
+    assert e.value.code == -5 and "naiveMK" in str(e.value)
+    ctx.close()
+
+
+def test_bad_descriptors_keep_the_previous_environment(cvr):
+    from cudavolumerenderer_amd import _lib
+    ctx, keep = make_ctx(cvr, "dense_cells")
+    good = env_image(7, 5)
+    ctx.set_environment(good, 1.0, ROT)
+    before, _ = launch(ctx, 1)
+    ok = np.ones((4, 4, 3), np.float32)
+    bad = [
+        (np.ones((1, 4, 3), np.float32), {}, "height"), (np.ones((4, 1, 3), np.float32), {}, "width"),
+        (np.ones((4, 4, 2), np.float32), {}, "channels"), (ok, {"scale": -1.0}, "scale"),
+        (ok, {"scale": float("inf")}, "scale"), (ok, {"rotation": [float("nan")] * 9}, "rotation"),
+    ]
+    for img, kw, text in bad:
+        with pytest.raises(cvr.CvrError) as e:
+            ctx.set_environment(img, **kw)
+        assert e.value.code == -1 and text in str(e.value), str(e.value)
+    # NULL pixels, an unknown location, and host memory named as device memory
+    lib = cvr.load()
+    for pixels, location, text in ((None, 0, "NULL"), (ok.ctypes.data, 7, "location"),
+                                   (ok.ctypes.data, _lib.ENV_DEVICE, "not device-accessible")):
+        d = _lib.EnvironmentDesc(4, 4, 3, location, pixels, 1.0)
+        assert lib.cvr_set_environment(ctx._h, d) == -1
+        assert text in lib.cvr_last_error(ctx._h).decode()
+    # a misaligned 4-channel device array
+    base = torch.ones(4 * 4 * 4 + 1, device=DEV, dtype=torch.float32)
+    d = _lib.EnvironmentDesc(4, 4, 4, _lib.ENV_DEVICE, base.data_ptr() + 4, 1.0)
+    assert lib.cvr_set_environment(ctx._h, d) == -1 and "aligned" in lib.cvr_last_error(ctx._h).decode()
+    # texel values: the smallest offending index, from a device tensor and from a host array
+    for channels in (3, 4):
+        for value in (-1.0, float("nan"), float("inf")):
+            img = env_image(7, 5, channels=channels)
+            first = (3 * 7 + 2) * channels + 1
+            img[3, 2, 1] = value
+            img[4, 6, 0] = value
+            for src in (torch.from_numpy(img).to(DEV), img):
+                with pytest.raises(cvr.CvrError) as e:
+                    ctx.set_environment(src)
+                assert e.value.code == -1 and f"component {first} " in str(e.value), str(e.value)
+    img = env_image(7, 5)
+    img[0, 0, 2] = -0.5
+    with pytest.raises(cvr.CvrError):
+        ctx.set_environment(img, 2.0)
+    ctx.set_environment(img, 0.0)  # scaled to -0: no negative contribution
+    ctx.set_environment(good, 1.0, ROT)
+    # inside an adaptive session the environment cannot change
+    ctx.set_iterations(4)
+    ctx.set_path_range(0, 2 ** 64 - 1)
+    with ctx.adaptive(cvr.AdaptiveDesc(2, 4, 2, 0.5, 0.01)):
+        for call in (lambda: ctx.set_environment(good), ctx.clear_environment):
+            with pytest.raises(cvr.CvrError) as e:
+                call()
+            assert e.value.code == -3
+    info = ctx.environment_info()
+    assert (info.width, info.height) == (7, 5)
+    after, _ = launch(ctx, 1)
+    assert np.array_equal(bits(after), bits(before))
+    ctx.close()
+
+
+# ------------------------------------------------------------------ 7. CLI --
+def read_pfm(path):
+    with open(path, "rb") as f:
+        assert f.readline().strip() == b"PF"
+        w, h = map(int, f.readline().split())
+        assert float(f.readline()) < 0
+        return np.frombuffer(f.read(), dtype="<f4").reshape(h, w, 3)[::-1]
+
+
+@pytest.mark.parametrize("devices", [None, "0,0"], ids=["one-context", "two-contexts"])
+def test_cli_envmap_equals_the_python_render(cvr, tmp_path, devices):
+    W = H = 32
+    env = env_image(16, 8)
+    envfile = tmp_path / "env.pfm"
+    envfile.write_bytes(b"PF\n16 8\n-1.0\n" + env[::-1].astype("<f4").tobytes())
+    assert np.array_equal(bits(cvr.read_image(str(envfile))), bits(env))
+    out = str(tmp_path / "out")
+    args = [CLI, "--interactive", "0", "--synthetic", "bucky", "-r", str(W), str(H), "-i", "1", "--envmap", str(envfile),
+            "--env-scale", "0.5", "--env-rotate-y", "30", "--pfm", "-o", out]
+    r = subprocess.run(args + (["--devices", devices] if devices else []), capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert "environment map" in r.stdout
+    got = read_pfm(out + ".pfm")
+    scene = cvr.Scene.synthetic("bucky")
+    ctx = cvr.Context(0, "regenerationSK")
+    ctx.set_medium(scene.medium)
+    iv, r2v = scene.camera(W, H)
+    ctx.set_camera(iv, r2v, (W, H))
+    ctx.set_environment(env, 0.5, cvr.rotation_y(30))
+    ctx.init()
+    img, _ = ctx.render_image(W, H, (1, 1), 1)
+    ctx.close()
+    assert img[..., :3].max() > 0
+    assert np.array_equal(bits(got), bits(img[..., :3]))
