@@ -99,3 +99,16 @@ variant-dnplain: $(OBJS)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o build/variants/dnplain/libcvr.so \
 	    $(filter-out $(OBJDIR)/cvr_denoise.o,$(OBJS)) build/variants/dnplain/cvr_denoise.o -Wl,-soname,libcvr.so -lz
 .PHONY: variant-dnplain
+# cvr_classify_gradient_host and the gradient descriptor's checks under AddressSanitizer and UBSan:
+# cvr_medium.cpp's host code alone is compiled with the sanitizers (-Xarch_host: the device code
+# is not) and linked with the library's other objects and a main of its own.  A CPU run, no GPU.
+gradient-host-asan: $(OBJS)
+	@mkdir -p build/asan
+	$(HIPCC) $(call hipflags,$(CSRC)/cvr_medium.cpp) -O1 -g -Xarch_host -fsanitize=address,undefined \
+	    -Xarch_host -fno-sanitize-recover=undefined -x hip -c $(CSRC)/cvr_medium.cpp -o build/asan/cvr_medium.o
+	g++ -O1 -g -std=c++17 -Wall -Iinclude -fsanitize=address,undefined -fno-sanitize-recover=undefined \
+	    -c tests/cpp/gradient_host_check.cpp -o build/asan/gradient_host_check.o
+	$(HIPCC) --offload-arch=$(ARCH) -fsanitize=address,undefined -o build/asan/gradient_host_check \
+	    build/asan/gradient_host_check.o $(filter-out $(OBJDIR)/cvr_medium.o,$(OBJS)) build/asan/cvr_medium.o -lz
+	build/asan/gradient_host_check
+.PHONY: gradient-host-asan

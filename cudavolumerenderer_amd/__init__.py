@@ -13,6 +13,7 @@ from ._lib import (  # noqa: F401
     DenoiseDesc, denoise_host,
     DeviceMediumDesc, MediumLayout, DEVMED_SPARSE, DEVMED_CONST_ALBEDO, DEVMED_MAX_DENSITY,
     TransferDesc, ScalarMediumDesc, classify_host, raw_transfer_table,
+    GradientTransferDesc, GradientMediumDesc, classify_gradient_host,
     SCALAR_F32, SCALAR_U8, SCALAR_U16, SCALAR_I16, TF_CEIL, TF_DENSITY_U,
     EnvironmentDesc, EnvironmentInfo, ENV_HOST, ENV_DEVICE, ENV_RECORD_DTYPE, environment_eval_host,
     environment_eval_host_fn, read_image, rotation_y,
@@ -28,6 +29,7 @@ __all__ = [
     "DenoiseDesc", "denoise_host",
     "DeviceMediumDesc", "MediumLayout", "DEVMED_SPARSE", "DEVMED_CONST_ALBEDO", "DEVMED_MAX_DENSITY",
     "TransferDesc", "ScalarMediumDesc", "classify_host", "raw_transfer_table",
+    "GradientTransferDesc", "GradientMediumDesc", "classify_gradient_host",
     "SCALAR_F32", "SCALAR_U8", "SCALAR_U16", "SCALAR_I16", "TF_CEIL", "TF_DENSITY_U",
     "EnvironmentDesc", "EnvironmentInfo", "ENV_HOST", "ENV_DEVICE", "ENV_RECORD_DTYPE", "environment_eval_host",
     "environment_eval_host_fn", "read_image", "rotation_y",

@@ -168,6 +168,24 @@ class ScalarMediumDesc(C.Structure):
                 ("max_density", C.c_float), ("g", C.c_float), ("roughness", C.c_float * 2), ("eta", C.c_float)]
 
 
+class GradientTransferDesc(C.Structure):
+    """cvr_gradient_transfer_desc: a table of m rows of n (r, g, b, density) entries in host
+    memory, the scalar range [lo, hi] of its rows and the gradient-magnitude range [glo, ghi] of
+    its columns, and the voxel spacing the gradient is taken with."""
+    _fields_ = [("n", C.c_uint32), ("m", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32),
+                ("table", C.c_void_p), ("lo", C.c_float), ("hi", C.c_float), ("glo", C.c_float),
+                ("ghi", C.c_float), ("spacing", C.c_float * 3)]
+
+
+class GradientMediumDesc(C.Structure):
+    """cvr_gradient_medium_desc: a scalar field in device memory and its gradient-magnitude
+    transfer function (cvr_set_medium_gradient)."""
+    _fields_ = [("res", C.c_uint32 * 3), ("flags", C.c_uint32), ("d_scalar", C.c_void_p),
+                ("scalar_type", C.c_uint32), ("reserved", C.c_uint32), ("transfer", GradientTransferDesc),
+                ("box_min", C.c_float * 3), ("box_max", C.c_float * 3), ("scale", C.c_float),
+                ("max_density", C.c_float), ("g", C.c_float), ("roughness", C.c_float * 2), ("eta", C.c_float)]
+
+
 class MediumLayout(C.Structure):
     """cvr_medium_layout: what an upload built (either path)."""
     _fields_ = [("sparse", C.c_uint32), ("albedo_uniform", C.c_uint32), ("n_leaves", C.c_uint32),
@@ -301,6 +319,9 @@ def load() -> C.CDLL:
         "cvr_raw_transfer_table": (I32, [FP]),
         "cvr_set_medium_scalar": (I32, [P, C.POINTER(ScalarMediumDesc)]),
         "cvr_set_medium_scene_transfer": (I32, [P, P, C.POINTER(TransferDesc), U32]),
+        "cvr_classify_gradient_host": (I32, [P, U32, C.POINTER(U32), C.POINTER(GradientTransferDesc), P, P, P]),
+        "cvr_set_medium_gradient": (I32, [P, C.POINTER(GradientMediumDesc)]),
+        "cvr_set_medium_scene_gradient": (I32, [P, P, C.POINTER(GradientTransferDesc), U32]),
         "cvr_set_environment": (I32, [P, C.POINTER(EnvironmentDesc)]),
         "cvr_clear_environment": (I32, [P]),
         "cvr_environment_info": (I32, [P, C.POINTER(EnvironmentInfo)]),
@@ -410,6 +431,42 @@ def classify_host(scalar, table, lo, hi, ceil=False, density_u=False):
     _check(load().cvr_classify_host(src.ctypes.data, _SCALAR_TYPES[src.dtype.name], src.size, C.byref(t),
                                     density.ctypes.data, albedo.ctypes.data))
     return density, albedo
+
+
+def _gradient_transfer_desc(table, lo, hi, glo, ghi, spacing):
+    """(GradientTransferDesc, the array it points into): table is (m, n, 4) floats, row j the
+    gradient entry j."""
+    tab = np.ascontiguousarray(table, dtype=np.float32)
+    if tab.ndim != 3 or tab.shape[2] != 4:
+        raise ValueError(f"table: shape {tab.shape}, expected (m, n, 4)")
+    if len(spacing) != 3:
+        raise ValueError("spacing: expected 3 floats (x, y, z)")
+    t = GradientTransferDesc(tab.shape[1], tab.shape[0], 0, 0, tab.ctypes.data, lo, hi, glo, ghi)
+    t.spacing[:] = [float(v) for v in spacing]
+    return t, tab
+
+
+def classify_gradient_host(scalar, table, lo, hi, glo, ghi, spacing=(1.0, 1.0, 1.0)):
+    """The gradient-magnitude transfer function's written statement on the CPU
+    (cvr_classify_gradient_host; no GPU): a (z, y, x) numpy array `scalar` of dtype uint8, uint16,
+    int16 or float32 and a table of (m, n, 4) floats (r, g, b, density), its n columns over the
+    scalar range [lo, hi] and its m rows over the gradient-magnitude range [glo, ghi], the
+    gradient taken with voxel spacing (x, y, z) -> (density (z, y, x), albedo (z, y, x, 4),
+    gradient magnitude (z, y, x)).  Context.set_medium_gradient computes the same bits on the
+    device."""
+    src = np.ascontiguousarray(scalar)
+    if src.dtype.name not in _SCALAR_TYPES:
+        raise ValueError(f"scalar: dtype {src.dtype}, expected uint8, uint16, int16 or float32")
+    if src.ndim != 3:
+        raise ValueError(f"scalar: shape {src.shape}, expected (z, y, x)")
+    t, _tab = _gradient_transfer_desc(table, lo, hi, glo, ghi, spacing)
+    density = np.empty(src.shape, np.float32)
+    albedo = np.empty(src.shape + (4,), np.float32)
+    mag = np.empty(src.shape, np.float32)
+    res = (C.c_uint32 * 3)(src.shape[2], src.shape[1], src.shape[0])
+    _check(load().cvr_classify_gradient_host(src.ctypes.data, _SCALAR_TYPES[src.dtype.name], res, C.byref(t),
+                                             density.ctypes.data, albedo.ctypes.data, mag.ctypes.data))
+    return density, albedo, mag
 
 
 def raw_transfer_table() -> np.ndarray:
@@ -809,6 +866,51 @@ class Context:
             torch.cuda.current_stream(self.device).synchronize()
         self._c(load().cvr_set_medium_scalar(self._h, C.byref(d)))
 
+    def set_medium_gradient(self, scalar, table, *, lo, hi, glo, ghi, spacing=(1.0, 1.0, 1.0), sparse=False,
+                            max_density=None, scalar_type=None, res=None, box_min=(-0.5,) * 3, box_max=(0.5,) * 3,
+                            scale=100.0, g=0.0, roughness=(0.1, 0.1), eta=None):
+        """The medium from a scalar field in device memory and a 2-D transfer table over the value
+        and the gradient magnitude, classified inside the build kernels (cvr_set_medium_gradient):
+        the state set_medium_device leaves on device copies of classify_gradient_host(scalar,
+        table, lo, hi, glo, ghi, spacing)'s density and albedo.  table: (m, n, 4) floats in host
+        memory, n >= 2, m >= 2, n * m <= 4096.  scalar and the other arguments are
+        set_medium_scalar's.  Synchronous; torch's current stream is synchronised first, the tensor
+        is only read and may be freed afterwards; a new table means a new call."""
+        is_tensor = hasattr(scalar, "data_ptr")
+        if res is None:
+            if not is_tensor:
+                raise ValueError("set_medium_gradient: res is required with an int address")
+            if len(scalar.shape) != 3:
+                raise ValueError(f"scalar: shape {tuple(scalar.shape)}, expected (z, y, x)")
+            nz, ny, nx = (int(v) for v in scalar.shape)
+        else:
+            nx, ny, nz = (int(v) for v in res)
+        if is_tensor:
+            _check_device_grid("scalar", scalar, (nz, ny, nx), self.device, tuple(_SCALAR_TYPES))
+        if scalar_type is None:
+            name = str(getattr(scalar, "dtype", "")).split(".")[-1]
+            if name not in _SCALAR_TYPES:
+                raise ValueError("set_medium_gradient: scalar_type is required with an int address")
+            scalar_type = _SCALAR_TYPES[name]
+        t, _tab = _gradient_transfer_desc(table, lo, hi, glo, ghi, spacing)
+        d = GradientMediumDesc()
+        d.res[:] = (nx, ny, nz)
+        d.flags = (DEVMED_SPARSE if sparse else 0) | (DEVMED_MAX_DENSITY if max_density is None else 0)
+        d.d_scalar = _device_ptr(scalar)
+        d.scalar_type = scalar_type
+        d.transfer = t
+        d.box_min[:] = box_min
+        d.box_max[:] = box_max
+        d.scale = scale
+        d.max_density = 0.0 if max_density is None else max_density
+        d.g = g
+        d.roughness[:] = roughness
+        d.eta = np.float32(np.float32(1.05) / np.float32(1.01)) if eta is None else eta
+        if is_tensor and type(scalar).__module__.split(".")[0] == "torch":
+            import torch
+            torch.cuda.current_stream(self.device).synchronize()
+        self._c(load().cvr_set_medium_gradient(self._h, C.byref(d)))
+
     def set_environment(self, image, scale: float = 1.0, rotation=None):
         """Light the scene with a latitude-longitude map (cvr_set_environment): an escaping path adds
         its throughput times the map's radiance in its direction.  image: a numpy (H, W, 3|4)
@@ -871,7 +973,7 @@ class Context:
         return ml
 
     def device_medium_ms(self):
-        """Device ms of the last set_medium_device or set_medium_scalar by group, with OPT_TIMING 1
+        """Device ms of the last set_medium_device, set_medium_scalar or set_medium_gradient by group, with OPT_TIMING 1
         (cvr_debug_device_medium_ms): density scan, albedo scan, leaf flags, scans and scatters,
         copy / gather, cells + bounds + brick words."""
         out = (C.c_double * 6)()

@@ -204,9 +204,52 @@ __host__ __device__ inline float scalar_voxel(const void* scalar, uint32_t type,
     default: return static_cast<const float*>(scalar)[i];
   }
 }
+// Gradient-magnitude transfer functions (cvr_set_medium_gradient, cvr_classify_gradient_host).
+// The 2-D classification cvr.h states, the one definition for the host and the build kernels, on
+// the same terms as transfer_classify (and correctly rounded sqrt).  table: m rows of n entries.
+struct GradientParams {
+  uint32_t n, m;  // entries per row (scalar axis), rows (gradient axis)
+  float lo, hi, glo, ghi;
+  float h1[3], h2[3];  // per axis x, y, z: 1.0f / spacing and 0.5f / spacing, rounded once on the host
+};
+// The lower and upper neighbour of coordinate c on an axis of n voxels, and the factor of their
+// difference: the central one when both exist, else the one-sided one.
+__host__ __device__ inline void gradient_neighbours(uint32_t c, uint32_t n, float h1, float h2, uint32_t& cm,
+                                                    uint32_t& cp, float& k) {
+  cm = c > 0u ? c - 1u : c;
+  cp = c + 1u < n ? c + 1u : c;
+  k = cp - cm == 2u ? h2 : h1;
+}
+__host__ __device__ inline float gradient_magnitude(float sxm, float sxp, float kx, float sym, float syp, float ky,
+                                                    float szm, float szp, float kz) {
+  const float gx = (sxp - sxm) * kx, gy = (syp - sym) * ky, gz = (szp - szm) * kz;
+  const float q = (gx * gx + gy * gy) + gz * gz;
+  return __builtin_sqrtf(q);
+}
+// s: the voxel; mag: its gradient magnitude.  Returns (r, g, b, density).
+__host__ __device__ inline float4 gradient_classify(float s, float mag, const float4* table, const GradientParams& p) {
+  const float t = (s - p.lo) / (p.hi - p.lo);
+  float u = t > 0.0f ? t : 0.0f;  // a NaN compares false: 0
+  u = u < 1.0f ? u : 1.0f;
+  const float w = (mag - p.glo) / (p.ghi - p.glo);
+  float v = w > 0.0f ? w : 0.0f;
+  v = v < 1.0f ? v : 1.0f;
+  const float xt = u * (float)(p.n - 1u), yt = v * (float)(p.m - 1u);
+  const uint32_t ci = (uint32_t)__builtin_floorf(xt), i = ci < p.n - 2u ? ci : p.n - 2u;
+  const uint32_t cj = (uint32_t)__builtin_floorf(yt), j = cj < p.m - 2u ? cj : p.m - 2u;
+  const float f = xt - (float)i, h = yt - (float)j;
+  const float4 P = table[j * p.n + i], Q = table[j * p.n + i + 1u];
+  const float4 R = table[(j + 1u) * p.n + i], W = table[(j + 1u) * p.n + i + 1u];
+  float4 a, b, e;
+  a.x = P.x + f * (Q.x - P.x), a.y = P.y + f * (Q.y - P.y), a.z = P.z + f * (Q.z - P.z), a.w = P.w + f * (Q.w - P.w);
+  b.x = R.x + f * (W.x - R.x), b.y = R.y + f * (W.y - R.y), b.z = R.z + f * (W.z - R.z), b.w = R.w + f * (W.w - R.w);
+  e.x = a.x + h * (b.x - a.x), e.y = a.y + h * (b.y - a.y), e.z = a.z + h * (b.z - a.z), e.w = a.w + h * (b.w - a.w);
+  return e;
+}
 // Where the build stages take a voxel's values from: the caller's two arrays (scalar null;
 // albedo null: none), or a scalar field of type scalar_type (cvr.h: CVR_SCALAR_*) classified
-// through a table in device memory.
+// through a table in device memory: the 1-D one by the value (tf), or, with `gradient`, the 2-D
+// one by the value and the gradient magnitude (gtf; res is the field's, the stencil needs it).
 struct VoxelSource {
   const float* density = nullptr;
   const float* albedo = nullptr;
@@ -214,10 +257,14 @@ struct VoxelSource {
   uint32_t scalar_type = 0;
   const float4* table = nullptr;
   TransferParams tf{};
+  bool gradient = false;
+  uint32_t res[3] = {0u, 0u, 0u};
+  GradientParams gtf{};
 };
 // Classified source, dense: one pass over the scalar field that finds what launch_scan_density and
 // launch_scan_albedo find together, and one that stores every voxel's density and albedo
-// (format 1: binary16) into the context's grids.
+// (format 1: binary16) into the context's grids.  n = the voxels; a gradient source is walked by
+// its res, z-planes marching through registers, with the same two results.
 hipError_t launch_scan_classified(const VoxelSource& src, size_t n, uint32_t format, MedScan* out, hipStream_t s);
 hipError_t launch_store_classified(const VoxelSource& src, size_t n, uint32_t format, void* density, void* albedo,
                                    hipStream_t s);

@@ -42,6 +42,9 @@ struct Options {
   std::string devices;  // --devices: a count or a comma list of device ids
   std::string medium_format = "float";  // --medium-format
   std::string transfer_file, transfer_mode = "linear";  // --transfer, --transfer-mode
+  std::string transfer2d_file;         // --transfer2d
+  std::vector<float> gradient_range;   // --gradient-range GLO GHI
+  std::vector<float> voxel_spacing{1.0f, 1.0f, 1.0f};  // --voxel-spacing X Y Z
   std::string envmap;  // --envmap FILE
   float env_scale = 1.0f;
   double env_rotate_y = 0.0;  // degrees
@@ -91,6 +94,14 @@ void usage() {
       "                                     of 'r g b density' spanning byte 0 .. the largest byte, in place of\n"
       "                                     the reference's built-in table (cvr_set_medium_scalar)\n"
       "  --transfer-mode linear|ceil (=linear)  interpolate between table entries, or take entry ceil(x)\n"
+      "  --transfer2d FILE                  Raw scenes (and --synthetic bucky): classify the scene's bytes by value\n"
+      "                                     and gradient magnitude through the 2-D table in FILE: a first line\n"
+      "                                     'n m', then n*m lines of 'r g b density', row by row (row j: gradient\n"
+      "                                     entry j; n >= 2, m >= 2, n*m <= 4096), the columns spanning byte 0 ..\n"
+      "                                     the largest byte (cvr_set_medium_gradient); needs --gradient-range,\n"
+      "                                     excludes --transfer\n"
+      "  --gradient-range GLO GHI           the gradient magnitudes the table's rows span (0 <= GLO < GHI)\n"
+      "  --voxel-spacing X Y Z (=1 1 1)     the voxel spacing the gradient is taken with (each > 0)\n"
       "  --envmap FILE(.hdr|.pfm)           light the scene with a latitude-longitude environment map in place\n"
       "                                     of the constant white one (cvr_set_environment; every device's\n"
       "                                     context keeps a copy; not with naiveMK or --rng-binding thread)\n"
@@ -160,6 +171,19 @@ int parse(int argc, char** argv, Options& o) {
     else if (a == "--medium-format") o.medium_format = need("medium-format");
     else if (a == "--transfer") o.transfer_file = need("transfer");
     else if (a == "--transfer-mode") o.transfer_mode = need("transfer-mode");
+    else if (a == "--transfer2d") o.transfer2d_file = need("transfer2d");
+    else if (a == "--gradient-range" || a == "--voxel-spacing") {
+      const bool range = a == "--gradient-range";
+      std::vector<float>& dst = range ? o.gradient_range : o.voxel_spacing;
+      const size_t want = range ? 2 : 3;
+      dst.clear();
+      while (i + 1 < argc && dst.size() < want && !(argv[i + 1][0] == '-' && argv[i + 1][1] == '-'))
+        dst.push_back(strtof(argv[++i], nullptr));
+      if (dst.size() != want) {
+        fprintf(stderr, "[ConfigParser] Error: %s needs %zu values\n", a.c_str(), want);
+        return 2;
+      }
+    }
     else if (a == "--envmap") o.envmap = need("envmap");
     else if (a == "--env-scale") o.env_scale = strtof(need("env-scale").c_str(), nullptr);
     else if (a == "--env-rotate-y") o.env_rotate_y = strtod(need("env-rotate-y").c_str(), nullptr);
@@ -287,6 +311,59 @@ bool read_transfer(const std::string& path, std::vector<float>& table) {
   return ok;
 }
 
+// --transfer2d FILE: a first data line 'n m', then n * m lines of 'r g b density', row by row
+// (blank lines and lines starting with # are skipped) into table; false with a message when the
+// file cannot be read, a line is not what it should be, or the entries are not n * m.
+bool read_transfer2d(const std::string& path, std::vector<float>& table, unsigned& n, unsigned& m) {
+  FILE* fp = fopen(path.c_str(), "r");
+  if (!fp) {
+    fprintf(stderr, "[ConfigParser] Error: --transfer2d: cannot read '%s'\n", path.c_str());
+    return false;
+  }
+  char line[512];
+  unsigned lineno = 0;
+  bool ok = true, have_size = false;
+  n = m = 0;
+  while (ok && fgets(line, sizeof(line), fp)) {
+    ++lineno;
+    const char* p = line;
+    while (*p == ' ' || *p == '\t') ++p;
+    if (*p == '#' || *p == '\n' || *p == '\r' || *p == 0) continue;
+    char extra;
+    if (!have_size) {
+      if (sscanf(p, "%u %u %c", &n, &m, &extra) != 2) {
+        fprintf(stderr, "[ConfigParser] Error: --transfer2d: line %u of '%s' is not 'n m'\n", lineno, path.c_str());
+        ok = false;
+      } else if (n < 2 || m < 2 || (unsigned long long)n * m > 4096) {
+        fprintf(stderr, "[ConfigParser] Error: --transfer2d: '%s' declares a %u x %u table: n >= 2, m >= 2, n*m <= 4096\n",
+                path.c_str(), n, m);
+        ok = false;
+      }
+      have_size = true;
+      continue;
+    }
+    float v[4];
+    if (sscanf(p, "%f %f %f %f %c", &v[0], &v[1], &v[2], &v[3], &extra) != 4) {
+      fprintf(stderr, "[ConfigParser] Error: --transfer2d: line %u of '%s' is not 'r g b density'\n", lineno,
+              path.c_str());
+      ok = false;
+    }
+    table.insert(table.end(), v, v + 4);
+    if (ok && table.size() > (size_t)4 * n * m) break;  // (too many: counted below)
+  }
+  fclose(fp);
+  if (ok && !have_size) {
+    fprintf(stderr, "[ConfigParser] Error: --transfer2d: '%s' holds no 'n m' line\n", path.c_str());
+    ok = false;
+  }
+  if (ok && table.size() != (size_t)4 * n * m) {
+    fprintf(stderr, "[ConfigParser] Error: --transfer2d: '%s' holds %s %u x %u = %u entries\n", path.c_str(),
+            table.size() < (size_t)4 * n * m ? "fewer than its" : "more than its", n, m, n * m);
+    ok = false;
+  }
+  return ok;
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
@@ -331,6 +408,10 @@ int main(int argc, char** argv) {
     fprintf(stderr, "Error: could not load scene (%d): %s\n", r, cvr_last_error(nullptr));
     return 1;
   }
+  if (!o.transfer2d_file.empty() && !o.transfer_file.empty()) {
+    fprintf(stderr, "[ConfigParser] Error: --transfer2d excludes --transfer\n");
+    return 2;
+  }
   // --transfer: the table, and a scene that has one byte per voxel to classify
   std::vector<float> transfer_table;
   cvr_transfer_desc transfer{};
@@ -350,6 +431,41 @@ int main(int argc, char** argv) {
     transfer.n = (uint32_t)(transfer_table.size() / 4);
     transfer.flags = o.transfer_mode == "ceil" ? CVR_TF_CEIL : 0;
     transfer.table = transfer_table.data();
+  }
+  // --transfer2d: the 2-D table, its gradient range and the voxel spacing
+  std::vector<float> transfer2d_table;
+  cvr_gradient_transfer_desc transfer2d{};
+  if (o.transfer2d_file.empty() && !o.gradient_range.empty()) {
+    fprintf(stderr, "[ConfigParser] Error: --gradient-range applies to --transfer2d only\n");
+    return 2;
+  }
+  if (!o.transfer2d_file.empty()) {
+    const uint8_t* raw = nullptr;
+    size_t n_raw = 0;
+    if (cvr_scene_raw_bytes(scene, &raw, &n_raw) != CVR_OK || !n_raw) {
+      fprintf(stderr, "[ConfigParser] Error: --transfer2d applies to Raw scenes only (and --synthetic bucky): this "
+                      "scene has no scalar bytes to classify\n");
+      return 2;
+    }
+    if (o.gradient_range.size() != 2) {
+      fprintf(stderr, "[ConfigParser] Error: --transfer2d needs --gradient-range GLO GHI\n");
+      return 2;
+    }
+    const float glo = o.gradient_range[0], ghi = o.gradient_range[1];
+    if (!std::isfinite(glo) || !std::isfinite(ghi) || !(glo >= 0.0f) || !(ghi > glo)) {
+      fprintf(stderr, "[ConfigParser] Error: --gradient-range must be finite with 0 <= GLO < GHI\n");
+      return 2;
+    }
+    for (float v : o.voxel_spacing)
+      if (!std::isfinite(v) || !(v > 0.0f)) {
+        fprintf(stderr, "[ConfigParser] Error: --voxel-spacing must be three finite values > 0\n");
+        return 2;
+      }
+    if (!read_transfer2d(o.transfer2d_file, transfer2d_table, transfer2d.n, transfer2d.m)) return 2;
+    transfer2d.table = transfer2d_table.data();
+    transfer2d.glo = glo;
+    transfer2d.ghi = ghi;
+    for (int k = 0; k < 3; ++k) transfer2d.spacing[k] = o.voxel_spacing[k];
   }
   // --envmap: the file's texels and the descriptor every context takes its copy from
   float* env_rgb = nullptr;
@@ -428,6 +544,8 @@ int main(int argc, char** argv) {
     if (!rc && o.medium_format == "half") rc = cvr_set_option(ctx, CVR_OPT_MEDIUM_FORMAT, CVR_FORMAT_F16);
     if (!rc && share) {
       rc = cvr_share_medium(ctx, share);
+    } else if (!rc && transfer2d.n) {
+      rc = cvr_set_medium_scene_gradient(ctx, scene, &transfer2d, sparse ? CVR_DEVMED_SPARSE : 0);
     } else if (!rc && transfer.n) {
       rc = cvr_set_medium_scene_transfer(ctx, scene, &transfer, sparse ? CVR_DEVMED_SPARSE : 0);
     } else if (!rc) {

@@ -1,7 +1,7 @@
 // cvr_medium.cpp - the medium of a context: the host uploads (dense, sparse) and the build from
-// device memory (two arrays, or a scalar field and a transfer function: build_from_device)
-// through one set of stages, the transfer function's host statement, and what the context tells
-// of the result.
+// device memory (two arrays, or a scalar field and a 1-D or gradient-magnitude transfer function:
+// build_from_device) through one set of stages, the transfer functions' host statements, and what
+// the context tells of the result.
 //
 // Each rule is stated once: the shape guards (dense_shape_check, sparse_shape_check), the dense
 // build from the grids on (finish_dense), the sparse build from a leaf table in device memory on
@@ -490,6 +490,30 @@ int source_voxel(cvr_ctx* c, const cvr::VoxelSource& src, const float* host_tabl
   }
   const size_t size = src.scalar_type == CVR_SCALAR_U8 ? 1 : src.scalar_type == CVR_SCALAR_F32 ? 4 : 2;
   alignas(4) unsigned char raw[4];
+  auto read = [&](size_t at, float* s) -> int {
+    HIP_TRY(c, hipMemcpy(raw, static_cast<const unsigned char*>(src.scalar) + at * size, size, hipMemcpyDeviceToHost));
+    *s = cvr::scalar_voxel(raw, src.scalar_type, 0);
+    return CVR_OK;
+  };
+  if (src.gradient) {
+    // the voxel and its up to six in-grid neighbours, as the kernels' stencil reads them
+    const uint32_t nx = src.res[0], ny = src.res[1];
+    const uint32_t q[3] = {(uint32_t)(i % nx), (uint32_t)((i / nx) % ny), (uint32_t)(i / ((size_t)nx * ny))};
+    const size_t stride[3] = {1, nx, (size_t)nx * ny};
+    float s = 0.0f, lo[3], hi[3], k[3];
+    int r = read(i, &s);
+    for (int a = 0; a < 3 && !r; ++a) {
+      uint32_t cm, cp;
+      cvr::gradient_neighbours(q[a], src.res[a], src.gtf.h1[a], src.gtf.h2[a], cm, cp, k[a]);
+      r = read(i - (q[a] - cm) * stride[a], &lo[a]);
+      if (!r) r = read(i + (cp - q[a]) * stride[a], &hi[a]);
+    }
+    if (r) return r;
+    const float mag = cvr::gradient_magnitude(lo[0], hi[0], k[0], lo[1], hi[1], k[1], lo[2], hi[2], k[2]);
+    const float4 e = cvr::gradient_classify(s, mag, reinterpret_cast<const float4*>(host_table), src.gtf);
+    out[0] = e.x, out[1] = e.y, out[2] = e.z, out[3] = 1.0f, out[4] = e.w;
+    return CVR_OK;
+  }
   HIP_TRY(c, hipMemcpy(raw, static_cast<const unsigned char*>(src.scalar) + i * size, size, hipMemcpyDeviceToHost));
   const float4 e = cvr::transfer_classify(cvr::scalar_voxel(raw, src.scalar_type, 0),
                                           reinterpret_cast<const float4*>(host_table), src.tf);
@@ -613,6 +637,35 @@ int transfer_check(std::string* err, const cvr_transfer_desc* t, F after_table) 
   if (!std::isfinite(t->lo) || !std::isfinite(t->hi) || !(t->hi > t->lo))
     return set_err(err, CVR_ERR_INVALID, "transfer range lo %g, hi %g: both finite and hi > lo", (double)t->lo,
                    (double)t->hi);
+  return CVR_OK;
+}
+
+// The 2-D descriptor's refusals in cvr.h's order for cvr_set_medium_gradient (which looks at
+// d_scalar with the table: after_table); the spacing's reciprocals go to *p
+template <class F>
+int gradient_check(std::string* err, const cvr_gradient_transfer_desc* t, F after_table, cvr::GradientParams* p) {
+  if (t->n < 2u || t->m < 2u || (uint64_t)t->n * t->m > 4096u)
+    return set_err(err, CVR_ERR_INVALID, "gradient transfer table of %u x %u entries (n >= 2, m >= 2, n * m <= 4096)",
+                   t->n, t->m);
+  if (t->flags || t->reserved)
+    return set_err(err, CVR_ERR_INVALID, "cvr_gradient_transfer_desc flags 0x%x, reserved 0x%x: both must be 0",
+                   t->flags, t->reserved);
+  if (!t->table) return set_err(err, CVR_ERR_INVALID, "transfer table is NULL");
+  if (int r = after_table()) return r;
+  if (!std::isfinite(t->lo) || !std::isfinite(t->hi) || !(t->hi > t->lo))
+    return set_err(err, CVR_ERR_INVALID, "transfer range lo %g, hi %g: both finite and hi > lo", (double)t->lo,
+                   (double)t->hi);
+  if (!std::isfinite(t->glo) || !std::isfinite(t->ghi) || !(t->glo >= 0.0f) || !(t->ghi > t->glo))
+    return set_err(err, CVR_ERR_INVALID, "gradient range glo %g, ghi %g: both finite, glo >= 0 and ghi > glo",
+                   (double)t->glo, (double)t->ghi);
+  for (int k = 0; k < 3; ++k)
+    if (!std::isfinite(t->spacing[k]) || !(t->spacing[k] > 0.0f))
+      return set_err(err, CVR_ERR_INVALID, "voxel spacing[%d] = %g: finite and > 0", k, (double)t->spacing[k]);
+  *p = cvr::GradientParams{t->n, t->m, t->lo, t->hi, t->glo, t->ghi, {}, {}};
+  for (int k = 0; k < 3; ++k) {
+    p->h1[k] = 1.0f / t->spacing[k];
+    p->h2[k] = 0.5f / t->spacing[k];
+  }
   return CVR_OK;
 }
 
@@ -927,6 +980,119 @@ int cvr_set_medium_scalar(cvr_ctx* c, const cvr_scalar_medium_desc* d) {
   src.table = d_table;
   src.tf = {t->n, t->flags, t->lo, t->hi};
   return build_from_device(c, {view_of(*d), d->flags, nullptr, d->max_density, &table[0].x}, src, b, tmp);
+}
+
+int cvr_classify_gradient_host(const void* scalar, uint32_t scalar_type, const uint32_t res[3],
+                               const cvr_gradient_transfer_desc* t, float* density, float* albedo,
+                               float* gradient_magnitude) {
+  if (!t || !res) return set_err(nullptr, CVR_ERR_INVALID, "NULL argument");
+  const uint32_t nx = res[0], ny = res[1], nz = res[2];
+  const size_t n_voxels = (size_t)nx * ny * nz;
+  if (n_voxels && !scalar) return set_err(nullptr, CVR_ERR_INVALID, "NULL argument");
+  if (scalar_type > CVR_SCALAR_I16) return set_err(nullptr, CVR_ERR_INVALID, "unknown scalar_type %u", scalar_type);
+  cvr::GradientParams p;
+  if (int r = gradient_check(nullptr, t, [] { return CVR_OK; }, &p)) return r;
+  // (the table as float4: copied, the caller's need not be 16-byte aligned)
+  std::vector<float4> table((size_t)t->n * t->m);
+  memcpy(table.data(), t->table, table.size() * sizeof(float4));
+  for (uint32_t z = 0; z < nz; ++z) {
+    uint32_t zm, zp;
+    float kz;
+    cvr::gradient_neighbours(z, nz, p.h1[2], p.h2[2], zm, zp, kz);
+    for (uint32_t y = 0; y < ny; ++y) {
+      uint32_t ym, yp;
+      float ky;
+      cvr::gradient_neighbours(y, ny, p.h1[1], p.h2[1], ym, yp, ky);
+      const size_t row = ((size_t)z * ny + y) * nx, rym = ((size_t)z * ny + ym) * nx, ryp = ((size_t)z * ny + yp) * nx,
+                   rzm = ((size_t)zm * ny + y) * nx, rzp = ((size_t)zp * ny + y) * nx;
+      for (uint32_t x = 0; x < nx; ++x) {
+        uint32_t xm, xp;
+        float kx;
+        cvr::gradient_neighbours(x, nx, p.h1[0], p.h2[0], xm, xp, kx);
+        auto S = [&](size_t i) { return cvr::scalar_voxel(scalar, scalar_type, i); };
+        const float mag = cvr::gradient_magnitude(S(row + xm), S(row + xp), kx, S(rym + x), S(ryp + x), ky, S(rzm + x),
+                                                  S(rzp + x), kz);
+        const float4 e = cvr::gradient_classify(S(row + x), mag, table.data(), p);
+        const size_t i = row + x;
+        if (density) density[i] = e.w;
+        if (albedo) albedo[4 * i] = e.x, albedo[4 * i + 1] = e.y, albedo[4 * i + 2] = e.z, albedo[4 * i + 3] = 1.0f;
+        if (gradient_magnitude) gradient_magnitude[i] = mag;
+      }
+    }
+  }
+  return CVR_OK;
+}
+
+int cvr_set_medium_gradient(cvr_ctx* c, const cvr_gradient_medium_desc* d) {
+  if (!c || !d) return set_err(c ? &c->err : nullptr, CVR_ERR_INVALID, "NULL argument");
+  CVR_NOT_IN_SESSION(c, "cvr_set_medium_gradient");
+  const uint32_t* res = d->res;
+  const bool sparse = (d->flags & CVR_DEVMED_SPARSE) != 0;
+  SparseBuild b{};
+  int r = sparse ? sparse_shape_check(c, res, &b.g) : dense_shape_check(c, res, (uint32_t)c->medium_format);
+  if (r) return r;
+  if (d->flags & ~(uint32_t)(CVR_DEVMED_SPARSE | CVR_DEVMED_MAX_DENSITY))
+    return set_err(&c->err, CVR_ERR_INVALID, "unknown cvr_gradient_medium_desc flags 0x%x", d->flags);
+  if (d->scalar_type > CVR_SCALAR_I16)
+    return set_err(&c->err, CVR_ERR_INVALID, "unknown scalar_type %u", d->scalar_type);
+  const cvr_gradient_transfer_desc* t = &d->transfer;
+  cvr::VoxelSource src;
+  r = gradient_check(&c->err, t, [&]() -> int {
+    return d->d_scalar ? CVR_OK : set_err(&c->err, CVR_ERR_INVALID, "d_scalar is NULL");
+  }, &src.gtf);
+  if (r) return r;
+  if ((r = ensure_device(c))) return r;
+  if (!device_readable(c, d->d_scalar))
+    return set_err(&c->err, CVR_ERR_INVALID, "d_scalar is not device-accessible memory of device %d", c->device);
+  const size_t size = d->scalar_type == CVR_SCALAR_U8 ? 1 : d->scalar_type == CVR_SCALAR_F32 ? 4 : 2;
+  if ((uintptr_t)d->d_scalar & (size - 1))
+    return set_err(&c->err, CVR_ERR_INVALID, "d_scalar must be %zu-byte aligned", size);
+  // the table goes to the device once; the kernels stage it in LDS per workgroup
+  const size_t entries = (size_t)t->n * t->m;
+  DevTemps tmp;
+  float4* d_table = nullptr;
+  HIP_TRY(c, tmp.alloc((void**)&d_table, entries * sizeof(float4)));
+  HIP_TRY(c, hipMemcpy(d_table, t->table, entries * sizeof(float4), hipMemcpyHostToDevice));
+  std::vector<float4> table(entries);
+  memcpy(table.data(), t->table, entries * sizeof(float4));
+  src.scalar = d->d_scalar;
+  src.scalar_type = d->scalar_type;
+  src.table = d_table;
+  src.gradient = true;
+  memcpy(src.res, res, sizeof(src.res));
+  return build_from_device(c, {view_of(*d), d->flags, nullptr, d->max_density, &table[0].x}, src, b, tmp);
+}
+
+int cvr_set_medium_scene_gradient(cvr_ctx* c, const cvr_scene* scene, const cvr_gradient_transfer_desc* t,
+                                  uint32_t flags) {
+  if (!c || !scene || !t) return set_err(c ? &c->err : nullptr, CVR_ERR_INVALID, "NULL argument");
+  const uint8_t* bytes = nullptr;
+  size_t n = 0;
+  cvr_medium_desc md{};
+  int r = cvr_scene_raw_bytes(scene, &bytes, &n);
+  if (!r) r = cvr_scene_medium(scene, &md);
+  if (r || !n || n != (size_t)md.res[0] * md.res[1] * md.res[2])
+    return set_err(&c->err, CVR_ERR_INVALID, "the scene has no raw bytes (one per voxel): not a Raw scene");
+  if ((r = ensure_device(c))) return r;
+  DevTemps tmp;
+  void* d_bytes = nullptr;
+  HIP_TRY(c, tmp.alloc(&d_bytes, n));
+  HIP_TRY(c, hipMemcpy(d_bytes, bytes, n, hipMemcpyHostToDevice));
+  cvr_gradient_medium_desc d{};
+  memcpy(d.res, md.res, sizeof(d.res));
+  d.flags = flags | CVR_DEVMED_MAX_DENSITY;
+  d.d_scalar = d_bytes;
+  d.scalar_type = CVR_SCALAR_U8;
+  d.transfer = *t;
+  d.transfer.lo = 0.0f;
+  d.transfer.hi = (float)*std::max_element(bytes, bytes + n);
+  memcpy(d.box_min, md.box_min, sizeof(d.box_min));
+  memcpy(d.box_max, md.box_max, sizeof(d.box_max));
+  d.scale = md.scale;
+  d.g = md.g;
+  d.roughness[0] = md.roughness[0], d.roughness[1] = md.roughness[1];
+  d.eta = md.eta;
+  return cvr_set_medium_gradient(c, &d);
 }
 
 int cvr_set_medium_scene_transfer(cvr_ctx* c, const cvr_scene* scene, const cvr_transfer_desc* t, uint32_t flags) {

@@ -1,7 +1,9 @@
-// cvr_medium_build.hip - the device-side front end of cvr_set_medium_device and
-// cvr_set_medium_scalar (gfx950): what the host uploads decide with loops over every voxel or
-// leaf, decided here from a voxel source in device memory, the caller's two arrays or a scalar
-// field classified through a transfer table staged in LDS.  Value scans (majorant, binary16 overflow, uniform albedo), the dense -> 8^3 leaves
+// cvr_medium_build.hip - the device-side front end of cvr_set_medium_device,
+// cvr_set_medium_scalar and cvr_set_medium_gradient (gfx950): what the host uploads decide with
+// loops over every voxel or leaf, decided here from a voxel source in device memory, the caller's
+// two arrays or a scalar field classified through a transfer table staged in LDS (1-D by the
+// value, or 2-D by the value and the gradient magnitude of a 6-neighbour stencil).  Value scans
+// (majorant, binary16 overflow, uniform albedo), the dense -> 8^3 leaves
 // rule of cvr.h (leaf flags, exclusive scan, gather), the cell-leaf table and the empty-region
 // mask.  The cells, bounds and brick words are then built by cvr_kernels.hip's kernels, unchanged.
 //
@@ -65,6 +67,8 @@ struct ArraySrc {
     d = D[i];
     if (A) a = A[i];
   }
+  // (the leaf kernels name a voxel by its coordinates too: only a stencil needs them)
+  __device__ void voxel(uint32_t, uint32_t, uint32_t, size_t i, float& d, float4& a) const { voxel(i, d, a); }
 };
 // A scalar field of type T classified through the transfer table (cvr.h; transfer_classify is the
 // statement).  stage() copies the table into the workgroup's dynamic LDS, n x 16 bytes, once;
@@ -90,6 +94,47 @@ struct ScalarSrc {
     a = make_float4(e.x, e.y, e.z, 1.0f);
   }
   __device__ void voxel(size_t i, float& d, float4& a) const { classified((float)S[i], d, a); }
+  __device__ void voxel(uint32_t, uint32_t, uint32_t, size_t i, float& d, float4& a) const { voxel(i, d, a); }
+};
+// A scalar field of type T classified through the 2-D table by its value and its gradient
+// magnitude (cvr.h; gradient_magnitude and gradient_classify are the statement).  stage() copies
+// the m x n table into the workgroup's dynamic LDS once.  voxel() reads the voxel and its up to
+// six in-grid neighbours from the field, wherever they lie: the gradient is the field's.
+template <class T>
+struct GradientSrc {
+  using Scalar = T;
+  const T* __restrict__ S;
+  const float4* __restrict__ table;
+  GradientParams p;
+  uint32_t nx, ny, nz;
+  uint32_t albedo;  // 0: the colours are not looked at (has_albedo() false)
+  const float4* lds;
+  __device__ void stage() {
+    extern __shared__ float4 s_table[];
+    for (uint32_t k = threadIdx.x; k < p.n * p.m; k += blockDim.x) s_table[k] = table[k];
+    __syncthreads();
+    lds = s_table;
+  }
+  __device__ bool has_albedo() const { return albedo != 0u; }
+  __device__ void classified(float s, float mag, float& d, float4& a) const {
+    const float4 e = gradient_classify(s, mag, lds, p);
+    d = e.w;
+    a = make_float4(e.x, e.y, e.z, 1.0f);
+  }
+  __device__ void voxel(uint32_t x, uint32_t y, uint32_t z, size_t i, float& d, float4& a) const {
+    uint32_t xm, xp, ym, yp, zm, zp;
+    float kx, ky, kz;
+    gradient_neighbours(x, nx, p.h1[0], p.h2[0], xm, xp, kx);
+    gradient_neighbours(y, ny, p.h1[1], p.h2[1], ym, yp, ky);
+    gradient_neighbours(z, nz, p.h1[2], p.h2[2], zm, zp, kz);
+    const size_t row = ((size_t)z * ny + y) * nx;
+    const float mag = gradient_magnitude((float)S[row + xm], (float)S[row + xp], kx,
+                                         (float)S[((size_t)z * ny + ym) * nx + x],
+                                         (float)S[((size_t)z * ny + yp) * nx + x], ky,
+                                         (float)S[((size_t)zm * ny + y) * nx + x],
+                                         (float)S[((size_t)zp * ny + y) * nx + x], kz);
+    classified((float)S[i], mag, d, a);
+  }
 };
 
 // ----------------------------------------------------------- value scans ---
@@ -283,6 +328,84 @@ __global__ __launch_bounds__(256) void k_classified(ScalarSrc<T> src, size_t n, 
   if (!kStore) commit_in_table_lds(ds, as, out);
 }
 
+// The gradient source's two dense passes (kStore as above).  The hand-round of k_classified does
+// not carry a stencil, so the field is walked by coordinates here: a task is 256 consecutive x of
+// one y over kGradZ consecutive z, and a work-item keeps its voxel's z - 1, z, z + 1 in registers
+// while it marches along z, so the z neighbours cost one load per voxel and step.  The x
+// neighbours come from the adjacent lanes (a load only in a wave's first and last lane), the y
+// neighbours are two loads of rows that the tasks of y - 1 and y + 1 read as their own (cache
+// hits, not memory traffic, when those tasks run close in time on one XCD: consecutive tasks are
+// consecutive x-runs, then consecutive y).  A wave's loads and stores of a step are 64 consecutive voxels.
+constexpr uint32_t kGradZ = 16;
+template <class T, bool kStore>
+__global__ __launch_bounds__(256) void k_gradient(GradientSrc<T> src, uint32_t format, void* __restrict__ density,
+                                                  void* __restrict__ albedo, MedScan* __restrict__ out) {
+  src.stage();
+  float d0;
+  float4 a0;
+  src.voxel(0u, 0u, 0u, 0, d0, a0);
+  DensityScan ds;
+  AlbedoScan as(a0);
+  const uint32_t nx = src.nx, ny = src.ny, nz = src.nz;
+  const T* __restrict__ S = src.S;
+  const uint32_t nxc = (nx + 255u) / 256u, nzc = (nz + kGradZ - 1u) / kGradZ;
+  const size_t ntasks = (size_t)nxc * ny * nzc;
+  const uint32_t lane = threadIdx.x & 63u;
+  // Workgroups are observed to be dealt round-robin over the 8 XCDs, each with an L2 of its own
+  // (nothing promises it: this is for speed only, any placement computes the same).  The block
+  // index is turned so that the workgroups of one XCD take consecutive tasks, and the rows of
+  // y - 1 and y + 1 are then found in the L2 that a neighbour task has just filled.
+  const uint32_t nb = gridDim.x;
+  const uint32_t vb = (nb & 7u) ? blockIdx.x : (blockIdx.x & 7u) * (nb >> 3) + (blockIdx.x >> 3);
+  for (size_t t = vb; t < ntasks; t += nb) {
+    const uint32_t xc = (uint32_t)(t % nxc), y = (uint32_t)((t / nxc) % ny), zc = (uint32_t)(t / ((size_t)nxc * ny));
+    const uint32_t x0 = xc * 256u + threadIdx.x;
+    const bool in = x0 < nx;
+    const uint32_t x = in ? x0 : nx - 1u;  // (lanes past the row read its last voxel and keep nothing)
+    uint32_t xm, xp, ym, yp;
+    float kx, ky;
+    gradient_neighbours(x, nx, src.p.h1[0], src.p.h2[0], xm, xp, kx);
+    gradient_neighbours(y, ny, src.p.h1[1], src.p.h2[1], ym, yp, ky);
+    const uint32_t z0 = zc * kGradZ, z1 = z0 + kGradZ < nz ? z0 + kGradZ : nz;
+    auto at = [&](uint32_t xx, uint32_t yy, uint32_t zz) { return (float)S[((size_t)zz * ny + yy) * nx + xx]; };
+    float prev = at(x, y, z0 > 0u ? z0 - 1u : z0), cur = at(x, y, z0);
+    for (uint32_t z = z0; z < z1; ++z) {
+      uint32_t zm, zp;
+      float kz;
+      gradient_neighbours(z, nz, src.p.h1[2], src.p.h2[2], zm, zp, kz);
+      const float next = zp != z ? at(x, y, zp) : cur;
+      const float sym = ym != y ? at(x, ym, z) : cur, syp = yp != y ? at(x, yp, z) : cur;
+      // every lane of the wave takes part in the two moves (the loop bounds are the workgroup's)
+      const float left = __shfl_up(cur, 1), right = __shfl_down(cur, 1);
+      const float sxm = xm == x ? cur : lane != 0u ? left : at(xm, y, z);
+      const float sxp = xp == x ? cur : lane != 63u ? right : at(xp, y, z);
+      const float mag = gradient_magnitude(sxm, sxp, kx, sym, syp, ky, prev, next, kz);
+      if (in) {
+        const size_t i = ((size_t)z * ny + y) * nx + x;
+        float d;
+        float4 a;
+        src.classified(cur, mag, d, a);
+        if (!kStore) {
+          ds.take(d, i, format);
+          as.take(a, i, format);
+        } else if (format) {
+          uint2 h;
+          h.x = half_bits(a.x) | half_bits(a.y) << 16;
+          h.y = half_bits(a.z) | half_bits(a.w) << 16;
+          reinterpret_cast<_Float16*>(density)[i] = (_Float16)d;
+          reinterpret_cast<uint2*>(albedo)[i] = h;
+        } else {
+          reinterpret_cast<float*>(density)[i] = d;
+          reinterpret_cast<float4*>(albedo)[i] = a;
+        }
+      }
+      prev = cur;
+      cur = next;
+    }
+  }
+  if (!kStore) commit_in_table_lds(ds, as, out);
+}
+
 // The context's albedo grid filled with one value (CVR_DEVMED_CONST_ALBEDO, dense).
 __global__ __launch_bounds__(256) void k_fill_albedo(void* __restrict__ dst, size_t n, uint32_t format, float4 v) {
   uint2 h;
@@ -317,7 +440,7 @@ __global__ __launch_bounds__(256) void k_leaf_flags(Src src, uint32_t nx, uint32
   if (with_albedo) {
     float d;
     float4 f;
-    src.voxel(0, d, f);
+    src.voxel(0u, 0u, 0u, 0, d, f);
     b0 = __float_as_uint(f.x), b1 = __float_as_uint(f.y), b2 = __float_as_uint(f.z), b3 = __float_as_uint(f.w);
   }
   DensityScan ds;
@@ -334,7 +457,7 @@ __global__ __launch_bounds__(256) void k_leaf_flags(Src src, uint32_t nx, uint32
           const size_t i = ((size_t)z * ny + y) * nx + x;
           float d;
           float4 a;
-          src.voxel(i, d, a);
+          src.voxel(x, y, z, i, d, a);
           if (kScan) {
             ds.take(d, i, format);
             as.take(a, i, format);
@@ -518,7 +641,7 @@ __global__ __launch_bounds__(256) void k_gather_leaves(Src src, uint32_t nx, uin
     const bool in = x < nx && y < ny && z < nz;
     float d = 0.0f;
     float4 a = bg;
-    if (in) src.voxel(((size_t)z * ny + y) * nx + x, d, a);
+    if (in) src.voxel(x, y, z, ((size_t)z * ny + y) * nx + x, d, a);
     if (kStore) {
       if (format)
         reinterpret_cast<_Float16*>(leaf_density)[p] = (_Float16)d;
@@ -552,9 +675,21 @@ uint32_t scan_grid(size_t n) { return (uint32_t)std::min<size_t>((n + 255) / 256
 template <class F>
 void with_source(const VoxelSource& v, bool with_albedo, F f) {
   // (the classified scan's reduction reuses the table's LDS: at least 8 entries)
-  const size_t lds = (size_t)std::max(v.tf.n, 8u) * sizeof(float4);
+  const size_t lds = (size_t)std::max(v.gradient ? v.gtf.n * v.gtf.m : v.tf.n, 8u) * sizeof(float4);
   const uint32_t al = with_albedo ? 1u : 0u;
-  if (!v.scalar)
+  auto gradient = [&](auto* S) {
+    using T = std::remove_cv_t<std::remove_pointer_t<decltype(S)>>;
+    f(GradientSrc<T>{S, v.table, v.gtf, v.res[0], v.res[1], v.res[2], al, nullptr}, lds);
+  };
+  if (v.gradient && v.scalar_type == 1u)
+    gradient(static_cast<const uint8_t*>(v.scalar));
+  else if (v.gradient && v.scalar_type == 2u)
+    gradient(static_cast<const uint16_t*>(v.scalar));
+  else if (v.gradient && v.scalar_type == 3u)
+    gradient(static_cast<const int16_t*>(v.scalar));
+  else if (v.gradient)
+    gradient(static_cast<const float*>(v.scalar));
+  else if (!v.scalar)
     f(ArraySrc{v.density, with_albedo ? reinterpret_cast<const float4*>(v.albedo) : nullptr}, (size_t)0);
   else if (v.scalar_type == 1u)
     f(ScalarSrc<uint8_t>{static_cast<const uint8_t*>(v.scalar), v.table, v.tf, al, nullptr}, lds);
@@ -571,10 +706,18 @@ hipError_t launch_classified(const VoxelSource& v, size_t n, uint32_t format, vo
                              MedScan* out, hipStream_t s) {
   if (!v.scalar) return hipErrorInvalidValue;
   with_source(v, true, [&](auto src, size_t lds) {
-    using T = typename decltype(src)::Scalar;
-    if constexpr (!std::is_void_v<T>)
+    using Src = decltype(src);
+    using T = typename Src::Scalar;
+    if constexpr (std::is_same_v<Src, ScalarSrc<T>>) {
       hipLaunchKernelGGL((k_classified<T, kStore>), dim3(scan_grid(n)), dim3(256), lds, s, src, n, format, density,
                          albedo, out);
+    } else if constexpr (!std::is_void_v<T>) {
+      const size_t ntasks = (size_t)((v.res[0] + 255u) / 256u) * v.res[1] * ((v.res[2] + kGradZ - 1u) / kGradZ);
+      // (a multiple of 8 workgroups where there are 8: the kernel's XCD turn needs one)
+      const uint32_t grid = (uint32_t)std::min<size_t>(ntasks, 4096);
+      hipLaunchKernelGGL((k_gradient<T, kStore>), dim3(grid >= 8u ? grid & ~7u : grid), dim3(256), lds, s,
+                         src, format, density, albedo, out);
+    }
   });
   return hipGetLastError();
 }

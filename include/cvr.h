@@ -33,6 +33,9 @@ extern "C" {
  *              6 + CVR_HAS_TRANSFER (likewise): cvr_transfer_desc, cvr_scalar_medium_desc,
  *                  cvr_classify_host, cvr_raw_transfer_table, cvr_set_medium_scalar,
  *                  cvr_set_medium_scene_transfer
+ *              6 + CVR_HAS_GRADIENT_TRANSFER (likewise): cvr_gradient_transfer_desc,
+ *                  cvr_gradient_medium_desc, cvr_classify_gradient_host, cvr_set_medium_gradient,
+ *                  cvr_set_medium_scene_gradient
  *              6 + CVR_HAS_ENVMAP (likewise): cvr_environment_desc, cvr_set_environment,
  *                  cvr_clear_environment, cvr_environment_info, cvr_environment_eval*, cvr_trace_env,
  *                  cvr_read_image, cvr_free_image
@@ -720,9 +723,9 @@ typedef struct cvr_device_medium_desc {
 } cvr_device_medium_desc; /* 96 bytes */
 int cvr_set_medium_device(cvr_ctx* ctx, const cvr_device_medium_desc* medium);
 /* Measurement only: with CVR_OPT_TIMING 1, the device milliseconds (HIP events) the last
- * cvr_set_medium_device or cvr_set_medium_scalar spent in {density scan, albedo scan, leaf flags, scans and scatters,
- * copy / conversion / gather, cells + bounds + brick words}; zeros otherwise.  Timing adds a host
- * synchronisation per group. */
+ * cvr_set_medium_device, cvr_set_medium_scalar or cvr_set_medium_gradient spent in {density scan,
+ * albedo scan, leaf flags, scans and scatters, copy / conversion / gather, cells + bounds + brick
+ * words}; zeros otherwise.  Timing adds a host synchronisation per group. */
 int cvr_debug_device_medium_ms(const cvr_ctx* ctx, double out_ms[6]);
 
 /* What was built, by either upload path (a shared medium: the source's).  mask: the empty-region
@@ -816,6 +819,94 @@ int cvr_set_medium_scalar(cvr_ctx* ctx, const cvr_scalar_medium_desc* medium);
  * BSDF parameters are the scene's; max_density is found on the device (flags: CVR_DEVMED_SPARSE
  * or 0).  A scene without raw bytes: CVR_ERR_INVALID. */
 int cvr_set_medium_scene_transfer(cvr_ctx* ctx, const cvr_scene* scene, const cvr_transfer_desc* transfer,
+                                  uint32_t flags);
+
+/* ---- gradient-magnitude transfer functions: 2-D tables classified on the device (extension
+ *      within ABI 6: CVR_HAS_GRADIENT_TRANSFER) -- */
+/* A scalar field and a table of m rows of n entries (r, g, b, density) give every voxel a
+ * density and an albedo from its value and the magnitude of its gradient, so that a homogeneous
+ * region and a material boundary of the same value can be told apart.  Row j belongs to gradient
+ * entry j; entry (j, i) is at j * n + i.  Every operation is fp32 +, -, x, /, sqrtf, floorf and
+ * comparisons in the order written here, no fused multiply-add, / and sqrtf correctly rounded, so
+ * the build kernels and cvr_classify_gradient_host return the same bits (one definition compiles
+ * for both, cvr_kernels.h).  For voxel (x, y, z) of a field of res = (nx, ny, nz), S(.) the voxel
+ * converted to float (exact for the integer types):
+ *   xm = x > 0 ? x - 1 : x, xp = x + 1 < nx ? x + 1 : x;
+ *   kx = (xp - xm == 2) ? hx2 : hx1, with hx1 = 1.0f / spacing[0] and hx2 = 0.5f / spacing[0]
+ *        computed once on the host in fp32;
+ *   gx = (S(xp, y, z) - S(xm, y, z)) * kx: a central difference in the interior, a one-sided one
+ *        on a face; on an axis of one voxel xp == xm and a finite field gives 0;
+ *   gy, gz likewise with spacing[1], spacing[2];
+ *   q = (gx * gx + gy * gy) + gz * gz, mag = sqrtf(q);
+ *   w = (mag - glo) / (ghi - glo), v = w > 0 ? w : 0, then v = v < 1 ? v : 1 (a NaN gives 0,
+ *        +inf gives 1);
+ *   u from s = S(x, y, z), lo, hi exactly as the 1-D statement above, xt = u * (float)(n - 1);
+ *   i = min((uint)floorf(xt), n - 2), f = xt - (float)i;
+ *   yt = v * (float)(m - 1), j = min((uint)floorf(yt), m - 2), h = yt - (float)j;
+ *   P = entry (j, i), Q = (j, i + 1), R = (j + 1, i), W = (j + 1, i + 1); per component c of r, g,
+ *   b, density: a_c = P_c + f * (Q_c - P_c), b_c = R_c + f * (W_c - R_c), e_c = a_c + h * (b_c - a_c)
+ *   (each one subtract, one multiply, one add, in that order);
+ *   albedo = (e_r, e_g, e_b, 1.0f), density = e's density.
+ * There is no CEIL and no DENSITY_U mode in 2-D: flags must be 0.
+ * Not supported: clip planes and crop boxes, gradient-based shading, classification at render
+ * time (the medium is classified once, when it is built), keeping the field. */
+#define CVR_HAS_GRADIENT_TRANSFER 1
+typedef struct cvr_gradient_transfer_desc {
+  uint32_t n, m;      /* n >= 2, m >= 2, n * m <= 4096 (64 KB of LDS, the 1-D table's budget) */
+  uint32_t flags;     /* 0 */
+  uint32_t reserved;  /* 0 */
+  const float* table; /* HOST, m * n * 4 floats */
+  float lo, hi;       /* finite, hi > lo */
+  float glo, ghi;     /* finite, 0 <= glo < ghi */
+  float spacing[3];   /* finite, > 0; (1, 1, 1): the gradient per voxel */
+} cvr_gradient_transfer_desc; /* 56 bytes */
+/* Host only, no GPU: the statement above over a field of res = (nx, ny, nz) voxels in host memory
+ * (x fastest).  density and gradient_magnitude (res product floats each) and albedo (4 floats per
+ * voxel) may each be NULL.  The descriptor is checked as cvr_set_medium_gradient checks it. */
+int cvr_classify_gradient_host(const void* scalar, uint32_t scalar_type, const uint32_t res[3],
+                               const cvr_gradient_transfer_desc* transfer, float* density, float* albedo,
+                               float* gradient_magnitude);
+/* cvr_set_medium_scalar with the statement above: its contract, with cvr_classify_gradient_host in
+ * the place of cvr_classify_host.  The context ends in the state cvr_set_medium_device leaves on
+ * device copies of that call's density and albedo (equal cvr_medium_info and cvr_medium_layout,
+ * the same paths bit for bit, dense and sparse, in both medium formats), and everything derived
+ * from values is derived from the classified values: the majorant, the binary16 overflow refusal
+ * with the host call's code and message, uniform-albedo detection, the leaf rule with voxel
+ * (0,0,0)'s classified albedo as background, and dropping the leaf albedo pool.  No dense array of
+ * the classified medium or of the gradient exists outside the context's storage.  A sparse build
+ * reads in-grid neighbours from the field even where they lie in a leaf that does not exist: the
+ * gradient is the field's.
+ * flags: CVR_DEVMED_SPARSE and / or CVR_DEVMED_MAX_DENSITY.
+ * Refusals, all CVR_ERR_INVALID with the previous medium kept, in this order:
+ *   1. the host call's shape guards, from res alone and before any pointer is looked at;
+ *   2. unknown flags (CVR_DEVMED_CONST_ALBEDO is one here) or scalar_type;
+ *   3. n < 2, m < 2 or n * m > 4096;
+ *   4. transfer flags or reserved not 0;
+ *   5. a NULL table or a NULL d_scalar;
+ *   6. lo / hi not finite, or hi <= lo;
+ *   7. glo / ghi not finite, glo < 0 or ghi <= glo;
+ *   8. a spacing that is not finite or not > 0;
+ *   9. a d_scalar that is not device-accessible memory of the context's device or is misaligned
+ *      for its type.
+ * Inside an adaptive session: CVR_ERR_STATE.
+ * Synchronous on the context's stream; the field is only read and may be freed afterwards, the
+ * context does not keep it.  cvr_debug_device_medium_ms reports this call's groups as it reports
+ * cvr_set_medium_scalar's. */
+typedef struct cvr_gradient_medium_desc {
+  uint32_t res[3];
+  uint32_t flags;
+  const void* d_scalar; /* device, res product elements of scalar_type, x fastest, contiguous */
+  uint32_t scalar_type; /* CVR_SCALAR_* */
+  uint32_t reserved;    /* 0 */
+  cvr_gradient_transfer_desc transfer;
+  float box_min[3], box_max[3];
+  float scale, max_density, g, roughness[2], eta;
+} cvr_gradient_medium_desc; /* 136 bytes */
+int cvr_set_medium_gradient(cvr_ctx* ctx, const cvr_gradient_medium_desc* medium);
+/* cvr_set_medium_gradient on a Raw scene's bytes, as cvr_set_medium_scene_transfer: CVR_SCALAR_U8
+ * with lo 0 and hi the largest byte (transfer's lo and hi are ignored); glo, ghi and spacing are
+ * the descriptor's.  flags: CVR_DEVMED_SPARSE or 0.  A scene without raw bytes: CVR_ERR_INVALID. */
+int cvr_set_medium_scene_gradient(cvr_ctx* ctx, const cvr_scene* scene, const cvr_gradient_transfer_desc* transfer,
                                   uint32_t flags);
 
 /* ---- environment-map lighting (extension within ABI 6: CVR_HAS_ENVMAP) -- */
