@@ -12,6 +12,7 @@ from ._lib import (  # noqa: F401
     OPT_MOMENTS, AdaptiveDesc, AdaptiveResult, AdaptiveSession, block_error,
     DenoiseDesc, denoise_host,
     DeviceMediumDesc, MediumLayout, DEVMED_SPARSE, DEVMED_CONST_ALBEDO, DEVMED_MAX_DENSITY,
+    MEDIUM_ARRAYS, build_geometry,
     TransferDesc, ScalarMediumDesc, classify_host, raw_transfer_table,
     GradientTransferDesc, GradientMediumDesc, classify_gradient_host,
     SCALAR_F32, SCALAR_U8, SCALAR_U16, SCALAR_I16, TF_CEIL, TF_DENSITY_U,
@@ -28,6 +29,7 @@ __all__ = [
     "OPT_MOMENTS", "AdaptiveDesc", "AdaptiveResult", "AdaptiveSession", "block_error",
     "DenoiseDesc", "denoise_host",
     "DeviceMediumDesc", "MediumLayout", "DEVMED_SPARSE", "DEVMED_CONST_ALBEDO", "DEVMED_MAX_DENSITY",
+    "MEDIUM_ARRAYS", "build_geometry",
     "TransferDesc", "ScalarMediumDesc", "classify_host", "raw_transfer_table",
     "GradientTransferDesc", "GradientMediumDesc", "classify_gradient_host",
     "SCALAR_F32", "SCALAR_U8", "SCALAR_U16", "SCALAR_I16", "TF_CEIL", "TF_DENSITY_U",

@@ -137,6 +137,11 @@ class DenoiseDesc(C.Structure):
 
 
 DEVMED_SPARSE, DEVMED_CONST_ALBEDO, DEVMED_MAX_DENSITY = 1, 2, 4
+# cvr_debug_copy_medium's arrays (CVR_MEDIUM_*), by index
+MEDIUM_ARRAYS = ("density", "albedo", "cells", "bounds", "leaf_table", "leaf_density", "leaf_albedo", "cell_slots",
+                 "sparse_cells", "brick_words", "mask")
+MEDIUM_BOUNDS = 3
+_MEDIUM_VALUE_ARRAYS = ("density", "albedo", "cells", "leaf_density", "leaf_albedo", "sparse_cells")
 
 
 class DeviceMediumDesc(C.Structure):
@@ -315,6 +320,8 @@ def load() -> C.CDLL:
         "cvr_set_medium_device": (I32, [P, C.POINTER(DeviceMediumDesc)]),
         "cvr_medium_layout": (I32, [P, C.POINTER(MediumLayout)]),
         "cvr_debug_device_medium_ms": (I32, [P, C.POINTER(C.c_double)]),
+        "cvr_debug_copy_medium": (I32, [P, I32, P, C.c_size_t, C.POINTER(C.c_size_t)]),
+        "cvr_debug_build_geometry": (I32, [C.POINTER(U32)]),
         "cvr_classify_host": (I32, [P, U32, C.c_size_t, C.POINTER(TransferDesc), P, P]),
         "cvr_raw_transfer_table": (I32, [FP]),
         "cvr_set_medium_scalar": (I32, [P, C.POINTER(ScalarMediumDesc)]),
@@ -467,6 +474,19 @@ def classify_gradient_host(scalar, table, lo, hi, glo, ghi, spacing=(1.0, 1.0, 1
     _check(load().cvr_classify_gradient_host(src.ctypes.data, _SCALAR_TYPES[src.dtype.name], res, C.byref(t),
                                              density.ctypes.data, albedo.ctypes.data, mag.ctypes.data))
     return density, albedo, mag
+
+
+def build_geometry() -> dict:
+    """The launch geometry of the medium build kernels (cvr_debug_build_geometry; no GPU needed),
+    by name."""
+    out = (C.c_uint32 * 16)()
+    _check(load().cvr_debug_build_geometry(out))
+    names = ("scan_grid", "stream_grid", "scan_tile", "scan_sums_chunk", "gradient_tasks", "gradient_z",
+             "leaf_run_voxels", "leaf_run_leaves", "leaf_flags_grid", "to_half_grid", "cells_grid", "bounds_grid",
+             "sparse_cells_grid", "sparse_bounds_grid")
+    if out[15] != len(names):
+        raise RuntimeError(f"cvr_debug_build_geometry fills {out[15]} entries, this binding knows {len(names)}")
+    return dict(zip(names, (int(v) for v in out)))
 
 
 def raw_transfer_table() -> np.ndarray:
@@ -979,6 +999,28 @@ class Context:
         out = (C.c_double * 6)()
         self._c(load().cvr_debug_device_medium_ms(self._h, out))
         return list(out)
+
+    def debug_medium_array(self, which):
+        """One stored array of the medium in use, as stored (cvr_debug_copy_medium).  which: a
+        MEDIUM_* value or its lower-case name ("density", "leaf_table", ...).  Returns a flat numpy
+        array of the natural dtype: float32 or float16 by the medium's format for values, uint32
+        for tables, words and the mask, uint8 for the dense bounds; None when the medium has no
+        such array."""
+        if isinstance(which, str):
+            which = MEDIUM_ARRAYS.index(which)
+        lib = load()
+        need = C.c_size_t(0)
+        code = lib.cvr_debug_copy_medium(self._h, which, None, 0, C.byref(need))
+        if need.value == 0:
+            self._c(code)
+            return None
+        if MEDIUM_ARRAYS[which] in _MEDIUM_VALUE_ARRAYS:
+            dtype = np.float16 if self.medium_info().format else np.float32
+        else:
+            dtype = np.uint8 if which == MEDIUM_BOUNDS else np.uint32
+        out = np.empty(need.value // np.dtype(dtype).itemsize, dtype)
+        self._c(lib.cvr_debug_copy_medium(self._h, which, out.ctypes.data, out.nbytes, C.byref(need)))
+        return out
 
     def set_camera(self, inv_view, raster_to_view, full_res):
         iv = np.ascontiguousarray(inv_view, np.float32)

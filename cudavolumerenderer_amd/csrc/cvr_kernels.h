@@ -124,6 +124,20 @@ hipError_t launch_build_cells(const float* density, uint32_t rx, uint32_t ry, ui
 // The half storage format (MediumParams::format 1; `format` above: `density` holds halves and
 // the cells are written as 8 halves): n fp32 values -> n binary16, round to nearest even.
 hipError_t launch_to_half(const float* src, void* dst, size_t n, hipStream_t s);
+// The launch geometry of the medium build: every cap and run length the build launches and their
+// kernels use, named once, so that cvr_debug_build_geometry (cvr.h) reports what runs.  Each
+// kernel below a cap loops over its grid; the tests size their media from these to make it loop.
+constexpr uint32_t kScanGridCap = 2048;    // scan_grid: the value scans and k_classified, 8 workgroups per CU
+constexpr uint32_t kStreamGridCap = 8192;  // stream_grid: k_fill_albedo, k_cell_leaf_flags, k_gather_leaves
+constexpr uint32_t kScanSteps = 8, kScanTile = 256 * kScanSteps;  // flags per workgroup of the flag scan
+constexpr uint32_t kScanSumsChunk = 1024;  // tile sums k_scan_sums takes per trip (its workgroup's size)
+constexpr uint32_t kGradTaskCap = 4096;    // k_gradient's grid: tasks beyond it are a workgroup's next trip
+constexpr uint32_t kGradZ = 16;            // z planes per k_gradient task
+constexpr uint32_t kLeafRunLeaves = 32, kLeafRunVoxels = 8 * kLeafRunLeaves;  // x run of one k_leaf_flags task
+constexpr uint32_t kLeafFlagsGridCap = 1u << 20;
+constexpr uint32_t kToHalfGridCap = 8192;
+constexpr uint32_t kBuildCellsGrid = 4096, kBuildBoundsGrid = 1024;  // fixed grids, each work-item looping
+constexpr uint32_t kBuildSparseCellsGrid = 8192, kBuildSparseBoundsGrid = 4096;
 // Media built from device memory (cvr_set_medium_device; cvr_medium_build.hip).  Every array below
 // is device memory; the launches are asynchronous on s and none waits on another workgroup.
 // What the value scans find, in device memory; the host sets ovf_* to ~0 and the rest to 0 first.

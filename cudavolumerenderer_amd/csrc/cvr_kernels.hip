@@ -1084,20 +1084,20 @@ hipError_t launch_build_bounds(const float* density, uint32_t rx, uint32_t ry, u
                                float max_density, uint8_t* bounds, hipStream_t s, uint32_t format) {
   const uint32_t B = 1u << bshift;
   const uint32_t bnx = (rx + B - 1) / B, bny = (ry + B - 1) / B, bnz = (rz + B - 1) / B;
-  hipLaunchKernelGGL(k_build_bounds, dim3(1024), dim3(256), 0, s, density, rx, ry, rz, bshift, bnx, bny, bnz,
+  hipLaunchKernelGGL(k_build_bounds, dim3(kBuildBoundsGrid), dim3(256), 0, s, density, rx, ry, rz, bshift, bnx, bny, bnz,
                      max_density, bounds, format);
   return hipGetLastError();
 }
 
 hipError_t launch_build_cells(const float* density, uint32_t rx, uint32_t ry, uint32_t rz, float4* cells,
                               hipStream_t s, uint32_t format) {
-  hipLaunchKernelGGL(k_build_cells, dim3(4096), dim3(256), 0, s, density, rx, ry, rz, cells, format);
+  hipLaunchKernelGGL(k_build_cells, dim3(kBuildCellsGrid), dim3(256), 0, s, density, rx, ry, rz, cells, format);
   return hipGetLastError();
 }
 
 hipError_t launch_to_half(const float* src, void* dst, size_t n, hipStream_t s) {
   if (n == 0) return hipSuccess;
-  const uint32_t grid = (uint32_t)std::min<size_t>((n + 255) / 256, 8192);
+  const uint32_t grid = (uint32_t)std::min<size_t>((n + 255) / 256, kToHalfGridCap);
   hipLaunchKernelGGL(k_to_half, dim3(grid), dim3(256), 0, s, src, reinterpret_cast<_Float16*>(dst), n);
   return hipGetLastError();
 }
@@ -1118,10 +1118,10 @@ hipError_t launch_debug_fastdiv(FastDiv f, const uint32_t* u, uint32_t* q, size_
 hipError_t launch_build_sparse(const MediumParams& m, const uint32_t* coords, size_t n_cell_leaves,
                                const uint32_t* cell_slot, uint32_t bnz, float max_density, int unbounded,
                                float4* cells, uint32_t* sbounds, hipStream_t s) {
-  hipLaunchKernelGGL(k_build_sparse_cells, dim3(8192), dim3(256), 0, s, m, coords, n_cell_leaves * 512, cells);
+  hipLaunchKernelGGL(k_build_sparse_cells, dim3(kBuildSparseCellsGrid), dim3(256), 0, s, m, coords, n_cell_leaves * 512, cells);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(k_build_sparse_bounds, dim3(4096), dim3(256), 0, s, m, cell_slot, bnz, max_density, unbounded,
+  hipLaunchKernelGGL(k_build_sparse_bounds, dim3(kBuildSparseBoundsGrid), dim3(256), 0, s, m, cell_slot, bnz, max_density, unbounded,
                      sbounds);
   return hipGetLastError();
 }

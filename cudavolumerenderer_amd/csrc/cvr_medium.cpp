@@ -1132,6 +1132,75 @@ int cvr_debug_device_medium_ms(const cvr_ctx* c, double out[6]) {
   return CVR_OK;
 }
 
+int cvr_debug_build_geometry(uint32_t out[16]) {
+  if (!out) return set_err(nullptr, CVR_ERR_INVALID, "NULL argument");
+  const uint32_t g[] = {cvr::kScanGridCap,   cvr::kStreamGridCap,    cvr::kScanTile,
+                        cvr::kScanSumsChunk, cvr::kGradTaskCap,      cvr::kGradZ,
+                        cvr::kLeafRunVoxels, cvr::kLeafRunLeaves,    cvr::kLeafFlagsGridCap,
+                        cvr::kToHalfGridCap, cvr::kBuildCellsGrid,   cvr::kBuildBoundsGrid,
+                        cvr::kBuildSparseCellsGrid, cvr::kBuildSparseBoundsGrid};
+  constexpr uint32_t n = sizeof(g) / sizeof(g[0]);
+  static_assert(n < 16, "the last slot holds the count");
+  for (uint32_t i = 0; i < 16; ++i) out[i] = i < n ? g[i] : 0u;
+  out[15] = n;
+  return CVR_OK;
+}
+
+int cvr_debug_copy_medium(const cvr_ctx* c, int which, void* host_dst, size_t bytes, size_t* needed) {
+  if (!c || !needed) return set_err(nullptr, CVR_ERR_INVALID, "NULL argument");
+  *needed = 0;
+  if (!c->have_medium) return set_err(nullptr, CVR_ERR_STATE, "no medium");
+  if (which < 0 || which >= CVR_MEDIUM_ARRAY_COUNT)
+    return set_err(nullptr, CVR_ERR_INVALID, "unknown medium array %d", which);
+  // (a shared medium: m and minfo are the source's, so the arrays are too)
+  const cvr::MediumParams& m = c->m;
+  const bool sparse = m.leaves != nullptr;
+  const size_t nleaf = sparse ? (size_t)m.lnx * m.lny * ((m.rz + 7u) / 8u) : 0;
+  const uint32_t S = 1u << m.bshift;
+  const size_t nwords = sparse ? (size_t)m.bnxy * ((m.rz + S - 1) / S) + 1 : 0;
+  // the leaf pools hold 512 voxels per leaf (the density pool's allocation is one voxel when there is no leaf)
+  const size_t np = sparse ? c->minfo.density_bytes / (512u * (m.format ? 2u : 4u)) * 512u : 0;
+  const void* src = nullptr;
+  size_t n = 0;
+  switch (which) {
+    case CVR_MEDIUM_DENSITY: if (!sparse) src = m.density, n = c->minfo.density_bytes; break;
+    case CVR_MEDIUM_ALBEDO: if (!sparse) src = m.albedo, n = c->minfo.albedo_bytes; break;
+    case CVR_MEDIUM_CELLS: if (!sparse) src = m.cells, n = c->minfo.cells_bytes; break;
+    case CVR_MEDIUM_BOUNDS: if (!sparse) src = m.bounds, n = c->minfo.bounds_bytes; break;
+    case CVR_MEDIUM_LEAF_TABLE: src = m.leaves, n = nleaf * sizeof(uint32_t); break;
+    case CVR_MEDIUM_LEAF_DENSITY: if (sparse) src = m.leaf_density, n = np * (m.format ? 2u : 4u); break;
+    case CVR_MEDIUM_LEAF_ALBEDO: if (sparse) src = m.leaf_albedo, n = c->minfo.albedo_bytes; break;
+    case CVR_MEDIUM_CELL_SLOTS: src = m.sbounds, n = nleaf * sizeof(uint32_t); break;
+    case CVR_MEDIUM_SPARSE_CELLS: if (sparse) src = m.cells, n = c->minfo.cells_bytes; break;
+    case CVR_MEDIUM_BRICK_WORDS: src = m.sbounds, n = nwords * sizeof(uint32_t); break;
+    case CVR_MEDIUM_MASK: src = m.emask, n = m.emask ? cvr::kEmaskWords * sizeof(uint32_t) : 0; break;
+  }
+  if (!src || !n) return CVR_OK;  // the medium has no such array
+  *needed = n;
+  if (!host_dst || bytes < n)
+    return set_err(nullptr, CVR_ERR_INVALID, "cvr_debug_copy_medium: array %d holds %zu bytes, the buffer %zu", which, n,
+                   bytes);
+  if (hipSetDevice(c->device) != hipSuccess || hipDeviceSynchronize() != hipSuccess)
+    return set_err(nullptr, CVR_ERR_HIP, "cvr_debug_copy_medium: the device is not ready");
+  if (which != CVR_MEDIUM_CELL_SLOTS) {
+    if (hipMemcpy(host_dst, src, n, hipMemcpyDeviceToHost) != hipSuccess)
+      return set_err(nullptr, CVR_ERR_HIP, "cvr_debug_copy_medium: reading array %d failed", which);
+    return CVR_OK;
+  }
+  // a leaf's cell-leaf slot is kept in the low 24 bits of the words of its bricks: the first one's
+  std::vector<uint32_t> words(nwords);
+  if (hipMemcpy(words.data(), src, nwords * sizeof(uint32_t), hipMemcpyDeviceToHost) != hipSuccess)
+    return set_err(nullptr, CVR_ERR_HIP, "cvr_debug_copy_medium: reading array %d failed", which);
+  uint32_t* slots = static_cast<uint32_t*>(host_dst);
+  const uint32_t up = 3u - m.bshift, lnz = (m.rz + 7u) / 8u;
+  for (uint32_t z = 0; z < lnz; ++z)
+    for (uint32_t y = 0; y < m.lny; ++y)
+      for (uint32_t x = 0; x < m.lnx; ++x)
+        slots[((size_t)z * m.lny + y) * m.lnx + x] =
+            words[((size_t)(z << up) * m.bny + (y << up)) * m.bnx + (x << up)] & 0xFFFFFFu;
+  return CVR_OK;
+}
+
 int cvr_medium_layout(const cvr_ctx* c, struct cvr_medium_layout* out) {
   if (!c || !out) return set_err(nullptr, CVR_ERR_INVALID, "NULL argument");
   if (!c->have_medium) return set_err(nullptr, CVR_ERR_STATE, "no medium");

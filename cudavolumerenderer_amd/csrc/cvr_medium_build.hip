@@ -21,7 +21,6 @@ namespace {
 
 constexpr uint32_t kNoLeaf = 0xFFFFFFFFu;  // CVR_NO_LEAF
 constexpr unsigned long long kNoIndex = ~0ull;
-constexpr uint32_t kScanSteps = 8, kScanTile = 256 * kScanSteps;  // flags per workgroup of the scan
 
 // finite and rounds to +-inf in binary16 (the host uploads' half_overflows)
 __device__ __forceinline__ bool half_overflow(float f) {
@@ -336,7 +335,6 @@ __global__ __launch_bounds__(256) void k_classified(ScalarSrc<T> src, size_t n, 
 // neighbours are two loads of rows that the tasks of y - 1 and y + 1 read as their own (cache
 // hits, not memory traffic, when those tasks run close in time on one XCD: consecutive tasks are
 // consecutive x-runs, then consecutive y).  A wave's loads and stores of a step are 64 consecutive voxels.
-constexpr uint32_t kGradZ = 16;
 template <class T, bool kStore>
 __global__ __launch_bounds__(256) void k_gradient(GradientSrc<T> src, uint32_t format, void* __restrict__ density,
                                                   void* __restrict__ albedo, MedScan* __restrict__ out) {
@@ -433,7 +431,7 @@ __global__ __launch_bounds__(256) void k_leaf_flags(Src src, uint32_t nx, uint32
                                                     uint32_t format, MedScan* __restrict__ scan) {
   constexpr bool kScan = !std::is_void_v<typename Src::Scalar>;
   src.stage();
-  const uint32_t nxc = (lnx + 31u) / 32u;
+  const uint32_t nxc = (lnx + kLeafRunLeaves - 1u) / kLeafRunLeaves;
   const size_t ntasks = (size_t)nxc * lny * lnz;
   const bool with_albedo = src.has_albedo();
   uint32_t b0 = 0, b1 = 0, b2 = 0, b3 = 0;
@@ -447,7 +445,7 @@ __global__ __launch_bounds__(256) void k_leaf_flags(Src src, uint32_t nx, uint32
   AlbedoScan as(make_float4(__uint_as_float(b0), __uint_as_float(b1), __uint_as_float(b2), __uint_as_float(b3)));
   for (size_t t = blockIdx.x; t < ntasks; t += gridDim.x) {
     const uint32_t xc = (uint32_t)(t % nxc), ly = (uint32_t)((t / nxc) % lny), lz = (uint32_t)(t / ((size_t)nxc * lny));
-    const uint32_t x = xc * 256u + threadIdx.x;
+    const uint32_t x = xc * kLeafRunVoxels + threadIdx.x;
     uint32_t any = 0;
     if (x < nx) {
 #pragma unroll 8
@@ -533,12 +531,12 @@ __global__ __launch_bounds__(256) void k_tile_counts(const uint32_t* __restrict_
 }
 
 // One workgroup: sums[0..nb) -> their exclusive prefix sums in place, *total the sum of all.
-__global__ __launch_bounds__(1024) void k_scan_sums(uint32_t* __restrict__ sums, uint32_t nb,
+__global__ __launch_bounds__(kScanSumsChunk) void k_scan_sums(uint32_t* __restrict__ sums, uint32_t nb,
                                                     uint32_t* __restrict__ total) {
   __shared__ uint32_t s_w[16];
   const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
   uint32_t carry = 0;
-  for (uint32_t base = 0; base < nb; base += 1024u) {
+  for (uint32_t base = 0; base < nb; base += kScanSumsChunk) {
     const uint32_t i = base + threadIdx.x;
     const uint32_t v = i < nb ? sums[i] : 0u;
     uint32_t x = v;
@@ -667,9 +665,9 @@ __global__ __launch_bounds__(256) void k_gather_leaves(Src src, uint32_t nx, uin
   }
 }
 
-uint32_t stream_grid(size_t n) { return (uint32_t)std::min<size_t>((n + 255) / 256, 8192); }
+uint32_t stream_grid(size_t n) { return (uint32_t)std::min<size_t>((n + 255) / 256, kStreamGridCap); }
 // the scans: 8 resident workgroups per CU of 256, each looping
-uint32_t scan_grid(size_t n) { return (uint32_t)std::min<size_t>((n + 255) / 256, 2048); }
+uint32_t scan_grid(size_t n) { return (uint32_t)std::min<size_t>((n + 255) / 256, kScanGridCap); }
 
 // f(src, lds): the source as the kernels take it and the dynamic LDS its table needs
 template <class F>
@@ -714,7 +712,7 @@ hipError_t launch_classified(const VoxelSource& v, size_t n, uint32_t format, vo
     } else if constexpr (!std::is_void_v<T>) {
       const size_t ntasks = (size_t)((v.res[0] + 255u) / 256u) * v.res[1] * ((v.res[2] + kGradZ - 1u) / kGradZ);
       // (a multiple of 8 workgroups where there are 8: the kernel's XCD turn needs one)
-      const uint32_t grid = (uint32_t)std::min<size_t>(ntasks, 4096);
+      const uint32_t grid = (uint32_t)std::min<size_t>(ntasks, kGradTaskCap);
       hipLaunchKernelGGL((k_gradient<T, kStore>), dim3(grid >= 8u ? grid & ~7u : grid), dim3(256), lds, s,
                          src, format, density, albedo, out);
     }
@@ -752,10 +750,10 @@ hipError_t launch_store_classified(const VoxelSource& src, size_t n, uint32_t fo
 
 hipError_t launch_leaf_flags(const VoxelSource& v, bool with_albedo, const uint32_t res[3], const uint32_t ln[3],
                              uint32_t* flags, uint32_t format, MedScan* scan, hipStream_t s) {
-  const size_t ntasks = (size_t)((ln[0] + 31u) / 32u) * ln[1] * ln[2];
+  const size_t ntasks = (size_t)((ln[0] + kLeafRunLeaves - 1u) / kLeafRunLeaves) * ln[1] * ln[2];
   with_source(v, with_albedo, [&](auto src, size_t lds) {
-    hipLaunchKernelGGL(k_leaf_flags<decltype(src)>, dim3((uint32_t)std::min<size_t>(ntasks, 1u << 20)), dim3(256), lds,
-                       s, src, res[0], res[1], res[2], ln[0], ln[1], ln[2], flags, format, scan);
+    hipLaunchKernelGGL(k_leaf_flags<decltype(src)>, dim3((uint32_t)std::min<size_t>(ntasks, kLeafFlagsGridCap)),
+                       dim3(256), lds, s, src, res[0], res[1], res[2], ln[0], ln[1], ln[2], flags, format, scan);
   });
   return hipGetLastError();
 }
@@ -771,7 +769,7 @@ size_t flag_scan_tiles(size_t n) { return (n + kScanTile - 1) / kScanTile; }
 hipError_t launch_flag_scan(const uint32_t* flags, size_t n, uint32_t* sums, uint32_t* total, hipStream_t s) {
   const uint32_t nb = (uint32_t)flag_scan_tiles(n);
   hipLaunchKernelGGL(k_tile_counts, dim3(nb), dim3(256), 0, s, flags, n, sums);
-  hipLaunchKernelGGL(k_scan_sums, dim3(1), dim3(1024), 0, s, sums, nb, total);
+  hipLaunchKernelGGL(k_scan_sums, dim3(1), dim3(kScanSumsChunk), 0, s, sums, nb, total);
   return hipGetLastError();
 }
 

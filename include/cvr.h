@@ -39,6 +39,7 @@ extern "C" {
  *              6 + CVR_HAS_ENVMAP (likewise): cvr_environment_desc, cvr_set_environment,
  *                  cvr_clear_environment, cvr_environment_info, cvr_environment_eval*, cvr_trace_env,
  *                  cvr_read_image, cvr_free_image
+ *              6 + CVR_HAS_MEDIUM_READBACK (likewise): cvr_debug_copy_medium, cvr_debug_build_geometry
  * CVR_ABI_VERSION is the ABI this header declares: 6, the library's (cvr_abi_version()).  ABI 6 only
  * adds to ABI 5, so a host that must also load an ABI 5 library can hold itself to that surface:
  * with CVR_ABI_TARGET defined as 5 before the include, the ABI 6 functions and structs are not
@@ -736,6 +737,41 @@ struct cvr_medium_layout {
   uint32_t mask[64];
 };
 int cvr_medium_layout(const cvr_ctx* ctx, struct cvr_medium_layout* out);
+
+/* ---- read-back of the stored medium (tests; extension within ABI 6: CVR_HAS_MEDIUM_READBACK) -- */
+/* Debug: one stored array of the medium in use (a shared medium: the source's), copied to the
+ * host as stored: fp32 or binary16 values by the medium's format, u32 words, u8 bounds.
+ * *needed always receives the array's size in bytes; an array the medium does not have (a dense
+ * array of a sparse medium, no albedo pool, bounds off, no mask) gives *needed = 0 and CVR_OK
+ * and copies nothing.  bytes < *needed (or a NULL host_dst): CVR_ERR_INVALID, nothing is
+ * copied, so a first call with bytes 0 asks for the size.  No medium: CVR_ERR_STATE.
+ * Synchronous (the device is synchronised first). */
+#define CVR_HAS_MEDIUM_READBACK 1
+enum { CVR_MEDIUM_DENSITY = 0,      /* dense: one value per voxel, x fastest */
+       CVR_MEDIUM_ALBEDO = 1,       /* dense: four values per voxel */
+       CVR_MEDIUM_CELLS = 2,        /* dense: 8 corner values per voxel (CVR_OPT_CELLS) */
+       CVR_MEDIUM_BOUNDS = 3,       /* dense: one u8 code per brick and the no-bound entry behind them */
+       CVR_MEDIUM_LEAF_TABLE = 4,   /* sparse: per leaf (z, y, x; x fastest) its slot or CVR_NO_LEAF */
+       CVR_MEDIUM_LEAF_DENSITY = 5, /* sparse: 512 values per slot */
+       CVR_MEDIUM_LEAF_ALBEDO = 6,  /* sparse: 512 x 4 values per slot */
+       CVR_MEDIUM_CELL_SLOTS = 7,   /* sparse: per leaf its cell-leaf slot, 0 the zero leaf.  Kept in the low
+                                       24 bits of the leaf's brick words: taken from the leaf's first brick */
+       CVR_MEDIUM_SPARSE_CELLS = 8, /* sparse: 512 cells of 8 corner values per cell-leaf slot */
+       CVR_MEDIUM_BRICK_WORDS = 9,  /* sparse: code << 24 | cell-leaf slot per brick and the no-bound word */
+       CVR_MEDIUM_MASK = 10,        /* sparse, bounded: the empty-region mask's 64 words */
+       CVR_MEDIUM_ARRAY_COUNT = 11 };
+int cvr_debug_copy_medium(const cvr_ctx* ctx, int which, void* host_dst, size_t bytes, size_t* needed);
+/* Debug, host only (no device is needed): the launch geometry of the medium build kernels, the
+ * constants the launches themselves use, so that a test can size a medium that makes a capped
+ * grid loop and fails when a cap moves.  out[0] the value scans' and classified passes' grid cap
+ * (workgroups of 256); [1] the streaming kernels' grid cap (albedo fill, cell-leaf flags, leaf
+ * gather); [2] flags per workgroup of the leaf scan (its tile); [3] tile sums the scan's middle
+ * launch takes per trip; [4] the gradient passes' grid cap in tasks and [5] the z planes of a
+ * task (a task: 256 x of one y); [6] the x run of a leaf-flag task in voxels and [7] in leaves,
+ * [8] that launch's grid cap; [9] the binary16 conversion's grid cap; [10] the dense cells',
+ * [11] dense bounds', [12] sparse cells' and [13] sparse brick words' fixed grids; [14] 0;
+ * [15] the number of entries filled, 14. */
+int cvr_debug_build_geometry(uint32_t out[16]);
 
 /* ---- transfer functions: scalar volumes classified on the device (extension within ABI 6:
  *      CVR_HAS_TRANSFER) -- */

@@ -62,6 +62,10 @@ def assert_same(host, dev, what):
     assert dev.medium_info().as_dict() == host.medium_info().as_dict(), what
     assert dev.medium_layout().as_dict() == host.medium_layout().as_dict(), what
     assert records(dev).tobytes() == records(host).tobytes(), what
+    # the whole stored medium, read back (cvr_debug_copy_medium): the paths touch a sliver of it
+    for name in cvr.MEDIUM_ARRAYS:
+        h, d = host.debug_medium_array(name), dev.debug_medium_array(name)
+        assert (h is None) == (d is None) and (h is None or h.tobytes() == d.tobytes()), f"{what}: stored {name}"
 
 
 def alternate(host_call, dev_call, reps):
