@@ -11,6 +11,7 @@ from ._lib import (  # noqa: F401
     OPT_MEDIUM_FORMAT, FORMAT_F32, FORMAT_F16, MediumInfo, half_round,
     OPT_MOMENTS, AdaptiveDesc, AdaptiveResult, AdaptiveSession, block_error,
     DenoiseDesc, denoise_host,
+    FeaturesDesc, DenoiseGuidedDesc, features_host, denoise_guided_host,
     DeviceMediumDesc, MediumLayout, DEVMED_SPARSE, DEVMED_CONST_ALBEDO, DEVMED_MAX_DENSITY,
     MEDIUM_ARRAYS, build_geometry,
     TransferDesc, ScalarMediumDesc, classify_host, raw_transfer_table,
@@ -28,6 +29,7 @@ __all__ = [
     "OPT_MEDIUM_FORMAT", "FORMAT_F32", "FORMAT_F16", "MediumInfo", "half_round",
     "OPT_MOMENTS", "AdaptiveDesc", "AdaptiveResult", "AdaptiveSession", "block_error",
     "DenoiseDesc", "denoise_host",
+    "FeaturesDesc", "DenoiseGuidedDesc", "features_host", "denoise_guided_host",
     "DeviceMediumDesc", "MediumLayout", "DEVMED_SPARSE", "DEVMED_CONST_ALBEDO", "DEVMED_MAX_DENSITY",
     "MEDIUM_ARRAYS", "build_geometry",
     "TransferDesc", "ScalarMediumDesc", "classify_host", "raw_transfer_table",

@@ -136,6 +136,25 @@ class DenoiseDesc(C.Structure):
         super().__init__(passes, sigma, floor, flags)
 
 
+class FeaturesDesc(C.Structure):
+    """cvr_features_desc: the primary-ray feature pass (step in cells of the finest axis, 1/8..8;
+    t_stop: the transmittance below which a ray's march ends, 0 = never; max_steps 1..65536)."""
+    _fields_ = [("step", C.c_float), ("t_stop", C.c_float), ("max_steps", C.c_uint32), ("flags", C.c_uint32)]
+
+    def __init__(self, step=1.0, t_stop=1.0 / 256.0, max_steps=4096, flags=0):
+        super().__init__(step, t_stop, max_steps, flags)
+
+
+class DenoiseGuidedDesc(C.Structure):
+    """cvr_denoise_guided_desc: the denoiser's parameters (base) and the widths of the three feature
+    terms (albedo, depth, opacity; <= 0 switches a term off)."""
+    _fields_ = [("base", DenoiseDesc), ("sigma_albedo", C.c_float), ("sigma_depth", C.c_float),
+                ("sigma_alpha", C.c_float), ("flags", C.c_uint32)]
+
+    def __init__(self, base: Optional[DenoiseDesc] = None, sigma_albedo=0.4, sigma_depth=0.1, sigma_alpha=0.4, flags=0):
+        super().__init__(DenoiseDesc() if base is None else base, sigma_albedo, sigma_depth, sigma_alpha, flags)
+
+
 DEVMED_SPARSE, DEVMED_CONST_ALBEDO, DEVMED_MAX_DENSITY = 1, 2, 4
 # cvr_debug_copy_medium's arrays (CVR_MEDIUM_*), by index
 MEDIUM_ARRAYS = ("density", "albedo", "cells", "bounds", "leaf_table", "leaf_density", "leaf_albedo", "cell_slots",
@@ -317,6 +336,13 @@ def load() -> C.CDLL:
         "cvr_denoise_host": (I32, [P, P, U32, U32, U32, P, C.POINTER(DenoiseDesc), P, P]),
         "cvr_denoise_buffers": (I32, [P, P, P, U32, U32, U32, P, C.POINTER(DenoiseDesc), P, P]),
         "cvr_denoise": (I32, [P, C.POINTER(DenoiseDesc), U32, P, C.c_size_t]),
+        "cvr_features_host": (I32, [C.POINTER(MediumDesc), FP, FP, FP, U32, U32, U32, U32, I32, C.POINTER(FeaturesDesc),
+                                    P, P]),
+        "cvr_features_buffers": (I32, [P, C.POINTER(FeaturesDesc), P, P]),
+        "cvr_features": (I32, [P, C.POINTER(FeaturesDesc), P, P, C.c_size_t]),
+        "cvr_denoise_guided_host": (I32, [P, P, U32, U32, U32, P, C.POINTER(DenoiseGuidedDesc), P, P, P, P]),
+        "cvr_denoise_guided_buffers": (I32, [P, P, P, U32, U32, U32, P, C.POINTER(DenoiseGuidedDesc), P, P, P, P]),
+        "cvr_denoise_guided": (I32, [P, C.POINTER(DenoiseGuidedDesc), C.POINTER(FeaturesDesc), U32, P, C.c_size_t]),
         "cvr_set_medium_device": (I32, [P, C.POINTER(DeviceMediumDesc)]),
         "cvr_medium_layout": (I32, [P, C.POINTER(MediumLayout)]),
         "cvr_debug_device_medium_ms": (I32, [P, C.POINTER(C.c_double)]),
@@ -410,6 +436,53 @@ def denoise_host(sum_rgba, m2_rgba, n_samples: Optional[int] = None, block_sampl
                                    None if counts is None else counts.ctypes.data, C.byref(desc), rgba.ctypes.data,
                                    var.ctypes.data))
     return rgba, var
+
+
+def denoise_guided_host(sum_rgba, m2_rgba, feat_rgba, feat_depth, n_samples: Optional[int] = None, block_samples=None,
+                        desc: Optional[DenoiseGuidedDesc] = None):
+    """The feature-guided filter's written statement on the CPU (cvr_denoise_guided_host; no GPU):
+    denoise_host's arguments plus the feature planes feat_rgba (h, w, 4) and feat_depth (h, w)
+    (features_host, Context.features) -> (rgba, var) as denoise_host.  With every sigma of `desc`
+    <= 0 the bits are denoise_host's."""
+    s1 = np.ascontiguousarray(sum_rgba, dtype=np.float32)
+    s2 = np.ascontiguousarray(m2_rgba, dtype=np.float32)
+    if s1.ndim != 3 or s1.shape[2] != 4 or s1.shape != s2.shape:
+        raise CvrError(-1, "denoise_guided_host: sum and m2 must both be (h, w, 4)")
+    h, w = s1.shape[:2]
+    f4 = np.ascontiguousarray(feat_rgba, dtype=np.float32)
+    fz = np.ascontiguousarray(feat_depth, dtype=np.float32)
+    if f4.shape != (h, w, 4) or fz.shape != (h, w):
+        raise CvrError(-1, "denoise_guided_host: feat_rgba must be (h, w, 4) and feat_depth (h, w)")
+    counts = None
+    if block_samples is not None:
+        counts = np.ascontiguousarray(block_samples, dtype=np.uint32)
+        if counts.size != (h // 8) * (w // 8):
+            raise CvrError(-1, "denoise_guided_host: block_samples must hold (h / 8) * (w / 8) counts")
+    desc = DenoiseGuidedDesc() if desc is None else desc
+    rgba = np.zeros((h, w, 4), np.float32)
+    var = np.zeros((h, w), np.float32)
+    _check(load().cvr_denoise_guided_host(s1.ctypes.data, s2.ctypes.data, w, h, n_samples or 0,
+                                          None if counts is None else counts.ctypes.data, C.byref(desc), f4.ctypes.data,
+                                          fz.ctypes.data, rgba.ctypes.data, var.ctypes.data))
+    return rgba, var
+
+
+def features_host(medium: "MediumDesc", inv_view, raster_to_view, full_res, tile=None, offset=(0, 0),
+                  world_to_aabb: int = 0, desc: Optional[FeaturesDesc] = None):
+    """The feature pass's written statement on the CPU (cvr_features_host; no GPU) on a dense
+    medium's host arrays, for tile (w, h) (default: full_res) at `offset` of the full image ->
+    (feat_rgba (h, w, 4): mean first-collision albedo and opacity, feat_depth (h, w): mean
+    collision depth over the box diagonal).  Context.features returns the same bits."""
+    iv = np.ascontiguousarray(inv_view, dtype=np.float32).reshape(12)
+    r2v = np.ascontiguousarray(raster_to_view, dtype=np.float32).reshape(2)
+    fr = np.asarray(full_res, dtype=np.float32).reshape(2)
+    w, h = (int(full_res[0]), int(full_res[1])) if tile is None else (int(tile[0]), int(tile[1]))
+    desc = FeaturesDesc() if desc is None else desc
+    rgba = np.zeros((max(h, 0), max(w, 0), 4), np.float32)
+    depth = np.zeros((max(h, 0), max(w, 0)), np.float32)
+    _check(load().cvr_features_host(C.byref(medium), _fp(iv), _fp(r2v), _fp(fr), w, h, int(offset[0]), int(offset[1]),
+                                    int(world_to_aabb), C.byref(desc), rgba.ctypes.data, depth.ctypes.data))
+    return rgba, depth
 
 
 def _transfer_desc(table, lo, hi, ceil, density_u):
@@ -1162,6 +1235,53 @@ class Context:
                                            n_samples or 0, _device_ptr(block_samples), C.byref(desc),
                                            _device_ptr(out_rgba), _device_ptr(out_var)))
 
+    def features(self, desc: Optional[FeaturesDesc] = None):
+        """The feature pass on the context's medium, camera, resolution and offset (cvr_features):
+        (feat_rgba (h, w, 4), feat_depth (h, w)), the bits of features_host.  Synchronous; the
+        context is only read.  Available inside an adaptive session."""
+        desc = FeaturesDesc() if desc is None else desc
+        w, h = self.resolution
+        rgba = np.zeros((h, w, 4), np.float32)
+        depth = np.zeros((h, w), np.float32)
+        self._c(load().cvr_features(self._h, C.byref(desc), C.c_void_p(rgba.ctypes.data), C.c_void_p(depth.ctypes.data),
+                                    rgba.size))
+        return rgba, depth
+
+    def features_buffers(self, out_rgba, out_depth=None, desc: Optional[FeaturesDesc] = None):
+        """The feature pass into device buffers (cvr_features_buffers), asynchronous on the context's
+        stream: out_rgba tile_w * tile_h * 4 floats (16-byte aligned), out_depth tile_w * tile_h
+        floats or None; each an int device address or an object with data_ptr() (a torch tensor)."""
+        desc = FeaturesDesc() if desc is None else desc
+        self._c(load().cvr_features_buffers(self._h, C.byref(desc), _device_ptr(out_rgba), _device_ptr(out_depth)))
+
+    def denoise_guided(self, desc: Optional[DenoiseGuidedDesc] = None, n_samples: Optional[int] = None,
+                       features: Optional[FeaturesDesc] = None, host_ptr=None) -> np.ndarray:
+        """Context.denoise with the feature guide (cvr_denoise_guided): the feature pass runs into
+        planes the context owns, then the guided filter on the framebuffer and its moments."""
+        desc = DenoiseGuidedDesc() if desc is None else desc
+        features = FeaturesDesc() if features is None else features
+        if isinstance(host_ptr, PinnedImage):
+            self._c(load().cvr_denoise_guided(self._h, C.byref(desc), C.byref(features), n_samples or 0, host_ptr.ptr,
+                                              host_ptr.floats))
+            return host_ptr.array
+        w, h = self.resolution
+        img = np.zeros((h, w, 4), np.float32)
+        self._c(load().cvr_denoise_guided(self._h, C.byref(desc), C.byref(features), n_samples or 0,
+                                          C.c_void_p(img.ctypes.data), img.size))
+        return img
+
+    def denoise_guided_buffers(self, sum_rgba, m2_rgba, feat_rgba, feat_depth, width: int, height: int, out_rgba,
+                               n_samples: Optional[int] = None, block_samples=None,
+                               desc: Optional[DenoiseGuidedDesc] = None, out_var=None):
+        """Context.denoise_buffers with two device feature planes of any origin
+        (cvr_denoise_guided_buffers): feat_rgba width * height * 4 floats (16-byte aligned),
+        feat_depth width * height floats."""
+        desc = DenoiseGuidedDesc() if desc is None else desc
+        self._c(load().cvr_denoise_guided_buffers(self._h, _device_ptr(sum_rgba), _device_ptr(m2_rgba), width, height,
+                                                  n_samples or 0, _device_ptr(block_samples), C.byref(desc),
+                                                  _device_ptr(feat_rgba), _device_ptr(feat_depth),
+                                                  _device_ptr(out_rgba), _device_ptr(out_var)))
+
     def adaptive(self, desc: AdaptiveDesc) -> "AdaptiveSession":
         """A noise-targeted render of the set tile as a context manager (cvr_adaptive_begin ..
         cvr_adaptive_end): `with ctx.adaptive(desc) as a: while not a.step().done: ...; img = a.image()`."""
@@ -1350,6 +1470,12 @@ class AdaptiveSession:
         """The session's image filtered with its moments, every block at its own sample count
         (Context.denoise inside the session)."""
         return self.ctx.denoise(desc, None, host_ptr)
+
+    def denoised_guided(self, desc: Optional[DenoiseGuidedDesc] = None, features: Optional[FeaturesDesc] = None,
+                        host_ptr=None) -> np.ndarray:
+        """The session's image so far through the feature-guided filter (Context.denoise_guided
+        inside the session)."""
+        return self.ctx.denoise_guided(desc, None, features, host_ptr)
 
 
 class PinnedImage:

@@ -175,6 +175,9 @@ struct cvr_ctx {
   // cvr_denoise*: the two scratch images the passes alternate between (dn_px pixels each)
   float4* d_dn = nullptr;
   size_t dn_px = 0;
+  // cvr_denoise_guided: the feature planes of its own pass, feat_px float4 then feat_px floats
+  float4* d_feat = nullptr;
+  size_t feat_px = 0;
   // cvr_set_environment: the context's own stored texels, the header as the kernels read it
   // (device memory, 64 bytes: LaunchParams::rec of the kMedEnv instances) and its host copy
   bool have_env = false;
@@ -194,6 +197,10 @@ void drop_dense(cvr_ctx* c);
 bool device_readable(const cvr_ctx* c, const void* p);
 // The context's environment map and its device header, freed and reset (cvr_environment.cpp)
 void free_environment(cvr_ctx* c);
+// The feature pass (cvr_features_api.cpp) for the context's medium, camera and tile: what the
+// entry points check (state, descriptor, tile), and the launch on the context's stream
+int features_check(cvr_ctx* c, const cvr_features_desc* d);
+int features_launch(cvr_ctx* c, const cvr_features_desc* d, float4* rgba, float* depth);
 // f32 -> binary16 -> f32, round to nearest even, subnormals kept (CVR_OPT_MEDIUM_FORMAT 1)
 float half_round1(float f);
 // first finite value of v[0..n) (of every `stride`-th group's first `take` values) that rounds to +-inf

@@ -42,6 +42,26 @@ __global__ __launch_bounds__(256) void k_denoise_prepare(const float4* __restric
 }
 
 // kLast: the pass that ends the filter stores the output image instead of the next pass's input.
+// The guided filter's passes (cvr_denoise_guided*): instances of their own below, the unguided
+// kernels' text and instruction streams stay as they were.
+template <bool kLast, class Guide>
+__device__ __forceinline__ void denoise_pass_body(const float4* __restrict__ src, float4* __restrict__ dst, uint32_t w,
+                                                  uint32_t h, uint32_t step, float sigma, float floor,
+                                                  const float4* __restrict__ sum, uint32_t n_samples,
+                                                  const uint32_t* __restrict__ counts, float* __restrict__ out_var,
+                                                  const Guide& guide) {
+  uint32_t x, y;
+  if (denoise_pixel(w, h, x, y)) {
+    const size_t i = (size_t)y * w + x;
+    const float4 f = denoise_pass(src, w, h, x, y, step, sigma, floor, guide);
+    if (kLast) {
+      dst[i] = denoise_final(f, sum[i], denoise_count(counts, n_samples, w, x, y));
+      if (out_var) out_var[i] = f.w < 0.0f ? -1.0f : f.w;
+    } else {
+      dst[i] = f;
+    }
+  }
+}
 template <bool kLast>
 __global__ __launch_bounds__(256) void k_denoise_pass(const float4* __restrict__ src, float4* __restrict__ dst,
                                                       uint32_t w, uint32_t h, uint32_t step, float sigma, float floor,
@@ -59,6 +79,14 @@ __global__ __launch_bounds__(256) void k_denoise_pass(const float4* __restrict__
     }
   }
 }
+template <bool kLast>
+__global__ __launch_bounds__(256) void k_denoise_pass_guided(const float4* __restrict__ src, float4* __restrict__ dst,
+                                                             uint32_t w, uint32_t h, uint32_t step, float sigma,
+                                                             float floor, const float4* __restrict__ sum,
+                                                             uint32_t n_samples, const uint32_t* __restrict__ counts,
+                                                             float* __restrict__ out_var, const DenoiseGuide guide) {
+  denoise_pass_body<kLast>(src, dst, w, h, step, sigma, floor, sum, n_samples, counts, out_var, guide);
+}
 
 #if CVR_DENOISE_LDS
 // The passes with step S = 1 and 2 stage their tile plus a halo of 2 S pixels in LDS first
@@ -73,6 +101,34 @@ struct DenoiseLdsTile {
   int x0, y0;  // image coordinate of tile[0]
   __device__ float4 operator()(int qx, int qy) const { return tile[(qy - y0) * LW + (qx - x0)]; }
 };
+template <bool kLast, uint32_t S, class Guide>
+__device__ __forceinline__ void denoise_pass_lds_body(float4* tile, const float4* __restrict__ src,
+                                                      float4* __restrict__ dst, uint32_t w, uint32_t h, float sigma,
+                                                      float floor, const float4* __restrict__ sum, uint32_t n_samples,
+                                                      const uint32_t* __restrict__ counts, float* __restrict__ out_var,
+                                                      const Guide& guide) {
+  using T = DenoiseLdsTile<S>;
+  uint32_t x, y;
+  const bool inside = denoise_pixel(w, h, x, y);
+  const int x0 = (int)(x - (threadIdx.x & (kTileW - 1u))) - T::R, y0 = (int)(y - (threadIdx.x >> 5)) - T::R;
+  for (int i = (int)threadIdx.x; i < T::LW * T::LH; i += 256) {
+    const int ly = i / T::LW, lx = i - ly * T::LW, gx = x0 + lx, gy = y0 + ly;
+    // (a position outside the image is never asked for: any value does)
+    tile[i] = (gx >= 0 && gx < (int)w && gy >= 0 && gy < (int)h) ? src[(size_t)gy * w + (size_t)gx]
+                                                                 : make_float4(0.0f, 0.0f, 0.0f, -1.0f);
+  }
+  __syncthreads();
+  if (inside) {
+    const size_t i = (size_t)y * w + x;
+    const float4 f = denoise_pass_at(T{tile, x0, y0}, w, h, x, y, S, sigma, floor, guide);
+    if (kLast) {
+      dst[i] = denoise_final(f, sum[i], denoise_count(counts, n_samples, w, x, y));
+      if (out_var) out_var[i] = f.w < 0.0f ? -1.0f : f.w;
+    } else {
+      dst[i] = f;
+    }
+  }
+}
 template <bool kLast, uint32_t S>
 __global__ __launch_bounds__(256) void k_denoise_pass_lds(const float4* __restrict__ src, float4* __restrict__ dst,
                                                           uint32_t w, uint32_t h, float sigma, float floor,
@@ -102,6 +158,16 @@ __global__ __launch_bounds__(256) void k_denoise_pass_lds(const float4* __restri
     }
   }
 }
+// (the feature planes are read from global memory: two pixels per tap, never filtered)
+template <bool kLast, uint32_t S>
+__global__ __launch_bounds__(256) void k_denoise_pass_lds_guided(const float4* __restrict__ src,
+                                                                 float4* __restrict__ dst, uint32_t w, uint32_t h,
+                                                                 float sigma, float floor, const float4* __restrict__ sum,
+                                                                 uint32_t n_samples, const uint32_t* __restrict__ counts,
+                                                                 float* __restrict__ out_var, const DenoiseGuide guide) {
+  __shared__ float4 tile[DenoiseLdsTile<S>::LW * DenoiseLdsTile<S>::LH];
+  denoise_pass_lds_body<kLast, S>(tile, src, dst, w, h, sigma, floor, sum, n_samples, counts, out_var, guide);
+}
 #endif
 
 uint32_t denoise_grid(uint32_t w, uint32_t h) {
@@ -122,47 +188,58 @@ hipError_t launch_denoise_prepare(const float4* sum, const float4* m2, uint32_t 
   return hipGetLastError();
 }
 
-hipError_t launch_denoise_pass(const float4* src, float4* dst, uint32_t w, uint32_t h, uint32_t step, float sigma,
-                               float floor, hipStream_t s) {
-  if (!denoise_shape_ok(w, h, nullptr) || !src || !dst || src == dst || step == 0 || step > 32u) return hipErrorInvalidValue;
+// One pass on stream s: the LDS-staged kernel for steps 1 and 2, plain taps above; guided instances with a guide.
+template <bool kLast>
+static void denoise_pass_dispatch(const float4* src, float4* dst, uint32_t w, uint32_t h, uint32_t step, float sigma,
+                                  float floor, const float4* sum, uint32_t n_samples, const uint32_t* counts,
+                                  float* out_var, const DenoiseGuide* guide, hipStream_t s) {
+  const dim3 grid(denoise_grid(w, h)), block(256);
 #if CVR_DENOISE_LDS
   if (step <= 2u) {
-    const float4* no_sum = nullptr;
-    const uint32_t* no_counts = nullptr;
-    float* no_var = nullptr;
-    if (step == 1u)
-      hipLaunchKernelGGL((k_denoise_pass_lds<false, 1>), dim3(denoise_grid(w, h)), dim3(256), 0, s, src, dst, w, h, sigma,
-                         floor, no_sum, 0u, no_counts, no_var);
-    else
-      hipLaunchKernelGGL((k_denoise_pass_lds<false, 2>), dim3(denoise_grid(w, h)), dim3(256), 0, s, src, dst, w, h, sigma,
-                         floor, no_sum, 0u, no_counts, no_var);
-    return hipGetLastError();
+    if (guide) {
+      if (step == 1u)
+        hipLaunchKernelGGL((k_denoise_pass_lds_guided<kLast, 1>), grid, block, 0, s, src, dst, w, h, sigma, floor, sum,
+                           n_samples, counts, out_var, *guide);
+      else
+        hipLaunchKernelGGL((k_denoise_pass_lds_guided<kLast, 2>), grid, block, 0, s, src, dst, w, h, sigma, floor, sum,
+                           n_samples, counts, out_var, *guide);
+    } else {
+      if (step == 1u)
+        hipLaunchKernelGGL((k_denoise_pass_lds<kLast, 1>), grid, block, 0, s, src, dst, w, h, sigma, floor, sum,
+                           n_samples, counts, out_var);
+      else
+        hipLaunchKernelGGL((k_denoise_pass_lds<kLast, 2>), grid, block, 0, s, src, dst, w, h, sigma, floor, sum,
+                           n_samples, counts, out_var);
+    }
+    return;
   }
 #endif
-  hipLaunchKernelGGL(k_denoise_pass<false>, dim3(denoise_grid(w, h)), dim3(256), 0, s, src, dst, w, h, step, sigma, floor,
-                     static_cast<const float4*>(nullptr), 0u, static_cast<const uint32_t*>(nullptr),
-                     static_cast<float*>(nullptr));
+  if (guide)
+    hipLaunchKernelGGL(k_denoise_pass_guided<kLast>, grid, block, 0, s, src, dst, w, h, step, sigma, floor, sum,
+                       n_samples, counts, out_var, *guide);
+  else
+    hipLaunchKernelGGL(k_denoise_pass<kLast>, grid, block, 0, s, src, dst, w, h, step, sigma, floor, sum, n_samples,
+                       counts, out_var);
+}
+static bool denoise_guide_ok(const DenoiseGuide* g) {
+  return !g || (g->rgba && g->depth && !((uintptr_t)g->rgba & 15u) && !((uintptr_t)g->depth & 3u));
+}
+
+hipError_t launch_denoise_pass(const float4* src, float4* dst, uint32_t w, uint32_t h, uint32_t step, float sigma,
+                               float floor, hipStream_t s, const DenoiseGuide* guide) {
+  if (!denoise_shape_ok(w, h, nullptr) || !src || !dst || src == dst || step == 0 || step > 32u || !denoise_guide_ok(guide))
+    return hipErrorInvalidValue;
+  denoise_pass_dispatch<false>(src, dst, w, h, step, sigma, floor, nullptr, 0u, nullptr, nullptr, guide, s);
   return hipGetLastError();
 }
 
 hipError_t launch_denoise_last(const float4* src, uint32_t w, uint32_t h, uint32_t step, float sigma, float floor,
                                const float4* sum, uint32_t n_samples, const uint32_t* counts, float4* out_rgba,
-                               float* out_var, hipStream_t s) {
-  if (!denoise_shape_ok(w, h, counts) || !src || !sum || !out_rgba || src == out_rgba || step == 0 || step > 32u)
+                               float* out_var, hipStream_t s, const DenoiseGuide* guide) {
+  if (!denoise_shape_ok(w, h, counts) || !src || !sum || !out_rgba || src == out_rgba || step == 0 || step > 32u ||
+      !denoise_guide_ok(guide))
     return hipErrorInvalidValue;
-#if CVR_DENOISE_LDS
-  if (step <= 2u) {
-    if (step == 1u)
-      hipLaunchKernelGGL((k_denoise_pass_lds<true, 1>), dim3(denoise_grid(w, h)), dim3(256), 0, s, src, out_rgba, w, h,
-                         sigma, floor, sum, n_samples, counts, out_var);
-    else
-      hipLaunchKernelGGL((k_denoise_pass_lds<true, 2>), dim3(denoise_grid(w, h)), dim3(256), 0, s, src, out_rgba, w, h,
-                         sigma, floor, sum, n_samples, counts, out_var);
-    return hipGetLastError();
-  }
-#endif
-  hipLaunchKernelGGL(k_denoise_pass<true>, dim3(denoise_grid(w, h)), dim3(256), 0, s, src, out_rgba, w, h, step, sigma,
-                     floor, sum, n_samples, counts, out_var);
+  denoise_pass_dispatch<true>(src, out_rgba, w, h, step, sigma, floor, sum, n_samples, counts, out_var, guide, s);
   return hipGetLastError();
 }
 

@@ -343,9 +343,40 @@ __host__ __device__ inline float4 denoise_prepare(const float4 s1, const float4 
 // One a-trous pass at pixel (x, y) of a w x h image, step `step`: the filtered pixel.  tap(qx, qy)
 // returns the image's pixel at a coordinate inside the image (it is asked for no other), from
 // wherever the caller keeps it: the order of the arithmetic does not depend on that.
-template <class Tap>
+// The guided filter (cvr_denoise_guided*): a valid centre's tap weight is divided once more, by g g
+// with g = 1 + ((f_a f_a + f_z f_z) + f_o f_o) from the noise-free feature planes read at p and q
+// (cvr.h); a sigma <= 0 leaves its term 0, and all three off give g = 1: the unguided bits.
+struct DenoiseNoGuide {
+  static constexpr bool on = false;
+  __host__ __device__ float weight(float wt, size_t, size_t) const { return wt; }
+};
+struct DenoiseGuide {
+  static constexpr bool on = true;
+  const float* rgba;   // feat_rgba, 4 floats per pixel (device side: 16-byte aligned)
+  const float* depth;  // feat_depth
+  float sigma_albedo, sigma_depth, sigma_alpha;
+  __host__ __device__ float4 feat(size_t i) const {
+#ifdef __HIP_DEVICE_COMPILE__
+    return reinterpret_cast<const float4*>(rgba)[i];
+#else
+    return make_float4(rgba[4 * i], rgba[4 * i + 1], rgba[4 * i + 2], rgba[4 * i + 3]);
+#endif
+  }
+  // the weight wt of tap q (pixel index iq) for centre p (pixel index ip)
+  __host__ __device__ float weight(float wt, size_t ip, size_t iq) const {
+    const float4 a = feat(ip), b = feat(iq);
+    float fa = 0.0f, fz = 0.0f, fo = 0.0f;
+    if (sigma_albedo > 0.0f) fa = ((fabsf(b.x - a.x) + fabsf(b.y - a.y)) + fabsf(b.z - a.z)) / sigma_albedo;
+    if (sigma_depth > 0.0f) fz = fabsf(depth[iq] - depth[ip]) / sigma_depth;
+    if (sigma_alpha > 0.0f) fo = fabsf(b.w - a.w) / sigma_alpha;
+    const float g = 1.0f + ((fa * fa + fz * fz) + fo * fo);
+    return wt / (g * g);
+  }
+};
+template <class Tap, class Guide = DenoiseNoGuide>
 __host__ __device__ __forceinline__ float4 denoise_pass_at(const Tap& tap, uint32_t w, uint32_t h, uint32_t x,
-                                                           uint32_t y, uint32_t step, float sigma, float floor) {
+                                                           uint32_t y, uint32_t step, float sigma, float floor,
+                                                           const Guide& guide = Guide{}) {
   const float G[3] = {0.25f, 0.5f, 0.25f};
   const float K[5] = {0.0625f, 0.25f, 0.375f, 0.25f, 0.0625f};
   const int iw = (int)w, ih = (int)h, px = (int)x, py = (int)y, s = (int)step;
@@ -379,6 +410,7 @@ __host__ __device__ __forceinline__ float4 denoise_pass_at(const Tap& tap, uint3
         const float a = fabsf(denoise_luma(q.x, q.y, q.z) - lp) / den;
         const float u = 1.0f + a * a;
         wt = wt / (u * u);
+        if (Guide::on) wt = guide.weight(wt, (size_t)py * w + (size_t)px, (size_t)qy * w + (size_t)qx);
       }
       cr += wt * q.x;
       cg += wt * q.y;
@@ -395,9 +427,11 @@ struct DenoiseImage {
   uint32_t w;
   __host__ __device__ float4 operator()(int qx, int qy) const { return src[(size_t)qy * w + (size_t)qx]; }
 };
+template <class Guide = DenoiseNoGuide>
 __host__ __device__ __forceinline__ float4 denoise_pass(const float4* src, uint32_t w, uint32_t h, uint32_t x,
-                                                        uint32_t y, uint32_t step, float sigma, float floor) {
-  return denoise_pass_at(DenoiseImage{src, w}, w, h, x, y, step, sigma, floor);
+                                                        uint32_t y, uint32_t step, float sigma, float floor,
+                                                        const Guide& guide = Guide{}) {
+  return denoise_pass_at(DenoiseImage{src, w}, w, h, x, y, step, sigma, floor, guide);
 }
 // The output pixel from the last pass's result f, the pixel's sum s1 and its n samples.
 __host__ __device__ inline float4 denoise_final(const float4 f, const float4 s1, uint32_t n) {
@@ -409,10 +443,11 @@ __host__ __device__ inline float4 denoise_final(const float4 f, const float4 s1,
 // host memory) and the filtered v, -1 for an invalid pixel, into out_var (may be null).
 hipError_t launch_denoise_prepare(const float4* sum, const float4* m2, uint32_t w, uint32_t h, uint32_t n_samples,
                                   const uint32_t* counts, float4* img, hipStream_t s);
+// guide non-null: the guided instances of the same kernels.
 hipError_t launch_denoise_pass(const float4* src, float4* dst, uint32_t w, uint32_t h, uint32_t step, float sigma,
-                               float floor, hipStream_t s);
+                               float floor, hipStream_t s, const DenoiseGuide* guide = nullptr);
 hipError_t launch_denoise_last(const float4* src, uint32_t w, uint32_t h, uint32_t step, float sigma, float floor,
                                const float4* sum, uint32_t n_samples, const uint32_t* counts, float4* out_rgba,
-                               float* out_var, hipStream_t s);
+                               float* out_var, hipStream_t s, const DenoiseGuide* guide = nullptr);
 
 }  // namespace cvr

@@ -16,7 +16,10 @@
 //   render, cvr_render_adaptive: every 8x8 block is sampled until its relative
 //   standard error is at most F, -i being the cap; also writes the samples map
 //   as <output>_samples.hdr), --denoise [--denoise-sigma F] [--denoise-passes N] (also
-//   write the variance-guided filter of the render, cvr_denoise, as <output>_denoised.hdr)
+//   write the variance-guided filter of the render, cvr_denoise, as <output>_denoised.hdr),
+//   --features [--feature-step F] (also write the primary-ray feature buffers, cvr_features, as
+//   <output>_albedo.hdr, <output>_alpha.hdr and <output>_depth.hdr), --denoise-guided
+//   [--guide-sigma A Z O] (--denoise through the feature-guided filter, cvr_denoise_guided)
 //
 // Differences from the reference, on purpose: the timer is wall clock (the
 // reference uses clock(), i.e. CPU time, Main.cpp:51-77); main does not wait
@@ -55,6 +58,10 @@ struct Options {
   bool denoise = false;  // --denoise given
   float denoise_sigma = 4.0f;
   unsigned denoise_passes = 5;
+  bool features = false;        // --features given
+  float feature_step = 1.0f;
+  bool denoise_guided = false;  // --denoise-guided given
+  float guide_sigma[3] = {0.4f, 0.1f, 0.4f};
   std::vector<float> default_albedo;
   bool interactive = true, unified = false;
   unsigned trials = 1, iterations = 20, device = 0, seed = 0;
@@ -121,6 +128,13 @@ void usage() {
       "                                     --iterations (>= 2) samples, two in the first launch and one per\n"
       "                                     later launch, which makes the output the same bits in every run\n"
       "                                     (one device, one tile)\n"
+      "  --denoise-guided                   --denoise through the feature-guided filter (cvr_denoise_guided: the\n"
+      "                                     feature pass guides the edge-stopping term); excludes --denoise\n"
+      "  --guide-sigma A Z O (=0.4 0.1 0.4) guided filter: widths of the albedo, depth and opacity terms (<= 0: off)\n"
+      "  --features                         also write the primary-ray feature buffers (cvr_features) as\n"
+      "                                     <output>_albedo.hdr, <output>_alpha.hdr and <output>_depth.hdr (and\n"
+      "                                     .pfm with --pfm); one tile on one device\n"
+      "  --feature-step F (=1)              feature pass: march step in cells of the finest axis, 1/8..8\n"
       "  --denoise-sigma F (=4)             denoiser: width of the edge-stopping term in standard deviations\n"
       "  --denoise-passes N (=5)            denoiser: a-trous passes, 1..6 (pass k has step 2^k)\n"
       "  --rng-binding path|thread (=path)  regenerationSK: thread = the reference's Rng(seed + tid)\n"
@@ -195,6 +209,11 @@ int parse(int argc, char** argv, Options& o) {
     else if (a == "--min-iterations") o.min_iterations = (unsigned)strtoul(need("min-iterations").c_str(), nullptr, 10);
     else if (a == "--pass-iterations") o.pass_iterations = (unsigned)strtoul(need("pass-iterations").c_str(), nullptr, 10);
     else if (a == "--denoise") o.denoise = true;
+    else if (a == "--denoise-guided") o.denoise_guided = true;
+    else if (a == "--guide-sigma") {
+      for (int k = 0; k < 3; ++k) o.guide_sigma[k] = strtof(need("guide-sigma").c_str(), nullptr);
+    } else if (a == "--features") o.features = true;
+    else if (a == "--feature-step") o.feature_step = strtof(need("feature-step").c_str(), nullptr);
     else if (a == "--denoise-sigma") o.denoise_sigma = strtof(need("denoise-sigma").c_str(), nullptr);
     else if (a == "--denoise-passes") o.denoise_passes = (unsigned)strtoul(need("denoise-passes").c_str(), nullptr, 10);
     else if (a == "--rng-binding") o.rng_binding = need("rng-binding");
@@ -573,13 +592,20 @@ int main(int argc, char** argv) {
   }
   const unsigned ntiles = o.tiles[0] * o.tiles[1];
   size_t n_dev = devs.size();
-  if ((o.adaptive || o.denoise) && (n_dev > 1 || ntiles > 1)) {
-    fprintf(stderr, "[ConfigParser] Error: %s renders one tile on one device (no --devices > 1, no "
-                    "--number-of-tiles above 1 1)\n", o.adaptive ? "--noise-target" : "--denoise");
+  if (o.denoise && o.denoise_guided) {
+    fprintf(stderr, "[ConfigParser] Error: --denoise-guided excludes --denoise (one filtered image)\n");
     return 2;
   }
-  if (o.denoise && !o.adaptive && o.iterations < 2) {
-    fprintf(stderr, "[ConfigParser] Error: --denoise needs --iterations of at least 2 (a variance per pixel)\n");
+  const bool filtered = o.denoise || o.denoise_guided;
+  if ((o.adaptive || filtered || o.features) && (n_dev > 1 || ntiles > 1)) {
+    fprintf(stderr, "[ConfigParser] Error: %s renders one tile on one device (no --devices > 1, no "
+                    "--number-of-tiles above 1 1)\n",
+            o.adaptive ? "--noise-target" : o.denoise ? "--denoise" : o.denoise_guided ? "--denoise-guided" : "--features");
+    return 2;
+  }
+  if (filtered && !o.adaptive && o.iterations < 2) {
+    fprintf(stderr, "[ConfigParser] Error: %s needs --iterations of at least 2 (a variance per pixel)\n",
+            o.denoise ? "--denoise" : "--denoise-guided");
     return 2;
   }
   const bool tile_mode = ntiles > 1;
@@ -628,8 +654,8 @@ int main(int argc, char** argv) {
     cvr_adaptive_result ares{};
     std::vector<uint32_t> block_samples;
     std::vector<float> denoised;
-    if (o.denoise) {
-      // the session step by step, filtered (cvr_denoise) before it ends.  Without --noise-target a
+    if (filtered) {
+      // the session step by step, filtered (cvr_denoise / cvr_denoise_guided) before it ends.  Without --noise-target a
       // session that never stops a block: every block takes every sample, the plain render's
       // paths.  It takes two samples in its first pass and one in each later pass, so that no
       // launch adds more than two values into a pixel on top of nothing, or one on top of a sum:
@@ -662,7 +688,12 @@ int main(int argc, char** argv) {
       }
       if (!r) r = cvr_adaptive_image(c, image.data(), image.size());
       if (!r) r = cvr_adaptive_maps(c, nullptr, block_samples.data());
-      if (!r) r = cvr_denoise(c, &dd, 0, denoised.data(), denoised.size());
+      if (!r && o.denoise) r = cvr_denoise(c, &dd, 0, denoised.data(), denoised.size());
+      if (!r && o.denoise_guided) {
+        const cvr_denoise_guided_desc gd = {dd, o.guide_sigma[0], o.guide_sigma[1], o.guide_sigma[2], 0u};
+        const cvr_features_desc fd = {o.feature_step, 1.0f / 256.0f, 4096u, 0u};
+        r = cvr_denoise_guided(c, &gd, &fd, 0, denoised.data(), denoised.size());
+      }
       if (!r) r = cvr_adaptive_end(c);
       if (r != CVR_OK) {
         fprintf(stderr, "Error: %s\n", cvr_last_error(c));
@@ -747,6 +778,19 @@ int main(int argc, char** argv) {
         return 1;
       }
     }
+    std::vector<float> feat, feat_depth;
+    if (o.features) {  // the guide buffers of the same view: one more pass over the medium, no samples
+      const cvr_features_desc fd = {o.feature_step, 1.0f / 256.0f, 4096u, 0u};
+      feat.assign((size_t)W * H * 4, 0.0f);
+      feat_depth.assign((size_t)W * H, 0.0f);
+      r = cvr_set_resolution(ctxs[0], W, H);
+      if (!r) r = cvr_set_offset(ctxs[0], 0, 0);
+      if (!r) r = cvr_features(ctxs[0], &fd, feat.data(), feat_depth.data(), feat.size());
+      if (r != CVR_OK) {
+        fprintf(stderr, "Error: %s\n", cvr_last_error(ctxs[0]));
+        return 1;
+      }
+    }
     struct cvr_medium_info mi;
     if (cvr_medium_info(ctxs[0], &mi) == CVR_OK)
       printf("medium on device    : %s, %llu bytes (density %llu, cells %llu, albedo %llu, bounds %llu)\n",
@@ -763,7 +807,22 @@ int main(int argc, char** argv) {
       fprintf(stderr, "Error: could not write %s.pfm\n", o.output.c_str());
       return 1;
     }
-    if (o.denoise && (cvr_write_hdr((o.output + "_denoised.hdr").c_str(), denoised.data(), W, H) != CVR_OK ||
+    if (o.features) {
+      // albedo as it is; opacity and depth as grey images (the scalar in all three channels)
+      std::vector<float> plane((size_t)W * H * 4, 1.0f);
+      const char* names[3] = {"_albedo", "_alpha", "_depth"};
+      for (int k = 0; k < 3; ++k) {
+        for (size_t i = 0; i < (size_t)W * H; ++i)
+          for (int ch = 0; ch < 3; ++ch)
+            plane[4 * i + ch] = k == 0 ? feat[4 * i + ch] : k == 1 ? feat[4 * i + 3] : feat_depth[i];
+        if (cvr_write_hdr((o.output + names[k] + ".hdr").c_str(), plane.data(), W, H) != CVR_OK ||
+            (o.pfm && write_pfm(o.output + names[k] + ".pfm", plane.data(), W, H))) {
+          fprintf(stderr, "Error: could not write %s%s.hdr%s\n", o.output.c_str(), names[k], o.pfm ? " / .pfm" : "");
+          return 1;
+        }
+      }
+    }
+    if (filtered && (cvr_write_hdr((o.output + "_denoised.hdr").c_str(), denoised.data(), W, H) != CVR_OK ||
                       (o.pfm && write_pfm(o.output + "_denoised.pfm", denoised.data(), W, H)))) {
       fprintf(stderr, "Error: could not write %s_denoised.hdr%s\n", o.output.c_str(), o.pfm ? " / .pfm" : "");
       return 1;

@@ -40,6 +40,9 @@ extern "C" {
  *                  cvr_clear_environment, cvr_environment_info, cvr_environment_eval*, cvr_trace_env,
  *                  cvr_read_image, cvr_free_image
  *              6 + CVR_HAS_MEDIUM_READBACK (likewise): cvr_debug_copy_medium, cvr_debug_build_geometry
+ *              6 + CVR_HAS_FEATURES (likewise): cvr_features_desc, cvr_features_host, cvr_features_buffers,
+ *                  cvr_features, cvr_denoise_guided_desc, cvr_denoise_guided_host, cvr_denoise_guided_buffers,
+ *                  cvr_denoise_guided
  * CVR_ABI_VERSION is the ABI this header declares: 6, the library's (cvr_abi_version()).  ABI 6 only
  * adds to ABI 5, so a host that must also load an ABI 5 library can hold itself to that surface:
  * with CVR_ABI_TARGET defined as 5 before the include, the ABI 6 functions and structs are not
@@ -1049,6 +1052,110 @@ int cvr_trace_env(cvr_ctx* ctx, uint32_t first, uint32_t count, cvr_env_record* 
  * dimension or (.hdr) a run that passes its scanline: CVR_ERR_IO. */
 int cvr_read_image(const char* path, uint32_t* width, uint32_t* height, float** rgb);
 void cvr_free_image(float* rgb);
+
+/* ---- primary-ray feature buffers (extension within ABI 6: CVR_HAS_FEATURES) -- */
+/* Noise-free guide buffers of the medium the context holds, and the classic emission-absorption
+ * preview of a transfer function: per pixel, one ray march along the straight camera ray through
+ * the pixel's centre gives the opacity, the mean first-collision albedo and the mean collision
+ * depth.  No RNG, no walk.  Every operation is fp32 +, -, x, /, sqrt in the order written here
+ * (correctly rounded, no fused multiply-add but the fma named below), so the device kernel and
+ * cvr_features_host return the same bits (one definition compiles for both, cvr_features.h).
+ * Per pixel (ix, iy) of the tile (resolution, offset, camera, CVR_OPT_WORLD_TO_AABB as set):
+ * Ray: camera_ray's operations with both pixel jitters 0.5f: px = (float)ix + (float)off_x,
+ *   rx = r2v_x (((px + 0.5f) 2) / full_res_x - 1), ry likewise, v = (rx, ry, 1) / sqrt((rx rx +
+ *   ry ry) + 1), o = column 3 of inv_view, d_a = (v_x M_a0 + v_y M_a1) + v_z M_a2.
+ * Chord: the walk's slab test.  Per axis i = 1 / d, tbot = i (box_min - o), ttop = i (box_max - o),
+ *   lo = minNum(ttop, tbot), hi = maxNum(ttop, tbot), where minNum / maxNum return the other
+ *   operand when the first is NaN and the first when the second is; a +-0 direction component
+ *   gives i = +-inf, and an origin on that axis' plane then a NaN that the other plane's +-inf
+ *   replaces.  enter = maxNum(maxNum(lo_x, lo_y), maxNum(lo_x, lo_z)), t1 = minNum(minNum(hi_x,
+ *   hi_y), minNum(hi_x, hi_z)), t0 = enter > 0 ? enter : 0 (0 for an eye inside the box).  There
+ *   is a chord iff t1 > enter and t1 > t0 (a NaN compares false); a pixel without one outputs
+ *   (0, 0, 0, 0) and depth 0.  Every ray the walk's box test calls a miss has no chord.
+ * Steps: delta = step min(min(e_x / res_x, e_y / res_y), e_z / res_z), e = box_max - box_min,
+ *   n = min(max_steps, ceil((t1 - t0) / delta)), t_i = t0 + ((float)i + 0.5f) delta for i < n; a
+ *   t_i >= t1 is dropped.
+ * Per step, from T = 1 and A = Z = W = 0:
+ *   p = o + t_i d (a multiply, then an add);
+ *   rho = the walk's interpolated density at p: c = p - shift, grid coordinate fma(c, g, +0) with
+ *     shift = box_min / e, g = res - 1 (quirk Q4; CVR_OPT_WORLD_TO_AABB 1: shift = box_min,
+ *     g = (res - 1) / e), corner floor, weights coordinate - corner, the reference's 8 clamped
+ *     taps (quirk Q5) and its trilinear, lerp(a, b, f) = fma(b, f, a (1 - f)), x then y then z;
+ *   s = (scale rho) delta; if not s > 0 the step contributes nothing; otherwise
+ *   a = s / (1 + s) (a rational step opacity: cvr_detmath.h has no exp), w = T a,
+ *   c = the walk's albedo at p: coordinate ((p - box_min) / e) (res - 1), the same taps and trilinear;
+ *   A_c += w c_c, Z += w t_i, W += w, T = T - w; the march ends after a step that leaves T < t_stop.
+ * Output: feat_rgba = (A_r / W, A_g / W, A_b / W, W), feat_depth = (Z / W) / sqrt((e_x e_x +
+ *   e_y e_y) + e_z e_z); all 0 where W = 0.
+ * The bit-equality contract covers media with finite, non-negative density and finite albedo;
+ * other media are read inside their arrays and return something.  Under the contract a step with
+ * rho = 0 changes no accumulator, so the device skips, exactly, the samples of a sparse medium
+ * that lie in an empty super-brick or in the zero cell leaf; it skips nothing else (a dense
+ * medium's brick-bound code 0 does not prove a zero brick).  The output does not depend on the
+ * storage: dense or sparse, CVR_OPT_CELLS, CVR_OPT_BOUNDS, CVR_OPT_UNIFORM_ALBEDO,
+ * CVR_OPT_EMPTY_MASK; a CVR_FORMAT_F16 medium gives the bits of the cvr_half_round-ed arrays.
+ * step in [1/8, 8], t_stop in [0, 1) (0: the march never stops early), max_steps 1..65536,
+ * flags 0: else CVR_ERR_INVALID.  The defaults of the bindings and the CLI are 1, 1/256, 4096.
+ * Not supported: a ray refracted at the GGX boundary (the ray is the straight camera ray; the
+ * buffers are guides, not radiance), shading or lighting, temporal accumulation. */
+#define CVR_HAS_FEATURES 1
+typedef struct cvr_features_desc {
+  float step;
+  float t_stop;
+  uint32_t max_steps;
+  uint32_t flags;
+} cvr_features_desc; /* 16 bytes */
+/* Host only, no GPU: the written statement on a dense medium's host arrays (a sparse medium is
+ * stated through its densified arrays, a half medium through its cvr_half_round-ed ones; g,
+ * roughness, eta and max_density are not read).  out_rgba: tile_w * tile_h * 4 floats;
+ * out_depth: tile_w * tile_h floats, may be NULL.  A NULL pointer, an empty grid, a zero side,
+ * more than 2^24 pixels, world_to_aabb other than 0 / 1: CVR_ERR_INVALID. */
+int cvr_features_host(const cvr_medium_desc* medium, const float inv_view[12], const float raster_to_view[2],
+                      const float full_res[2], uint32_t tile_w, uint32_t tile_h, uint32_t off_x, uint32_t off_y,
+                      int world_to_aabb, const cvr_features_desc* desc, float* out_rgba, float* out_depth);
+/* The pass on the context's medium (own or shared, any storage), camera, resolution and offset,
+ * into device memory or the device address of pinned host memory (d_out_rgba 16-byte aligned;
+ * d_out_depth may be NULL), asynchronous on the context's stream.  Reads the context and writes
+ * nothing of it: not the framebuffer, the moments, the seed or the stats.  Available between
+ * cvr_adaptive_begin and cvr_adaptive_end.  No medium, camera or resolution: CVR_ERR_STATE. */
+int cvr_features_buffers(cvr_ctx* ctx, const cvr_features_desc* desc, float* d_out_rgba, float* d_out_depth);
+/* The same into host memory (host_rgba: tile_w * tile_h * 4 floats, host_floats smaller:
+ * CVR_ERR_INVALID; host_depth: tile_w * tile_h floats or NULL).  Synchronous.  Pinned or
+ * registered memory is stored into by the kernel, other memory through a staging copy. */
+int cvr_features(cvr_ctx* ctx, const cvr_features_desc* desc, float* host_rgba, float* host_depth,
+                 size_t host_floats);
+/* The feature-guided filter: the filter written at CVR_HAS_DENOISE with three more edge-stopping
+ * terms from the feature planes F = feat_rgba and z = feat_depth.  In the 5x5 loop, for a valid
+ * centre p and tap q, the tap's weight becomes  w = (h_j h_i) / (u u) / (g g)  with u as there and
+ *   g = 1 + ((f_a f_a + f_z f_z) + f_o f_o),
+ *   f_a = ((|F_r(q) - F_r(p)| + |F_g(q) - F_g(p)|) + |F_b(q) - F_b(p)|) / sigma_albedo,
+ *   f_z = |z(q) - z(p)| / sigma_depth,  f_o = |F_w(q) - F_w(p)| / sigma_alpha;
+ * a sigma <= 0 switches its term off (f = 0).  The planes are noise-free: they are read at p and
+ * q and never filtered, and play no part in validity, in the 3x3 variance estimate or in the
+ * in-painting of an invalid centre.  With all three sigmas <= 0, g = 1 and w / 1 = w: the bits
+ * of cvr_denoise.  Same operations on host and device: the same bits.
+ * base as cvr_denoise_desc; a sigma that is NaN or +inf, flags != 0: CVR_ERR_INVALID.  The
+ * defaults of the bindings and the CLI: base 5, 4.0, 0.01; sigmas 0.4, 0.1, 0.4 (profiles/features/README.md).
+ * Not supported: albedo demodulation (the colour is filtered as it is), temporal accumulation. */
+typedef struct cvr_denoise_guided_desc {
+  cvr_denoise_desc base;
+  float sigma_albedo, sigma_depth, sigma_alpha;
+  uint32_t flags;
+} cvr_denoise_guided_desc; /* 32 bytes */
+/* cvr_denoise_host's arguments plus the two planes (feat_rgba w * h * 4 floats, feat_depth w * h). */
+int cvr_denoise_guided_host(const float* sum_rgba, const float* m2_rgba, uint32_t w, uint32_t h, uint32_t n_samples,
+                            const uint32_t* block_samples, const cvr_denoise_guided_desc* desc,
+                            const float* feat_rgba, const float* feat_depth, float* out_rgba, float* out_var);
+/* cvr_denoise_buffers' arguments plus two device planes of any origin (d_feat_rgba 16-byte aligned). */
+int cvr_denoise_guided_buffers(cvr_ctx* ctx, const float* d_sum_rgba, const float* d_m2_rgba, uint32_t w, uint32_t h,
+                               uint32_t n_samples, const uint32_t* d_block_samples,
+                               const cvr_denoise_guided_desc* desc, const float* d_feat_rgba, const float* d_feat_depth,
+                               float* d_out_rgba, float* d_out_var);
+/* cvr_denoise with the guide: runs the feature pass (`features`) into planes the context owns
+ * (they grow as the denoiser's scratch images do), then filters the context's sums.  State,
+ * n_samples and the adaptive session as cvr_denoise. */
+int cvr_denoise_guided(cvr_ctx* ctx, const cvr_denoise_guided_desc* desc, const cvr_features_desc* features,
+                       uint32_t n_samples, float* host_rgba, size_t host_floats);
 #endif /* CVR_ABI_VERSION >= 6 */
 
 /* Pinned, device-mapped host memory for cvr_render_share_to_host /
