@@ -13,7 +13,8 @@ HIPFLAGS := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -ffp-contract=off \
 OBJDIR ?= build/obj
 SRCS_HIP := $(CSRC)/cvr_kernels.hip $(CSRC)/cvr_persistent.hip $(CSRC)/cvr_pool.hip $(CSRC)/cvr_wpool.hip $(CSRC)/cvr_wavefront.hip \
             $(CSRC)/cvr_denoise.hip $(CSRC)/cvr_medium_build.hip $(CSRC)/cvr_env.hip $(CSRC)/cvr_features.hip
-SRCS_CPP := $(CSRC)/cvr_api.cpp $(CSRC)/cvr_medium.cpp $(CSRC)/cvr_environment.cpp $(CSRC)/cvr_features_api.cpp $(CSRC)/cvr_image_io.cpp $(CSRC)/cvr_scene.cpp $(CSRC)/cvr_vdb.cpp $(CSRC)/cvr_mhd.cpp $(CSRC)/cvr_xml.cpp
+SRCS_CPP := $(CSRC)/cvr_api.cpp $(CSRC)/cvr_launch.cpp $(CSRC)/cvr_frame.cpp $(CSRC)/cvr_adaptive.cpp \
+            $(CSRC)/cvr_denoise_api.cpp $(CSRC)/cvr_medium.cpp $(CSRC)/cvr_environment.cpp $(CSRC)/cvr_features_api.cpp $(CSRC)/cvr_image_io.cpp $(CSRC)/cvr_scene.cpp $(CSRC)/cvr_vdb.cpp $(CSRC)/cvr_mhd.cpp $(CSRC)/cvr_xml.cpp
 OBJS := $(patsubst $(CSRC)/%.hip,$(OBJDIR)/%.o,$(SRCS_HIP)) $(patsubst $(CSRC)/%.cpp,$(OBJDIR)/%.o,$(SRCS_CPP))
 HDRS := include/cvr.h include/cvr_detmath.h $(wildcard $(CSRC)/*.h)
 # Per-file flags, HIPFLAGS_<file name without .hip>; every rule that compiles a .hip file goes through
@@ -113,17 +114,17 @@ gradient-host-asan: $(OBJS)
 	build/asan/gradient_host_check
 .PHONY: gradient-host-asan
 # cvr_features_host and cvr_denoise_guided_host under AddressSanitizer and UBSan, the same way: the
-# host code of cvr_features_api.cpp and cvr_api.cpp (which hold the two statements) is compiled with
+# host code of cvr_features_api.cpp and cvr_denoise_api.cpp (which hold the two statements) is compiled with
 # the sanitizers and linked with the library's other objects and a main of its own.  A CPU run, no GPU.
 features-host-asan: $(OBJS)
 	@mkdir -p build/asan
-	$(foreach f,cvr_features_api cvr_api,$(HIPCC) $(call hipflags,$(CSRC)/$(f).cpp) -O1 -g -Xarch_host \
+	$(foreach f,cvr_features_api cvr_denoise_api,$(HIPCC) $(call hipflags,$(CSRC)/$(f).cpp) -O1 -g -Xarch_host \
 	    -fsanitize=address,undefined -Xarch_host -fno-sanitize-recover=undefined -x hip -c $(CSRC)/$(f).cpp \
 	    -o build/asan/$(f).o &&) true
 	g++ -O1 -g -std=c++17 -Wall -Iinclude -fsanitize=address,undefined -fno-sanitize-recover=undefined \
 	    -c tests/cpp/features_host_check.cpp -o build/asan/features_host_check.o
 	$(HIPCC) --offload-arch=$(ARCH) -fsanitize=address,undefined -o build/asan/features_host_check \
-	    build/asan/features_host_check.o $(filter-out $(OBJDIR)/cvr_features_api.o $(OBJDIR)/cvr_api.o,$(OBJS)) \
-	    build/asan/cvr_features_api.o build/asan/cvr_api.o -lz
+	    build/asan/features_host_check.o $(filter-out $(OBJDIR)/cvr_features_api.o $(OBJDIR)/cvr_denoise_api.o,$(OBJS)) \
+	    build/asan/cvr_features_api.o build/asan/cvr_denoise_api.o -lz
 	build/asan/features_host_check
 .PHONY: features-host-asan

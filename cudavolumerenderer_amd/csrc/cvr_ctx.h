@@ -1,5 +1,5 @@
 // cvr_ctx.h - the context behind the C ABI's cvr_ctx handle and what its call sites need with it
-// (internal: cvr_api.cpp, cvr_medium.cpp).
+// (internal: the cvr_*.cpp sources of the library; what the launch path shares is in cvr_host.h).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -10,41 +10,16 @@
 #include "cvr_env.h"
 #include "cvr_kernels.h"
 
-struct cvr_ctx {
-  int device = 0;
-  int kernel = CVR_KERNEL_REGENERATION_SK;
-  std::string err;
-
-  hipStream_t own_stream = nullptr;
-  hipStream_t stream = nullptr;
-  hipEvent_t ev_start = nullptr, ev_stop = nullptr;
-  bool timed = false;
-
-  // medium in HBM
-  float* d_density = nullptr;
-  float4* d_albedo = nullptr;
-  float4* d_cells = nullptr;  // corner-replicated density (MediumParams::cells)
-  bool use_cells = true;
-  bool uniform_albedo = true;  // CVR_OPT_UNIFORM_ALBEDO
-  uint8_t* d_bounds = nullptr;  // brick bounds (MediumParams::bounds)
-  uint32_t bound_shift = 2;     // log2 brick size, 0 = off
-  bool bound_shift_set = false; // CVR_OPT_BOUNDS given (else sparse media use 8^3 bricks)
-  size_t n_voxels = 0;
-  uint32_t grids_format = 0;  // format d_density / d_albedo were allocated for
-  // sparse medium (cvr_set_medium_sparse)
-  uint32_t* d_leaves = nullptr;
-  float* d_leaf_density = nullptr;
-  float4* d_leaf_albedo = nullptr;
-  uint32_t* d_sbounds = nullptr;
-  uint32_t* d_emask = nullptr;       // empty-region mask (MediumParams::emask)
-  uint32_t* d_block_perm = nullptr;  // cvr_set_block_order
-  void* d_rec_active = nullptr;      // cvr_trace_launch: records of the launch in progress
-  uint32_t block_perm_n = 0;
+namespace cvr {
+// The launcher settings a helper context of cvr_render_frame takes from its parent in one assignment
+// (cvr_frame.cpp copy_settings): a setting declared here travels to the helpers, so the bands of one
+// frame render under the same settings.  Resources (streams, buffers, caches, the grids computed at
+// init) and what a helper must not take are members of cvr_ctx itself.
+struct Settings {
+  // the parent's medium (re-shared every frame: the parent may have loaded another)
+  cvr::MediumParams m{};
   size_t n_cell_leaves = 0;  // cell-leaf pool slots (incl. the zero slot)
   bool have_medium = false;
-  cvr::MediumParams m{};
-  int medium_format = 0;     // CVR_OPT_MEDIUM_FORMAT (the next set-medium's; the medium's own is m.format)
-  struct cvr_medium_info minfo{};  // cvr_medium_info of the medium in use (own or shared)
 
   // launcher state (the reference's __constant__ symbols)
   float inv_view[12] = {1, 0, 0, 0, 0, -1, 0, 0, 0, 0, -1, 100};
@@ -59,25 +34,11 @@ struct cvr_ctx {
   uint32_t shard_rank = 0, shard_world = 1;  // cvr_set_block_shard
   uint32_t seed = 0;
 
-  float4* d_out_owned = nullptr;
-  size_t out_owned_px = 0;
-  float4* d_out = nullptr;  // active output (owned or external)
-  bool external_out = false;
-
-  unsigned char* d_work = nullptr;  // queue heads + stats counters (kWork* layout)
-  float4* d_pool_T = nullptr;       // wave-pool scheduler: event-only slot part (LaunchParams::pool_T)
-  unsigned char* d_smk = nullptr;   // thread-bound streamingMK: slot buffers, flags, RNG states, counters
-  size_t smk_n = 0;                 // threads d_smk is carved for
-  size_t pool_T_n = 0;
   uint32_t n_queues = 8;            // work-order bands (one per XCD)
   uint32_t subqueues = 8;           // wave pool: queues per band (CVR_OPT_SUBQUEUES)
   int drain = -1;                   // wave pool: drain-mode event trigger (CVR_OPT_DRAIN; -1 = 1)
   int order = 2;                    // 1: pixel-block/sample-inner order when the launch allows it; 2: blocks
                                     // in 2-D Morton order within each band
-  // cached Morton permutation of the launch's blocks (order 2), for the block layout in zkey
-  uint32_t* d_zperm = nullptr;
-  std::vector<uint32_t> h_zperm;
-  uint64_t zkey[5] = {0, 0, 0, 0, 0};
 
   // options
   uint32_t max_segments = 1u << 20;
@@ -90,11 +51,7 @@ struct cvr_ctx {
   int world_to_aabb = 0;  // CVR_OPT_WORLD_TO_AABB (Q4)
   int mk_compaction = 0;  // CVR_OPT_MK_COMPACTION (Q11)
 
-  int cu_count = 0;
-  int persistent_grid = 0;
-  int pool_grid = 0;
   uint32_t pool_tail = 16;
-  int wpool_grid = 0, wpool_grid_sparse = 0;
   // wave-pool register/LDS budget in waves per SIMD (CVR_OPT_WAVES: 3, 4, 5);
   // 0 = the default, 5 (dense and sparse, split slots)
   int wpool_waves = 0;
@@ -103,16 +60,74 @@ struct cvr_ctx {
   int empty_mask = 1;     // CVR_OPT_EMPTY_MASK
   int count_words = 0;    // CVR_OPT_COUNT_WORDS
   uint32_t swap_batch = 8;
-  int track_grid = 0;
-  bool inited = false;
   int scheduler = -1;  // 0 persistent, 1 wavefront pair, 2 workgroup pool, 3 wave-private pool, -1 per kernel id
   int waves = 4;      // persistent kernel register budget (waves per SIMD)
+  uint32_t pool_max = 1u << 21;  // CVR_OPT_POOL: the wavefront pool's slots at most
+};
+}  // namespace cvr
+
+struct cvr_ctx : cvr::Settings {
+  int device = 0;
+  int kernel = CVR_KERNEL_REGENERATION_SK;
+  std::string err;
+
+  hipStream_t own_stream = nullptr;
+  hipStream_t stream = nullptr;
+  hipEvent_t ev_start = nullptr, ev_stop = nullptr;
+  bool timed = false;
+
+  // medium in HBM
+  float* d_density = nullptr;
+  float4* d_albedo = nullptr;
+  float4* d_cells = nullptr;  // corner-replicated density (MediumParams::cells)
+  // Not in Settings on purpose: use_cells, uniform_albedo, bound_shift and medium_format take effect
+  // at the next medium upload, and a helper shares its parent's medium as built.
+  bool use_cells = true;
+  bool uniform_albedo = true;  // CVR_OPT_UNIFORM_ALBEDO
+  uint8_t* d_bounds = nullptr;  // brick bounds (MediumParams::bounds)
+  uint32_t bound_shift = 2;     // log2 brick size, 0 = off
+  bool bound_shift_set = false; // CVR_OPT_BOUNDS given (else sparse media use 8^3 bricks)
+  size_t n_voxels = 0;
+  uint32_t grids_format = 0;  // format d_density / d_albedo were allocated for
+  // sparse medium (cvr_set_medium_sparse)
+  uint32_t* d_leaves = nullptr;
+  float* d_leaf_density = nullptr;
+  float4* d_leaf_albedo = nullptr;
+  uint32_t* d_sbounds = nullptr;
+  uint32_t* d_emask = nullptr;       // empty-region mask (MediumParams::emask)
+  uint32_t* d_block_perm = nullptr;  // cvr_set_block_order
+  uint32_t block_perm_n = 0;
+  int medium_format = 0;     // CVR_OPT_MEDIUM_FORMAT (the next set-medium's; the medium's own is m.format)
+  struct cvr_medium_info minfo{};  // cvr_medium_info of the medium in use (own or shared)
+
+  // Not in Settings on purpose: external_out here, and frame_flush, moments and wf_timing below.  A
+  // helper always renders into its parent's buffer, without moments, in-launch output or timing.
+  float4* d_out_owned = nullptr;
+  size_t out_owned_px = 0;
+  float4* d_out = nullptr;  // active output (owned or external)
+  bool external_out = false;
+
+  unsigned char* d_work = nullptr;  // queue heads + stats counters (kWork* layout)
+  float4* d_pool_T = nullptr;       // wave-pool scheduler: event-only slot part (LaunchParams::pool_T)
+  unsigned char* d_smk = nullptr;   // thread-bound streamingMK: slot buffers, flags, RNG states, counters
+  size_t smk_n = 0;                 // threads d_smk is carved for
+  size_t pool_T_n = 0;
+  // cached Morton permutation of the launch's blocks (order 2), for the block layout in zkey
+  uint32_t* d_zperm = nullptr;
+  std::vector<uint32_t> h_zperm;
+  uint64_t zkey[5] = {0, 0, 0, 0, 0};
+
+  int cu_count = 0;
+  int persistent_grid = 0;
+  int pool_grid = 0;
+  int wpool_grid = 0, wpool_grid_sparse = 0;
+  int track_grid = 0;
+  bool inited = false;
 
   // wavefront pool (cvr_wavefront.hip)
   unsigned char* d_pool = nullptr;
   size_t pool_bytes = 0;
   uint32_t pool_cap = 0;  // slots the allocation holds
-  uint32_t pool_max = 1u << 21;
   cvr::WfPool pool{};
   unsigned int* h_alive = nullptr;  // pinned ring of per-iteration flags
   std::vector<hipEvent_t> it_events;
@@ -125,11 +140,9 @@ struct cvr_ctx {
 
   cvr_stats last{};
 
-  // cvr_render_frame: this launch's band of block rows (band_count 0: every block), the
-  // helper contexts that render the frame's other bands (each with its own stream and work
-  // queues, sharing this context's medium and framebuffer), the copy stream, and the
-  // normalised device image the bands are copied from
-  uint32_t band_first = 0, band_count = 0;
+  // cvr_render_frame: the helper contexts that render the frame's other bands (each with its own
+  // stream and work queues, sharing this context's medium and framebuffer), the copy stream, and
+  // the normalised device image the bands are copied from
   std::vector<cvr_ctx*> frame_kids;
   hipStream_t frame_copy = nullptr;
   hipEvent_t frame_ev[4] = {nullptr, nullptr, nullptr, nullptr};  // [0] cleared, [1 + k] band k rendered
@@ -137,14 +150,13 @@ struct cvr_ctx {
   size_t frame_px = 0;
   // cvr_render_frame's in-launch output (CVR_OPT_FRAME_FLUSH, wave pool): [FrameFlush
   // header | per-block ended-path counts], the flushers' status words (pinned), the
-  // header as last written, and the counts the next launch takes (null: none)
+  // header as last written
   int frame_flush = 1;
   unsigned char* d_flush = nullptr;
   size_t flush_blocks = 0;
   unsigned int* h_flush_status = nullptr;
   cvr::FrameFlush flush_hdr{};
   bool flush_hdr_valid = false;  // d_flush holds flush_hdr
-  unsigned int* frame_done_active = nullptr;
   uint32_t flush_last_blocks = 0, flush_fallbacks = 0;
 
   // CVR_OPT_MOMENTS: the owned framebuffer holds a second float4 per pixel behind the tile
@@ -158,7 +170,6 @@ struct cvr_ctx {
   // the adaptive session
   struct Adaptive {
     bool on = false;        // between cvr_adaptive_begin and cvr_adaptive_end
-    bool internal = false;  // the session's own launch is running through the public entry points
     cvr_adaptive_desc d{};
     uint32_t n_blocks = 0, passes = 0;
     int done = 0;
@@ -209,10 +220,10 @@ bool half_overflows(const float* v, size_t n, size_t stride, size_t take, size_t
 float half_majorant(float max_density);
 }  // namespace cvr
 
-// Calls that are out of order inside an adaptive session (the session's own launches pass).
+// Calls that are out of order inside an adaptive session.
 #define CVR_NOT_IN_SESSION(c, what)                                                                       \
   do {                                                                                                    \
-    if ((c)->ad.on && !(c)->ad.internal)                                                                  \
+    if ((c)->ad.on)                                                                                       \
       return cvr::set_err(&(c)->err, CVR_ERR_STATE, "%s inside an adaptive session (cvr_adaptive_end first)", what); \
   } while (0)
 

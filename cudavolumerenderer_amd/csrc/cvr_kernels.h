@@ -10,7 +10,7 @@
 
 namespace cvr {
 
-// Per-context work area (cvr_api.cpp d_work, zeroed per launch), in bytes:
+// Per-context work area (cvr_ctx d_work, zeroed per launch: cvr_launch.cpp), in bytes:
 // 16 u64 stats at 0, 16 u64 diagnostic counters at 128, up to 64 queue heads
 // from 256 (one 64-byte line each, LaunchParams::queue).
 constexpr size_t kWorkStats = 0, kWorkDebug = 128, kWorkQueues = 256, kMaxQueues = 64;

@@ -222,7 +222,7 @@ CVR_DEV float bound_value(uint32_t c) { return __uint_as_float((c << 19) + kBoun
 
 // u32 division by a launch-invariant divisor: q = (t + ((u - t) >> s1)) >> s2
 // with t = mulhi(u, m) (round-up method, exact for every u32 and d >= 1;
-// host side: cvr_api.cpp make_fastdiv).
+// host side: cvr_launch.cpp make_fastdiv).
 struct FastDiv {
   uint32_t m, sh;  // sh = s1 | s2 << 8
 };
@@ -246,7 +246,7 @@ struct LaunchParams {
   float4* out;            // tile accumulator, tile_px float4
   unsigned int* queue;    // work-queue heads, one per 64-byte line (zeroed per launch)
   unsigned long long* stats;  // CVR_STAT_* counters (zeroed per launch)
-  float4* pool_T;         // wave-pool scheduler: event-only slot part, grid * slots float4 (cvr_api wpool_slots)
+  float4* pool_T;         // wave-pool scheduler: event-only slot part, grid * slots float4 (cvr_launch.cpp, wpool_slots)
   // Debug (cvr_trace_launch): the wave pool writes each path's final record
   // (cvr_path_record) at rec[path_id - path_first]; a u32 path-id array of
   // grid * slots entries sits just below rec.  Null in production.

@@ -334,6 +334,49 @@ def test_render_frame_equals_render_image(cvr, kernel, parts, res):
     c.close()
 
 
+def test_render_frame_bands_honour_the_owners_settings(cvr):
+    """The helper contexts that render a frame's other bands take the owner's
+    settings: with non-default options, a seed and a path range on the owner,
+    cvr_render_frame in three bands (a 64 x 24 tile has three block rows) has
+    the counters and the pixels of a plain launch + copy under the same
+    settings.  The settings matter: the same launch at default options has
+    other step and truncation counts.  Pixels: each holds the range's two
+    samples, so the bound is assert_pixels_close's for two contributions."""
+    w, h, iters, seed = 64, 24, 4, 12345
+    scene = cvr.Scene.synthetic("manix")
+    c = cvr.Context(0, "regenerationSK")
+    c.set_medium(scene.medium)
+    iv, r2v = cvr.default_camera(w, h)
+    c.set_camera(iv, r2v, (w, h))
+    c.init()
+    c.set_resolution(w, h)
+    c.set_iterations(iters)
+    c.set_offset(0, 0)
+    c.set_option(cvr.OPT_FRAME_FLUSH, 0)
+    c.set_path_range(w * h, 2 * w * h)  # whole samples 1 and 2 of the launch's four
+
+    def launch_copy():
+        c.set_seed(seed)
+        c.clear_output()
+        c.launch_render()
+        c.synchronize()
+        return c.copy_output(w, h, float(iters)), c.stats()
+
+    _, dst = launch_copy()  # the default options
+    c.set_option(cvr.OPT_MAX_SEGMENTS, 2)
+    c.set_option(cvr.OPT_WORLD_TO_AABB, 1)
+    c.set_option(cvr.OPT_SUBQUEUES, 1)
+    ref, rst = launch_copy()
+    assert rst.paths == 2 * w * h and rst.truncated > 0
+    assert rst.steps != dst.steps and rst.truncated != dst.truncated, "the settings change nothing"
+    c.set_seed(seed)
+    img, st = c.render_frame(None, 3)
+    for k in ("paths", "segments", "steps", "density", "albedo", "escaped", "truncated", "fetches"):
+        assert getattr(st, k) == getattr(rst, k), k
+    assert_pixels_close(img[..., :3], ref[..., :3], 2, "render_frame in bands, the owner's settings")
+    c.close()
+
+
 def test_framebuffer_growth_keeps_work_order_tables(cvr):
     """growing the owned framebuffer (cvr_set_resolution to a
     larger tile after renders with the Morton work order and a block order)

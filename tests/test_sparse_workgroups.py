@@ -1,7 +1,7 @@
 """The sparse wave pool's four-pool workgroups (round 6, cvr_wpool.hip kWpgSparse): each
 wave of a workgroup keeps its own pool, lists and queue cursor, and the workgroup shares
 one LDS copy of the launch parameters and the empty-region mask.  A wave-pool grid counts
-waves in whole workgroups (cvr_api.cpp wpool_launch_grid), so any grid option renders the
+waves in whole workgroups (cvr_launch.cpp wpool_launch_grid), so any grid option renders the
 same paths: equal counters and pixels up to the summation order against the default grid,
 and per-path records equal to the oracle's with a one-workgroup grid
 (RegenerationVolPTsk_kernel.cuh:146-232 through Utilities.cuh:129-155)."""
