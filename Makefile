@@ -12,9 +12,9 @@ HIPFLAGS := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -ffp-contract=off \
             -fhip-fp32-correctly-rounded-divide-sqrt -Iinclude -I$(CSRC) -Wall
 OBJDIR ?= build/obj
 SRCS_HIP := $(CSRC)/cvr_kernels.hip $(CSRC)/cvr_persistent.hip $(CSRC)/cvr_pool.hip $(CSRC)/cvr_wpool.hip $(CSRC)/cvr_wavefront.hip \
-            $(CSRC)/cvr_denoise.hip $(CSRC)/cvr_medium_build.hip $(CSRC)/cvr_env.hip $(CSRC)/cvr_features.hip
+            $(CSRC)/cvr_denoise.hip $(CSRC)/cvr_medium_build.hip $(CSRC)/cvr_env.hip $(CSRC)/cvr_features.hip $(CSRC)/cvr_field.hip
 SRCS_CPP := $(CSRC)/cvr_api.cpp $(CSRC)/cvr_launch.cpp $(CSRC)/cvr_frame.cpp $(CSRC)/cvr_adaptive.cpp \
-            $(CSRC)/cvr_denoise_api.cpp $(CSRC)/cvr_medium.cpp $(CSRC)/cvr_environment.cpp $(CSRC)/cvr_features_api.cpp $(CSRC)/cvr_image_io.cpp $(CSRC)/cvr_scene.cpp $(CSRC)/cvr_vdb.cpp $(CSRC)/cvr_mhd.cpp $(CSRC)/cvr_xml.cpp
+            $(CSRC)/cvr_denoise_api.cpp $(CSRC)/cvr_medium.cpp $(CSRC)/cvr_environment.cpp $(CSRC)/cvr_features_api.cpp $(CSRC)/cvr_field_api.cpp $(CSRC)/cvr_image_io.cpp $(CSRC)/cvr_scene.cpp $(CSRC)/cvr_vdb.cpp $(CSRC)/cvr_mhd.cpp $(CSRC)/cvr_xml.cpp
 OBJS := $(patsubst $(CSRC)/%.hip,$(OBJDIR)/%.o,$(SRCS_HIP)) $(patsubst $(CSRC)/%.cpp,$(OBJDIR)/%.o,$(SRCS_CPP))
 HDRS := include/cvr.h include/cvr_detmath.h $(wildcard $(CSRC)/*.h)
 # Per-file flags, HIPFLAGS_<file name without .hip>; every rule that compiles a .hip file goes through
@@ -128,3 +128,16 @@ features-host-asan: $(OBJS)
 	    build/asan/cvr_features_api.o build/asan/cvr_denoise_api.o -lz
 	build/asan/features_host_check
 .PHONY: features-host-asan
+# cvr_field_stats_host and cvr_field_histogram_host under AddressSanitizer and UBSan, the same way:
+# cvr_field_api.cpp's host code (the two statements index a voxel's neighbours) is compiled with the
+# sanitizers and linked with the library's other objects and a main of its own.  A CPU run, no GPU.
+field-host-asan: $(OBJS)
+	@mkdir -p build/asan
+	$(HIPCC) $(call hipflags,$(CSRC)/cvr_field_api.cpp) -O1 -g -Xarch_host -fsanitize=address,undefined \
+	    -Xarch_host -fno-sanitize-recover=undefined -x hip -c $(CSRC)/cvr_field_api.cpp -o build/asan/cvr_field_api.o
+	g++ -O1 -g -std=c++17 -Wall -Iinclude -fsanitize=address,undefined -fno-sanitize-recover=undefined \
+	    -c tests/cpp/field_host_check.cpp -o build/asan/field_host_check.o
+	$(HIPCC) --offload-arch=$(ARCH) -fsanitize=address,undefined -o build/asan/field_host_check \
+	    build/asan/field_host_check.o $(filter-out $(OBJDIR)/cvr_field_api.o,$(OBJS)) build/asan/cvr_field_api.o -lz
+	build/asan/field_host_check
+.PHONY: field-host-asan

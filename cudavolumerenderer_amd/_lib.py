@@ -10,6 +10,7 @@ from __future__ import annotations
 import ctypes as C
 import math
 import os
+from collections import namedtuple
 from typing import Optional, Sequence
 
 import numpy as np
@@ -210,6 +211,30 @@ class GradientMediumDesc(C.Structure):
                 ("max_density", C.c_float), ("g", C.c_float), ("roughness", C.c_float * 2), ("eta", C.c_float)]
 
 
+class FieldDesc(C.Structure):
+    """cvr_field_desc: a scalar field (device memory for the Context calls, host memory for the
+    *_host statements) and the voxel spacing its gradient is taken with."""
+    _fields_ = [("res", C.c_uint32 * 3), ("scalar_type", C.c_uint32), ("scalar", C.c_void_p),
+                ("spacing", C.c_float * 3), ("reserved", C.c_uint32)]
+
+
+class FieldStatsStruct(C.Structure):
+    """struct cvr_field_stats."""
+    _fields_ = [("vmin", C.c_float), ("vmax", C.c_float), ("gmax", C.c_float), ("reserved", C.c_uint32),
+                ("nan_values", C.c_uint64), ("nan_gradients", C.c_uint64)]
+
+
+class HistogramDesc(C.Structure):
+    """cvr_histogram_desc: n value bins over [lo, hi] by m gradient-magnitude bins over [glo, ghi]."""
+    _fields_ = [("n", C.c_uint32), ("m", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32),
+                ("lo", C.c_float), ("hi", C.c_float), ("glo", C.c_float), ("ghi", C.c_float)]
+
+
+# What field_stats_host and Context.field_stats return: numpy float32 vmin, vmax, gmax (their bits
+# are the library's) and the two NaN counts
+FieldStats = namedtuple("FieldStats", "vmin vmax gmax nan_values nan_gradients")
+
+
 class MediumLayout(C.Structure):
     """cvr_medium_layout: what an upload built (either path)."""
     _fields_ = [("sparse", C.c_uint32), ("albedo_uniform", C.c_uint32), ("n_leaves", C.c_uint32),
@@ -355,6 +380,12 @@ def load() -> C.CDLL:
         "cvr_classify_gradient_host": (I32, [P, U32, C.POINTER(U32), C.POINTER(GradientTransferDesc), P, P, P]),
         "cvr_set_medium_gradient": (I32, [P, C.POINTER(GradientMediumDesc)]),
         "cvr_set_medium_scene_gradient": (I32, [P, P, C.POINTER(GradientTransferDesc), U32]),
+        "cvr_field_stats_host": (I32, [C.POINTER(FieldDesc), C.POINTER(FieldStatsStruct)]),
+        "cvr_field_histogram_host": (I32, [C.POINTER(FieldDesc), C.POINTER(HistogramDesc), P]),
+        "cvr_field_stats": (I32, [P, C.POINTER(FieldDesc), C.POINTER(FieldStatsStruct)]),
+        "cvr_field_histogram": (I32, [P, C.POINTER(FieldDesc), C.POINTER(HistogramDesc), P]),
+        "cvr_field_histogram_buffers": (I32, [P, C.POINTER(FieldDesc), C.POINTER(HistogramDesc), P]),
+        "cvr_debug_field_geometry": (I32, [C.POINTER(U32)]),
         "cvr_set_environment": (I32, [P, C.POINTER(EnvironmentDesc)]),
         "cvr_clear_environment": (I32, [P]),
         "cvr_environment_info": (I32, [P, C.POINTER(EnvironmentInfo)]),
@@ -560,6 +591,71 @@ def build_geometry() -> dict:
     if out[15] != len(names):
         raise RuntimeError(f"cvr_debug_build_geometry fills {out[15]} entries, this binding knows {len(names)}")
     return dict(zip(names, (int(v) for v in out)))
+
+
+def field_geometry() -> dict:
+    """The launch geometry of the field kernels (cvr_debug_field_geometry; no GPU needed), by name."""
+    out = (C.c_uint32 * 8)()
+    _check(load().cvr_debug_field_geometry(out))
+    names = ("walk_tasks", "walk_z", "hist1d_grid", "lds_bins", "max_bins")
+    if out[7] != len(names):
+        raise RuntimeError(f"cvr_debug_field_geometry fills {out[7]} entries, this binding knows {len(names)}")
+    return dict(zip(names, (int(v) for v in out)))
+
+
+def _field_desc(ptr, scalar_type, res, spacing):
+    if len(spacing) != 3:
+        raise ValueError("spacing: expected 3 floats (x, y, z)")
+    f = FieldDesc()
+    f.res[:] = [int(v) for v in res]
+    f.scalar_type = scalar_type
+    f.scalar = ptr
+    f.spacing[:] = [float(v) for v in spacing]
+    return f
+
+
+def _histogram_desc(n, m, lo, hi, glo, ghi):
+    if m > 1 and (glo is None or ghi is None):
+        raise ValueError("field_histogram: glo and ghi are required with m > 1")
+    return HistogramDesc(n, m, 0, 0, lo, hi, 0.0 if glo is None else glo, 0.0 if ghi is None else ghi)
+
+
+def _field_stats(st: "FieldStatsStruct") -> "FieldStats":
+    return FieldStats(np.float32(st.vmin), np.float32(st.vmax), np.float32(st.gmax), int(st.nan_values),
+                      int(st.nan_gradients))
+
+
+def _host_field(scalar, spacing):
+    src = np.ascontiguousarray(scalar)
+    if src.dtype.name not in _SCALAR_TYPES:
+        raise ValueError(f"scalar: dtype {src.dtype}, expected uint8, uint16, int16 or float32")
+    if src.ndim != 3:
+        raise ValueError(f"scalar: shape {src.shape}, expected (z, y, x)")
+    return src, _field_desc(src.ctypes.data, _SCALAR_TYPES[src.dtype.name], src.shape[::-1], spacing)
+
+
+def field_stats_host(scalar, spacing=(1.0, 1.0, 1.0)) -> "FieldStats":
+    """The field statistics' written statement on the CPU (cvr_field_stats_host; no GPU): of a
+    (z, y, x) numpy array of dtype uint8, uint16, int16 or float32, the smallest and largest
+    non-NaN value, the largest non-NaN gradient magnitude (the gradient of
+    classify_gradient_host, with voxel spacing (x, y, z)) and the counts of NaN values and NaN
+    magnitudes.  Context.field_stats returns the same bits from the device."""
+    _src, f = _host_field(scalar, spacing)
+    st = FieldStatsStruct()
+    _check(load().cvr_field_stats_host(C.byref(f), C.byref(st)))
+    return _field_stats(st)
+
+
+def field_histogram_host(scalar, n, m=1, *, lo, hi, glo=None, ghi=None, spacing=(1.0, 1.0, 1.0)) -> np.ndarray:
+    """The histogram's written statement on the CPU (cvr_field_histogram_host; no GPU): the (m, n)
+    uint32 counts of the voxels of a (z, y, x) numpy array nearest each node of a table of m rows
+    (gradient magnitude over [glo, ghi]) of n entries (value over [lo, hi]).  m = 1: the 1-D
+    histogram, no gradient.  Context.field_histogram returns the same counts from the device."""
+    _src, f = _host_field(scalar, spacing)
+    h = _histogram_desc(n, m, lo, hi, glo, ghi)
+    counts = np.empty((max(int(m), 0), max(int(n), 0)), np.uint32)
+    _check(load().cvr_field_histogram_host(C.byref(f), C.byref(h), counts.ctypes.data))
+    return counts
 
 
 def raw_transfer_table() -> np.ndarray:
@@ -1003,6 +1099,67 @@ class Context:
             import torch
             torch.cuda.current_stream(self.device).synchronize()
         self._c(load().cvr_set_medium_gradient(self._h, C.byref(d)))
+
+    def _device_field(self, what, scalar, spacing, scalar_type, res):
+        """(FieldDesc, is a torch tensor) of what set_medium_gradient accepts as `scalar`, with its checks."""
+        is_tensor = hasattr(scalar, "data_ptr")
+        if res is None:
+            if not is_tensor:
+                raise ValueError(f"{what}: res is required with an int address")
+            if len(scalar.shape) != 3:
+                raise ValueError(f"scalar: shape {tuple(scalar.shape)}, expected (z, y, x)")
+            nz, ny, nx = (int(v) for v in scalar.shape)
+        else:
+            nx, ny, nz = (int(v) for v in res)
+        if is_tensor:
+            _check_device_grid("scalar", scalar, (nz, ny, nx), self.device, tuple(_SCALAR_TYPES))
+        if scalar_type is None:
+            name = str(getattr(scalar, "dtype", "")).split(".")[-1]
+            if name not in _SCALAR_TYPES:
+                raise ValueError(f"{what}: scalar_type is required with an int address")
+            scalar_type = _SCALAR_TYPES[name]
+        f = _field_desc(_device_ptr(scalar), scalar_type, (nx, ny, nz), spacing)
+        return f, is_tensor and type(scalar).__module__.split(".")[0] == "torch"
+
+    def field_stats(self, scalar, spacing=(1.0, 1.0, 1.0), scalar_type=None, res=None) -> "FieldStats":
+        """field_stats_host of a scalar field in device memory (cvr_field_stats), the same bits:
+        the lo, hi and ghi a transfer table can be aimed with.  scalar is what set_medium_gradient
+        accepts.  Synchronous; torch's current stream is synchronised first; the context's medium
+        and framebuffer are not touched."""
+        f, torch_tensor = self._device_field("field_stats", scalar, spacing, scalar_type, res)
+        if torch_tensor:
+            import torch
+            torch.cuda.current_stream(self.device).synchronize()
+        st = FieldStatsStruct()
+        self._c(load().cvr_field_stats(self._h, C.byref(f), C.byref(st)))
+        return _field_stats(st)
+
+    def field_histogram(self, scalar, n, m=1, *, lo, hi, glo=None, ghi=None, spacing=(1.0, 1.0, 1.0), out=None,
+                        scalar_type=None, res=None):
+        """field_histogram_host of a scalar field in device memory (cvr_field_histogram), the same
+        counts, as an (m, n) numpy uint32 array.  With out= a device tensor or address of n * m
+        32-bit words the counts are written there (cvr_field_histogram_buffers: ordered on the
+        context's stream, not synchronised, every word overwritten) and `out` is returned.  scalar
+        is what set_medium_gradient accepts; torch's current stream is synchronised first."""
+        f, torch_tensor = self._device_field("field_histogram", scalar, spacing, scalar_type, res)
+        h = _histogram_desc(n, m, lo, hi, glo, ghi)
+        if out is not None and hasattr(out, "data_ptr"):
+            size = getattr(out, "element_size", lambda: 4)()
+            numel = getattr(out, "numel", lambda: int(n) * int(m))()
+            if size != 4 or numel != int(n) * int(m):
+                raise ValueError(f"out: {numel} elements of {size} bytes, expected {int(n) * int(m)} 32-bit words")
+            contiguous = getattr(out, "is_contiguous", None)
+            if contiguous is not None and not contiguous():
+                raise ValueError("out: not contiguous")
+        if torch_tensor:
+            import torch
+            torch.cuda.current_stream(self.device).synchronize()
+        if out is not None:
+            self._c(load().cvr_field_histogram_buffers(self._h, C.byref(f), C.byref(h), _device_ptr(out)))
+            return out
+        counts = np.empty((max(int(m), 0), max(int(n), 0)), np.uint32)
+        self._c(load().cvr_field_histogram(self._h, C.byref(f), C.byref(h), counts.ctypes.data))
+        return counts
 
     def set_environment(self, image, scale: float = 1.0, rotation=None):
         """Light the scene with a latitude-longitude map (cvr_set_environment): an escaping path adds

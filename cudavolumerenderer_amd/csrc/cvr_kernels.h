@@ -260,6 +260,64 @@ __host__ __device__ inline float4 gradient_classify(float s, float mag, const fl
   e.x = a.x + h * (b.x - a.x), e.y = a.y + h * (b.y - a.y), e.z = a.z + h * (b.z - a.z), e.w = a.w + h * (b.w - a.w);
   return e;
 }
+// Field statistics and value-gradient histograms (cvr_field_stats, cvr_field_histogram and their
+// *_host statements; cvr_field.hip).  The coordinates are the classification's u and v, bit for
+// bit, and a bin is the nearest table node: the one definition for the host and the kernels, on
+// the same terms as transfer_classify.
+struct FieldBins {
+  uint32_t n, m;  // value bins, gradient bins (m == 1: no gradient axis)
+  float lo, hi, glo, ghi;
+};
+// u of a value s over [lo, hi] (v of a magnitude over [glo, ghi]): a NaN gives 0
+__host__ __device__ inline float field_unit(float s, float lo, float hi) {
+  const float t = (s - lo) / (hi - lo);
+  float u = t > 0.0f ? t : 0.0f;  // a NaN compares false: 0
+  u = u < 1.0f ? u : 1.0f;
+  return u;
+}
+// The bin of coordinate c (0..1) on an axis of k nodes: the nearest node, ties upward, with no
+// rounded c * (k - 1) + 0.5: f = x - (float)i0 is exact.
+__host__ __device__ inline uint32_t field_bin(float c, uint32_t k) {
+  const float x = c * (float)(k - 1u);
+  const uint32_t fl = (uint32_t)__builtin_floorf(x), i0 = fl < k - 1u ? fl : k - 1u;
+  const float f = x - (float)i0;
+  const uint32_t b = i0 + (f >= 0.5f ? 1u : 0u);
+  return b < k - 1u ? b : k - 1u;
+}
+// A float's bits as an integer that orders as the values do, -0 below +0 (NaNs lie outside
+// [key(-inf), key(+inf)]), and back
+__host__ __device__ inline uint32_t field_key(uint32_t bits) {
+  return bits ^ ((bits >> 31) ? 0xFFFFFFFFu : 0x80000000u);
+}
+__host__ __device__ inline uint32_t field_unkey(uint32_t key) {
+  return key ^ ((key >> 31) ? 0x80000000u : 0xFFFFFFFFu);
+}
+constexpr uint32_t kFieldKeyPosInf = 0xFF800000u, kFieldKeyNegInf = 0x007FFFFFu;  // field_key of +inf, -inf
+// The launch geometry of the field kernels, named once (cvr_debug_field_geometry reports them)
+constexpr uint32_t kFieldTaskCap = 4096;     // the stencil walk's grid: tasks beyond it are a workgroup's next trip
+constexpr uint32_t kFieldZ = 16;             // z planes per task of the walk (a task: 256 x of one y)
+constexpr uint32_t kFieldGrid1D = 2048;      // the 1-D histogram's grid cap (workgroups of 256)
+constexpr uint32_t kFieldLdsBins = 16384;    // bins a workgroup-private LDS histogram holds (64 KB)
+constexpr uint32_t kFieldMaxBins = 65536;    // the largest n * m
+// The field as the kernels take it: res and the spacing's reciprocals (GradientParams' h1, h2)
+struct FieldSrc {
+  const void* scalar = nullptr;
+  uint32_t scalar_type = 0;
+  uint32_t res[3] = {0u, 0u, 0u};
+  float h1[3] = {1.0f, 1.0f, 1.0f}, h2[3] = {0.5f, 0.5f, 0.5f};
+};
+// What the statistics pass finds, in device memory; the host sets kmin = kFieldKeyPosInf,
+// kmax = kFieldKeyNegInf and the rest to 0 first.
+struct FieldScan {
+  uint32_t kmin, kmax;   // field_key of the smallest and the largest non-NaN value
+  uint32_t gmax_bits;    // bits of the largest non-NaN gradient magnitude (>= +0: they order as the values)
+  uint32_t pad;
+  unsigned long long nan_values, nan_gradients;
+};
+// Asynchronous on s; none waits on another workgroup.  The histogram launch clears and then
+// fills all n * m words of d_counts; m == 1 reads neither glo, ghi nor h1, h2.
+hipError_t launch_field_stats(const FieldSrc& f, FieldScan* d_out, hipStream_t s);
+hipError_t launch_field_histogram(const FieldSrc& f, const FieldBins& b, uint32_t* d_counts, hipStream_t s);
 // Where the build stages take a voxel's values from: the caller's two arrays (scalar null;
 // albedo null: none), or a scalar field of type scalar_type (cvr.h: CVR_SCALAR_*) classified
 // through a table in device memory: the 1-D one by the value (tf), or, with `gradient`, the 2-D

@@ -20,6 +20,9 @@
 //   --features [--feature-step F] (also write the primary-ray feature buffers, cvr_features, as
 //   <output>_albedo.hdr, <output>_alpha.hdr and <output>_depth.hdr), --denoise-guided
 //   [--guide-sigma A Z O] (--denoise through the feature-guided filter, cvr_denoise_guided)
+//   --field-stats, --histogram FILE [--histogram-bins N [M]], --gradient-range auto (the value range,
+//   largest gradient magnitude and value-gradient histogram of a Raw scene's bytes, found on the
+//   device: cvr_field_stats, cvr_field_histogram; with --iterations 0 without a render)
 //
 // Differences from the reference, on purpose: the timer is wall clock (the
 // reference uses clock(), i.e. CPU time, Main.cpp:51-77); main does not wait
@@ -47,6 +50,10 @@ struct Options {
   std::string transfer_file, transfer_mode = "linear";  // --transfer, --transfer-mode
   std::string transfer2d_file;         // --transfer2d
   std::vector<float> gradient_range;   // --gradient-range GLO GHI
+  bool gradient_auto = false;          // --gradient-range auto
+  bool field_stats = false;            // --field-stats
+  std::string histogram_file;          // --histogram FILE
+  std::vector<unsigned> histogram_bins{256, 256};  // --histogram-bins N [M]
   std::vector<float> voxel_spacing{1.0f, 1.0f, 1.0f};  // --voxel-spacing X Y Z
   std::string envmap;  // --envmap FILE
   float env_scale = 1.0f;
@@ -108,7 +115,18 @@ void usage() {
       "                                     the largest byte (cvr_set_medium_gradient); needs --gradient-range,\n"
       "                                     excludes --transfer\n"
       "  --gradient-range GLO GHI           the gradient magnitudes the table's rows span (0 <= GLO < GHI)\n"
+      "  --gradient-range auto              0 and the field's largest gradient magnitude, found on the device\n"
+      "                                     (cvr_field_stats)\n"
       "  --voxel-spacing X Y Z (=1 1 1)     the voxel spacing the gradient is taken with (each > 0)\n"
+      "  --field-stats                      Raw scenes (and --synthetic bucky): print the bytes' value range, largest\n"
+      "                                     gradient magnitude and NaN counts (cvr_field_stats)\n"
+      "  --histogram FILE                   Raw scenes (and --synthetic bucky): write the histogram of the bytes over\n"
+      "                                     the nodes of an N x M table (cvr_field_histogram): a first line 'n m',\n"
+      "                                     then m lines of n counts, row j the gradient bin j; the values span byte\n"
+      "                                     0 .. the largest byte, the gradient --gradient-range (not needed with M 1)\n"
+      "  --histogram-bins N [M] (=256 256)  value bins and gradient bins (N >= 2, N*M <= 65536; M omitted: 1, no gradient)\n"
+      "                                     --field-stats, --histogram and --gradient-range auto take --voxel-spacing;\n"
+      "                                     with --iterations 0 they run without a render\n"
       "  --envmap FILE(.hdr|.pfm)           light the scene with a latitude-longitude environment map in place\n"
       "                                     of the constant white one (cvr_set_environment; every device's\n"
       "                                     context keeps a copy; not with naiveMK or --rng-binding thread)\n"
@@ -191,10 +209,28 @@ int parse(int argc, char** argv, Options& o) {
       std::vector<float>& dst = range ? o.gradient_range : o.voxel_spacing;
       const size_t want = range ? 2 : 3;
       dst.clear();
+      if (range && i + 1 < argc && std::string(argv[i + 1]) == "auto") {
+        o.gradient_auto = true;
+        ++i;
+        continue;
+      }
+      o.gradient_auto = range ? false : o.gradient_auto;
       while (i + 1 < argc && dst.size() < want && !(argv[i + 1][0] == '-' && argv[i + 1][1] == '-'))
         dst.push_back(strtof(argv[++i], nullptr));
       if (dst.size() != want) {
         fprintf(stderr, "[ConfigParser] Error: %s needs %zu values\n", a.c_str(), want);
+        return 2;
+      }
+    }
+    else if (a == "--field-stats") o.field_stats = true;
+    else if (a == "--histogram") o.histogram_file = need("histogram");
+    else if (a == "--histogram-bins") {
+      o.histogram_bins.clear();
+      while (i + 1 < argc && o.histogram_bins.size() < 2 && argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9')
+        o.histogram_bins.push_back((unsigned)strtoul(argv[++i], nullptr, 10));
+      if (o.histogram_bins.size() == 1) o.histogram_bins.push_back(1u);
+      if (o.histogram_bins.size() != 2) {
+        fprintf(stderr, "[ConfigParser] Error: --histogram-bins needs 1 or 2 values\n");
         return 2;
       }
     }
@@ -330,6 +366,77 @@ bool read_transfer(const std::string& path, std::vector<float>& table) {
   return ok;
 }
 
+// --field-stats, --gradient-range auto and --histogram: the scene's bytes as a u8 field with lo 0
+// and hi the largest byte, on `device`.  The bytes are handed to the device calls in pinned,
+// device-mapped host memory (this program links no HIP of its own); the context holds no medium.
+// *gmax receives the largest gradient magnitude when the statistics ran.
+int field_pass(const Options& o, int device, int kernel, const cvr_scene* scene, float* gmax) {
+  const uint8_t* raw = nullptr;
+  size_t n_raw = 0;
+  cvr_medium_desc md{};
+  if (cvr_scene_raw_bytes(scene, &raw, &n_raw) != CVR_OK || !n_raw || cvr_scene_medium(scene, &md) != CVR_OK ||
+      n_raw != (size_t)md.res[0] * md.res[1] * md.res[2])
+    return 1;
+  void* pinned = nullptr;
+  cvr_ctx* ctx = nullptr;
+  auto done = [&](int code) {
+    if (ctx) cvr_destroy(ctx);
+    if (pinned) cvr_host_free(pinned);
+    return code;
+  };
+  auto failed = [&]() {
+    fprintf(stderr, "Error: %s\n", cvr_last_error(ctx));
+    return done(1);
+  };
+  if (cvr_host_alloc(n_raw, &pinned) != CVR_OK || cvr_create(device, kernel, &ctx) != CVR_OK) return failed();
+  memcpy(pinned, raw, n_raw);
+  cvr_field_desc f{};
+  memcpy(f.res, md.res, sizeof(f.res));
+  f.scalar_type = CVR_SCALAR_U8;
+  f.scalar = pinned;
+  for (int k = 0; k < 3; ++k) f.spacing[k] = o.voxel_spacing[k];
+  struct cvr_field_stats st {};
+  if (o.field_stats || o.gradient_auto) {
+    if (cvr_field_stats(ctx, &f, &st) != CVR_OK) return failed();
+    *gmax = st.gmax;
+    if (o.field_stats)
+      printf("field statistics    : values %.9g .. %.9g, largest gradient magnitude %.9g, NaN values %llu, NaN "
+             "gradients %llu\n",
+             (double)st.vmin, (double)st.vmax, (double)st.gmax, (unsigned long long)st.nan_values,
+             (unsigned long long)st.nan_gradients);
+    if (o.gradient_auto && !(st.gmax > 0.0f && std::isfinite(st.gmax))) {
+      fprintf(stderr, "[ConfigParser] Error: --gradient-range auto: the field's largest gradient magnitude is %g (a "
+                      "constant field has no gradient range)\n", (double)st.gmax);
+      return done(2);
+    }
+  }
+  if (!o.histogram_file.empty()) {
+    cvr_histogram_desc h{};
+    h.n = o.histogram_bins[0], h.m = o.histogram_bins[1];
+    h.lo = 0.0f, h.hi = (float)*std::max_element(raw, raw + n_raw);
+    if (h.m > 1u) {
+      h.glo = o.gradient_auto ? 0.0f : o.gradient_range[0];
+      h.ghi = o.gradient_auto ? st.gmax : o.gradient_range[1];
+    }
+    std::vector<uint32_t> counts((size_t)h.n * h.m);
+    if (cvr_field_histogram(ctx, &f, &h, counts.data()) != CVR_OK) return failed();
+    FILE* fp = fopen(o.histogram_file.c_str(), "w");
+    bool ok = fp != nullptr && fprintf(fp, "%u %u\n", h.n, h.m) > 0;
+    for (uint32_t j = 0; ok && j < h.m; ++j)
+      for (uint32_t i = 0; ok && i < h.n; ++i)
+        ok = fprintf(fp, i + 1u < h.n ? "%u " : "%u\n", counts[(size_t)j * h.n + i]) > 0;
+    if (fp && fclose(fp) != 0) ok = false;
+    if (!ok) {
+      fprintf(stderr, "Error: could not write %s\n", o.histogram_file.c_str());
+      return done(1);
+    }
+    printf("histogram           : %u x %u bins over values %g .. %g", h.n, h.m, (double)h.lo, (double)h.hi);
+    if (h.m > 1u) printf(" and gradient magnitudes %g .. %.9g", (double)h.glo, (double)h.ghi);
+    printf(", written to %s\n", o.histogram_file.c_str());
+  }
+  return done(0);
+}
+
 // --transfer2d FILE: a first data line 'n m', then n * m lines of 'r g b density', row by row
 // (blank lines and lines starting with # are skipped) into table; false with a message when the
 // file cannot be read, a line is not what it should be, or the entries are not n * m.
@@ -454,8 +561,43 @@ int main(int argc, char** argv) {
   // --transfer2d: the 2-D table, its gradient range and the voxel spacing
   std::vector<float> transfer2d_table;
   cvr_gradient_transfer_desc transfer2d{};
-  if (o.transfer2d_file.empty() && !o.gradient_range.empty()) {
-    fprintf(stderr, "[ConfigParser] Error: --gradient-range applies to --transfer2d only\n");
+  const bool want_histogram = !o.histogram_file.empty(), histogram_2d = want_histogram && o.histogram_bins[1] > 1u;
+  const bool field_work = o.field_stats || want_histogram || o.gradient_auto;
+  if (o.transfer2d_file.empty() && !want_histogram && (!o.gradient_range.empty() || o.gradient_auto)) {
+    fprintf(stderr, "[ConfigParser] Error: --gradient-range applies to --transfer2d only (and to --histogram)\n");
+    return 2;
+  }
+  if (field_work) {
+    const uint8_t* raw = nullptr;
+    size_t n_raw = 0;
+    if (cvr_scene_raw_bytes(scene, &raw, &n_raw) != CVR_OK || !n_raw) {
+      fprintf(stderr, "[ConfigParser] Error: %s applies to Raw scenes only (and --synthetic bucky): this scene has no "
+                      "scalar bytes\n", o.field_stats ? "--field-stats" : want_histogram ? "--histogram" : "--gradient-range auto");
+      return 2;
+    }
+    const unsigned hn = o.histogram_bins[0], hm = o.histogram_bins[1];
+    if (want_histogram && (hn < 2u || hm < 1u || (unsigned long long)hn * hm > 65536ull)) {
+      fprintf(stderr, "[ConfigParser] Error: --histogram-bins %u %u: N >= 2, M >= 1, N*M <= 65536\n", hn, hm);
+      return 2;
+    }
+    if (histogram_2d && !o.gradient_auto && o.gradient_range.size() != 2) {
+      fprintf(stderr, "[ConfigParser] Error: --histogram with M > 1 needs --gradient-range GLO GHI (or auto)\n");
+      return 2;
+    }
+    if (histogram_2d && !o.gradient_auto) {
+      const float glo = o.gradient_range[0], ghi = o.gradient_range[1];
+      if (!std::isfinite(glo) || !std::isfinite(ghi) || !(glo >= 0.0f) || !(ghi > glo)) {
+        fprintf(stderr, "[ConfigParser] Error: --gradient-range must be finite with 0 <= GLO < GHI\n");
+        return 2;
+      }
+    }
+    for (float v : o.voxel_spacing)
+      if (!std::isfinite(v) || !(v > 0.0f)) {
+        fprintf(stderr, "[ConfigParser] Error: --voxel-spacing must be three finite values > 0\n");
+        return 2;
+      }
+  } else if (o.histogram_bins != std::vector<unsigned>{256u, 256u}) {
+    fprintf(stderr, "[ConfigParser] Error: --histogram-bins applies to --histogram only\n");
     return 2;
   }
   if (!o.transfer2d_file.empty()) {
@@ -466,11 +608,12 @@ int main(int argc, char** argv) {
                       "scene has no scalar bytes to classify\n");
       return 2;
     }
-    if (o.gradient_range.size() != 2) {
+    if (o.gradient_range.size() != 2 && !o.gradient_auto) {
       fprintf(stderr, "[ConfigParser] Error: --transfer2d needs --gradient-range GLO GHI\n");
       return 2;
     }
-    const float glo = o.gradient_range[0], ghi = o.gradient_range[1];
+    // (auto: a placeholder range here, the device statistics' below)
+    const float glo = o.gradient_auto ? 0.0f : o.gradient_range[0], ghi = o.gradient_auto ? 1.0f : o.gradient_range[1];
     if (!std::isfinite(glo) || !std::isfinite(ghi) || !(glo >= 0.0f) || !(ghi > glo)) {
       fprintf(stderr, "[ConfigParser] Error: --gradient-range must be finite with 0 <= GLO < GHI\n");
       return 2;
@@ -589,6 +732,19 @@ int main(int argc, char** argv) {
     fprintf(stderr, "[ConfigParser] Error: --devices needs a count (N >= 1) or a list of two or more device ids "
                     "(d0,d1,...), digits only\n");
     return 2;
+  }
+  if (field_work) {
+    float gmax = 0.0f;
+    if (int fr = field_pass(o, devs[0], kernel, scene, &gmax)) return fr;
+    if (o.gradient_auto && transfer2d.n) {
+      transfer2d.glo = 0.0f;
+      transfer2d.ghi = gmax;
+      printf("[ConfigParser] gradient range set to 0 .. %.9g.\n", (double)gmax);
+    }
+    if (o.iterations == 0) {  // the field's numbers alone: no render, no image
+      cvr_free_image(env_rgb);
+      return 0;
+    }
   }
   const unsigned ntiles = o.tiles[0] * o.tiles[1];
   size_t n_dev = devs.size();

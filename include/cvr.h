@@ -43,6 +43,9 @@ extern "C" {
  *              6 + CVR_HAS_FEATURES (likewise): cvr_features_desc, cvr_features_host, cvr_features_buffers,
  *                  cvr_features, cvr_denoise_guided_desc, cvr_denoise_guided_host, cvr_denoise_guided_buffers,
  *                  cvr_denoise_guided
+ *              6 + CVR_HAS_FIELD_HISTOGRAM (likewise): cvr_field_desc, cvr_field_stats, cvr_histogram_desc,
+ *                  cvr_field_stats_host, cvr_field_histogram_host, cvr_field_stats, cvr_field_histogram,
+ *                  cvr_field_histogram_buffers, cvr_debug_field_geometry
  * CVR_ABI_VERSION is the ABI this header declares: 6, the library's (cvr_abi_version()).  ABI 6 only
  * adds to ABI 5, so a host that must also load an ABI 5 library can hold itself to that surface:
  * with CVR_ABI_TARGET defined as 5 before the include, the ABI 6 functions and structs are not
@@ -947,6 +950,96 @@ int cvr_set_medium_gradient(cvr_ctx* ctx, const cvr_gradient_medium_desc* medium
  * the descriptor's.  flags: CVR_DEVMED_SPARSE or 0.  A scene without raw bytes: CVR_ERR_INVALID. */
 int cvr_set_medium_scene_gradient(cvr_ctx* ctx, const cvr_scene* scene, const cvr_gradient_transfer_desc* transfer,
                                   uint32_t flags);
+
+/* ---- field statistics and value-gradient histograms (extension within ABI 6:
+ *      CVR_HAS_FIELD_HISTOGRAM) -- */
+/* What the two classifications above need to be aimed: the value range and the largest gradient
+ * magnitude of a scalar field (lo, hi and ghi of their descriptors), and the histogram of its
+ * voxels over the nodes of a 1-D or 2-D table, the joint histogram of value and gradient magnitude
+ * a 2-D table is designed on.  The gradient is the one stated above and is never stored.
+ * Every operation is fp32 +, -, x, /, sqrtf, floorf and comparisons in the order written, no
+ * fused multiply-add, / and sqrtf correctly rounded; the results are integer counts and
+ * order-independent extrema, so the device calls return exactly what the *_host statements return
+ * (one definition compiles for both, cvr_kernels.h).  For voxel (x, y, z), S(.) the voxel converted
+ * to float:
+ *   mag = the gradient magnitude of CVR_HAS_GRADIENT_TRANSFER's statement, with its one-sided rule
+ *         on a face and hx1 = 1.0f / spacing[0], hx2 = 0.5f / spacing[0] (and y, z) computed once on
+ *         the host;
+ *   u:  t = (s - lo) / (hi - lo), u = t > 0 ? t : 0, then u = u < 1 ? u : 1 (a NaN gives 0): the
+ *       classifications' u, bit for bit;
+ *   v:  likewise from mag, glo and ghi;
+ *   the bin of a coordinate c on an axis of k nodes: x = c * (float)(k - 1),
+ *       i0 = min((uint)floorf(x), k - 1), f = x - (float)i0 (exact),
+ *       bin = min(i0 + (f >= 0.5f ? 1 : 0), k - 1): the nearest table node, ties upward, with no
+ *       rounded x + 0.5.  Values outside [lo, hi] fall into the edge bins, as the classification
+ *       clamps them; a NaN into bin 0.
+ * Histogram: n value bins by m gradient bins, the shape of an m-row, n-entry table;
+ *   counts[j * n + i] = the number of voxels with value bin i and gradient bin j, as uint32.
+ *   2 <= n, 1 <= m, n * m <= 65536.  m == 1 is the 1-D histogram: no gradient is computed and glo,
+ *   ghi and spacing are neither read nor judged.  The counts sum to the voxel count; a field of
+ *   more than 2^32 - 1 voxels is refused.
+ * Statistics:
+ *   vmin, vmax over the voxels whose value is not NaN, ordered by the total order of the bits that
+ *     puts -0 below +0 (so the returned bits are defined); with no such voxel +inf and -inf;
+ *   gmax over the voxels whose magnitude is not NaN (+inf counts); with none, 0;
+ *   nan_values, nan_gradients: the voxels whose value, whose magnitude is NaN (inf - inf is one).
+ * Refusals, all CVR_ERR_INVALID, in this order:
+ *   1. NULL arguments (the context, a descriptor, the statistics' output);
+ *   2. a zero extent, or more than 2^32 - 1 voxels: from res alone, before any pointer is looked at;
+ *   3. an unknown scalar_type, or a non-zero reserved or flags;
+ *   4. n < 2, m < 1 or n * m > 65536;
+ *   5. lo / hi not finite, or hi <= lo;
+ *   6. for m > 1 only: glo / ghi not finite, glo < 0 or ghi <= glo;
+ *   7. for m > 1 only, and always for the statistics: a spacing that is not finite or not > 0;
+ *   8. a NULL scalar or counts pointer;
+ *   9. a scalar (the device calls: or d_counts) that is misaligned for its type, or, the device
+ *      calls, is not device-accessible memory of the context's device.
+ * The device calls take the device and the stream from the context and otherwise only read it:
+ * they work with or without a medium and inside an adaptive session, and leave cvr_medium_info,
+ * the medium and the framebuffer untouched.  cvr_field_stats and cvr_field_histogram are
+ * synchronous and the field may be freed when they return; cvr_field_histogram_buffers is ordered
+ * on the context's stream and does not synchronise, and it overwrites all n * m words of d_counts,
+ * so the caller need not clear them.
+ * Not supported: weighted or float histograms, histograms of the stored medium or of a sparse
+ * leaf pool, percentiles or automatic table design, second-derivative axes, keeping the field. */
+#define CVR_HAS_FIELD_HISTOGRAM 1
+typedef struct cvr_field_desc {
+  uint32_t res[3];
+  uint32_t scalar_type; /* CVR_SCALAR_* */
+  const void* scalar;   /* device for the context calls, host for *_host; res product elements, x fastest */
+  float spacing[3];     /* finite, > 0; read where a gradient is taken */
+  uint32_t reserved;    /* 0 */
+} cvr_field_desc; /* 40 bytes */
+/* (a struct tag only: the name cvr_field_stats is the device call's, so the struct is written
+ * `struct cvr_field_stats` in C and in C++) */
+struct cvr_field_stats {
+  float vmin, vmax, gmax;
+  uint32_t reserved; /* 0 */
+  uint64_t nan_values, nan_gradients;
+}; /* 32 bytes */
+typedef struct cvr_histogram_desc {
+  uint32_t n, m;     /* value bins, gradient bins */
+  uint32_t flags;    /* 0 */
+  uint32_t reserved; /* 0 */
+  float lo, hi;      /* finite, hi > lo */
+  float glo, ghi;    /* m > 1: finite, 0 <= glo < ghi */
+} cvr_histogram_desc; /* 32 bytes */
+/* Host only, no GPU: the statements above over a field in host memory. */
+int cvr_field_stats_host(const cvr_field_desc* field, struct cvr_field_stats* stats);
+int cvr_field_histogram_host(const cvr_field_desc* field, const cvr_histogram_desc* histogram, uint32_t* counts);
+/* The same of a field in device memory; host_counts: n * m words of host memory, d_counts: of
+ * device memory. */
+int cvr_field_stats(cvr_ctx* ctx, const cvr_field_desc* field, struct cvr_field_stats* stats);
+int cvr_field_histogram(cvr_ctx* ctx, const cvr_field_desc* field, const cvr_histogram_desc* histogram,
+                        uint32_t* host_counts);
+int cvr_field_histogram_buffers(cvr_ctx* ctx, const cvr_field_desc* field, const cvr_histogram_desc* histogram,
+                                uint32_t* d_counts);
+/* Debug, host only: the launch geometry of the field kernels, as cvr_debug_build_geometry reports
+ * the build's.  out[0] the stencil walk's grid cap in tasks and [1] the z planes of a task (a
+ * task: 256 x of one y); [2] the 1-D histogram's grid cap (workgroups of 256 lanes, 16 bytes per
+ * lane and trip for the integer types); [3] the most bins a workgroup keeps in LDS (more: global
+ * atomics); [4] the largest n * m; [5], [6] 0; [7] the number of entries filled, 5. */
+int cvr_debug_field_geometry(uint32_t out[8]);
 
 /* ---- environment-map lighting (extension within ABI 6: CVR_HAS_ENVMAP) -- */
 /* Without an environment every path that leaves the box adds its throughput T: a constant white
