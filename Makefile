@@ -100,44 +100,27 @@ variant-dnplain: $(OBJS)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o build/variants/dnplain/libcvr.so \
 	    $(filter-out $(OBJDIR)/cvr_denoise.o,$(OBJS)) build/variants/dnplain/cvr_denoise.o -Wl,-soname,libcvr.so -lz
 .PHONY: variant-dnplain
-# cvr_classify_gradient_host and the gradient descriptor's checks under AddressSanitizer and UBSan:
-# cvr_medium.cpp's host code alone is compiled with the sanitizers (-Xarch_host: the device code
-# is not) and linked with the library's other objects and a main of its own.  A CPU run, no GPU.
-gradient-host-asan: $(OBJS)
+# Host statements under AddressSanitizer and UBSan: the host code alone of the listed sources is
+# compiled with the sanitizers (-Xarch_host: the device code is not) and linked with the library's
+# other objects and a check program with a main of its own.  A CPU run, no GPU.  The loop over a
+# voxel's neighbours (cvr_gradient.h) is compiled into cvr_medium.cpp and cvr_field_api.cpp.
+#   $(1): the stem of <stem>-host-asan and tests/cpp/<stem>_host_check.cpp, $(2): the sources' names
+define host_asan
+$(1)-host-asan: $$(OBJS)
 	@mkdir -p build/asan
-	$(HIPCC) $(call hipflags,$(CSRC)/cvr_medium.cpp) -O1 -g -Xarch_host -fsanitize=address,undefined \
-	    -Xarch_host -fno-sanitize-recover=undefined -x hip -c $(CSRC)/cvr_medium.cpp -o build/asan/cvr_medium.o
+	$$(foreach f,$(2),$$(HIPCC) $$(call hipflags,$$(CSRC)/$$(f).cpp) -O1 -g -Xarch_host -fsanitize=address,undefined \
+	    -Xarch_host -fno-sanitize-recover=undefined -x hip -c $$(CSRC)/$$(f).cpp -o build/asan/$$(f).o &&) true
 	g++ -O1 -g -std=c++17 -Wall -Iinclude -fsanitize=address,undefined -fno-sanitize-recover=undefined \
-	    -c tests/cpp/gradient_host_check.cpp -o build/asan/gradient_host_check.o
-	$(HIPCC) --offload-arch=$(ARCH) -fsanitize=address,undefined -o build/asan/gradient_host_check \
-	    build/asan/gradient_host_check.o $(filter-out $(OBJDIR)/cvr_medium.o,$(OBJS)) build/asan/cvr_medium.o -lz
-	build/asan/gradient_host_check
-.PHONY: gradient-host-asan
-# cvr_features_host and cvr_denoise_guided_host under AddressSanitizer and UBSan, the same way: the
-# host code of cvr_features_api.cpp and cvr_denoise_api.cpp (which hold the two statements) is compiled with
-# the sanitizers and linked with the library's other objects and a main of its own.  A CPU run, no GPU.
-features-host-asan: $(OBJS)
-	@mkdir -p build/asan
-	$(foreach f,cvr_features_api cvr_denoise_api,$(HIPCC) $(call hipflags,$(CSRC)/$(f).cpp) -O1 -g -Xarch_host \
-	    -fsanitize=address,undefined -Xarch_host -fno-sanitize-recover=undefined -x hip -c $(CSRC)/$(f).cpp \
-	    -o build/asan/$(f).o &&) true
-	g++ -O1 -g -std=c++17 -Wall -Iinclude -fsanitize=address,undefined -fno-sanitize-recover=undefined \
-	    -c tests/cpp/features_host_check.cpp -o build/asan/features_host_check.o
-	$(HIPCC) --offload-arch=$(ARCH) -fsanitize=address,undefined -o build/asan/features_host_check \
-	    build/asan/features_host_check.o $(filter-out $(OBJDIR)/cvr_features_api.o $(OBJDIR)/cvr_denoise_api.o,$(OBJS)) \
-	    build/asan/cvr_features_api.o build/asan/cvr_denoise_api.o -lz
-	build/asan/features_host_check
-.PHONY: features-host-asan
-# cvr_field_stats_host and cvr_field_histogram_host under AddressSanitizer and UBSan, the same way:
-# cvr_field_api.cpp's host code (the two statements index a voxel's neighbours) is compiled with the
-# sanitizers and linked with the library's other objects and a main of its own.  A CPU run, no GPU.
-field-host-asan: $(OBJS)
-	@mkdir -p build/asan
-	$(HIPCC) $(call hipflags,$(CSRC)/cvr_field_api.cpp) -O1 -g -Xarch_host -fsanitize=address,undefined \
-	    -Xarch_host -fno-sanitize-recover=undefined -x hip -c $(CSRC)/cvr_field_api.cpp -o build/asan/cvr_field_api.o
-	g++ -O1 -g -std=c++17 -Wall -Iinclude -fsanitize=address,undefined -fno-sanitize-recover=undefined \
-	    -c tests/cpp/field_host_check.cpp -o build/asan/field_host_check.o
-	$(HIPCC) --offload-arch=$(ARCH) -fsanitize=address,undefined -o build/asan/field_host_check \
-	    build/asan/field_host_check.o $(filter-out $(OBJDIR)/cvr_field_api.o,$(OBJS)) build/asan/cvr_field_api.o -lz
-	build/asan/field_host_check
-.PHONY: field-host-asan
+	    -c tests/cpp/$(1)_host_check.cpp -o build/asan/$(1)_host_check.o
+	$$(HIPCC) --offload-arch=$$(ARCH) -fsanitize=address,undefined -o build/asan/$(1)_host_check \
+	    build/asan/$(1)_host_check.o $$(filter-out $$(patsubst %,$$(OBJDIR)/%.o,$(2)),$$(OBJS)) \
+	    $$(patsubst %,build/asan/%.o,$(2)) -lz
+	build/asan/$(1)_host_check
+.PHONY: $(1)-host-asan
+endef
+# cvr_classify_gradient_host and the gradient descriptor's checks
+$(eval $(call host_asan,gradient,cvr_medium))
+# cvr_features_host and cvr_denoise_guided_host
+$(eval $(call host_asan,features,cvr_features_api cvr_denoise_api))
+# cvr_field_stats_host and cvr_field_histogram_host
+$(eval $(call host_asan,field,cvr_field_api))

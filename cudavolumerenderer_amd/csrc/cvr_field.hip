@@ -1,11 +1,12 @@
 // Field statistics and value-gradient histograms of a scalar field in device memory
 // (cvr_field_stats, cvr_field_histogram; cvr.h states what is computed, cvr_kernels.h holds the
-// one definition of u, v and the bin rule).  Every result is an integer count or an
-// order-independent extremum, so any schedule returns the host statement's numbers exactly.
+// one definition of the bin rule, cvr_gradient.h that of u, v and the gradient).  Every result is
+// an integer count or an order-independent extremum, so any schedule returns the host statement's
+// numbers exactly.
 //
-// The 2-D histogram and the statistics need the gradient and take k_gradient's walk
-// (cvr_medium_build.hip), restated here so that the build kernels' instruction streams stay as
-// they are.  The 1-D histogram has no stencil and streams the field 16 bytes per lane.
+// The 2-D histogram and the statistics need the gradient: k_field_walk runs gradient_walk
+// (cvr_gradient.h), the walk k_gradient (cvr_medium_build.hip) classifies from, and bins or scans
+// what it hands over.  The 1-D histogram has no stencil and streams the field 16 bytes per lane.
 //
 // A workgroup keeps its histogram in LDS (sized to the bins it holds, not to the limit, so that
 // small tables leave the CU its occupancy), updates it with non-returning LDS adds and flushes it
@@ -22,6 +23,7 @@
 #include <algorithm>
 #include <type_traits>
 
+#include "cvr_device.h"
 #include "cvr_kernels.h"
 
 // 0: every lane adds its own 1 (the A/B partner of the merge, profiles/histogram/README.md)
@@ -31,25 +33,6 @@
 
 namespace cvr {
 namespace {
-
-__device__ __forceinline__ uint32_t wave_min_u32(uint32_t v) {
-  for (int o = 32; o; o >>= 1) {
-    const uint32_t t = __shfl_xor(v, o);
-    v = t < v ? t : v;
-  }
-  return v;
-}
-__device__ __forceinline__ uint32_t wave_max_u32(uint32_t v) {
-  for (int o = 32; o; o >>= 1) {
-    const uint32_t t = __shfl_xor(v, o);
-    v = t > v ? t : v;
-  }
-  return v;
-}
-__device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v) {
-  for (int o = 32; o; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
 
 // hist[bin] += 1 for every lane with `active`; every lane of the wave calls this.  The lanes that
 // hold the first active lane's bin are counted by a ballot and added by that lane alone (a wave
@@ -118,12 +101,12 @@ struct StatScan {
   }
   __device__ __forceinline__ void commit(FieldScan* __restrict__ out) {
     __shared__ uint32_t s_red[4][5];
-    kmin = wave_min_u32(kmin);
-    kmax = wave_max_u32(kmax);
-    gmax = wave_max_u32(gmax);
+    kmin = wave_min(kmin);
+    kmax = wave_max(kmax);
+    gmax = wave_max(gmax);
     // (a work-item's counts and a wave's sums stay below 2^32: the field has fewer voxels)
-    nan_v = wave_sum_u32(nan_v);
-    nan_g = wave_sum_u32(nan_g);
+    nan_v = wave_sum(nan_v);
+    nan_g = wave_sum(nan_g);
     const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
     if (lane == 0) {
       s_red[w][0] = kmin, s_red[w][1] = kmax, s_red[w][2] = gmax, s_red[w][3] = nan_v, s_red[w][4] = nan_g;
@@ -147,59 +130,24 @@ struct StatScan {
   }
 };
 
-// The stencil walk: a task is 256 consecutive x of one y over kFieldZ consecutive z; a work-item
-// keeps its voxel's z - 1, z, z + 1 in registers while it marches along z, the x neighbours come
-// from the adjacent lanes (a load only in a wave's first and last lane), the y neighbours are two
-// loads of rows that the tasks of y - 1 and y + 1 read as their own.  The block index is turned
-// as k_gradient turns it, so that the workgroups of one XCD take consecutive tasks and those rows
-// are found in the L2 a neighbour task has just filled (speed only: any placement counts the same).
-// kHist: the histogram of blockIdx.y's band of `band` bins into counts; otherwise the statistics into out.
+// The stencil pass over gradient_walk (cvr_gradient.h).  kHist: the histogram of blockIdx.y's band
+// of `band` bins into counts, merged across the wave, so every lane bins; otherwise the statistics
+// of the lanes inside the row into out.
 template <class T, bool kHist>
 __global__ __launch_bounds__(256) void k_field_walk(const T* __restrict__ S, uint32_t nx, uint32_t ny, uint32_t nz,
-                                                    float h1x, float h2x, float h1y, float h2y, float h1z, float h2z,
-                                                    FieldBins b, uint32_t band, uint32_t* __restrict__ counts,
-                                                    FieldScan* __restrict__ out) {
+                                                    GradientAxes axes, FieldBins b, uint32_t band,
+                                                    uint32_t* __restrict__ counts, FieldScan* __restrict__ out) {
   Band hist(kHist ? b.n * b.m : 0u, band);
   StatScan st;
-  const uint32_t nxc = (nx + 255u) / 256u, nzc = (nz + kFieldZ - 1u) / kFieldZ;
-  const size_t ntasks = (size_t)nxc * ny * nzc;
-  const uint32_t lane = threadIdx.x & 63u;
-  const uint32_t nb = gridDim.x;
-  const uint32_t vb = (nb & 7u) ? blockIdx.x : (blockIdx.x & 7u) * (nb >> 3) + (blockIdx.x >> 3);
-  for (size_t t = vb; t < ntasks; t += nb) {
-    const uint32_t xc = (uint32_t)(t % nxc), y = (uint32_t)((t / nxc) % ny), zc = (uint32_t)(t / ((size_t)nxc * ny));
-    const uint32_t x0 = xc * 256u + threadIdx.x;
-    const bool in = x0 < nx;
-    const uint32_t x = in ? x0 : nx - 1u;  // (lanes past the row read its last voxel and count nothing)
-    uint32_t xm, xp, ym, yp;
-    float kx, ky;
-    gradient_neighbours(x, nx, h1x, h2x, xm, xp, kx);
-    gradient_neighbours(y, ny, h1y, h2y, ym, yp, ky);
-    const uint32_t z0 = zc * kFieldZ, z1 = z0 + kFieldZ < nz ? z0 + kFieldZ : nz;
-    auto at = [&](uint32_t xx, uint32_t yy, uint32_t zz) { return (float)S[((size_t)zz * ny + yy) * nx + xx]; };
-    float prev = at(x, y, z0 > 0u ? z0 - 1u : z0), cur = at(x, y, z0);
-    for (uint32_t z = z0; z < z1; ++z) {
-      uint32_t zm, zp;
-      float kz;
-      gradient_neighbours(z, nz, h1z, h2z, zm, zp, kz);
-      const float next = zp != z ? at(x, y, zp) : cur;
-      const float sym = ym != y ? at(x, ym, z) : cur, syp = yp != y ? at(x, yp, z) : cur;
-      // every lane of the wave takes part in the two moves (the loop bounds are the workgroup's)
-      const float left = __shfl_up(cur, 1), right = __shfl_down(cur, 1);
-      const float sxm = xm == x ? cur : lane != 0u ? left : at(xm, y, z);
-      const float sxp = xp == x ? cur : lane != 63u ? right : at(xp, y, z);
-      const float mag = gradient_magnitude(sxm, sxp, kx, sym, syp, ky, prev, next, kz);
-      if constexpr (kHist) {
-        const uint32_t i = field_bin(field_unit(cur, b.lo, b.hi), b.n);
-        const uint32_t j = field_bin(field_unit(mag, b.glo, b.ghi), b.m);
-        hist.add(j * b.n + i, in);
-      } else {
-        if (in) st.take(cur, mag);
-      }
-      prev = cur;
-      cur = next;
+  gradient_walk(S, nx, ny, nz, axes, [&](bool in, uint32_t, uint32_t, uint32_t, float cur, float mag) {
+    if constexpr (kHist) {
+      const uint32_t i = field_bin(unit_clamp(cur, b.lo, b.hi), b.n);
+      const uint32_t j = field_bin(unit_clamp(mag, b.glo, b.ghi), b.m);
+      hist.add(j * b.n + i, in);
+    } else {
+      if (in) st.take(cur, mag);
     }
-  }
+  });
   if constexpr (kHist)
     hist.flush(counts);
   else
@@ -233,7 +181,7 @@ __global__ __launch_bounds__(256) void k_field_hist1d(const T* __restrict__ S, s
       for (uint32_t k = 0; k < V; ++k) {
         const uint32_t byte = k * kSize;
         const T v = (T)(w[byte >> 2] >> ((byte & 3u) * 8u));
-        hist.add(field_bin(field_unit((float)v, b.lo, b.hi), b.n), active);
+        hist.add(field_bin(unit_clamp((float)v, b.lo, b.hi), b.n), active);
       }
     }
   }
@@ -242,7 +190,7 @@ __global__ __launch_bounds__(256) void k_field_hist1d(const T* __restrict__ S, s
     const size_t e = e0 + lane;
     const bool active = e < rest;
     const size_t i = !active ? 0 : e < head ? e : body_end + (e - head);
-    hist.add(field_bin(field_unit((float)S[i], b.lo, b.hi), b.n), active);
+    hist.add(field_bin(unit_clamp((float)S[i], b.lo, b.hi), b.n), active);
   }
   hist.flush(counts);
 }
@@ -270,20 +218,17 @@ hipError_t with_type(uint32_t scalar_type, F f) {
   }
 }
 
-size_t walk_tasks(const FieldSrc& f) {
-  return (size_t)((f.res[0] + 255u) / 256u) * f.res[1] * ((f.res[2] + kFieldZ - 1u) / kFieldZ);
-}
+size_t walk_tasks(const FieldSrc& f) { return gradient_walk_tasks(f.res[0], f.res[1], f.res[2]); }
 
 }  // namespace
 
 hipError_t launch_field_stats(const FieldSrc& f, FieldScan* d_out, hipStream_t s) {
   const size_t voxels = (size_t)f.res[0] * f.res[1] * f.res[2];
-  const uint32_t grid = field_grid(walk_tasks(f), voxels, 0u, kFieldTaskCap);
+  const uint32_t grid = field_grid(walk_tasks(f), voxels, 0u, kWalkTaskCap);
   return with_type(f.scalar_type, [&](auto* tag) {
     using T = std::remove_cv_t<std::remove_pointer_t<decltype(tag)>>;
     hipLaunchKernelGGL((k_field_walk<T, false>), dim3(grid), dim3(256), 0, s, static_cast<const T*>(f.scalar),
-                       f.res[0], f.res[1], f.res[2], f.h1[0], f.h2[0], f.h1[1], f.h2[1], f.h1[2], f.h2[2], FieldBins{},
-                       0u, (uint32_t*)nullptr, d_out);
+                       f.res[0], f.res[1], f.res[2], f.axes, FieldBins{}, 0u, (uint32_t*)nullptr, d_out);
     return hipGetLastError();
   });
 }
@@ -299,10 +244,9 @@ hipError_t launch_field_histogram(const FieldSrc& f, const FieldBins& b, uint32_
     using T = std::remove_cv_t<std::remove_pointer_t<decltype(tag)>>;
     const T* S = static_cast<const T*>(f.scalar);
     if (b.m > 1u) {
-      const uint32_t grid = field_grid(walk_tasks(f), voxels, band, kFieldTaskCap);
+      const uint32_t grid = field_grid(walk_tasks(f), voxels, band, kWalkTaskCap);
       hipLaunchKernelGGL((k_field_walk<T, true>), dim3(grid, nbands), dim3(256), lds_bytes, s, S, f.res[0], f.res[1],
-                         f.res[2], f.h1[0], f.h2[0], f.h1[1], f.h2[1], f.h1[2], f.h2[2], b, band, d_counts,
-                         (FieldScan*)nullptr);
+                         f.res[2], f.axes, b, band, d_counts, (FieldScan*)nullptr);
     } else {
       // a workgroup's trip: 256 lanes of 16 bytes (a float field: of one voxel)
       const size_t per_trip = 256u * (sizeof(T) < 4 ? 16u / sizeof(T) : 1u);

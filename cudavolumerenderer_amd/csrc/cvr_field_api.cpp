@@ -1,7 +1,7 @@
 // cvr_field_api.cpp - C ABI of the field statistics and value-gradient histograms (cvr.h,
 // CVR_HAS_FIELD_HISTOGRAM): the host statements on a field in host memory and the device passes on
 // one in device memory.  The context supplies the device and the stream and is otherwise only
-// read.  The per-voxel definitions: cvr_kernels.h; the kernels: cvr_field.hip.
+// read.  The per-voxel definitions: cvr_kernels.h, cvr_gradient.h; the kernels: cvr_field.hip.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -64,11 +64,7 @@ cvr::FieldSrc source_of(const cvr_field_desc* f, bool gradient) {
   s.scalar = f->scalar;
   s.scalar_type = f->scalar_type;
   memcpy(s.res, f->res, sizeof(s.res));
-  if (gradient)
-    for (int k = 0; k < 3; ++k) {
-      s.h1[k] = 1.0f / f->spacing[k];
-      s.h2[k] = 0.5f / f->spacing[k];
-    }
+  if (gradient) s.axes = cvr::gradient_axes(f->spacing);
   return s;
 }
 
@@ -76,30 +72,10 @@ cvr::FieldBins bins_of(const cvr_histogram_desc* h) {
   return cvr::FieldBins{h->n, h->m, h->lo, h->hi, h->m > 1u ? h->glo : 0.0f, h->m > 1u ? h->ghi : 1.0f};
 }
 
-// fn(s, mag) for every voxel of a host field, x fastest: the statement's loop
+// fn(i, s, mag) for every voxel of a host field, x fastest: the statement's loop
 template <class F>
 void for_each_voxel(const cvr::FieldSrc& s, F fn) {
-  const uint32_t nx = s.res[0], ny = s.res[1], nz = s.res[2];
-  auto S = [&](size_t i) { return cvr::scalar_voxel(s.scalar, s.scalar_type, i); };
-  for (uint32_t z = 0; z < nz; ++z) {
-    uint32_t zm, zp;
-    float kz;
-    cvr::gradient_neighbours(z, nz, s.h1[2], s.h2[2], zm, zp, kz);
-    for (uint32_t y = 0; y < ny; ++y) {
-      uint32_t ym, yp;
-      float ky;
-      cvr::gradient_neighbours(y, ny, s.h1[1], s.h2[1], ym, yp, ky);
-      const size_t row = ((size_t)z * ny + y) * nx, rym = ((size_t)z * ny + ym) * nx, ryp = ((size_t)z * ny + yp) * nx,
-                   rzm = ((size_t)zm * ny + y) * nx, rzp = ((size_t)zp * ny + y) * nx;
-      for (uint32_t x = 0; x < nx; ++x) {
-        uint32_t xm, xp;
-        float kx;
-        cvr::gradient_neighbours(x, nx, s.h1[0], s.h2[0], xm, xp, kx);
-        fn(S(row + x), cvr::gradient_magnitude(S(row + xm), S(row + xp), kx, S(rym + x), S(ryp + x), ky, S(rzm + x),
-                                               S(rzp + x), kz));
-      }
-    }
-  }
+  cvr::gradient_for_each([&](size_t i) { return cvr::scalar_voxel(s.scalar, s.scalar_type, i); }, s.res, s.axes, fn);
 }
 
 void stats_from_scan(const cvr::FieldScan& sc, struct cvr_field_stats* out) {
@@ -131,7 +107,7 @@ int cvr_field_stats_host(const cvr_field_desc* f, struct cvr_field_stats* out) {
   if (int r = field_check(nullptr, f, nullptr, nullptr)) return r;
   if (int r = aligned_check(nullptr, f)) return r;
   cvr::FieldScan sc = kEmptyScan;
-  for_each_voxel(source_of(f, true), [&](float s, float mag) {
+  for_each_voxel(source_of(f, true), [&](size_t, float s, float mag) {
     if (s == s) {
       uint32_t bits;
       memcpy(&bits, &s, 4);
@@ -160,15 +136,15 @@ int cvr_field_histogram_host(const cvr_field_desc* f, const cvr_histogram_desc* 
   const cvr::FieldBins b = bins_of(h);
   memset(counts, 0, (size_t)b.n * b.m * sizeof(uint32_t));
   if (b.m > 1u) {
-    for_each_voxel(source_of(f, true), [&](float s, float mag) {
-      const uint32_t i = cvr::field_bin(cvr::field_unit(s, b.lo, b.hi), b.n);
-      const uint32_t j = cvr::field_bin(cvr::field_unit(mag, b.glo, b.ghi), b.m);
+    for_each_voxel(source_of(f, true), [&](size_t, float s, float mag) {
+      const uint32_t i = cvr::field_bin(cvr::unit_clamp(s, b.lo, b.hi), b.n);
+      const uint32_t j = cvr::field_bin(cvr::unit_clamp(mag, b.glo, b.ghi), b.m);
       ++counts[(size_t)j * b.n + i];
     });
   } else {
     const size_t voxels = (size_t)f->res[0] * f->res[1] * f->res[2];
     for (size_t v = 0; v < voxels; ++v)
-      ++counts[cvr::field_bin(cvr::field_unit(cvr::scalar_voxel(f->scalar, f->scalar_type, v), b.lo, b.hi), b.n)];
+      ++counts[cvr::field_bin(cvr::unit_clamp(cvr::scalar_voxel(f->scalar, f->scalar_type, v), b.lo, b.hi), b.n)];
   }
   return CVR_OK;
 }
@@ -224,7 +200,7 @@ int cvr_field_histogram(cvr_ctx* c, const cvr_field_desc* f, const cvr_histogram
 
 int cvr_debug_field_geometry(uint32_t out[8]) {
   if (!out) return set_err(nullptr, CVR_ERR_INVALID, "NULL argument");
-  const uint32_t v[8] = {cvr::kFieldTaskCap, cvr::kFieldZ, cvr::kFieldGrid1D, cvr::kFieldLdsBins, cvr::kFieldMaxBins,
+  const uint32_t v[8] = {cvr::kWalkTaskCap, cvr::kWalkZ, cvr::kFieldGrid1D, cvr::kFieldLdsBins, cvr::kFieldMaxBins,
                          0u, 0u, 5u};
   memcpy(out, v, sizeof(v));
   return CVR_OK;

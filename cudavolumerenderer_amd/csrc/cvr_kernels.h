@@ -5,6 +5,7 @@
 #include <stdint.h>
 
 #include "cvr_env.h"
+#include "cvr_gradient.h"
 #include "cvr_walk.h"
 #include "cvr_wpool_select.h"
 
@@ -127,12 +128,11 @@ hipError_t launch_to_half(const float* src, void* dst, size_t n, hipStream_t s);
 // The launch geometry of the medium build: every cap and run length the build launches and their
 // kernels use, named once, so that cvr_debug_build_geometry (cvr.h) reports what runs.  Each
 // kernel below a cap loops over its grid; the tests size their media from these to make it loop.
+// (k_gradient's task cap and z run are the walk's: kWalkTaskCap, kWalkZ of cvr_gradient.h.)
 constexpr uint32_t kScanGridCap = 2048;    // scan_grid: the value scans and k_classified, 8 workgroups per CU
 constexpr uint32_t kStreamGridCap = 8192;  // stream_grid: k_fill_albedo, k_cell_leaf_flags, k_gather_leaves
 constexpr uint32_t kScanSteps = 8, kScanTile = 256 * kScanSteps;  // flags per workgroup of the flag scan
 constexpr uint32_t kScanSumsChunk = 1024;  // tile sums k_scan_sums takes per trip (its workgroup's size)
-constexpr uint32_t kGradTaskCap = 4096;    // k_gradient's grid: tasks beyond it are a workgroup's next trip
-constexpr uint32_t kGradZ = 16;            // z planes per k_gradient task
 constexpr uint32_t kLeafRunLeaves = 32, kLeafRunVoxels = 8 * kLeafRunLeaves;  // x run of one k_leaf_flags task
 constexpr uint32_t kLeafFlagsGridCap = 1u << 20;
 constexpr uint32_t kToHalfGridCap = 8192;
@@ -189,9 +189,7 @@ struct TransferParams {
   float lo, hi;
 };
 __host__ __device__ inline float4 transfer_classify(float s, const float4* table, const TransferParams& p) {
-  const float t = (s - p.lo) / (p.hi - p.lo);
-  float u = t > 0.0f ? t : 0.0f;  // a NaN compares false: 0
-  u = u < 1.0f ? u : 1.0f;
+  const float u = unit_clamp(s, p.lo, p.hi);
   const float x = u * (float)(p.n - 1u);
   float4 e;
   if (p.flags & 1u) {
@@ -218,63 +216,14 @@ __host__ __device__ inline float scalar_voxel(const void* scalar, uint32_t type,
     default: return static_cast<const float*>(scalar)[i];
   }
 }
-// Gradient-magnitude transfer functions (cvr_set_medium_gradient, cvr_classify_gradient_host).
-// The 2-D classification cvr.h states, the one definition for the host and the build kernels, on
-// the same terms as transfer_classify (and correctly rounded sqrt).  table: m rows of n entries.
-struct GradientParams {
-  uint32_t n, m;  // entries per row (scalar axis), rows (gradient axis)
-  float lo, hi, glo, ghi;
-  float h1[3], h2[3];  // per axis x, y, z: 1.0f / spacing and 0.5f / spacing, rounded once on the host
-};
-// The lower and upper neighbour of coordinate c on an axis of n voxels, and the factor of their
-// difference: the central one when both exist, else the one-sided one.
-__host__ __device__ inline void gradient_neighbours(uint32_t c, uint32_t n, float h1, float h2, uint32_t& cm,
-                                                    uint32_t& cp, float& k) {
-  cm = c > 0u ? c - 1u : c;
-  cp = c + 1u < n ? c + 1u : c;
-  k = cp - cm == 2u ? h2 : h1;
-}
-__host__ __device__ inline float gradient_magnitude(float sxm, float sxp, float kx, float sym, float syp, float ky,
-                                                    float szm, float szp, float kz) {
-  const float gx = (sxp - sxm) * kx, gy = (syp - sym) * ky, gz = (szp - szm) * kz;
-  const float q = (gx * gx + gy * gy) + gz * gz;
-  return __builtin_sqrtf(q);
-}
-// s: the voxel; mag: its gradient magnitude.  Returns (r, g, b, density).
-__host__ __device__ inline float4 gradient_classify(float s, float mag, const float4* table, const GradientParams& p) {
-  const float t = (s - p.lo) / (p.hi - p.lo);
-  float u = t > 0.0f ? t : 0.0f;  // a NaN compares false: 0
-  u = u < 1.0f ? u : 1.0f;
-  const float w = (mag - p.glo) / (p.ghi - p.glo);
-  float v = w > 0.0f ? w : 0.0f;
-  v = v < 1.0f ? v : 1.0f;
-  const float xt = u * (float)(p.n - 1u), yt = v * (float)(p.m - 1u);
-  const uint32_t ci = (uint32_t)__builtin_floorf(xt), i = ci < p.n - 2u ? ci : p.n - 2u;
-  const uint32_t cj = (uint32_t)__builtin_floorf(yt), j = cj < p.m - 2u ? cj : p.m - 2u;
-  const float f = xt - (float)i, h = yt - (float)j;
-  const float4 P = table[j * p.n + i], Q = table[j * p.n + i + 1u];
-  const float4 R = table[(j + 1u) * p.n + i], W = table[(j + 1u) * p.n + i + 1u];
-  float4 a, b, e;
-  a.x = P.x + f * (Q.x - P.x), a.y = P.y + f * (Q.y - P.y), a.z = P.z + f * (Q.z - P.z), a.w = P.w + f * (Q.w - P.w);
-  b.x = R.x + f * (W.x - R.x), b.y = R.y + f * (W.y - R.y), b.z = R.z + f * (W.z - R.z), b.w = R.w + f * (W.w - R.w);
-  e.x = a.x + h * (b.x - a.x), e.y = a.y + h * (b.y - a.y), e.z = a.z + h * (b.z - a.z), e.w = a.w + h * (b.w - a.w);
-  return e;
-}
 // Field statistics and value-gradient histograms (cvr_field_stats, cvr_field_histogram and their
 // *_host statements; cvr_field.hip).  The coordinates are the classification's u and v, bit for
-// bit, and a bin is the nearest table node: the one definition for the host and the kernels, on
-// the same terms as transfer_classify.
+// bit (unit_clamp, cvr_gradient.h), and a bin is the nearest table node: the one definition for
+// the host and the kernels, on the same terms as transfer_classify.
 struct FieldBins {
   uint32_t n, m;  // value bins, gradient bins (m == 1: no gradient axis)
   float lo, hi, glo, ghi;
 };
-// u of a value s over [lo, hi] (v of a magnitude over [glo, ghi]): a NaN gives 0
-__host__ __device__ inline float field_unit(float s, float lo, float hi) {
-  const float t = (s - lo) / (hi - lo);
-  float u = t > 0.0f ? t : 0.0f;  // a NaN compares false: 0
-  u = u < 1.0f ? u : 1.0f;
-  return u;
-}
 // The bin of coordinate c (0..1) on an axis of k nodes: the nearest node, ties upward, with no
 // rounded c * (k - 1) + 0.5: f = x - (float)i0 is exact.
 __host__ __device__ inline uint32_t field_bin(float c, uint32_t k) {
@@ -294,17 +243,15 @@ __host__ __device__ inline uint32_t field_unkey(uint32_t key) {
 }
 constexpr uint32_t kFieldKeyPosInf = 0xFF800000u, kFieldKeyNegInf = 0x007FFFFFu;  // field_key of +inf, -inf
 // The launch geometry of the field kernels, named once (cvr_debug_field_geometry reports them)
-constexpr uint32_t kFieldTaskCap = 4096;     // the stencil walk's grid: tasks beyond it are a workgroup's next trip
-constexpr uint32_t kFieldZ = 16;             // z planes per task of the walk (a task: 256 x of one y)
 constexpr uint32_t kFieldGrid1D = 2048;      // the 1-D histogram's grid cap (workgroups of 256)
 constexpr uint32_t kFieldLdsBins = 16384;    // bins a workgroup-private LDS histogram holds (64 KB)
 constexpr uint32_t kFieldMaxBins = 65536;    // the largest n * m
-// The field as the kernels take it: res and the spacing's reciprocals (GradientParams' h1, h2)
+// The field as the kernels take it: res and the spacing's reciprocals
 struct FieldSrc {
   const void* scalar = nullptr;
   uint32_t scalar_type = 0;
   uint32_t res[3] = {0u, 0u, 0u};
-  float h1[3] = {1.0f, 1.0f, 1.0f}, h2[3] = {0.5f, 0.5f, 0.5f};
+  GradientAxes axes;
 };
 // What the statistics pass finds, in device memory; the host sets kmin = kFieldKeyPosInf,
 // kmax = kFieldKeyNegInf and the rest to 0 first.

@@ -490,33 +490,30 @@ int source_voxel(cvr_ctx* c, const cvr::VoxelSource& src, const float* host_tabl
   }
   const size_t size = src.scalar_type == CVR_SCALAR_U8 ? 1 : src.scalar_type == CVR_SCALAR_F32 ? 4 : 2;
   alignas(4) unsigned char raw[4];
-  auto read = [&](size_t at, float* s) -> int {
+  // one scalar from the device; the first failure is kept in `failed`, and nothing is copied after it
+  // (the 0 a failed read returns reaches no result: `failed` is returned before anything is classified)
+  int failed = CVR_OK;
+  auto copy = [&](size_t at) -> int {
     HIP_TRY(c, hipMemcpy(raw, static_cast<const unsigned char*>(src.scalar) + at * size, size, hipMemcpyDeviceToHost));
-    *s = cvr::scalar_voxel(raw, src.scalar_type, 0);
     return CVR_OK;
   };
+  auto read = [&](size_t at) {
+    if (failed || (failed = copy(at))) return 0.0f;
+    return cvr::scalar_voxel(raw, src.scalar_type, 0);
+  };
+  const float s = read(i);
+  float4 e;
   if (src.gradient) {
     // the voxel and its up to six in-grid neighbours, as the kernels' stencil reads them
     const uint32_t nx = src.res[0], ny = src.res[1];
-    const uint32_t q[3] = {(uint32_t)(i % nx), (uint32_t)((i / nx) % ny), (uint32_t)(i / ((size_t)nx * ny))};
-    const size_t stride[3] = {1, nx, (size_t)nx * ny};
-    float s = 0.0f, lo[3], hi[3], k[3];
-    int r = read(i, &s);
-    for (int a = 0; a < 3 && !r; ++a) {
-      uint32_t cm, cp;
-      cvr::gradient_neighbours(q[a], src.res[a], src.gtf.h1[a], src.gtf.h2[a], cm, cp, k[a]);
-      r = read(i - (q[a] - cm) * stride[a], &lo[a]);
-      if (!r) r = read(i + (cp - q[a]) * stride[a], &hi[a]);
-    }
-    if (r) return r;
-    const float mag = cvr::gradient_magnitude(lo[0], hi[0], k[0], lo[1], hi[1], k[1], lo[2], hi[2], k[2]);
-    const float4 e = cvr::gradient_classify(s, mag, reinterpret_cast<const float4*>(host_table), src.gtf);
-    out[0] = e.x, out[1] = e.y, out[2] = e.z, out[3] = 1.0f, out[4] = e.w;
-    return CVR_OK;
+    const float mag = cvr::gradient_at(read, (uint32_t)(i % nx), (uint32_t)((i / nx) % ny),
+                                       (uint32_t)(i / ((size_t)nx * ny)), src.res, src.gtf.axes);
+    if (failed) return failed;
+    e = cvr::gradient_classify(s, mag, reinterpret_cast<const float4*>(host_table), src.gtf);
+  } else {
+    if (failed) return failed;
+    e = cvr::transfer_classify(s, reinterpret_cast<const float4*>(host_table), src.tf);
   }
-  HIP_TRY(c, hipMemcpy(raw, static_cast<const unsigned char*>(src.scalar) + i * size, size, hipMemcpyDeviceToHost));
-  const float4 e = cvr::transfer_classify(cvr::scalar_voxel(raw, src.scalar_type, 0),
-                                          reinterpret_cast<const float4*>(host_table), src.tf);
   out[0] = e.x, out[1] = e.y, out[2] = e.z, out[3] = 1.0f, out[4] = e.w;
   return CVR_OK;
 }
@@ -661,11 +658,7 @@ int gradient_check(std::string* err, const cvr_gradient_transfer_desc* t, F afte
   for (int k = 0; k < 3; ++k)
     if (!std::isfinite(t->spacing[k]) || !(t->spacing[k] > 0.0f))
       return set_err(err, CVR_ERR_INVALID, "voxel spacing[%d] = %g: finite and > 0", k, (double)t->spacing[k]);
-  *p = cvr::GradientParams{t->n, t->m, t->lo, t->hi, t->glo, t->ghi, {}, {}};
-  for (int k = 0; k < 3; ++k) {
-    p->h1[k] = 1.0f / t->spacing[k];
-    p->h2[k] = 0.5f / t->spacing[k];
-  }
+  *p = cvr::GradientParams{t->n, t->m, t->lo, t->hi, t->glo, t->ghi, cvr::gradient_axes(t->spacing)};
   return CVR_OK;
 }
 
@@ -995,31 +988,14 @@ int cvr_classify_gradient_host(const void* scalar, uint32_t scalar_type, const u
   // (the table as float4: copied, the caller's need not be 16-byte aligned)
   std::vector<float4> table((size_t)t->n * t->m);
   memcpy(table.data(), t->table, table.size() * sizeof(float4));
-  for (uint32_t z = 0; z < nz; ++z) {
-    uint32_t zm, zp;
-    float kz;
-    cvr::gradient_neighbours(z, nz, p.h1[2], p.h2[2], zm, zp, kz);
-    for (uint32_t y = 0; y < ny; ++y) {
-      uint32_t ym, yp;
-      float ky;
-      cvr::gradient_neighbours(y, ny, p.h1[1], p.h2[1], ym, yp, ky);
-      const size_t row = ((size_t)z * ny + y) * nx, rym = ((size_t)z * ny + ym) * nx, ryp = ((size_t)z * ny + yp) * nx,
-                   rzm = ((size_t)zm * ny + y) * nx, rzp = ((size_t)zp * ny + y) * nx;
-      for (uint32_t x = 0; x < nx; ++x) {
-        uint32_t xm, xp;
-        float kx;
-        cvr::gradient_neighbours(x, nx, p.h1[0], p.h2[0], xm, xp, kx);
-        auto S = [&](size_t i) { return cvr::scalar_voxel(scalar, scalar_type, i); };
-        const float mag = cvr::gradient_magnitude(S(row + xm), S(row + xp), kx, S(rym + x), S(ryp + x), ky, S(rzm + x),
-                                                  S(rzp + x), kz);
-        const float4 e = cvr::gradient_classify(S(row + x), mag, table.data(), p);
-        const size_t i = row + x;
-        if (density) density[i] = e.w;
-        if (albedo) albedo[4 * i] = e.x, albedo[4 * i + 1] = e.y, albedo[4 * i + 2] = e.z, albedo[4 * i + 3] = 1.0f;
-        if (gradient_magnitude) gradient_magnitude[i] = mag;
-      }
-    }
-  }
+  cvr::gradient_for_each([&](size_t i) { return cvr::scalar_voxel(scalar, scalar_type, i); }, res, p.axes,
+                         [&](size_t i, float s, float mag) {
+                           const float4 e = cvr::gradient_classify(s, mag, table.data(), p);
+                           if (density) density[i] = e.w;
+                           if (albedo)
+                             albedo[4 * i] = e.x, albedo[4 * i + 1] = e.y, albedo[4 * i + 2] = e.z, albedo[4 * i + 3] = 1.0f;
+                           if (gradient_magnitude) gradient_magnitude[i] = mag;
+                         });
   return CVR_OK;
 }
 
@@ -1135,7 +1111,7 @@ int cvr_debug_device_medium_ms(const cvr_ctx* c, double out[6]) {
 int cvr_debug_build_geometry(uint32_t out[16]) {
   if (!out) return set_err(nullptr, CVR_ERR_INVALID, "NULL argument");
   const uint32_t g[] = {cvr::kScanGridCap,   cvr::kStreamGridCap,    cvr::kScanTile,
-                        cvr::kScanSumsChunk, cvr::kGradTaskCap,      cvr::kGradZ,
+                        cvr::kScanSumsChunk, cvr::kWalkTaskCap,      cvr::kWalkZ,
                         cvr::kLeafRunVoxels, cvr::kLeafRunLeaves,    cvr::kLeafFlagsGridCap,
                         cvr::kToHalfGridCap, cvr::kBuildCellsGrid,   cvr::kBuildBoundsGrid,
                         cvr::kBuildSparseCellsGrid, cvr::kBuildSparseBoundsGrid};

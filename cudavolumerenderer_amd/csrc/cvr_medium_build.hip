@@ -14,6 +14,7 @@
 #include <algorithm>
 #include <type_traits>
 
+#include "cvr_device.h"
 #include "cvr_kernels.h"
 
 namespace cvr {
@@ -31,27 +32,12 @@ __device__ __forceinline__ uint32_t half_bits(float f) {
   const _Float16 h = (_Float16)f;
   return (uint32_t)__builtin_bit_cast(unsigned short, h);
 }
-__device__ __forceinline__ float wave_max(float v) {
-  for (int o = 32; o; o >>= 1) {
-    const float t = __shfl_xor(v, o);
-    v = t > v ? t : v;
-  }
-  return v;
-}
-__device__ __forceinline__ unsigned long long wave_min(unsigned long long v) {
-  for (int o = 32; o; o >>= 1) {
-    const unsigned long long t = __shfl_xor(v, o);
-    v = t < v ? t : v;
-  }
-  return v;
-}
-__device__ __forceinline__ uint32_t wave_or(uint32_t v) {
-  for (int o = 32; o; o >>= 1) v |= __shfl_xor(v, o);
-  return v;
-}
-__device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
-  for (int o = 32; o; o >>= 1) v += __shfl_xor(v, o);
-  return v;
+// a float4's four components as binary16, round to nearest even: the half format's albedo voxel
+__device__ __forceinline__ uint2 half4_bits(const float4 a) {
+  uint2 h;
+  h.x = half_bits(a.x) | half_bits(a.y) << 16;
+  h.y = half_bits(a.z) | half_bits(a.w) << 16;
+  return h;
 }
 
 // ---------------------------------------------------------- voxel sources ---
@@ -105,7 +91,7 @@ struct GradientSrc {
   const T* __restrict__ S;
   const float4* __restrict__ table;
   GradientParams p;
-  uint32_t nx, ny, nz;
+  uint32_t res[3];
   uint32_t albedo;  // 0: the colours are not looked at (has_albedo() false)
   const float4* lds;
   __device__ void stage() {
@@ -121,17 +107,7 @@ struct GradientSrc {
     a = make_float4(e.x, e.y, e.z, 1.0f);
   }
   __device__ void voxel(uint32_t x, uint32_t y, uint32_t z, size_t i, float& d, float4& a) const {
-    uint32_t xm, xp, ym, yp, zm, zp;
-    float kx, ky, kz;
-    gradient_neighbours(x, nx, p.h1[0], p.h2[0], xm, xp, kx);
-    gradient_neighbours(y, ny, p.h1[1], p.h2[1], ym, yp, ky);
-    gradient_neighbours(z, nz, p.h1[2], p.h2[2], zm, zp, kz);
-    const size_t row = ((size_t)z * ny + y) * nx;
-    const float mag = gradient_magnitude((float)S[row + xm], (float)S[row + xp], kx,
-                                         (float)S[((size_t)z * ny + ym) * nx + x],
-                                         (float)S[((size_t)z * ny + yp) * nx + x], ky,
-                                         (float)S[((size_t)zm * ny + y) * nx + x],
-                                         (float)S[((size_t)zp * ny + y) * nx + x], kz);
+    const float mag = gradient_at([&](size_t at) { return (float)S[at]; }, x, y, z, res, p.axes);
     classified((float)S[i], mag, d, a);
   }
 };
@@ -258,11 +234,27 @@ __device__ __forceinline__ void commit_in_table_lds(DensityScan& ds, AlbedoScan&
   as.commit(reinterpret_cast<uint32_t*>(s_mx + 4), s_ov + 4, out);
 }
 
-// The classified source's two dense passes over the scalar field.  kStore false: the scan, which
-// finds what k_scan_density and k_scan_albedo find, of the classified values, together.  kStore
-// true: every voxel's density and albedo into the context's grids (format 1: as binary16).
-// Integer scalars are loaded 16 bytes per lane: the field is cut into a head up to the first
-// 16-byte boundary, whole 16-byte groups, and a tail; a wave loads 64 groups (1 KiB) and hands the
+// What both classified passes do with voxel i's density d and albedo a.  kStore false: the scan,
+// which finds what k_scan_density and k_scan_albedo find, of the classified values, together.
+// kStore true: the voxel into the context's grids (format 1: as binary16).
+template <bool kStore>
+__device__ __forceinline__ void emit(size_t i, float d, const float4 a, uint32_t format, DensityScan& ds,
+                                     AlbedoScan& as, void* __restrict__ density, void* __restrict__ albedo) {
+  if (!kStore) {
+    ds.take(d, i, format);
+    as.take(a, i, format);
+  } else if (format) {
+    reinterpret_cast<_Float16*>(density)[i] = (_Float16)d;
+    reinterpret_cast<uint2*>(albedo)[i] = half4_bits(a);
+  } else {
+    reinterpret_cast<float*>(density)[i] = d;
+    reinterpret_cast<float4*>(albedo)[i] = a;
+  }
+}
+
+// The classified source's two dense passes over the scalar field (kStore: emit above).  Integer
+// scalars are loaded 16 bytes per lane: the field is cut into a head up to the first 16-byte
+// boundary, whole 16-byte groups, and a tail; a wave loads 64 groups (1 KiB) and hands the
 // voxels round with lane shuffles so that in each of its V steps lane l has voxel 64 k + l of the
 // wave's run, and the stores of a step are consecutive.  Head and tail (a float field: every
 // voxel) are taken one voxel per lane.  The workgroup reduction's scratch is the table's LDS, after
@@ -281,19 +273,7 @@ __global__ __launch_bounds__(256) void k_classified(ScalarSrc<T> src, size_t n, 
     float d;
     float4 a;
     src.classified(s, d, a);
-    if (!kStore) {
-      ds.take(d, i, format);
-      as.take(a, i, format);
-    } else if (format) {
-      uint2 h;
-      h.x = half_bits(a.x) | half_bits(a.y) << 16;
-      h.y = half_bits(a.z) | half_bits(a.w) << 16;
-      reinterpret_cast<_Float16*>(density)[i] = (_Float16)d;
-      reinterpret_cast<uint2*>(albedo)[i] = h;
-    } else {
-      reinterpret_cast<float*>(density)[i] = d;
-      reinterpret_cast<float4*>(albedo)[i] = a;
-    }
+    emit<kStore>(i, d, a, format, ds, as, density, albedo);
   };
   constexpr uint32_t kSize = (uint32_t)sizeof(T), V = kSize < 4u ? 16u / kSize : 1u;
   size_t head = 0, body_end = 0;
@@ -327,14 +307,10 @@ __global__ __launch_bounds__(256) void k_classified(ScalarSrc<T> src, size_t n, 
   if (!kStore) commit_in_table_lds(ds, as, out);
 }
 
-// The gradient source's two dense passes (kStore as above).  The hand-round of k_classified does
-// not carry a stencil, so the field is walked by coordinates here: a task is 256 consecutive x of
-// one y over kGradZ consecutive z, and a work-item keeps its voxel's z - 1, z, z + 1 in registers
-// while it marches along z, so the z neighbours cost one load per voxel and step.  The x
-// neighbours come from the adjacent lanes (a load only in a wave's first and last lane), the y
-// neighbours are two loads of rows that the tasks of y - 1 and y + 1 read as their own (cache
-// hits, not memory traffic, when those tasks run close in time on one XCD: consecutive tasks are
-// consecutive x-runs, then consecutive y).  A wave's loads and stores of a step are 64 consecutive voxels.
+// The gradient source's two dense passes (kStore: emit above).  The hand-round of k_classified
+// does not carry a stencil, so the field is walked by coordinates: gradient_walk (cvr_gradient.h)
+// hands every voxel's value and gradient magnitude to the lambda, and a lane inside the row
+// classifies and emits its voxel.  A wave's stores of a step are 64 consecutive voxels.
 template <class T, bool kStore>
 __global__ __launch_bounds__(256) void k_gradient(GradientSrc<T> src, uint32_t format, void* __restrict__ density,
                                                   void* __restrict__ albedo, MedScan* __restrict__ out) {
@@ -344,71 +320,21 @@ __global__ __launch_bounds__(256) void k_gradient(GradientSrc<T> src, uint32_t f
   src.voxel(0u, 0u, 0u, 0, d0, a0);
   DensityScan ds;
   AlbedoScan as(a0);
-  const uint32_t nx = src.nx, ny = src.ny, nz = src.nz;
-  const T* __restrict__ S = src.S;
-  const uint32_t nxc = (nx + 255u) / 256u, nzc = (nz + kGradZ - 1u) / kGradZ;
-  const size_t ntasks = (size_t)nxc * ny * nzc;
-  const uint32_t lane = threadIdx.x & 63u;
-  // Workgroups are observed to be dealt round-robin over the 8 XCDs, each with an L2 of its own
-  // (nothing promises it: this is for speed only, any placement computes the same).  The block
-  // index is turned so that the workgroups of one XCD take consecutive tasks, and the rows of
-  // y - 1 and y + 1 are then found in the L2 that a neighbour task has just filled.
-  const uint32_t nb = gridDim.x;
-  const uint32_t vb = (nb & 7u) ? blockIdx.x : (blockIdx.x & 7u) * (nb >> 3) + (blockIdx.x >> 3);
-  for (size_t t = vb; t < ntasks; t += nb) {
-    const uint32_t xc = (uint32_t)(t % nxc), y = (uint32_t)((t / nxc) % ny), zc = (uint32_t)(t / ((size_t)nxc * ny));
-    const uint32_t x0 = xc * 256u + threadIdx.x;
-    const bool in = x0 < nx;
-    const uint32_t x = in ? x0 : nx - 1u;  // (lanes past the row read its last voxel and keep nothing)
-    uint32_t xm, xp, ym, yp;
-    float kx, ky;
-    gradient_neighbours(x, nx, src.p.h1[0], src.p.h2[0], xm, xp, kx);
-    gradient_neighbours(y, ny, src.p.h1[1], src.p.h2[1], ym, yp, ky);
-    const uint32_t z0 = zc * kGradZ, z1 = z0 + kGradZ < nz ? z0 + kGradZ : nz;
-    auto at = [&](uint32_t xx, uint32_t yy, uint32_t zz) { return (float)S[((size_t)zz * ny + yy) * nx + xx]; };
-    float prev = at(x, y, z0 > 0u ? z0 - 1u : z0), cur = at(x, y, z0);
-    for (uint32_t z = z0; z < z1; ++z) {
-      uint32_t zm, zp;
-      float kz;
-      gradient_neighbours(z, nz, src.p.h1[2], src.p.h2[2], zm, zp, kz);
-      const float next = zp != z ? at(x, y, zp) : cur;
-      const float sym = ym != y ? at(x, ym, z) : cur, syp = yp != y ? at(x, yp, z) : cur;
-      // every lane of the wave takes part in the two moves (the loop bounds are the workgroup's)
-      const float left = __shfl_up(cur, 1), right = __shfl_down(cur, 1);
-      const float sxm = xm == x ? cur : lane != 0u ? left : at(xm, y, z);
-      const float sxp = xp == x ? cur : lane != 63u ? right : at(xp, y, z);
-      const float mag = gradient_magnitude(sxm, sxp, kx, sym, syp, ky, prev, next, kz);
-      if (in) {
-        const size_t i = ((size_t)z * ny + y) * nx + x;
-        float d;
-        float4 a;
-        src.classified(cur, mag, d, a);
-        if (!kStore) {
-          ds.take(d, i, format);
-          as.take(a, i, format);
-        } else if (format) {
-          uint2 h;
-          h.x = half_bits(a.x) | half_bits(a.y) << 16;
-          h.y = half_bits(a.z) | half_bits(a.w) << 16;
-          reinterpret_cast<_Float16*>(density)[i] = (_Float16)d;
-          reinterpret_cast<uint2*>(albedo)[i] = h;
-        } else {
-          reinterpret_cast<float*>(density)[i] = d;
-          reinterpret_cast<float4*>(albedo)[i] = a;
-        }
-      }
-      prev = cur;
-      cur = next;
-    }
-  }
+  const uint32_t nx = src.res[0], ny = src.res[1];
+  gradient_walk(src.S, nx, ny, src.res[2], src.p.axes,
+                [&](bool in, uint32_t x, uint32_t y, uint32_t z, float cur, float mag) {
+                  if (!in) return;
+                  float d;
+                  float4 a;
+                  src.classified(cur, mag, d, a);
+                  emit<kStore>(((size_t)z * ny + y) * nx + x, d, a, format, ds, as, density, albedo);
+                });
   if (!kStore) commit_in_table_lds(ds, as, out);
 }
 
 // The context's albedo grid filled with one value (CVR_DEVMED_CONST_ALBEDO, dense).
 __global__ __launch_bounds__(256) void k_fill_albedo(void* __restrict__ dst, size_t n, uint32_t format, float4 v) {
-  uint2 h;
-  h.x = half_bits(v.x) | half_bits(v.y) << 16;
-  h.y = half_bits(v.z) | half_bits(v.w) << 16;
+  const uint2 h = half4_bits(v);
   for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
     if (format)
       reinterpret_cast<uint2*>(dst)[i] = h;
@@ -654,10 +580,7 @@ __global__ __launch_bounds__(256) void k_gather_leaves(Src src, uint32_t nx, uin
             half_overflow(a.x) ? 4 * p : half_overflow(a.y) ? 4 * p + 1 : half_overflow(a.z) ? 4 * p + 2 : kNoIndex;
         if (at != kNoIndex) atomicMin(&out->ovf_albedo, at);
       } else if (format) {
-        uint2 h;
-        h.x = half_bits(a.x) | half_bits(a.y) << 16;
-        h.y = half_bits(a.z) | half_bits(a.w) << 16;
-        reinterpret_cast<uint2*>(leaf_albedo)[p] = h;
+        reinterpret_cast<uint2*>(leaf_albedo)[p] = half4_bits(a);
       } else {
         reinterpret_cast<float4*>(leaf_albedo)[p] = a;
       }
@@ -677,7 +600,7 @@ void with_source(const VoxelSource& v, bool with_albedo, F f) {
   const uint32_t al = with_albedo ? 1u : 0u;
   auto gradient = [&](auto* S) {
     using T = std::remove_cv_t<std::remove_pointer_t<decltype(S)>>;
-    f(GradientSrc<T>{S, v.table, v.gtf, v.res[0], v.res[1], v.res[2], al, nullptr}, lds);
+    f(GradientSrc<T>{S, v.table, v.gtf, {v.res[0], v.res[1], v.res[2]}, al, nullptr}, lds);
   };
   if (v.gradient && v.scalar_type == 1u)
     gradient(static_cast<const uint8_t*>(v.scalar));
@@ -710,9 +633,8 @@ hipError_t launch_classified(const VoxelSource& v, size_t n, uint32_t format, vo
       hipLaunchKernelGGL((k_classified<T, kStore>), dim3(scan_grid(n)), dim3(256), lds, s, src, n, format, density,
                          albedo, out);
     } else if constexpr (!std::is_void_v<T>) {
-      const size_t ntasks = (size_t)((v.res[0] + 255u) / 256u) * v.res[1] * ((v.res[2] + kGradZ - 1u) / kGradZ);
-      // (a multiple of 8 workgroups where there are 8: the kernel's XCD turn needs one)
-      const uint32_t grid = (uint32_t)std::min<size_t>(ntasks, kGradTaskCap);
+      // (a multiple of 8 workgroups where there are 8: the walk's XCD turn needs one)
+      const uint32_t grid = (uint32_t)std::min<size_t>(gradient_walk_tasks(v.res[0], v.res[1], v.res[2]), kWalkTaskCap);
       hipLaunchKernelGGL((k_gradient<T, kStore>), dim3(grid >= 8u ? grid & ~7u : grid), dim3(256), lds, s,
                          src, format, density, albedo, out);
     }

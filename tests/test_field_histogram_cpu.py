@@ -248,3 +248,10 @@ def test_field_geometry_and_the_shapes_that_cross_it(cvr):
     assert g["hist1d_grid"] * 256 * 16 < n < g["hist1d_grid"] * 256 * 16 + 64 and n // 256 > g["hist1d_grid"]
     # one bin past any 16-bit counter
     assert hr.field("constant_u8").scalar.size == 262144
+
+
+def test_the_build_and_the_field_kernels_report_one_walk(cvr):
+    """k_gradient and k_field_walk run one walk (csrc/cvr_gradient.h): both geometry reports give
+    its task cap and its z run."""
+    b, f = cvr.build_geometry(), cvr.field_geometry()
+    assert (b["gradient_tasks"], b["gradient_z"]) == (f["walk_tasks"], f["walk_z"])
