@@ -124,3 +124,5 @@ $(eval $(call host_asan,gradient,cvr_medium))
 $(eval $(call host_asan,features,cvr_features_api cvr_denoise_api))
 # cvr_field_stats_host and cvr_field_histogram_host
 $(eval $(call host_asan,field,cvr_field_api))
+# cvr_clip_host and the clip descriptor's checks
+$(eval $(call host_asan,clip,cvr_medium))

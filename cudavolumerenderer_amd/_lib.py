@@ -211,6 +211,24 @@ class GradientMediumDesc(C.Structure):
                 ("max_density", C.c_float), ("g", C.c_float), ("roughness", C.c_float * 2), ("eta", C.c_float)]
 
 
+CLIP_MAX_PLANES = 8
+
+
+class ClipDesc(C.Structure):
+    """cvr_clip_desc: the crop box lo <= c < hi in voxel indices (x, y, z) and up to 8 planes
+    (A, B, C, D) in voxel-index space; a voxel is kept iff the box holds it and every plane's
+    ((A x + B y) + C z) + D >= 0."""
+    _fields_ = [("lo", C.c_uint32 * 3), ("hi", C.c_uint32 * 3), ("n_planes", C.c_uint32), ("flags", C.c_uint32),
+                ("planes", (C.c_float * 4) * CLIP_MAX_PLANES)]
+
+    def as_dict(self):
+        return {"lo": tuple(self.lo), "hi": tuple(self.hi),
+                "planes": [tuple(np.float32(v) for v in self.planes[k]) for k in range(self.n_planes)]}
+
+
+assert C.sizeof(ClipDesc) == 160
+
+
 class FieldDesc(C.Structure):
     """cvr_field_desc: a scalar field (device memory for the Context calls, host memory for the
     *_host statements) and the voxel spacing its gradient is taken with."""
@@ -380,6 +398,11 @@ def load() -> C.CDLL:
         "cvr_classify_gradient_host": (I32, [P, U32, C.POINTER(U32), C.POINTER(GradientTransferDesc), P, P, P]),
         "cvr_set_medium_gradient": (I32, [P, C.POINTER(GradientMediumDesc)]),
         "cvr_set_medium_scene_gradient": (I32, [P, P, C.POINTER(GradientTransferDesc), U32]),
+        "cvr_set_clip": (I32, [P, C.POINTER(ClipDesc)]),
+        "cvr_clear_clip": (I32, [P]),
+        "cvr_get_clip": (I32, [P, C.POINTER(ClipDesc), C.POINTER(I32)]),
+        "cvr_clip_host": (I32, [C.POINTER(U32), C.POINTER(ClipDesc), P, P, P]),
+        "cvr_medium_clip_info": (I32, [P, C.POINTER(ClipDesc), C.POINTER(U64)]),
         "cvr_field_stats_host": (I32, [C.POINTER(FieldDesc), C.POINTER(FieldStatsStruct)]),
         "cvr_field_histogram_host": (I32, [C.POINTER(FieldDesc), C.POINTER(HistogramDesc), P]),
         "cvr_field_stats": (I32, [P, C.POINTER(FieldDesc), C.POINTER(FieldStatsStruct)]),
@@ -578,6 +601,61 @@ def classify_gradient_host(scalar, table, lo, hi, glo, ghi, spacing=(1.0, 1.0, 1
     _check(load().cvr_classify_gradient_host(src.ctypes.data, _SCALAR_TYPES[src.dtype.name], res, C.byref(t),
                                              density.ctypes.data, albedo.ctypes.data, mag.ctypes.data))
     return density, albedo, mag
+
+
+def _clip_desc(lo=None, hi=None, planes=()) -> ClipDesc:
+    """The descriptor of a crop box (lo, hi: (x, y, z) voxel indices, None: no bound) and planes
+    ((A, B, C, D) each).  More than 8 planes are passed on for the library to refuse."""
+    planes = [tuple(float(v) for v in p) for p in planes]
+    if any(len(p) != 4 for p in planes):
+        raise ValueError("planes: expected (A, B, C, D) each")
+    d = ClipDesc()
+    d.lo[:] = [int(v) for v in (lo if lo is not None else (0, 0, 0))]
+    d.hi[:] = [min(int(v), 0xFFFFFFFF) for v in (hi if hi is not None else (0xFFFFFFFF,) * 3)]
+    d.n_planes = len(planes)
+    for k, p in enumerate(planes[:CLIP_MAX_PLANES]):
+        d.planes[k][:] = p
+    return d
+
+
+def clip_host(res, lo=None, hi=None, planes=(), density=None, albedo=None):
+    """The clip region's written statement on the CPU (cvr_clip_host; no GPU) for a grid of
+    res = (nx, ny, nz) voxels: -> (keep (z, y, x) uint8, density, albedo), the two arrays copies of
+    the given ones ((z, y, x) and (z, y, x, 4) float32; None stays None) with every clipped voxel
+    set to density 0 and voxel (0, 0, 0)'s albedo.  The device builds of a Context with the same
+    set_clip store exactly these values."""
+    nx, ny, nz = (int(v) for v in res)
+    d = _clip_desc(lo, hi, planes)
+    keep = np.empty((nz, ny, nx), np.uint8)
+    dn = al = None
+    if density is not None:
+        dn = np.array(density, dtype=np.float32, order="C", copy=True)
+        if dn.shape != (nz, ny, nx):
+            raise ValueError(f"density: shape {dn.shape}, expected {(nz, ny, nx)}")
+    if albedo is not None:
+        al = np.array(albedo, dtype=np.float32, order="C", copy=True)
+        if al.shape != (nz, ny, nx, 4):
+            raise ValueError(f"albedo: shape {al.shape}, expected {(nz, ny, nx, 4)}")
+    r = (C.c_uint32 * 3)(nx, ny, nz)
+    _check(load().cvr_clip_host(r, C.byref(d), dn.ctypes.data if dn is not None else None,
+                                al.ctypes.data if al is not None else None, keep.ctypes.data))
+    return keep, dn, al
+
+
+def plane_from_box(point, normal, box_min, box_max, res):
+    """A clip plane given by a point on it and its normal in box coordinates (the side the normal
+    points to is kept) -> (A, B, C, D) float32 in voxel-index space for a grid of res = (nx, ny,
+    nz) voxels in the box [box_min, box_max], voxel index i_a = (p_a - min_a) / extent_a *
+    (res_a - 1).  An axis of one voxel has no extent in index space: its coefficient is 0."""
+    p, n = np.asarray(point, np.float64), np.asarray(normal, np.float64)
+    lo, hi = np.asarray(box_min, np.float64), np.asarray(box_max, np.float64)
+    cells = np.asarray(res, np.float64) - 1.0
+    if p.shape != (3,) or n.shape != (3,) or lo.shape != (3,) or hi.shape != (3,) or cells.shape != (3,):
+        raise ValueError("plane_from_box: point, normal, box_min, box_max and res are 3 numbers each")
+    # p_a = min_a + i_a * extent_a / cells_a, so n . (p - point) = sum_a n_a extent_a / cells_a * i_a + n . (min - point)
+    abc = np.where(cells > 0.0, n * (hi - lo) / np.where(cells > 0.0, cells, 1.0), 0.0)
+    dd = float(np.dot(n, lo - p))
+    return tuple(np.float32(v) for v in (abc[0], abc[1], abc[2], dd))
 
 
 def build_geometry() -> dict:
@@ -1099,6 +1177,34 @@ class Context:
             import torch
             torch.cuda.current_stream(self.device).synchronize()
         self._c(load().cvr_set_medium_gradient(self._h, C.byref(d)))
+
+    def set_clip(self, lo=None, hi=None, planes=()):
+        """The clip region of the next device builds (cvr_set_clip): a crop box lo <= c < hi in
+        (x, y, z) voxel indices (None: no bound; hi past the grid means "to the end") and up to 8
+        planes (A, B, C, D) in voxel-index space (plane_from_box makes one from box coordinates).
+        set_medium_device, set_medium_scalar and set_medium_gradient then store a voxel outside
+        the region as empty (density 0, voxel 0's albedo): clip_host is the statement.  The
+        medium already built is not touched; the host uploads refuse while a clip is set."""
+        d = _clip_desc(lo, hi, planes)
+        self._c(load().cvr_set_clip(self._h, C.byref(d)))
+
+    def clear_clip(self):
+        self._c(load().cvr_clear_clip(self._h))
+
+    @property
+    def clip(self):
+        """The clip set on the context as {"lo", "hi", "planes"}, or None."""
+        d, on = ClipDesc(), C.c_int(0)
+        self._c(load().cvr_get_clip(self._h, C.byref(d), C.byref(on)))
+        return d.as_dict() if on.value else None
+
+    def medium_clip_info(self):
+        """(the clip the medium in use was built under as {"lo", "hi", "planes"}, the number of
+        voxels it keeps, counted on the device during the build); a medium built without a clip:
+        the region that keeps everything and the grid's voxel count."""
+        d, kept = ClipDesc(), C.c_uint64(0)
+        self._c(load().cvr_medium_clip_info(self._h, C.byref(d), C.byref(kept)))
+        return d.as_dict(), int(kept.value)
 
     def _device_field(self, what, scalar, spacing, scalar_type, res):
         """(FieldDesc, is a torch tensor) of what set_medium_gradient accepts as `scalar`, with its checks."""

@@ -99,6 +99,13 @@ struct cvr_ctx : cvr::Settings {
   uint32_t block_perm_n = 0;
   int medium_format = 0;     // CVR_OPT_MEDIUM_FORMAT (the next set-medium's; the medium's own is m.format)
   struct cvr_medium_info minfo{};  // cvr_medium_info of the medium in use (own or shared)
+  // cvr_set_clip: taken at the next device build (not in Settings, as use_cells above); and what
+  // the medium in use (own or shared) was built under, cvr_medium_clip_info's
+  bool clip_set = false;
+  cvr_clip_desc clip{};
+  bool medium_clipped = false;
+  cvr_clip_desc medium_clip{};
+  uint64_t medium_kept = 0;
 
   // Not in Settings on purpose: external_out here, and frame_flush, moments and wf_timing below.  A
   // helper always renders into its parent's buffer, without moments, in-launch output or timing.

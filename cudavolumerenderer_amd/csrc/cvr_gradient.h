@@ -132,9 +132,12 @@ __host__ __device__ inline size_t gradient_walk_tasks(uint32_t nx, uint32_t ny, 
 // hits, not memory traffic, when those tasks run close in time on one XCD: consecutive tasks are
 // consecutive x-runs, then consecutive y).  A wave's loads of a step are 64 consecutive voxels.
 // The grid is at most kWalkTaskCap workgroups, a multiple of 8 where there are 8.
-template <class T, class F>
+// skip(xb, x0, y, z0, z1), asked by every lane once per task before anything is read: true leaves
+// the task out (its voxels are x in [xb, xb + 256) of row y over z in [z0, z1); x0 is the lane's
+// x, which may lie past the row).  Its answer must be the workgroup's.
+template <class T, class F, class Skip>
 __device__ __forceinline__ void gradient_walk(const T* __restrict__ S, uint32_t nx, uint32_t ny, uint32_t nz,
-                                              const GradientAxes& a, F&& fn) {
+                                              const GradientAxes& a, F&& fn, Skip&& skip) {
   const uint32_t nxc = (nx + 255u) / 256u;
   const size_t ntasks = gradient_walk_tasks(nx, ny, nz);
   const uint32_t lane = threadIdx.x & 63u;
@@ -147,13 +150,14 @@ __device__ __forceinline__ void gradient_walk(const T* __restrict__ S, uint32_t 
   for (size_t t = vb; t < ntasks; t += nb) {
     const uint32_t xc = (uint32_t)(t % nxc), y = (uint32_t)((t / nxc) % ny), zc = (uint32_t)(t / ((size_t)nxc * ny));
     const uint32_t x0 = xc * 256u + threadIdx.x;
+    const uint32_t z0 = zc * kWalkZ, z1 = z0 + kWalkZ < nz ? z0 + kWalkZ : nz;
+    if (skip(xc * 256u, x0, y, z0, z1)) continue;
     const bool in = x0 < nx;
     const uint32_t x = in ? x0 : nx - 1u;  // (lanes past the row read its last voxel)
     uint32_t xm, xp, ym, yp;
     float kx, ky;
     gradient_neighbours(x, nx, a.h1[0], a.h2[0], xm, xp, kx);
     gradient_neighbours(y, ny, a.h1[1], a.h2[1], ym, yp, ky);
-    const uint32_t z0 = zc * kWalkZ, z1 = z0 + kWalkZ < nz ? z0 + kWalkZ : nz;
     auto at = [&](uint32_t xx, uint32_t yy, uint32_t zz) { return (float)S[((size_t)zz * ny + yy) * nx + xx]; };
     float prev = at(x, y, z0 > 0u ? z0 - 1u : z0), cur = at(x, y, z0);
     for (uint32_t z = z0; z < z1; ++z) {
@@ -171,6 +175,12 @@ __device__ __forceinline__ void gradient_walk(const T* __restrict__ S, uint32_t 
       cur = next;
     }
   }
+}
+// The walk over every task
+template <class T, class F>
+__device__ __forceinline__ void gradient_walk(const T* __restrict__ S, uint32_t nx, uint32_t ny, uint32_t nz,
+                                              const GradientAxes& a, F&& fn) {
+  gradient_walk(S, nx, ny, nz, a, fn, [](uint32_t, uint32_t, uint32_t, uint32_t, uint32_t) { return false; });
 }
 
 }  // namespace cvr

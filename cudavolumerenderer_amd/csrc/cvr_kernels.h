@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "cvr_clip.h"
 #include "cvr_env.h"
 #include "cvr_gradient.h"
 #include "cvr_walk.h"
@@ -142,6 +143,7 @@ constexpr uint32_t kBuildSparseCellsGrid = 8192, kBuildSparseBoundsGrid = 4096;
 // is device memory; the launches are asynchronous on s and none waits on another workgroup.
 // What the value scans find, in device memory; the host sets ovf_* to ~0 and the rest to 0 first.
 struct VoxelSource;  // below: the caller's arrays, or a scalar field and a transfer table
+constexpr uint32_t kKeptSlots = 32;  // words a clipped build's kept-voxel count is spread over (MedScan::kept)
 struct MedScan {
   unsigned long long ovf_density;  // smallest index whose finite value rounds to +-inf in binary16 (format 1)
   unsigned long long ovf_albedo;   // the same over the albedo's r, g, b (index 4 voxel + channel)
@@ -149,6 +151,9 @@ struct MedScan {
   uint32_t albedo_flags;           // bit 0: an rgb (format 1: rounded to half) differs from voxel 0's;
                                    // bit 1: a voxel's 16 bytes differ from voxel 0's
   uint32_t total[2];               // totals of the two flag scans (launch_flag_scan)
+  // a clipped build: the voxels its clip keeps, added by the store or leaf-flag pass, a
+  // workgroup's count to slot blockIdx.x % kKeptSlots; the host adds the slots
+  unsigned long long kept[kKeptSlots];
 };
 hipError_t launch_scan_density(const float* density, size_t n, uint32_t format, MedScan* out, hipStream_t s);
 hipError_t launch_scan_albedo(const float* albedo, size_t n, uint32_t format, MedScan* out, hipStream_t s);
@@ -279,14 +284,28 @@ struct VoxelSource {
   bool gradient = false;
   uint32_t res[3] = {0u, 0u, 0u};
   GradientParams gtf{};
+  // The clip region the build honours (cvr_clip.h; host memory, hi clamped to the grid), or null.
+  // With one, every launch below that takes the source runs its clipped instance: a voxel the
+  // region does not keep is (0, the unclipped voxel 0's albedo) and is not read.
+  const ClipRegion* clip = nullptr;
+  float clip_a0[4] = {0.0f, 0.0f, 0.0f, 0.0f};  // with it: the unclipped source's albedo of voxel 0
 };
+// The arrays' source, dense, with a clip: one pass in the place of launch_scan_density and
+// launch_scan_albedo (albedo null: the densities alone), of the clipped values, and one in the
+// place of the copy or launch_to_half, which stores every voxel (albedo null: the density grid
+// alone) and adds the kept voxels to scan->kept.  res is the grid's.
+hipError_t launch_scan_clipped(const VoxelSource& src, const uint32_t res[3], uint32_t format, MedScan* out,
+                               hipStream_t s);
+hipError_t launch_store_clipped(const VoxelSource& src, const uint32_t res[3], uint32_t format, void* density,
+                                void* albedo, MedScan* scan, hipStream_t s);
 // Classified source, dense: one pass over the scalar field that finds what launch_scan_density and
 // launch_scan_albedo find together, and one that stores every voxel's density and albedo
 // (format 1: binary16) into the context's grids.  n = the voxels; a gradient source is walked by
 // its res, z-planes marching through registers, with the same two results.
+// With a clip (src.clip, src.res the grid's) the store adds the kept voxels to scan->kept.
 hipError_t launch_scan_classified(const VoxelSource& src, size_t n, uint32_t format, MedScan* out, hipStream_t s);
 hipError_t launch_store_classified(const VoxelSource& src, size_t n, uint32_t format, void* density, void* albedo,
-                                   hipStream_t s);
+                                   MedScan* scan, hipStream_t s);
 // cvr_debug_fastdiv (tests): q[i] = fastdiv(u[i], f) on the device, u and q device arrays.
 hipError_t launch_debug_fastdiv(FastDiv f, const uint32_t* u, uint32_t* q, size_t n, hipStream_t s);
 hipError_t launch_tile_to_image(const float4* tile, uint32_t tw, uint32_t th, float4* image, uint32_t iw,

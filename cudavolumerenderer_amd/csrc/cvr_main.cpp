@@ -29,6 +29,7 @@
 // for Enter; --interactive true has no GL viewer here (out of scope, SURVEY
 // §2.1) and falls back to the headless path with a notice.
 #include <algorithm>
+#include <cerrno>
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -55,6 +56,8 @@ struct Options {
   std::string histogram_file;          // --histogram FILE
   std::vector<unsigned> histogram_bins{256, 256};  // --histogram-bins N [M]
   std::vector<float> voxel_spacing{1.0f, 1.0f, 1.0f};  // --voxel-spacing X Y Z
+  std::vector<unsigned> crop;          // --crop X0 Y0 Z0 X1 Y1 Z1
+  std::vector<float> clip_planes;      // --clip-plane A B C D, four values per plane given
   std::string envmap;  // --envmap FILE
   float env_scale = 1.0f;
   double env_rotate_y = 0.0;  // degrees
@@ -127,6 +130,13 @@ void usage() {
       "  --histogram-bins N [M] (=256 256)  value bins and gradient bins (N >= 2, N*M <= 65536; M omitted: 1, no gradient)\n"
       "                                     --field-stats, --histogram and --gradient-range auto take --voxel-spacing;\n"
       "                                     with --iterations 0 they run without a render\n"
+      "  --crop X0 Y0 Z0 X1 Y1 Z1           with --transfer or --transfer2d: keep the voxels X0 <= x < X1, Y0 <= y < Y1,\n"
+      "                                     Z0 <= z < Z1 (voxel indices; past the grid: to its end) and store the\n"
+      "                                     others as empty (cvr_set_clip)\n"
+      "  --clip-plane A B C D               with --transfer or --transfer2d, up to 8 times: keep the voxels with\n"
+      "                                     A x + B y + C z + D >= 0 in voxel indices; --field-stats then also prints\n"
+      "                                     the number of voxels the clip keeps, as the render's build counted\n"
+      "                                     them (with --iterations 0 the medium is built once for the count)\n"
       "  --envmap FILE(.hdr|.pfm)           light the scene with a latitude-longitude environment map in place\n"
       "                                     of the constant white one (cvr_set_environment; every device's\n"
       "                                     context keeps a copy; not with naiveMK or --rng-binding thread)\n"
@@ -218,6 +228,39 @@ int parse(int argc, char** argv, Options& o) {
       while (i + 1 < argc && dst.size() < want && !(argv[i + 1][0] == '-' && argv[i + 1][1] == '-'))
         dst.push_back(strtof(argv[++i], nullptr));
       if (dst.size() != want) {
+        fprintf(stderr, "[ConfigParser] Error: %s needs %zu values\n", a.c_str(), want);
+        return 2;
+      }
+    }
+    else if (a == "--crop" || a == "--clip-plane") {
+      // (a plane's coefficients may be negative: only another option ends the values; a crop's
+      // are voxel indices, digits only, up to 2^32 - 1)
+      const size_t want = a == "--crop" ? 6 : 4;
+      size_t got = 0;
+      if (a == "--crop") o.crop.clear();
+      while (i + 1 < argc && got < want && !(argv[i + 1][0] == '-' && argv[i + 1][1] == '-')) {
+        ++got;
+        const char* v = argv[++i];
+        char* end = nullptr;
+        if (a == "--crop") {
+          errno = 0;
+          const unsigned long long u = strtoull(v, &end, 10);
+          if (!(v[0] >= '0' && v[0] <= '9') || *end != '\0' || errno || u > 0xFFFFFFFFull) {
+            fprintf(stderr, "[ConfigParser] Error: --crop value '%s' is not a voxel index (digits only, at most "
+                            "4294967295)\n", v);
+            return 2;
+          }
+          o.crop.push_back((unsigned)u);
+        } else {
+          const float f = strtof(v, &end);
+          if (end == v || *end != '\0') {
+            fprintf(stderr, "[ConfigParser] Error: --clip-plane value '%s' is not a number\n", v);
+            return 2;
+          }
+          o.clip_planes.push_back(f);
+        }
+      }
+      if (got != want) {
         fprintf(stderr, "[ConfigParser] Error: %s needs %zu values\n", a.c_str(), want);
         return 2;
       }
@@ -364,6 +407,17 @@ bool read_transfer(const std::string& path, std::vector<float>& table) {
     ok = false;
   }
   return ok;
+}
+
+// the scene's grid resolution
+struct Res3 {
+  uint32_t v[3];
+};
+Res3 md_res_of(const cvr_scene* scene) {
+  cvr_medium_desc md{};
+  Res3 r{{0u, 0u, 0u}};
+  if (cvr_scene_medium(scene, &md) == CVR_OK) memcpy(r.v, md.res, sizeof(r.v));
+  return r;
 }
 
 // --field-stats, --gradient-range auto and --histogram: the scene's bytes as a u8 field with lo 0
@@ -629,6 +683,39 @@ int main(int argc, char** argv) {
     transfer2d.ghi = ghi;
     for (int k = 0; k < 3; ++k) transfer2d.spacing[k] = o.voxel_spacing[k];
   }
+  // --crop, --clip-plane: the clip region of the device build (the host uploads do not clip)
+  cvr_clip_desc clip{};
+  const bool have_clip = !o.crop.empty() || !o.clip_planes.empty();
+  if (have_clip) {
+    const uint8_t* raw = nullptr;
+    size_t n_raw = 0;
+    if (cvr_scene_raw_bytes(scene, &raw, &n_raw) != CVR_OK || !n_raw) {
+      fprintf(stderr, "[ConfigParser] Error: --crop and --clip-plane apply to Raw scenes only (and --synthetic bucky): "
+                      "this scene has no scalar bytes to classify on the device\n");
+      return 2;
+    }
+    if (!transfer.n && !transfer2d.n) {
+      fprintf(stderr, "[ConfigParser] Error: --crop and --clip-plane need --transfer or --transfer2d (the clip is applied "
+                      "where the device build classifies the voxel)\n");
+      return 2;
+    }
+    if (o.clip_planes.size() > 4u * CVR_CLIP_MAX_PLANES) {
+      fprintf(stderr, "[ConfigParser] Error: at most %d --clip-plane\n", CVR_CLIP_MAX_PLANES);
+      return 2;
+    }
+    for (int k = 0; k < 3; ++k) {
+      clip.lo[k] = o.crop.empty() ? 0u : o.crop[k];
+      clip.hi[k] = o.crop.empty() ? 0xFFFFFFFFu : o.crop[3 + k];
+    }
+    clip.n_planes = (uint32_t)(o.clip_planes.size() / 4);
+    memcpy(clip.planes, o.clip_planes.data(), o.clip_planes.size() * sizeof(float));
+    // (the library's own check of the descriptor, before any device is touched)
+    const Res3 clip_res = md_res_of(scene);
+    if (cvr_clip_host(clip_res.v, &clip, nullptr, nullptr, nullptr) != CVR_OK) {
+      fprintf(stderr, "[ConfigParser] Error: --crop / --clip-plane: %s\n", cvr_last_error(nullptr));
+      return 2;
+    }
+  }
   // --envmap: the file's texels and the descriptor every context takes its copy from
   float* env_rgb = nullptr;
   cvr_environment_desc env{};
@@ -704,6 +791,7 @@ int main(int argc, char** argv) {
     if (!rc && o.world_to_aabb == "fixed") rc = cvr_set_option(ctx, CVR_OPT_WORLD_TO_AABB, 1);
     if (!rc && o.mk_compaction == "reference") rc = cvr_set_option(ctx, CVR_OPT_MK_COMPACTION, 1);
     if (!rc && o.medium_format == "half") rc = cvr_set_option(ctx, CVR_OPT_MEDIUM_FORMAT, CVR_FORMAT_F16);
+    if (!rc && have_clip && !share) rc = cvr_set_clip(ctx, &clip);
     if (!rc && share) {
       rc = cvr_share_medium(ctx, share);
     } else if (!rc && transfer2d.n) {
@@ -727,6 +815,18 @@ int main(int argc, char** argv) {
     }
     return ctx;
   };
+  // --field-stats with a clip: the kept voxels, as the build of ctx's medium counted them
+  auto print_kept = [&](cvr_ctx* ctx) -> int {
+    uint64_t kept = 0;
+    if (cvr_medium_clip_info(ctx, nullptr, &kept) != CVR_OK) {
+      fprintf(stderr, "Error: %s\n", cvr_last_error(ctx));
+      return 1;
+    }
+    const Res3 res = md_res_of(scene);
+    printf("clip                : kept voxels %llu of %llu\n", (unsigned long long)kept,
+           (unsigned long long)res.v[0] * res.v[1] * res.v[2]);
+    return 0;
+  };
   const std::vector<int> devs = parse_devices(o.devices, o.device);
   if (devs.empty()) {
     fprintf(stderr, "[ConfigParser] Error: --devices needs a count (N >= 1) or a list of two or more device ids "
@@ -742,6 +842,15 @@ int main(int argc, char** argv) {
       printf("[ConfigParser] gradient range set to 0 .. %.9g.\n", (double)gmax);
     }
     if (o.iterations == 0) {  // the field's numbers alone: no render, no image
+      if (o.field_stats && have_clip) {
+        // the kept voxels are counted by the build itself, and nothing renders: a context of this
+        // pass's own builds the medium once for the count
+        cvr_ctx* c = make_ctx(devs[0], nullptr);
+        if (!c) return 1;
+        const int kr = print_kept(c);
+        cvr_destroy(c);
+        if (kr) return kr;
+      }
       cvr_free_image(env_rgb);
       return 0;
     }
@@ -805,6 +914,8 @@ int main(int argc, char** argv) {
       }
       ctxs.push_back(c);
     }
+    // (the first trial's render context: its build counted the kept voxels, no build of its own)
+    if (t == 0 && o.field_stats && have_clip && print_kept(ctxs[0])) return 1;
     cvr_stats st{};
     const auto t0 = std::chrono::steady_clock::now();
     cvr_adaptive_result ares{};

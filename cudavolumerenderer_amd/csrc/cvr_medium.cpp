@@ -305,6 +305,7 @@ int finish_dense(cvr_ctx* c, const MediumView& v, uint32_t fmt, float max_densit
                       : cvr::V3{uniform_rgb[0], uniform_rgb[1], uniform_rgb[2]};
   }
   set_minfo(c, fmt, max_density, n * B.d, c->d_cells ? n * B.c : 0, n * B.a, bounds_bytes);
+  c->medium_clipped = false;  // (build_from_device notes its clip after this)
   c->have_medium = true;
   return CVR_OK;
 }
@@ -466,6 +467,7 @@ int finish_sparse(cvr_ctx* c, const SparseBuild& b, DevTemps& tmp, DevmedTimer& 
   set_minfo(c, b.fmt, b.max_density, (np ? np : 1) * B.d, c->d_cells ? ncl * 512 * B.c : 0,
             c->d_leaf_albedo ? np * B.a : 0,
             (g.nb + 1 + g.nleaf + (c->d_emask ? cvr::kEmaskWords : 0)) * sizeof(uint32_t));
+  c->medium_clipped = false;  // (build_from_device notes its clip after this)
   c->have_medium = true;
   return CVR_OK;
 }
@@ -516,6 +518,21 @@ int source_voxel(cvr_ctx* c, const cvr::VoxelSource& src, const float* host_tabl
   }
   out[0] = e.x, out[1] = e.y, out[2] = e.z, out[3] = 1.0f, out[4] = e.w;
   return CVR_OK;
+}
+
+// The same of a voxel as a build stores it: behind a clip, a voxel the region does not keep is
+// (first's albedo, 0), first being the unclipped voxel 0's values.
+int stored_voxel(cvr_ctx* c, const cvr::VoxelSource& src, const float* host_table, size_t i, bool with_albedo,
+                 const float first[5], float out[5]) {
+  if (src.clip) {
+    const uint32_t nx = src.res[0], ny = src.res[1];
+    if (!cvr::clip_keeps(*src.clip, (uint32_t)(i % nx), (uint32_t)((i / nx) % ny), (uint32_t)(i / ((size_t)nx * ny)))) {
+      memcpy(out, first, 4 * sizeof(float));
+      out[4] = 0.0f;
+      return CVR_OK;
+    }
+  }
+  return source_voxel(c, src, host_table, i, with_albedo, out);
 }
 
 // What the descriptors of the two device calls say besides the source
@@ -600,7 +617,7 @@ int devmed_sparse(cvr_ctx* c, const DeviceBuild& d, const cvr::VoxelSource& src,
         const size_t i = ((size_t)z * res[1] + y) * res[0] + x;
         if (x < res[0] && y < res[1] && z < res[2]) {
           float v[5];
-          if ((r = source_voxel(c, src, d.host_table, i, !in_density, v))) return r;
+          if ((r = stored_voxel(c, src, d.host_table, i, !in_density, bg, v))) return r;
           value = in_density ? v[4] : v[at % 4];
         } else {
           value = in_density ? 0.0f : bg[at % 4];
@@ -664,8 +681,24 @@ int gradient_check(std::string* err, const cvr_gradient_transfer_desc* t, F afte
 
 // Both device calls from their checked arguments on: one sequence of stages for either source.
 // b.g is filled for a sparse build; tmp may already hold the call's allocations (the table).
-int build_from_device(cvr_ctx* c, const DeviceBuild& d, const cvr::VoxelSource& src, SparseBuild& b, DevTemps& tmp) {
+// The context's clip, when set, is taken here: the source then carries the region, every launch
+// that takes the source runs its clipped instance, and the medium notes what it was built under.
+int build_from_device(cvr_ctx* c, const DeviceBuild& d, const cvr::VoxelSource& unclipped, SparseBuild& b,
+                      DevTemps& tmp) {
   const uint32_t* res = d.v.res;
+  cvr::VoxelSource src = unclipped;
+  cvr::ClipRegion region{};
+  const cvr_clip_desc clip = c->clip;
+  if (c->clip_set) {
+    for (int a = 0; a < 3; ++a) {
+      region.lo[a] = clip.lo[a];
+      region.hi[a] = std::min(clip.hi[a], res[a]);
+    }
+    region.n_planes = clip.n_planes;
+    memcpy(region.planes, clip.planes, sizeof(region.planes));
+    src.clip = &region;
+    memcpy(src.res, res, sizeof(src.res));
+  }
   const bool sparse = (d.flags & CVR_DEVMED_SPARSE) != 0, konst = (d.flags & CVR_DEVMED_CONST_ALBEDO) != 0;
   const bool classified = src.scalar != nullptr;
   const uint32_t fmt = (uint32_t)c->medium_format;
@@ -674,12 +707,26 @@ int build_from_device(cvr_ctx* c, const DeviceBuild& d, const cvr::VoxelSource& 
   HIP_TRY(c, hipStreamSynchronize(c->stream));
   DevmedTimer tm(c);
   // the value scans: majorant, binary16 overflow, albedo sameness
-  cvr::MedScan scan{~0ull, ~0ull, 0u, 0u, {0u, 0u}};
+  cvr::MedScan scan{~0ull, ~0ull, 0u, 0u, {0u, 0u}, {}};
+  // the clip the medium was built under and the kept voxels its store or leaf-flag pass counted
+  auto note_clip = [&](int result, const cvr::MedScan* d_counted) -> int {
+    if (result || !src.clip) return result;
+    unsigned long long slots[cvr::kKeptSlots], kept = 0;
+    HIP_TRY(c, hipMemcpy(slots, d_counted->kept, sizeof(slots), hipMemcpyDeviceToHost));
+    for (unsigned long long v : slots) kept += v;
+    c->medium_clipped = true;
+    c->medium_clip = clip;
+    c->medium_kept = kept;
+    return CVR_OK;
+  };
   cvr::MedScan* d_scan = nullptr;
   HIP_TRY(c, tmp.alloc((void**)&d_scan, sizeof(scan)));
   HIP_TRY(c, hipMemcpy(d_scan, &scan, sizeof(scan), hipMemcpyHostToDevice));
   float first[5] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
   if (konst) memcpy(first, d.const_albedo, 4 * sizeof(float));
+  // voxel 0's values (the background, and what a clipped voxel's albedo is), of the unclipped source
+  if (!konst && (r = source_voxel(c, unclipped, d.host_table, 0, true, first))) return r;
+  if (src.clip) memcpy(src.clip_a0, first, sizeof(src.clip_a0));
   const bool scan_density = fmt || (d.flags & CVR_DEVMED_MAX_DENSITY),
              scan_albedo = !konst && (fmt || sparse || c->uniform_albedo);
   if (classified) {
@@ -687,6 +734,15 @@ int build_from_device(cvr_ctx* c, const DeviceBuild& d, const cvr::VoxelSource& 
     if (!sparse && (scan_density || scan_albedo)) {
       tm.begin();
       HIP_TRY(c, cvr::launch_scan_classified(src, n, fmt, d_scan, c->stream));
+      tm.end(0);
+    }
+  } else if (src.clip) {
+    // one pass finds both scans' results of the clipped values
+    if (scan_density || scan_albedo) {
+      cvr::VoxelSource sv = src;
+      if (!scan_albedo) sv.albedo = nullptr;
+      tm.begin();
+      HIP_TRY(c, cvr::launch_scan_clipped(sv, res, fmt, d_scan, c->stream));
       tm.end(0);
     }
   } else {
@@ -702,14 +758,13 @@ int build_from_device(cvr_ctx* c, const DeviceBuild& d, const cvr::VoxelSource& 
     }
   }
   HIP_TRY(c, hipStreamSynchronize(c->stream));
-  if (!konst && (r = source_voxel(c, src, d.host_table, 0, true, first))) return r;
   HIP_TRY(c, hipMemcpy(&scan, d_scan, sizeof(scan), hipMemcpyDeviceToHost));
   const float max_density = majorant_of(d, scan, fmt);
   if (sparse) {
     b.v = d.v;
     b.fmt = fmt;
     b.max_density = max_density;
-    return devmed_sparse(c, d, src, b, scan, first, d_scan, tmp, tm);
+    return note_clip(devmed_sparse(c, d, src, b, scan, first, d_scan, tmp, tm), d_scan);
   }
   if (fmt) {
     // cvr_set_medium's refusal: density before albedo, the smallest index (a constant albedo's
@@ -720,7 +775,7 @@ int build_from_device(cvr_ctx* c, const DeviceBuild& d, const cvr::VoxelSource& 
     bool bad_a = false;
     float v[5];
     if (bad_d) {
-      if ((r = source_voxel(c, src, d.host_table, at, false, v))) return r;
+      if ((r = stored_voxel(c, src, d.host_table, at, false, first, v))) return r;
       value = v[4];
     } else if (konst) {
       for (size_t k = 0; k < 3 && !bad_a; ++k)
@@ -728,7 +783,7 @@ int build_from_device(cvr_ctx* c, const DeviceBuild& d, const cvr::VoxelSource& 
     } else if (scan.ovf_albedo != ~0ull) {
       bad_a = true;
       at = (size_t)scan.ovf_albedo;
-      if ((r = source_voxel(c, src, d.host_table, at / 4, true, v))) return r;
+      if ((r = stored_voxel(c, src, d.host_table, at / 4, true, first, v))) return r;
       value = v[at % 4];
     }
     if (bad_d || bad_a) {
@@ -741,7 +796,9 @@ int build_from_device(cvr_ctx* c, const DeviceBuild& d, const cvr::VoxelSource& 
   if ((r = dense_grids(c, n, fmt))) return r;
   tm.begin();
   if (classified) {
-    HIP_TRY(c, cvr::launch_store_classified(src, n, fmt, c->d_density, c->d_albedo, c->stream));
+    HIP_TRY(c, cvr::launch_store_classified(src, n, fmt, c->d_density, c->d_albedo, d_scan, c->stream));
+  } else if (src.clip) {
+    HIP_TRY(c, cvr::launch_store_clipped(src, res, fmt, c->d_density, konst ? nullptr : c->d_albedo, d_scan, c->stream));
   } else if (fmt) {
     HIP_TRY(c, cvr::launch_to_half(src.density, c->d_density, n, c->stream));
     if (!konst) HIP_TRY(c, cvr::launch_to_half(src.albedo, c->d_albedo, 4 * n, c->stream));
@@ -753,7 +810,33 @@ int build_from_device(cvr_ctx* c, const DeviceBuild& d, const cvr::VoxelSource& 
   if (konst) HIP_TRY(c, cvr::launch_fill_albedo(c->d_albedo, n, fmt, d.const_albedo, c->stream));
   tm.end(4);
   const bool same = c->uniform_albedo && (konst || !(scan.albedo_flags & 1u));
-  return finish_dense(c, d.v, fmt, max_density, same ? first : nullptr, tm);
+  return note_clip(finish_dense(c, d.v, fmt, max_density, same ? first : nullptr, tm), d_scan);
+}
+
+// cvr_set_clip's refusals, in cvr.h's order
+int clip_check(std::string* err, const cvr_clip_desc* d) {
+  if (!d) return set_err(err, CVR_ERR_INVALID, "cvr_clip_desc is NULL");
+  if (d->flags) return set_err(err, CVR_ERR_INVALID, "cvr_clip_desc flags 0x%x: must be 0", d->flags);
+  if (d->n_planes > CVR_CLIP_MAX_PLANES)
+    return set_err(err, CVR_ERR_INVALID, "%u clip planes (at most %d)", d->n_planes, CVR_CLIP_MAX_PLANES);
+  for (int a = 0; a < 3; ++a)
+    if (d->lo[a] > d->hi[a])
+      return set_err(err, CVR_ERR_INVALID, "crop lo[%d] = %u above hi[%d] = %u", a, d->lo[a], a, d->hi[a]);
+  for (uint32_t k = 0; k < d->n_planes; ++k)
+    for (int j = 0; j < 4; ++j)
+      if (!std::isfinite(d->planes[k][j]))
+        return set_err(err, CVR_ERR_INVALID, "clip plane %u coefficient %d = %g: not finite", k, j,
+                       (double)d->planes[k][j]);
+  for (uint32_t k = 0; k < d->n_planes; ++k)
+    if (d->planes[k][0] == 0.0f && d->planes[k][1] == 0.0f && d->planes[k][2] == 0.0f)
+      return set_err(err, CVR_ERR_INVALID, "clip plane %u has a zero normal (A = B = C = 0)", k);
+  return CVR_OK;
+}
+// the descriptor that keeps everything
+cvr_clip_desc clip_everything() {
+  cvr_clip_desc d{};
+  d.hi[0] = d.hi[1] = d.hi[2] = 0xFFFFFFFFu;
+  return d;
 }
 }  // namespace
 
@@ -762,6 +845,8 @@ extern "C" {
 int cvr_set_medium(cvr_ctx* c, const cvr_medium_desc* md) {
   if (!c || !md) return set_err(c ? &c->err : nullptr, CVR_ERR_INVALID, "NULL argument");
   CVR_NOT_IN_SESSION(c, "cvr_set_medium");
+  if (c->clip_set)
+    return set_err(&c->err, CVR_ERR_UNSUPPORTED, "cvr_set_medium with a clip set: only the device builds clip (cvr_clear_clip first)");
   // (the shape is judged first, from the numbers alone, then the arrays)
   const uint32_t fmt = (uint32_t)c->medium_format;
   int r = dense_shape_check(c, md->res, fmt);
@@ -822,6 +907,9 @@ int cvr_set_medium(cvr_ctx* c, const cvr_medium_desc* md) {
 int cvr_set_medium_sparse(cvr_ctx* c, const cvr_sparse_medium_desc* sd) {
   if (!c || !sd) return set_err(c ? &c->err : nullptr, CVR_ERR_INVALID, "NULL argument");
   CVR_NOT_IN_SESSION(c, "cvr_set_medium_sparse");
+  if (c->clip_set)
+    return set_err(&c->err, CVR_ERR_UNSUPPORTED,
+                   "cvr_set_medium_sparse with a clip set: only the device builds clip (cvr_clear_clip first)");
   // (as in cvr_set_medium, the shape is judged first, from the numbers alone, then the arrays;
   // an empty grid is sparse_shape_check's to refuse, before leaf_dims)
   const uint32_t* res = sd->res;
@@ -1222,6 +1310,9 @@ int cvr_share_medium(cvr_ctx* c, const cvr_ctx* src) {
   c->m = src->m;
   c->minfo = src->minfo;
   c->n_cell_leaves = src->n_cell_leaves;
+  c->medium_clipped = src->medium_clipped;
+  c->medium_clip = src->medium_clip;
+  c->medium_kept = src->medium_kept;
   c->have_medium = true;
   c->inited = false;
   return CVR_OK;
@@ -1231,6 +1322,67 @@ int cvr_medium_info(const cvr_ctx* c, struct cvr_medium_info* out) {
   if (!c || !out) return set_err(nullptr, CVR_ERR_INVALID, "NULL argument");
   if (!c->have_medium) return set_err(nullptr, CVR_ERR_STATE, "no medium");
   *out = c->minfo;
+  return CVR_OK;
+}
+
+int cvr_set_clip(cvr_ctx* c, const cvr_clip_desc* d) {
+  if (!c) return set_err(nullptr, CVR_ERR_INVALID, "NULL argument");
+  CVR_NOT_IN_SESSION(c, "cvr_set_clip");
+  if (int r = clip_check(&c->err, d)) return r;
+  c->clip = *d;
+  c->clip_set = true;
+  return CVR_OK;
+}
+
+int cvr_clear_clip(cvr_ctx* c) {
+  if (!c) return set_err(nullptr, CVR_ERR_INVALID, "NULL argument");
+  CVR_NOT_IN_SESSION(c, "cvr_clear_clip");
+  c->clip_set = false;
+  return CVR_OK;
+}
+
+int cvr_get_clip(const cvr_ctx* c, cvr_clip_desc* d, int* set) {
+  if (!c) return set_err(nullptr, CVR_ERR_INVALID, "NULL argument");
+  if (d) *d = c->clip_set ? c->clip : clip_everything();
+  if (set) *set = c->clip_set ? 1 : 0;
+  return CVR_OK;
+}
+
+int cvr_clip_host(const uint32_t res[3], const cvr_clip_desc* d, float* density, float* albedo, uint8_t* keep) {
+  if (!res) return set_err(nullptr, CVR_ERR_INVALID, "NULL argument");
+  if (int r = clip_check(nullptr, d)) return r;
+  const uint32_t nx = res[0], ny = res[1], nz = res[2];
+  if (!nx || !ny || !nz) return set_err(nullptr, CVR_ERR_INVALID, "empty grid");
+  if ((uint64_t)nx * ny > 0xFFFFFFFFull || (uint64_t)nx * ny * nz > 0xFFFFFFFFull)
+    return set_err(nullptr, CVR_ERR_INVALID, "grid exceeds 2^32 voxels");
+  cvr::ClipRegion r{};
+  for (int a = 0; a < 3; ++a) {
+    r.lo[a] = d->lo[a];
+    r.hi[a] = std::min(d->hi[a], res[a]);
+  }
+  r.n_planes = d->n_planes;
+  memcpy(r.planes, d->planes, sizeof(r.planes));
+  // (voxel 0's albedo before voxel 0 itself may be overwritten with it)
+  float a0[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+  if (albedo) memcpy(a0, albedo, sizeof(a0));
+  size_t i = 0;
+  for (uint32_t z = 0; z < nz; ++z)
+    for (uint32_t y = 0; y < ny; ++y)
+      for (uint32_t x = 0; x < nx; ++x, ++i) {
+        const bool k = cvr::clip_keeps(r, x, y, z);
+        if (keep) keep[i] = k ? 1 : 0;
+        if (k) continue;
+        if (density) density[i] = 0.0f;
+        if (albedo) memcpy(albedo + 4 * i, a0, sizeof(a0));
+      }
+  return CVR_OK;
+}
+
+int cvr_medium_clip_info(const cvr_ctx* c, cvr_clip_desc* d, uint64_t* kept) {
+  if (!c) return set_err(nullptr, CVR_ERR_INVALID, "NULL argument");
+  if (!c->have_medium) return set_err(nullptr, CVR_ERR_STATE, "no medium");
+  if (d) *d = c->medium_clipped ? c->medium_clip : clip_everything();
+  if (kept) *kept = c->medium_clipped ? c->medium_kept : (uint64_t)c->m.rx * c->m.ry * c->m.rz;
   return CVR_OK;
 }
 

@@ -6,6 +6,8 @@
 // (majorant, binary16 overflow, uniform albedo), the dense -> 8^3 leaves
 // rule of cvr.h (leaf flags, exclusive scan, gather), the cell-leaf table and the empty-region
 // mask.  The cells, bounds and brick words are then built by cvr_kernels.hip's kernels, unchanged.
+// A source may stand behind a clip region (cvr.h: CVR_HAS_CLIP; Clipped below): the same stages
+// then run clipped instances, and a context without a clip runs the ones it always ran.
 //
 // No kernel here waits on another workgroup: the exclusive scan is three launches (per-tile
 // counts, one workgroup over the tile sums, scatter), ordered by the stream.
@@ -15,6 +17,7 @@
 #include <type_traits>
 
 #include "cvr_device.h"
+#include "cvr_host.h"
 #include "cvr_kernels.h"
 
 namespace cvr {
@@ -111,6 +114,56 @@ struct GradientSrc {
     classified((float)S[i], mag, d, a);
   }
 };
+// a or, for a clipped voxel, a0, by component (a select of the two float4 objects would be a select
+// of their addresses, and a0's is the kernel's by-value argument: it would be copied to scratch)
+__device__ __forceinline__ float4 keep_or(bool keep, const float4 a, const float4 a0) {
+  return make_float4(keep ? a.x : a0.x, keep ? a.y : a0.y, keep ? a.z : a0.z, keep ? a.w : a0.w);
+}
+// Any of the three behind a clip region (cvr_clip.h; cvr.h states the clipped voxel): the region
+// travels with the source, by value, and so does a0, the unclipped source's albedo of voxel 0,
+// which every clipped voxel gets (the host reads or classifies it once: source_voxel, whose bits
+// are the kernels').  voxel() reads the source's voxel and then applies the test as a select, so
+// the loads of an unrolled loop still issue together (a test before the load put every load
+// behind a branch of its own); what is provably clipped is left unread by the kernels, a task or
+// a wave at a time.  A kept voxel is the source's, a gradient source's stencil reading its
+// neighbours from the field, clipped or not.
+template <class Src>
+struct Clipped {
+  using Scalar = typename Src::Scalar;
+  Src s;
+  ClipRegion r;
+  float4 a0;
+  __device__ void stage() { s.stage(); }
+  __device__ bool has_albedo() const { return s.has_albedo(); }
+  __device__ bool keeps(uint32_t x, uint32_t y, uint32_t z) const { return clip_keeps(r, x, y, z); }
+  // returns whether the voxel is kept
+  __device__ bool voxel(uint32_t x, uint32_t y, uint32_t z, size_t i, float& d, float4& a) const {
+    s.voxel(x, y, z, i, d, a);
+    const bool keep = keeps(x, y, z);
+    d = keep ? d : 0.0f;
+    a = keep_or(keep, a, a0);
+    return keep;
+  }
+};
+template <class Src>
+struct is_clipped : std::false_type {};
+template <class Src>
+struct is_clipped<Clipped<Src>> : std::true_type {};
+// A work-item's count of kept voxels into out->kept: the workgroup's sum through LDS, then one
+// atomic per workgroup that kept any, on one of kKeptSlots words by the workgroup's index (16 384
+// atomics on a single word, one per wave of a 4096-workgroup launch, cost more than the pass they
+// closed; the host adds the slots).  Every work-item of the workgroup calls it, once, at the end.
+__device__ __forceinline__ void commit_kept(uint32_t kept, MedScan* __restrict__ out) {
+  __shared__ uint32_t s_kept[4];
+  const uint32_t w = wave_sum(kept);
+  __syncthreads();  // (the table's LDS or a scan's scratch is not touched: s_kept is its own)
+  if ((threadIdx.x & 63u) == 0) s_kept[threadIdx.x >> 6] = w;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const uint32_t all = s_kept[0] + s_kept[1] + s_kept[2] + s_kept[3];
+    if (all) atomicAdd(&out->kept[blockIdx.x % kKeptSlots], (unsigned long long)all);
+  }
+}
 
 // ----------------------------------------------------------- value scans ---
 // Streaming reads: consecutive lanes read consecutive 16 bytes (1 KiB per wave and load), a wave
@@ -332,6 +385,201 @@ __global__ __launch_bounds__(256) void k_gradient(GradientSrc<T> src, uint32_t f
   if (!kStore) commit_in_table_lds(ds, as, out);
 }
 
+// ------------------------------------------------- clipped dense passes ---
+// The dense passes of a clipped build (Clipped above).  They index the grid linearly, so a voxel's
+// coordinates come from its index: a dense grid has fewer than 2^32 voxels, and i / nx and
+// (i / nx) / ny are divisions of a u32 by launch constants, one multiply-high and two shifts each
+// (fastdiv, cvr_walk.h), with no 64-bit and no hardware divide.  A wave's run of consecutive
+// voxels is first judged whole, from the rows of its first and last voxel: when every row of the
+// run lies outside the crop box in z or in y, the wave loads nothing (the decision is the wave's:
+// one scalar branch) and a store pass writes the clipped voxel to each.
+struct LinearGrid {
+  uint32_t nx, ny;
+  FastDiv dx, dy;
+  __device__ __forceinline__ void coords(uint32_t i, uint32_t& x, uint32_t& y, uint32_t& z) const {
+    const uint32_t row = fastdiv(i, dx);
+    x = i - row * nx;
+    z = fastdiv(row, dy);
+    y = row - z * ny;
+  }
+  // voxels i0..i1 (i0 <= i1, a wave's run) lie in rows that the crop box excludes
+  __device__ __forceinline__ bool rows_outside(const ClipRegion& r, uint32_t i0, uint32_t i1) const {
+    const uint32_t r0 = fastdiv(i0, dx), r1 = fastdiv(i1, dx), z0 = fastdiv(r0, dy), z1 = fastdiv(r1, dy);
+    bool out = z1 < r.lo[2] || z0 >= r.hi[2];
+    if (z0 == z1) out = out || r1 - z0 * ny < r.lo[1] || r0 - z0 * ny >= r.hi[1];
+    return __builtin_amdgcn_readfirstlane((int)out) != 0;
+  }
+};
+
+// What a clipped dense pass does with voxel i, not in a skipped run: its coordinates, the test,
+// the source's value through load() if it is kept, and emit.  Returns whether it is kept.
+template <bool kStore, class Src, class Load>
+__device__ __forceinline__ bool emit_clipped(const Src& src, const LinearGrid& g, size_t i, Load&& load, uint32_t format,
+                                             DensityScan& ds, AlbedoScan& as, void* __restrict__ density,
+                                             void* __restrict__ albedo) {
+  uint32_t x, y, z;
+  g.coords((uint32_t)i, x, y, z);
+  float d = 0.0f;
+  float4 a = src.a0;
+  const bool keep = src.keeps(x, y, z);
+  if (keep) load(d, a);
+  emit<kStore>(i, d, a, format, ds, as, density, albedo);
+  return keep;
+}
+
+// k_classified behind a clip: the same head, 16-byte groups and tail, the same hand-round.  The
+// scan (kStore false) leaves a skipped run alone: a clipped voxel is (0, a0), which no result of
+// the scans depends on, but for a0's own binary16 overflow, taken once at voxel 0.  The store adds
+// the kept voxels to out->kept.
+template <class T, bool kStore>
+__global__ __launch_bounds__(256) void k_classified_clip(Clipped<ScalarSrc<T>> src, size_t n, LinearGrid g,
+                                                         uint32_t format, void* __restrict__ density,
+                                                         void* __restrict__ albedo, MedScan* __restrict__ out) {
+  src.stage();
+  DensityScan ds;
+  AlbedoScan as(src.a0);
+  uint32_t kept = 0;
+  if (!kStore && blockIdx.x == 0 && threadIdx.x == 0) as.take(src.a0, 0, format);
+  // (scalar(): the voxel's scalar, asked for only when the voxel is kept)
+  auto take = [&](size_t i, auto&& scalar) {
+    kept += emit_clipped<kStore>(
+        src, g, i, [&](float& d, float4& a) { src.s.classified(scalar(), d, a); }, format, ds, as, density, albedo);
+  };
+  constexpr uint32_t kSize = (uint32_t)sizeof(T), V = kSize < 4u ? 16u / kSize : 1u;
+  size_t head = 0, body_end = 0;
+  if constexpr (V > 1u) {
+    head = ((16u - (uint32_t)((uintptr_t)src.s.S & 15u)) & 15u) / kSize;
+    head = head < n ? head : n;
+    const size_t groups = (n - head) / V;
+    body_end = head + groups * V;
+    const uint4* __restrict__ S16 = reinterpret_cast<const uint4*>(src.s.S + head);
+    const uint32_t lane = threadIdx.x & 63u;
+    const size_t wave = ((size_t)blockIdx.x * 256 + threadIdx.x) >> 6, nwaves = (size_t)gridDim.x * 4;
+    // (the bounds are the wave's: every lane takes part in the shuffles)
+    for (size_t g0 = wave * 64; g0 < groups; g0 += nwaves * 64) {
+      const size_t first = head + g0 * V, last = (first + 64u * V < body_end ? first + 64u * V : body_end) - 1u;
+      const bool skip = g.rows_outside(src.r, (uint32_t)first, (uint32_t)last);
+      if (!kStore && skip) continue;
+      const uint4 q = !skip && g0 + lane < groups ? S16[g0 + lane] : make_uint4(0u, 0u, 0u, 0u);
+#pragma unroll
+      for (uint32_t k = 0; k < V; ++k) {
+        const uint32_t j = k * 64u + lane, from = j / V, byte = (j % V) * kSize;
+        const uint32_t w0 = __shfl(q.x, from), w1 = __shfl(q.y, from), w2 = __shfl(q.z, from), w3 = __shfl(q.w, from);
+        const uint32_t w = byte < 4u ? w0 : byte < 8u ? w1 : byte < 12u ? w2 : w3;
+        const T v = (T)(w >> ((byte & 3u) * 8u));
+        const size_t i = first + j;
+        if (i < body_end) take(i, [&] { return (float)v; });
+      }
+    }
+  }
+  const size_t rest = head + (n - body_end);
+  for (size_t e = (size_t)blockIdx.x * 256 + threadIdx.x; e < rest; e += (size_t)gridDim.x * 256) {
+    const size_t i = e < head ? e : body_end + (e - head);
+    take(i, [&] { return (float)src.s.S[i]; });
+  }
+  if (!kStore)
+    commit_in_table_lds(ds, as, out);
+  else
+    commit_kept(kept, out);
+}
+
+// k_gradient behind a clip: the walk reads the field as it does without one (a kept voxel's
+// stencil needs its clipped neighbours), and a lane tests its voxel before it classifies it.  A
+// task whose box (256 x of one row over 16 planes) is provably clipped is not walked: the
+// workgroup's decision; the store writes the clipped voxel to each of its voxels, the scan has
+// nothing to take of them but a0's own overflow, taken once at voxel 0.
+template <class T, bool kStore>
+__global__ __launch_bounds__(256) void k_gradient_clip(Clipped<GradientSrc<T>> src, uint32_t format,
+                                                       void* __restrict__ density, void* __restrict__ albedo,
+                                                       MedScan* __restrict__ out) {
+  src.stage();
+  DensityScan ds;
+  AlbedoScan as(src.a0);
+  uint32_t kept = 0;
+  const uint32_t nx = src.s.res[0], ny = src.s.res[1];
+  if (!kStore && blockIdx.x == 0 && threadIdx.x == 0) as.take(src.a0, 0, format);
+  gradient_walk(
+      src.s.S, nx, ny, src.s.res[2], src.s.p.axes,
+      [&](bool in, uint32_t x, uint32_t y, uint32_t z, float cur, float mag) {
+        if (!in) return;
+        float d = 0.0f;
+        float4 a = src.a0;
+        if (src.keeps(x, y, z)) {
+          src.s.classified(cur, mag, d, a);
+          ++kept;
+        }
+        emit<kStore>(((size_t)z * ny + y) * nx + x, d, a, format, ds, as, density, albedo);
+      },
+      [&](uint32_t xb, uint32_t x, uint32_t y, uint32_t z0, uint32_t z1) {
+        const uint32_t xe = xb + 255u;
+        const uint32_t e0[3] = {xb, y, z0}, e1[3] = {xe < nx ? xe : nx - 1u, y, z1 - 1u};
+        if (!clip_box_outside(src.r, e0, e1)) return false;
+        if (kStore && x < nx)
+          for (uint32_t z = z0; z < z1; ++z)
+            emit<true>(((size_t)z * ny + y) * nx + x, 0.0f, src.a0, format, ds, as, density, albedo);
+        return true;
+      });
+  if (!kStore)
+    commit_in_table_lds(ds, as, out);
+  else
+    commit_kept(kept, out);
+}
+
+// The arrays' source behind a clip, dense: one voxel per lane, a wave's run 64 consecutive voxels
+// (256 bytes of density, 1 KiB of albedo per load).  kStore false: k_scan_density's and, with an
+// albedo array, k_scan_albedo's results of the clipped values, together.  kStore true: the voxels
+// into the context's density grid and, with an albedo array, its albedo grid (format 1: as
+// binary16), and the kept voxels into out->kept.
+template <bool kStore>
+__global__ __launch_bounds__(256) void k_arrays_clip(Clipped<ArraySrc> src, size_t n, LinearGrid g, uint32_t format,
+                                                     void* __restrict__ density, void* __restrict__ albedo,
+                                                     MedScan* __restrict__ out) {
+  src.stage();
+  const bool with_albedo = src.has_albedo();
+  DensityScan ds;
+  AlbedoScan as(src.a0);
+  uint32_t kept = 0;
+  if (!kStore && with_albedo && blockIdx.x == 0 && threadIdx.x == 0) as.take(src.a0, 0, format);
+  // (the bounds are the workgroup's; a wave past the end has no voxel)
+  for (size_t base = (size_t)blockIdx.x * 256; base < n; base += (size_t)gridDim.x * 256) {
+    const size_t i0 = base + (threadIdx.x & ~63u), i = base + threadIdx.x;
+    if (i0 >= n) continue;
+    const bool skip = g.rows_outside(src.r, (uint32_t)i0, (uint32_t)(i0 + 63u < n ? i0 + 63u : n - 1u));
+    if (!kStore && skip) continue;
+    if (i >= n) continue;
+    uint32_t x, y, z;
+    g.coords((uint32_t)i, x, y, z);
+    float d = 0.0f;
+    float4 a = src.a0;
+    if (!skip) {
+      src.s.voxel(i, d, a);
+      const bool keep = src.keeps(x, y, z);
+      d = keep ? d : 0.0f;
+      a = keep_or(keep, a, src.a0);
+      kept += keep;
+    }
+    if (!kStore) {
+      ds.take(d, i, format);
+      if (with_albedo) as.take(a, i, format);
+    } else if (format) {
+      reinterpret_cast<_Float16*>(density)[i] = (_Float16)d;
+      if (with_albedo) reinterpret_cast<uint2*>(albedo)[i] = half4_bits(a);
+    } else {
+      reinterpret_cast<float*>(density)[i] = d;
+      if (with_albedo) reinterpret_cast<float4*>(albedo)[i] = a;
+    }
+  }
+  __shared__ float s_mx[4];
+  __shared__ unsigned long long s_ov[8];
+  __shared__ uint32_t s_fl[4];
+  if (!kStore) {
+    ds.commit(s_mx, s_ov, out);
+    as.commit(s_fl, s_ov + 4, out);
+  } else {
+    commit_kept(kept, out);
+  }
+}
+
 // The context's albedo grid filled with one value (CVR_DEVMED_CONST_ALBEDO, dense).
 __global__ __launch_bounds__(256) void k_fill_albedo(void* __restrict__ dst, size_t n, uint32_t format, float4 v) {
   const uint2 h = half4_bits(v);
@@ -355,7 +603,7 @@ template <class Src>
 __global__ __launch_bounds__(256) void k_leaf_flags(Src src, uint32_t nx, uint32_t ny, uint32_t nz, uint32_t lnx,
                                                     uint32_t lny, uint32_t lnz, uint32_t* __restrict__ flags,
                                                     uint32_t format, MedScan* __restrict__ scan) {
-  constexpr bool kScan = !std::is_void_v<typename Src::Scalar>;
+  constexpr bool kScan = !std::is_void_v<typename Src::Scalar>, kClip = is_clipped<Src>::value;
   src.stage();
   const uint32_t nxc = (lnx + kLeafRunLeaves - 1u) / kLeafRunLeaves;
   const size_t ntasks = (size_t)nxc * lny * lnz;
@@ -369,11 +617,27 @@ __global__ __launch_bounds__(256) void k_leaf_flags(Src src, uint32_t nx, uint32
   }
   DensityScan ds;
   AlbedoScan as(make_float4(__uint_as_float(b0), __uint_as_float(b1), __uint_as_float(b2), __uint_as_float(b3)));
+  [[maybe_unused]] uint32_t kept = 0;
+  if constexpr (kClip && kScan) {
+    // voxel 0's albedo is a0 kept or clipped, and a skipped task is not scanned: its binary16
+    // overflow, the smallest index there can be, is taken here
+    if (blockIdx.x == 0 && threadIdx.x == 0) as.take(src.a0, 0, format);
+  }
   for (size_t t = blockIdx.x; t < ntasks; t += gridDim.x) {
     const uint32_t xc = (uint32_t)(t % nxc), ly = (uint32_t)((t / nxc) % lny), lz = (uint32_t)(t / ((size_t)nxc * lny));
     const uint32_t x = xc * kLeafRunVoxels + threadIdx.x;
     uint32_t any = 0;
-    if (x < nx) {
+    bool read = x < nx;
+    if constexpr (kClip) {
+      // the task's in-grid extent, wholly clipped by its box test (the workgroup's decision): no
+      // leaf of it exists, and the field is not read
+      const uint32_t xe = xc * kLeafRunVoxels + kLeafRunVoxels - 1u;
+      const uint32_t e0[3] = {xc * kLeafRunVoxels, ly * 8u, lz * 8u};
+      const uint32_t e1[3] = {xe < nx ? xe : nx - 1u, ly * 8u + 7u < ny ? ly * 8u + 7u : ny - 1u,
+                              lz * 8u + 7u < nz ? lz * 8u + 7u : nz - 1u};
+      read = read && !clip_box_outside(src.r, e0, e1);
+    }
+    if (read) {
 #pragma unroll 8
       for (uint32_t r = 0; r < 64u; ++r) {
         const uint32_t y = ly * 8u + (r & 7u), z = lz * 8u + (r >> 3);
@@ -381,7 +645,10 @@ __global__ __launch_bounds__(256) void k_leaf_flags(Src src, uint32_t nx, uint32
           const size_t i = ((size_t)z * ny + y) * nx + x;
           float d;
           float4 a;
-          src.voxel(x, y, z, i, d, a);
+          if constexpr (kClip)
+            kept += src.voxel(x, y, z, i, d, a);
+          else
+            src.voxel(x, y, z, i, d, a);
           if (kScan) {
             ds.take(d, i, format);
             as.take(a, i, format);
@@ -401,6 +668,7 @@ __global__ __launch_bounds__(256) void k_leaf_flags(Src src, uint32_t nx, uint32
     if ((x & 7u) == 0 && lx < lnx) flags[((size_t)lz * lny + ly) * lnx + lx] = any;
   }
   if constexpr (kScan) commit_in_table_lds(ds, as, scan);
+  if constexpr (kClip) commit_kept(kept, scan);
 }
 
 // flags[leaf] = 1 iff the leaf or one of its 7 forward neighbours exists (it needs a cell leaf)
@@ -562,7 +830,19 @@ __global__ __launch_bounds__(256) void k_gather_leaves(Src src, uint32_t nx, uin
     const uint32_t leaf = slot_leaf[p >> 9], local = (uint32_t)p & 511u;
     const uint32_t lx = leaf % lnx, ly = (leaf / lnx) % lny, lz = leaf / (lnx * lny);
     const uint32_t x = lx * 8u + (local & 7u), y = ly * 8u + ((local >> 3) & 7u), z = lz * 8u + (local >> 6);
-    const bool in = x < nx && y < ny && z < nz;
+    bool in = x < nx && y < ny && z < nz;
+    if constexpr (is_clipped<Src>::value) {
+      // A wave's 64 pool voxels are one 8 x 8 slice (one z) of one leaf.  The slice's in-grid box
+      // is judged by the box test (outside the crop, or its corners on one plane's negative side:
+      // the wave's decision), and a clipped slice is written as (0, bg) unread.  bg is a0: the
+      // clipped voxel's albedo and the out-of-grid voxel's are the same 16 bytes.  (The leaf's
+      // whole box is not asked: a stored leaf has a kept voxel.)
+      if (z < nz) {
+        const uint32_t x0 = lx * 8u, y0 = ly * 8u;
+        const uint32_t e0[3] = {x0, y0, z}, e1[3] = {x0 + 7u < nx ? x0 + 7u : nx - 1u, y0 + 7u < ny ? y0 + 7u : ny - 1u, z};
+        in = in && !clip_box_outside(src.r, e0, e1);
+      }
+    }
     float d = 0.0f;
     float4 a = bg;
     if (in) src.voxel(x, y, z, ((size_t)z * ny + y) * nx + x, d, a);
@@ -622,14 +902,35 @@ void with_source(const VoxelSource& v, bool with_albedo, F f) {
     f(ScalarSrc<float>{static_cast<const float*>(v.scalar), v.table, v.tf, al, nullptr}, lds);
 }
 
+float4 clip_a0(const VoxelSource& v) { return make_float4(v.clip_a0[0], v.clip_a0[1], v.clip_a0[2], v.clip_a0[3]); }
+// The same, behind the source's clip region when it has one: f then gets a Clipped source, and
+// the launch runs the kernel's clipped instance (a source without a clip runs today's)
+template <class F>
+void with_clipped_source(const VoxelSource& v, bool with_albedo, F f) {
+  with_source(v, with_albedo, [&](auto src, size_t lds) {
+    if (v.clip)
+      f(Clipped<decltype(src)>{src, *v.clip, clip_a0(v)}, lds);
+    else
+      f(src, lds);
+  });
+}
+LinearGrid linear_grid(const uint32_t res[3]) { return {res[0], res[1], make_fastdiv(res[0]), make_fastdiv(res[1])}; }
+
 template <bool kStore>
 hipError_t launch_classified(const VoxelSource& v, size_t n, uint32_t format, void* density, void* albedo,
                              MedScan* out, hipStream_t s) {
   if (!v.scalar) return hipErrorInvalidValue;
-  with_source(v, true, [&](auto src, size_t lds) {
+  with_clipped_source(v, true, [&](auto src, size_t lds) {
     using Src = decltype(src);
     using T = typename Src::Scalar;
-    if constexpr (std::is_same_v<Src, ScalarSrc<T>>) {
+    if constexpr (std::is_same_v<Src, Clipped<ScalarSrc<T>>>) {
+      hipLaunchKernelGGL((k_classified_clip<T, kStore>), dim3(scan_grid(n)), dim3(256), lds, s, src, n,
+                         linear_grid(v.res), format, density, albedo, out);
+    } else if constexpr (is_clipped<Src>::value && !std::is_void_v<T>) {
+      const uint32_t grid = (uint32_t)std::min<size_t>(gradient_walk_tasks(v.res[0], v.res[1], v.res[2]), kWalkTaskCap);
+      hipLaunchKernelGGL((k_gradient_clip<T, kStore>), dim3(grid >= 8u ? grid & ~7u : grid), dim3(256), lds, s,
+                         src, format, density, albedo, out);
+    } else if constexpr (std::is_same_v<Src, ScalarSrc<T>>) {
       hipLaunchKernelGGL((k_classified<T, kStore>), dim3(scan_grid(n)), dim3(256), lds, s, src, n, format, density,
                          albedo, out);
     } else if constexpr (!std::is_void_v<T>) {
@@ -666,14 +967,34 @@ hipError_t launch_scan_classified(const VoxelSource& src, size_t n, uint32_t for
 }
 
 hipError_t launch_store_classified(const VoxelSource& src, size_t n, uint32_t format, void* density, void* albedo,
-                                   hipStream_t s) {
-  return launch_classified<true>(src, n, format, density, albedo, nullptr, s);
+                                   MedScan* scan, hipStream_t s) {
+  return launch_classified<true>(src, n, format, density, albedo, scan, s);
+}
+
+hipError_t launch_scan_clipped(const VoxelSource& v, const uint32_t res[3], uint32_t format, MedScan* out,
+                               hipStream_t s) {
+  if (!v.clip || v.scalar) return hipErrorInvalidValue;
+  const size_t n = (size_t)res[0] * res[1] * res[2];
+  const Clipped<ArraySrc> src{{v.density, reinterpret_cast<const float4*>(v.albedo)}, *v.clip, clip_a0(v)};
+  hipLaunchKernelGGL(k_arrays_clip<false>, dim3(scan_grid(n)), dim3(256), 0, s, src, n, linear_grid(res), format,
+                     nullptr, nullptr, out);
+  return hipGetLastError();
+}
+
+hipError_t launch_store_clipped(const VoxelSource& v, const uint32_t res[3], uint32_t format, void* density,
+                                void* albedo, MedScan* scan, hipStream_t s) {
+  if (!v.clip || v.scalar) return hipErrorInvalidValue;
+  const size_t n = (size_t)res[0] * res[1] * res[2];
+  const Clipped<ArraySrc> src{{v.density, reinterpret_cast<const float4*>(v.albedo)}, *v.clip, clip_a0(v)};
+  hipLaunchKernelGGL(k_arrays_clip<true>, dim3(stream_grid(n)), dim3(256), 0, s, src, n, linear_grid(res), format,
+                     density, albedo, scan);
+  return hipGetLastError();
 }
 
 hipError_t launch_leaf_flags(const VoxelSource& v, bool with_albedo, const uint32_t res[3], const uint32_t ln[3],
                              uint32_t* flags, uint32_t format, MedScan* scan, hipStream_t s) {
   const size_t ntasks = (size_t)((ln[0] + kLeafRunLeaves - 1u) / kLeafRunLeaves) * ln[1] * ln[2];
-  with_source(v, with_albedo, [&](auto src, size_t lds) {
+  with_clipped_source(v, with_albedo, [&](auto src, size_t lds) {
     hipLaunchKernelGGL(k_leaf_flags<decltype(src)>, dim3((uint32_t)std::min<size_t>(ntasks, kLeafFlagsGridCap)),
                        dim3(256), lds, s, src, res[0], res[1], res[2], ln[0], ln[1], ln[2], flags, format, scan);
   });
@@ -716,7 +1037,7 @@ hipError_t launch_gather_leaves(const VoxelSource& v, bool with_albedo, const ui
   const size_t np = n_leaves * 512;
   if (np == 0) return hipSuccess;
   const float4 b = make_float4(bg[0], bg[1], bg[2], bg[3]);
-  with_source(v, with_albedo, [&](auto src, size_t lds) {
+  with_clipped_source(v, with_albedo, [&](auto src, size_t lds) {
     using Src = decltype(src);
     if (check)
       hipLaunchKernelGGL((k_gather_leaves<Src, false>), dim3(stream_grid(np)), dim3(256), lds, s, src, res[0], res[1],

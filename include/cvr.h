@@ -46,6 +46,8 @@ extern "C" {
  *              6 + CVR_HAS_FIELD_HISTOGRAM (likewise): cvr_field_desc, cvr_field_stats, cvr_histogram_desc,
  *                  cvr_field_stats_host, cvr_field_histogram_host, cvr_field_stats, cvr_field_histogram,
  *                  cvr_field_histogram_buffers, cvr_debug_field_geometry
+ *              6 + CVR_HAS_CLIP (likewise): cvr_clip_desc, cvr_set_clip, cvr_clear_clip, cvr_get_clip,
+ *                  cvr_clip_host, cvr_medium_clip_info
  * CVR_ABI_VERSION is the ABI this header declares: 6, the library's (cvr_abi_version()).  ABI 6 only
  * adds to ABI 5, so a host that must also load an ABI 5 library can hold itself to that surface:
  * with CVR_ABI_TARGET defined as 5 before the include, the ABI 6 functions and structs are not
@@ -890,7 +892,7 @@ int cvr_set_medium_scene_transfer(cvr_ctx* ctx, const cvr_scene* scene, const cv
  *   (each one subtract, one multiply, one add, in that order);
  *   albedo = (e_r, e_g, e_b, 1.0f), density = e's density.
  * There is no CEIL and no DENSITY_U mode in 2-D: flags must be 0.
- * Not supported: clip planes and crop boxes, gradient-based shading, classification at render
+ * Not supported: gradient-based shading, classification at render
  * time (the medium is classified once, when it is built), keeping the field. */
 #define CVR_HAS_GRADIENT_TRANSFER 1
 typedef struct cvr_gradient_transfer_desc {
@@ -950,6 +952,78 @@ int cvr_set_medium_gradient(cvr_ctx* ctx, const cvr_gradient_medium_desc* medium
  * the descriptor's.  flags: CVR_DEVMED_SPARSE or 0.  A scene without raw bytes: CVR_ERR_INVALID. */
 int cvr_set_medium_scene_gradient(cvr_ctx* ctx, const cvr_scene* scene, const cvr_gradient_transfer_desc* transfer,
                                   uint32_t flags);
+
+/* ---- crop box and clip planes for media built from device memory (extension within ABI 6:
+ *      CVR_HAS_CLIP) -- */
+/* A clip region cuts the volume open where the voxel is classified: the three device builds
+ * (cvr_set_medium_device, cvr_set_medium_scalar, cvr_set_medium_gradient and their _scene_ forms)
+ * store a voxel outside the region as empty.  Every operation is an integer comparison or fp32 +,
+ * x and a comparison in the order written here, no fused multiply-add, so the build kernels and
+ * cvr_clip_host decide the same voxels (one definition compiles for both, cvr_clip.h).  For voxel
+ * (x, y, z) of a grid of res voxels:
+ *   crop:   lo[a] <= c_a < min(hi[a], res[a]) on each axis a, in integer voxel indices; hi above
+ *           res is allowed and means "to the end";
+ *   planes: for plane k < n_planes with planes[k] = (A, B, C, D), coefficients in voxel-index space,
+ *           t = ((A * (float)x + B * (float)y) + C * (float)z) + D, each product rounded, summed
+ *           in that order; the plane keeps the voxel iff t >= 0 (a tie is kept, a NaN t is not);
+ *   kept:   iff the crop keeps the voxel and every plane keeps it.
+ * A clipped voxel's density is +0.0f and its albedo is the 16 bytes of the unclipped source's voxel
+ * (0, 0, 0); the same holds for voxel 0 itself.  That is the value the leaf rule compares against
+ * and the sparse background, so a leaf whose in-grid voxels are all clipped does not exist, and a
+ * dense grid clipped to one colour region is still detected as uniform.  Colour within one cell
+ * of the cut interpolates toward that background, exactly as it already does at the border of a
+ * leaf that does not exist.  A kept voxel is exactly what the unclipped call stores; for
+ * cvr_set_medium_gradient its gradient neighbours are read from the field whether they are
+ * clipped or not: the gradient is the uncut field's, and a cut surface is no material boundary.
+ *
+ * Contract: with a clip set, a device build leaves the context in the state that
+ * cvr_set_medium_device with no clip leaves on device copies of cvr_clip_host's output (for the
+ * classified routes: cvr_clip_host applied to cvr_classify_host's / cvr_classify_gradient_host's
+ * arrays): equal cvr_medium_info and cvr_medium_layout, every stored array equal byte for byte,
+ * the same paths bit for bit, dense and sparse, in both formats.  Everything derived from values
+ * is derived from the clipped values: the CVR_DEVMED_MAX_DENSITY majorant, the binary16 overflow
+ * refusal with its code, message and index, uniform-albedo detection, the leaf rule, dropping the
+ * leaf albedo pool.  A given max_density is used as given.  An all-clipped grid behaves as the
+ * call behaves on an all-zero density.  A context that sets no clip runs what it ran before.
+ *
+ * The clip is context state, taken at the next device build as CVR_OPT_CELLS is taken; the medium
+ * already built is not touched.  cvr_set_clip refuses with CVR_ERR_INVALID, in this order:
+ *   1. a NULL descriptor;
+ *   2. flags not 0;
+ *   3. n_planes > CVR_CLIP_MAX_PLANES;
+ *   4. lo[a] > hi[a] on some axis (lo == hi is an empty crop: everything is clipped);
+ *   5. a coefficient of a plane k < n_planes that is not finite;
+ *   6. a plane k < n_planes whose A, B and C are all zero.
+ * Inside an adaptive session cvr_set_clip and cvr_clear_clip return CVR_ERR_STATE.
+ * With a clip set the host uploads cvr_set_medium and cvr_set_medium_sparse return
+ * CVR_ERR_UNSUPPORTED and keep the previous medium; cvr_share_medium shares whatever the source
+ * built, with its clip information.
+ * Not supported: cuts at ray level (sub-voxel smooth cut surfaces), per-voxel mask or label
+ * volumes, clipping of cvr_features, cvr_field_stats or cvr_field_histogram (they still see the
+ * whole field), the host uploads, inverted or unioned regions. */
+#define CVR_HAS_CLIP 1
+#define CVR_CLIP_MAX_PLANES 8
+typedef struct cvr_clip_desc {
+  uint32_t lo[3], hi[3]; /* the crop box in voxel indices, lo <= c < hi; (0,0,0) and UINT32_MAX: no crop */
+  uint32_t n_planes;     /* 0..CVR_CLIP_MAX_PLANES */
+  uint32_t flags;        /* 0 */
+  float planes[CVR_CLIP_MAX_PLANES][4]; /* A, B, C, D; the entries from n_planes on are ignored */
+} cvr_clip_desc; /* 160 bytes */
+int cvr_set_clip(cvr_ctx* ctx, const cvr_clip_desc* clip);
+int cvr_clear_clip(cvr_ctx* ctx);
+/* The context's clip (*set 1) or, with none set, the descriptor that keeps everything (*set 0).
+ * Either pointer may be NULL. */
+int cvr_get_clip(const cvr_ctx* ctx, cvr_clip_desc* clip, int* set);
+/* Host only, no GPU: the statement above, in place, on host arrays of a grid of res voxels (x
+ * fastest).  density (one float per voxel), albedo (4 floats per voxel) and keep (one byte per
+ * voxel: 1 kept, 0 clipped) may each be NULL.  The descriptor is checked as cvr_set_clip checks
+ * it; an empty grid or more than 2^32 - 1 voxels: CVR_ERR_INVALID. */
+int cvr_clip_host(const uint32_t res[3], const cvr_clip_desc* clip, float* density, float* albedo, uint8_t* keep);
+/* The clip the current medium (own or shared) was built under and the number of voxels it keeps,
+ * counted on the device in the build's own store or leaf-flag pass.  A medium built without a
+ * clip: the descriptor that keeps everything and the grid's voxel count.  Either pointer may be
+ * NULL.  CVR_ERR_STATE: no medium. */
+int cvr_medium_clip_info(const cvr_ctx* ctx, cvr_clip_desc* clip, uint64_t* kept);
 
 /* ---- field statistics and value-gradient histograms (extension within ABI 6:
  *      CVR_HAS_FIELD_HISTOGRAM) -- */
