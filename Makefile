@@ -28,7 +28,7 @@ HDRS := include/cvr.h include/cvr_detmath.h $(wildcard $(CSRC)/*.h)
 HIPFLAGS_cvr_wpool := -fno-slp-vectorize
 hipflags = $(HIPFLAGS) $(HIPFLAGS_$(basename $(notdir $(1)))) $(DEFS)
 
-all: $(PKG)/libcvr.so $(PKG)/cvr build/launcher_order build/wpool_select build/wpool_select_env oracle
+all: $(PKG)/libcvr.so $(PKG)/cvr build/launcher_order build/wpool_select build/wpool_select_env build/regen_plan oracle
 
 $(OBJDIR)/%.o: $(CSRC)/%.hip $(HDRS)
 	@mkdir -p $(OBJDIR)
@@ -60,6 +60,19 @@ build/wpool_select: tests/cpp/wpool_select.cpp $(CSRC)/cvr_wpool_select.h
 build/wpool_select_env: tests/cpp/wpool_select_env.cpp $(CSRC)/cvr_wpool_select.h
 	@mkdir -p build
 	g++ -O2 -std=c++17 -Wall -Wextra -I$(CSRC) -o $@ $<
+
+# Host-only C++ test: the regeneration burst's bookkeeping against a unit-by-unit model
+# (tests/test_regen_plan.py); no HIP.
+build/regen_plan: tests/cpp/regen_plan.cpp $(CSRC)/cvr_regen_plan.h
+	@mkdir -p build
+	g++ -O2 -std=c++17 -Wall -Wextra -I$(CSRC) -o $@ $<
+# The same program under AddressSanitizer and UBSan, run once (a CPU run)
+regen-plan-asan: tests/cpp/regen_plan.cpp $(CSRC)/cvr_regen_plan.h
+	@mkdir -p build/asan
+	g++ -O1 -g -std=c++17 -Wall -Wextra -I$(CSRC) -fsanitize=address,undefined -fno-sanitize-recover=undefined \
+	    -o build/asan/regen_plan $<
+	build/asan/regen_plan
+.PHONY: regen-plan-asan
 
 oracle:
 	$(MAKE) -C oracle

@@ -19,14 +19,19 @@
 //   * EVENT: once 64 events are waiting, the tracking lanes park (t, rng) in
 //     their slots and the wave handles 64 events at once, boundary events
 //     first, then collisions, so each part runs one kind of event code on a
-//     full wave; roulette, regeneration and the AABB test follow, and each
-//     path goes back to the track-ready ring or the boundary list.
+//     full wave; roulette and the AABB test follow, and each path goes back
+//     to the track-ready ring or the boundary list.  New camera paths are made
+//     in a phase of their own at the start of the section, in bursts across
+//     the whole wave (the regeneration phase, below); the instances with
+//     naiveMK's walk, in-launch output, moments or an environment make them
+//     inside the batch instead, as its third part.
 // The pool is private to the wave and the wave runs in lockstep, so the lists
 // need no atomics and no barriers: their counters are wave-uniform scalars.
 #include <hip/hip_runtime.h>
 
 #include "cvr_env.h"
 #include "cvr_kernels.h"
+#include "cvr_regen_plan.h"
 #include "cvr_walk.h"
 
 // Woodcock steps per track iteration between swap/event checks.
@@ -64,6 +69,28 @@
 // end, with its live paths and event batches after that point.
 #ifndef CVR_WPOOL_TAILSTAMP
 #define CVR_WPOOL_TAILSTAMP 0
+#endif
+// The regeneration phase (EVENT, below): camera paths are made in bursts across the whole wave
+// before the batch's items are chosen, in the instances without naiveMK's walk, in-launch
+// output, second moments or an environment.  0 (experiment builds): every instance regenerates
+// inside the batch, as those four kinds do.
+#ifndef CVR_WPOOL_REGEN_PHASE
+#define CVR_WPOOL_REGEN_PHASE 1
+#endif
+// Units a burst makes per free slot (regen_width): more than one, because some paths miss the box.
+#ifndef CVR_WPOOL_REGEN_OVER
+#define CVR_WPOOL_REGEN_OVER 2
+#endif
+// Free slots that start a phase: with fewer (and something to track) the wave waits, and the event
+// trigger does not count them, so that a burst runs on most of the wave's lanes instead of a few
+// in every batch (profiles/round8/README.md).
+#ifndef CVR_WPOOL_REGEN_MIN
+#define CVR_WPOOL_REGEN_MIN 32
+#endif
+// Diagnostic build (make variant NAME=rstat DEFS=-DCVR_WPOOL_REGENSTAT=1, tools/regen_stats.py):
+// per launch, the batches, their parts, the regeneration runs and the camera paths that missed.
+#ifndef CVR_WPOOL_REGENSTAT
+#define CVR_WPOOL_REGENSTAT 0
 #endif
 constexpr int kLook = CVR_WPOOL_LOOK;
 // The track loop runs CVR_WPOOL_UNROLL / kLook groups: a variant build with
@@ -322,7 +349,77 @@ __device__ __forceinline__ void record_end(const LaunchParams& L, uint32_t gw, u
   static_cast<PathRecord*>(L.rec)[pid - L.path_first] = r;
 }
 
+// The same for a camera path that missed the box in the regeneration phase: it never had a slot,
+// so its record goes by its path id.
+__device__ __forceinline__ void record_miss(const LaunchParams& L, uint32_t pid, const PathState& ps) {
+  PathRecord r = {};
+  r.image_id = ps.image_id;
+  r.flags = 1u;
+  r.T[0] = ps.T.x;
+  r.T[1] = ps.T.y;
+  r.T[2] = ps.T.z;
+  r.n_segments = 1u;
+  static_cast<PathRecord*>(L.rec)[pid - L.path_first] = r;
+}
 
+// splat_wave for the regeneration phase's misses.  A miss has no freed slot to sum in: the
+// leader of pixel number j (in lane order) borrows free-stack entry n_free - 1 - j, a slot
+// that holds no path (the burst's accepted hits are stored after this, by the same wave, and
+// LDS operations of one wave are performed in order).  Pixels beyond the n_free-th splat per lane.
+template <class Pool>
+__device__ __forceinline__ void splat_misses(Pool& S, const LaunchParams& L, const PathState& ps, bool esc,
+                                             uint32_t n_free, uint32_t lane) {
+#if defined(CVR_DIAG_NO_SPLAT)
+  (void)S; (void)L; (void)ps; (void)esc; (void)n_free; (void)lane;
+  return;
+#endif
+  unsigned long long rest = __ballot(esc);
+  if (rest == 0ull) return;
+  if (!(fresh(L).wflags & kSplatCombine)) {
+    if (esc) splat(L, ps);
+    return;
+  }
+  uint32_t leader = lane;
+  bool multi = false;  // wave-uniform: some pixel gets two or more misses
+  while (rest != 0ull) {
+    const uint32_t l0 = (uint32_t)__builtin_ctzll(rest);
+    const uint32_t id0 = __builtin_amdgcn_readlane(ps.image_id, l0);
+    const unsigned long long g = __ballot(esc && ps.image_id == id0);
+    if (esc && ps.image_id == id0) leader = l0;
+    multi |= (g & (g - 1ull)) != 0ull;
+    rest &= ~g;
+  }
+  if (!multi) {
+    if (esc) splat(L, ps);
+    return;
+  }
+  const bool lead = esc && leader == lane;
+  const uint32_t lr = lane_rank(__ballot(lead));
+  uint32_t sl = 0xFFFFFFFFu;  // the borrowed slot, none for the pixels beyond the free slots
+  if (lead && lr < n_free) sl = S.ln[n_free - 1u - lr];
+  sl = (uint32_t)__shfl((int)sl, (int)leader);
+  const bool comb = esc && sl != 0xFFFFFFFFu;
+  if (esc && !comb) splat(L, ps);
+  float* acc = reinterpret_cast<float*>(&S.a[comb ? sl : 0u]);
+  if (comb && lead) {
+    acc[0] = ps.T.x;
+    acc[1] = ps.T.y;
+    acc[2] = ps.T.z;
+  }
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  if (comb && !lead) {
+    __hip_atomic_fetch_add(acc + 0, ps.T.x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    __hip_atomic_fetch_add(acc + 1, ps.T.y, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    __hip_atomic_fetch_add(acc + 2, ps.T.z, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+  }
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  if (comb && lead) {
+    PathState q{};
+    q.image_id = ps.image_id;
+    q.T = mk3(acc[0], acc[1], acc[2]);
+    splat(L, q);
+  }
+}
 
 // ---- in-launch output (cvr_render_frame) -----------------------------------
 // getImage (CudaVolPath.cpp:339-347, ImageBufferTransfer.cu:61-78: Scale, then
@@ -495,6 +592,10 @@ __device__ void frame_flusher(const LaunchParams& L, uint32_t f, uint32_t lane) 
 constexpr uint32_t kTailWaves = 16384;
 __device__ unsigned long long g_tail[8 * kTailWaves];
 #endif
+#if CVR_WPOOL_REGENSTAT
+constexpr int kRegenStats = 12;
+__device__ unsigned long long g_regen[kRegenStats];
+#endif
 // kMedMoments: moments[i] = L.out[L.tile_px + i], a fixed offset, so that every other instance keeps its
 // kernel-argument layout, its LDS copy of the launch parameters and its pool slot count (PoolSize: sizeof).
 static_assert(sizeof(LaunchParams) == 256 && sizeof(MediumParams) == 256,
@@ -540,6 +641,8 @@ __global__ __launch_bounds__(64 * wpg_of(kMedMk, kWaves), kWaves) void k_wpool(M
   constexpr bool kMoments = (kMedMk & kMedMoments) != 0;
   constexpr bool kEnv = (kMedMk & kMedEnv) != 0;
   constexpr int kMed = kMedMk & 3;
+  // camera paths come from the regeneration phase (EVENT); the other instances make them in the batch
+  constexpr bool kBurst = CVR_WPOOL_REGEN_PHASE && !kMK && !kFlush && !kMoments && !kEnv;
   static_assert(!kEnv || (kWaves == kWpoolWaves && !kMK && !kRecord && !kFlush && !kCountWords),
                 "environment: the default budget, no naiveMK walk, records, in-launch output or word counts");
   static_assert(!kMoments || (!kMK && !kRecord && !kFlush && !kCountWords && !(kMedMk & kMedHalf)),
@@ -630,6 +733,12 @@ __global__ __launch_bounds__(64 * wpg_of(kMedMk, kWaves), kWaves) void k_wpool(M
     S.dead = 0ull;
     S.pend = 0u;
   }
+#if CVR_WPOOL_REGENSTAT
+  // 0 batches, 1 regeneration runs (batches with new items / bursts), 2-4 sums of tb, tc, tn (phase:
+  // accepted hits), 5 camera paths that missed, 6 sum of n_ln at the trigger over the 7 batches
+  // entered before exhaustion, 8 sum of burst widths, 9 units made and taken back, 10 phases
+  uint32_t rs[kRegenStats] = {};
+#endif
   uint32_t n_over = 0;  // wave-uniform: segments whose last Woodcock step passed max_t
   // home queue: the XCD's band, and within it sub-queue (the wave's number among
   // its XCD's waves) mod sub (workgroups are dealt round-robin over the 8 XCDs)
@@ -643,6 +752,9 @@ __global__ __launch_bounds__(64 * wpg_of(kMedMk, kWaves), kWaves) void k_wpool(M
   // wave-uniform list state
   uint32_t ready_head = 0, n_ready = 0, n_lb = 0, n_lc = 0;
   uint32_t n_ln = kSlots;  // slots waiting for a new path (all of them at the start)
+  // kBurst: what the event trigger counts of n_ln: all of it once a phase will run on it
+  // (n_ln >= CVR_WPOOL_REGEN_MIN) and as the drain's stand-in, else nothing
+  uint32_t n_lt = kSlots;
   for (uint32_t i = lane; i < (uint32_t)kSlots; i += 64u) S.ln[i] = (uint8_t)i;
 
   for (;;) {
@@ -701,7 +813,7 @@ __global__ __launch_bounds__(64 * wpg_of(kMedMk, kWaves), kWaves) void k_wpool(M
       // nothing left to track.  Park: tracking lanes return (t, rng) to the
       // pool, finished lanes are filed.  (Once the queues are empty n_ln is a
       // stand-in that lowers this threshold: see the end of the event batch.)
-      if (n_lb + n_lc + n_ln + n_fin >= 64u || (n_act == 0u && n_ready == 0u)) {
+      if (n_lb + n_lc + (kBurst ? n_lt : n_ln) + n_fin >= 64u || (n_act == 0u && n_ready == 0u)) {
         if (fst == 2 && !(t < max_t)) fst = 3;
         if (slot >= 0) store_track(S, (uint32_t)slot, t, rng);
         const unsigned long long mr = (__ballot(slot >= 0) & __ballot(fst == 0));
@@ -855,7 +967,144 @@ __global__ __launch_bounds__(64 * wpg_of(kMedMk, kWaves), kWaves) void k_wpool(M
     me.albedo_bg = mk3(opaque_s(m.albedo_bg.x), opaque_s(m.albedo_bg.y), opaque_s(m.albedo_bg.z));
     if constexpr (kMed == kMedDense)  // a run-time flag only in the generic instance
       me.albedo_uniform = __float_as_uint(opaque_s(__uint_as_float(m.albedo_uniform)));
-    // One batch of up to 64 items, [boundary | collision | new].  New items
+#if CVR_WPOOL_REGENSTAT
+    if (!(S.cur[2] & kCurExhausted)) {
+      rs[6] += n_ln;
+      ++rs[7];
+    }
+#endif
+    // ---- regeneration phase (kBurst instances) ------------------------------
+    // Camera paths are made here, before the batch's items are chosen, in bursts
+    // across the whole wave: the next W consecutive units of the wave's chunk,
+    // one per lane (regen_width: CVR_WPOOL_REGEN_OVER per free slot, since some
+    // miss).  A path that hits the box takes a free slot (store_full) and goes
+    // to the ready ring (it starts inside) or to the boundary list with its
+    // entry distance, from where the batch below pops it in this same section.
+    // A path that misses ends here: counted, recorded, splatted, with no slot,
+    // no item lane of the batch and no later batch.  When more paths hit than
+    // slots are free, the burst commits the units before the first hit without
+    // a slot and the cursor goes back to that unit (regen_plan,
+    // cvr_regen_plan.h): the lanes from there on have stored nothing, and a
+    // later burst makes their paths again, the same paths (the RNG is bound to
+    // the path id).  One phase runs one burst, and a second only when the end
+    // of the chunk cut the first short.  Scheduling only: the same path ids,
+    // each made once, so counters and records are unchanged and pixels are
+    // summed in another order.
+    //
+    // Termination.  Every pass of the outer loop steps a lane, runs an event,
+    // commits a unit or marks the queues exhausted.  EVENT is entered with
+    // n_lb + n_lc + n_ln + n_fin >= 64 or with nothing to track, and not with
+    // every list empty and (n_ln == 0 or exhausted) (the break above).  The
+    // trigger counts of n_ln what n_lt says: all of it when a phase will run
+    // on it (n_ln >= CVR_WPOOL_REGEN_MIN) or as the drain's stand-in, else 0.
+    // With nothing to track, n_ready is 0 here (no lane was parked), so either
+    // an event waits and the batch runs it, or n_ln >= 1 and the queues are
+    // not exhausted, and the phase runs whatever the minimum says: its dequeue
+    // marks them exhausted, or the burst has W >= 1 and commits its first unit
+    // (a miss needs no slot; a first hit has rank 0 < n_ln).  With the trigger's
+    // sum at 64: either n_lt is 0 or the stand-in, and at least one event waits
+    // (the stand-in is below 64 while a path lives), or n_lt = n_ln >= the
+    // minimum and the phase runs as above.  A pass that entered TRACK with a
+    // tracking lane stepped it.  There are no waits on another wave.  After
+    // exhaustion n_ln is the drain rule's stand-in (end of this section) and
+    // names no slot: the phase clears it, so the batch's ended paths are filed
+    // from entry 0 of the free stack, whose entries are never read again.
+    if constexpr (kBurst) {
+      uint32_t cqh = __builtin_amdgcn_readfirstlane(S.cur[2]);
+      if (cqh & kCurExhausted) {
+        n_ln = 0u;
+      } else if (n_ln >= (uint32_t)CVR_WPOOL_REGEN_MIN || (n_ln != 0u && n_ready == 0u)) {
+        uint32_t cnext = __builtin_amdgcn_readfirstlane(S.cur[0]), cend = __builtin_amdgcn_readfirstlane(S.cur[1]);
+        float4* __restrict__ gTn = L.pool_T + (size_t)(kWpg > 1 ? gw : blockIdx.x) * kSlots;
+#if CVR_WPOOL_REGENSTAT
+        ++rs[10];
+#endif
+#pragma nounroll
+        for (uint32_t pass = 0; pass < 2u; ++pass) {
+          if (cnext == cend) {
+            // (the dequeue of the in-batch regeneration below)
+            uint32_t b = 0xFFFFFFFFu, qsel = 0;
+            if (lane == 0) {
+              unsigned long long dead = S.dead;
+              for (uint32_t k = 0; k < L.n_queues; ++k) {
+                const uint32_t q = ((cqh >> 8) + k) % L.n_queues;
+                if ((dead >> q) & 1ull) continue;
+                const uint32_t g = atomicAdd(L.queue + 16 * q, L.chunk);
+                if (g < queue_units(L, q)) {
+                  b = g;
+                  qsel = q;
+                  break;
+                }
+                dead |= 1ull << q;
+              }
+              S.dead = dead;
+            }
+            b = __shfl(b, 0);
+            qsel = __shfl(qsel, 0);
+            if (b == 0xFFFFFFFFu) {
+              cqh |= kCurExhausted;
+              break;
+            }
+            cqh = qsel | qsel << 8;
+            cnext = b;
+            cend = min(b + L.chunk, queue_units(L, qsel));
+          }
+          const uint32_t W = regen_width(n_ln, cend - cnext, (uint32_t)CVR_WPOOL_REGEN_OVER);
+          const bool cut = W < regen_width(n_ln, kRegenLanes, (uint32_t)CVR_WPOOL_REGEN_OVER);  // by the chunk's end
+          PathState ps{};
+          Isect is{};
+          uint32_t pid = 0;
+          bool hit = false;
+          if (lane < W) {
+            pid = unit_to_path(L, cqh & 0xFFu, cnext + lane);
+            path_begin(L, pid, ps);
+            // first segment: AABB test (NaiveVolPTsk_kernel.cuh:33-47)
+            hit = aabb_intersect(me, ps.o, ps.d, is);
+          }
+          const unsigned long long hits = __ballot(hit);
+          const RegenBurst B = regen_plan(hits, W, n_ln);
+          const bool acc = hit && lane < B.committed, miss = !hit && lane < B.committed;
+          // the misses first: their sums borrow free slots that the accepted hits then fill
+          if (kRecord && miss) record_miss(L, pid, ps);
+          splat_misses(S, L, ps, miss, n_ln, lane);
+          asm volatile("" ::: "memory");  // (the leaders' reads of their sums stay above the stores below)
+          uint32_t s = 0;
+          if (acc) {
+            s = S.ln[n_ln - 1u - lane_rank(hits)];
+            store_full(S, gTn, s, ps, is, 1u, ps.image_id);
+            if (kRecord) rec_pids<kSlots, kWpg>(L, gw)[s] = pid;
+          }
+          const unsigned long long mi = __ballot(acc && is.inside), mo = __ballot(acc && !is.inside);
+          if (acc && is.inside) S.ready[(ready_head + n_ready + lane_rank(mi)) % kSlots] = (uint8_t)s;
+          if (acc && !is.inside) S.lb[n_lb + lane_rank(mo)] = (uint8_t)s;
+          n_ready += (uint32_t)__popcll(mi);
+          n_lb += (uint32_t)__popcll(mo);
+          n_ln -= B.accepted;
+          cnext += B.committed;
+          if (lane == 0) {
+            S.cnt[STAT_PATHS] += B.committed;
+            S.cnt[STAT_SEGMENTS] += B.committed;
+            S.cnt[STAT_ESCAPED] += B.committed - B.accepted;
+          }
+#if CVR_WPOOL_REGENSTAT
+          ++rs[1];
+          rs[4] += B.accepted;
+          rs[5] += B.committed - B.accepted;
+          rs[8] += W;
+          rs[9] += W - B.committed;
+#endif
+          if (!cut || n_ln == 0u) break;
+        }
+        if (lane == 0) {
+          S.cur[0] = cnext;
+          S.cur[1] = cend;
+          S.cur[2] = cqh;
+        }
+      }
+    }
+    // One batch of up to 64 items, [boundary | collision | new] ([boundary |
+    // collision] after a regeneration phase, which has filed its paths' box
+    // entries in the boundary list).  Without the phase, new items
     // are regenerated first: a camera path's first segment is an AABB test
     // and, when it hits the box from outside, a boundary event, which then
     // runs in this batch's boundary part together with the filed boundary
@@ -879,20 +1128,35 @@ __global__ __launch_bounds__(64 * wpg_of(kMedMk, kWaves), kWaves) void k_wpool(M
 #ifndef CVR_WPOOL_KIND_MIN_C
 #define CVR_WPOOL_KIND_MIN_C 24
 #endif
+// With the regeneration phase a burst's entries arrive in the boundary list together, and a
+// collision batch that leaves them waiting should be fuller: 32 (profiles/round8/README.md: with
+// the phase C2 +0.6 % over 24; without the phase 32 is worth nothing, so the others keep 24).
+#ifndef CVR_WPOOL_KIND_MIN_C_PHASE
+#define CVR_WPOOL_KIND_MIN_C_PHASE 32
+#endif
+      constexpr uint32_t kKindMinC = kBurst ? CVR_WPOOL_KIND_MIN_C_PHASE : CVR_WPOOL_KIND_MIN_C;
+      // (kBurst: the phase above has made the new paths; the batch is [boundary | collision])
+      const uint32_t n_new = kBurst ? 0u : n_ln;
       uint32_t tb, tc, tn;
       if (n_lb >= (uint32_t)CVR_WPOOL_KIND_MIN) {
         tb = min(n_lb, 64u);
         tc = 0;
-        tn = min(n_ln, 64u - tb);
-      } else if (n_lc >= (uint32_t)CVR_WPOOL_KIND_MIN_C) {
+        tn = min(n_new, 64u - tb);
+      } else if (n_lc >= kKindMinC) {
         tb = 0;
         tc = min(n_lc, 64u);
-        tn = n_ln < 64u ? 0u : min(n_ln, 64u - tc);
+        tn = n_new < 64u ? 0u : min(n_new, 64u - tc);
       } else {
         tb = min(n_lb, 64u);
         tc = min(n_lc, 64u - tb);
-        tn = min(n_ln, 64u - tb - tc);
+        tn = min(n_new, 64u - tb - tc);
       }
+#if CVR_WPOOL_REGENSTAT
+      ++rs[0];
+      rs[2] += tb;
+      rs[3] += tc;
+      if (!kBurst) rs[4] += tn;
+#endif
       uint32_t kind = K_NONE, s = 0;
       if (lane < tb) {
         kind = K_BOUNDARY;
@@ -918,8 +1182,11 @@ __global__ __launch_bounds__(64 * wpg_of(kMedMk, kWaves), kWaves) void k_wpool(M
       bool alive = false;
       bool truncated = false, escaped = false, seg_first = false, seg_next = false;  // counted by ballots
       // ---- regeneration (new items): the wave's cursor into the global queues
-      const unsigned long long want = __ballot(kind == K_NEW);
+      const unsigned long long want = kBurst ? 0ull : __ballot(kind == K_NEW);
       if (want != 0ull) {
+#if CVR_WPOOL_REGENSTAT
+        ++rs[1];
+#endif
         const uint32_t rank = lane_rank(want);
         bool got = false;
         uint32_t given = 0;  // new items [0, given) get a path
@@ -1097,6 +1364,9 @@ __global__ __launch_bounds__(64 * wpg_of(kMedMk, kWaves), kWaves) void k_wpool(M
       // the reference's per-iteration RAYS_STATISTICS count)
       {
         const uint32_t n_seg = (uint32_t)(__popcll(__ballot(seg_first)) + __popcll(__ballot(seg_next)));
+#if CVR_WPOOL_REGENSTAT
+        rs[5] += (uint32_t)__popcll(__ballot(seg_first && escaped));
+#endif
         const uint32_t n_esc = (uint32_t)__popcll(__ballot(escaped)), n_tr = (uint32_t)__popcll(__ballot(truncated));
         if (lane == 0) {
           S.cnt[STAT_SEGMENTS] += n_seg;
@@ -1149,6 +1419,9 @@ __global__ __launch_bounds__(64 * wpg_of(kMedMk, kWaves), kWaves) void k_wpool(M
         const uint32_t d = fresh(L).wflags & kDrainMask;
         n_ln = d ? 64u - min(64u, (n_live * d + d) / (d + 1u)) : 0u;
       }
+      if constexpr (kBurst) n_lt = n_ln;
+    } else if constexpr (kBurst) {
+      n_lt = n_ln >= (uint32_t)CVR_WPOOL_REGEN_MIN ? n_ln : 0u;
     }
   }
 
@@ -1179,6 +1452,13 @@ __global__ __launch_bounds__(64 * wpg_of(kMedMk, kWaves), kWaves) void k_wpool(M
       if (lane == 0) add_counted(L, agg);
     }
   }
+#if CVR_WPOOL_REGENSTAT
+  if (lane == 0) {
+#pragma unroll
+    for (int k = 0; k < kRegenStats; ++k)
+      if (rs[k]) __hip_atomic_fetch_add(g_regen + k, (unsigned long long)rs[k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+#endif
   // ---- counters ------------------------------------------------------------
   {
     unsigned long long steps = c_steps, fetch = c_fetch;
@@ -1283,6 +1563,17 @@ extern "C" int cvr_debug_tailstamps_clear() {
   void* p = nullptr;
   if (hipGetSymbolAddress(&p, HIP_SYMBOL(g_tail)) != hipSuccess) return -2;
   return hipMemset(p, 0, sizeof(unsigned long long) * 8 * kTailWaves) == hipSuccess ? 0 : -2;
+}
+#endif
+
+#if CVR_WPOOL_REGENSTAT
+// (diagnostic build) the launches' regeneration counters since the last clear, kRegenStats u64
+extern "C" int cvr_debug_regenstats(unsigned long long* host, int clear) {
+  void* p = nullptr;
+  if (hipGetSymbolAddress(&p, HIP_SYMBOL(g_regen)) != hipSuccess) return -2;
+  if (hipMemcpy(host, p, sizeof(unsigned long long) * kRegenStats, hipMemcpyDeviceToHost) != hipSuccess) return -2;
+  if (clear && hipMemset(p, 0, sizeof(unsigned long long) * kRegenStats) != hipSuccess) return -2;
+  return kRegenStats;
 }
 #endif
 
