@@ -139,3 +139,5 @@ $(eval $(call host_asan,features,cvr_features_api cvr_denoise_api))
 $(eval $(call host_asan,field,cvr_field_api))
 # cvr_clip_host and the clip descriptor's checks
 $(eval $(call host_asan,clip,cvr_medium))
+# cvr_classify_labels_host and the labelled descriptor's checks
+$(eval $(call host_asan,labels,cvr_medium))

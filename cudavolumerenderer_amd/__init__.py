@@ -16,6 +16,7 @@ from ._lib import (  # noqa: F401
     MEDIUM_ARRAYS, build_geometry,
     TransferDesc, ScalarMediumDesc, classify_host, raw_transfer_table,
     GradientTransferDesc, GradientMediumDesc, classify_gradient_host,
+    LabelTransferDesc, LabeledMediumDesc, classify_labels_host,
     ClipDesc, CLIP_MAX_PLANES, clip_host, plane_from_box,
     FieldDesc, HistogramDesc, FieldStats, field_stats_host, field_histogram_host, field_geometry,
     SCALAR_F32, SCALAR_U8, SCALAR_U16, SCALAR_I16, TF_CEIL, TF_DENSITY_U,
@@ -36,6 +37,7 @@ __all__ = [
     "MEDIUM_ARRAYS", "build_geometry",
     "TransferDesc", "ScalarMediumDesc", "classify_host", "raw_transfer_table",
     "GradientTransferDesc", "GradientMediumDesc", "classify_gradient_host",
+    "LabelTransferDesc", "LabeledMediumDesc", "classify_labels_host",
     "ClipDesc", "CLIP_MAX_PLANES", "clip_host", "plane_from_box",
     "FieldDesc", "HistogramDesc", "FieldStats", "field_stats_host", "field_histogram_host", "field_geometry",
     "SCALAR_F32", "SCALAR_U8", "SCALAR_U16", "SCALAR_I16", "TF_CEIL", "TF_DENSITY_U",

@@ -211,6 +211,25 @@ class GradientMediumDesc(C.Structure):
                 ("max_density", C.c_float), ("g", C.c_float), ("roughness", C.c_float * 2), ("eta", C.c_float)]
 
 
+class LabelTransferDesc(C.Structure):
+    """cvr_label_transfer_desc: a table of m rows of n (r, g, b, density) entries in host memory,
+    row j the transfer function of label j, and the scalar range [lo, hi] every row spans."""
+    _fields_ = [("n", C.c_uint32), ("m", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32),
+                ("table", C.c_void_p), ("lo", C.c_float), ("hi", C.c_float)]
+
+
+class LabeledMediumDesc(C.Structure):
+    """cvr_labeled_medium_desc: a scalar field and a label volume in device memory and the
+    per-label transfer table (cvr_set_medium_labeled)."""
+    _fields_ = [("res", C.c_uint32 * 3), ("flags", C.c_uint32), ("d_scalar", C.c_void_p),
+                ("scalar_type", C.c_uint32), ("reserved", C.c_uint32), ("transfer", LabelTransferDesc),
+                ("box_min", C.c_float * 3), ("box_max", C.c_float * 3), ("scale", C.c_float),
+                ("max_density", C.c_float), ("g", C.c_float), ("roughness", C.c_float * 2), ("eta", C.c_float),
+                ("d_labels", C.c_void_p)]
+
+
+assert C.sizeof(LabelTransferDesc) == 32 and C.sizeof(LabeledMediumDesc) == 120
+
 CLIP_MAX_PLANES = 8
 
 
@@ -398,6 +417,10 @@ def load() -> C.CDLL:
         "cvr_classify_gradient_host": (I32, [P, U32, C.POINTER(U32), C.POINTER(GradientTransferDesc), P, P, P]),
         "cvr_set_medium_gradient": (I32, [P, C.POINTER(GradientMediumDesc)]),
         "cvr_set_medium_scene_gradient": (I32, [P, P, C.POINTER(GradientTransferDesc), U32]),
+        "cvr_classify_labels_host": (I32, [P, U32, P, C.c_size_t, C.POINTER(LabelTransferDesc), P, P, P]),
+        "cvr_set_medium_labeled": (I32, [P, C.POINTER(LabeledMediumDesc)]),
+        "cvr_medium_label_info": (I32, [P, C.POINTER(U32), C.POINTER(U64)]),
+        "cvr_set_medium_scene_labels": (I32, [P, P, C.POINTER(LabelTransferDesc), P, C.c_size_t, U32]),
         "cvr_set_clip": (I32, [P, C.POINTER(ClipDesc)]),
         "cvr_clear_clip": (I32, [P]),
         "cvr_get_clip": (I32, [P, C.POINTER(ClipDesc), C.POINTER(I32)]),
@@ -601,6 +624,40 @@ def classify_gradient_host(scalar, table, lo, hi, glo, ghi, spacing=(1.0, 1.0, 1
     _check(load().cvr_classify_gradient_host(src.ctypes.data, _SCALAR_TYPES[src.dtype.name], res, C.byref(t),
                                              density.ctypes.data, albedo.ctypes.data, mag.ctypes.data))
     return density, albedo, mag
+
+
+def _label_transfer_desc(table, lo, hi, ceil, density_u):
+    """(LabelTransferDesc, the array it points into): table is (m, n, 4) floats, row j the
+    transfer function of label j."""
+    tab = np.ascontiguousarray(table, dtype=np.float32)
+    if tab.ndim != 3 or tab.shape[2] != 4:
+        raise ValueError(f"table: shape {tab.shape}, expected (m, n, 4)")
+    t = LabelTransferDesc(tab.shape[1], tab.shape[0], (TF_CEIL if ceil else 0) | (TF_DENSITY_U if density_u else 0), 0,
+                          tab.ctypes.data, lo, hi)
+    return t, tab
+
+
+def classify_labels_host(scalar, labels, table, lo, hi, ceil=False, density_u=False):
+    """The labelled classification's written statement on the CPU (cvr_classify_labels_host; no
+    GPU): a numpy array `scalar` of dtype uint8, uint16, int16 or float32, a uint8 array `labels`
+    of the same element count and a table of (m, n, 4) floats (r, g, b, density), row j the
+    transfer function of label j over the scalar range [lo, hi] (a label byte >= m takes row 0)
+    -> (density scalar.shape, albedo scalar.shape + (4,), counts: 256 uint64, the voxels with
+    each label byte).  ceil and density_u are classify_host's.  Context.set_medium_labeled
+    computes the same bits on the device."""
+    src = np.ascontiguousarray(scalar)
+    if src.dtype.name not in _SCALAR_TYPES:
+        raise ValueError(f"scalar: dtype {src.dtype}, expected uint8, uint16, int16 or float32")
+    lab = np.ascontiguousarray(labels)
+    if lab.dtype != np.uint8 or lab.size != src.size:
+        raise ValueError(f"labels: dtype {lab.dtype}, {lab.size} elements, expected uint8 and {src.size}")
+    t, _tab = _label_transfer_desc(table, lo, hi, ceil, density_u)
+    density = np.empty(src.shape, np.float32)
+    albedo = np.empty(src.shape + (4,), np.float32)
+    counts = np.zeros(256, np.uint64)
+    _check(load().cvr_classify_labels_host(src.ctypes.data, _SCALAR_TYPES[src.dtype.name], lab.ctypes.data, src.size,
+                                           C.byref(t), density.ctypes.data, albedo.ctypes.data, counts.ctypes.data))
+    return density, albedo, counts
 
 
 def _clip_desc(lo=None, hi=None, planes=()) -> ClipDesc:
@@ -1177,6 +1234,72 @@ class Context:
             import torch
             torch.cuda.current_stream(self.device).synchronize()
         self._c(load().cvr_set_medium_gradient(self._h, C.byref(d)))
+
+    def set_medium_labeled(self, scalar, labels, table, *, lo, hi, ceil=False, density_u=False, sparse=False,
+                           max_density=None, scalar_type=None, res=None, box_min=(-0.5,) * 3, box_max=(0.5,) * 3,
+                           scale=100.0, g=0.0, roughness=(0.1, 0.1), eta=None):
+        """The medium from a scalar field and a label volume in device memory and a table of one
+        transfer function per label, classified inside the build kernels (cvr_set_medium_labeled):
+        the state set_medium_device leaves on device copies of classify_labels_host(scalar, labels,
+        table, lo, hi, ceil, density_u)'s density and albedo.  table: (m, n, 4) floats in host
+        memory, n >= 2, 1 <= m <= 256, n * m <= 4096; a label byte >= m takes row 0.  labels: a
+        uint8 tensor (contiguous, on the context's device, as many elements as scalar: checked
+        here, ValueError), or anything with data_ptr(), or an int device address, of any alignment.
+        scalar and the other arguments are set_medium_scalar's; views at an offset are fine for
+        both.  Synchronous; torch's current stream is synchronised first, both tensors are only
+        read and may be freed afterwards; a new table means a new call."""
+        is_tensor = hasattr(scalar, "data_ptr")
+        if res is None:
+            if not is_tensor:
+                raise ValueError("set_medium_labeled: res is required with an int address")
+            if len(scalar.shape) != 3:
+                raise ValueError(f"scalar: shape {tuple(scalar.shape)}, expected (z, y, x)")
+            nz, ny, nx = (int(v) for v in scalar.shape)
+        else:
+            nx, ny, nz = (int(v) for v in res)
+        if is_tensor:
+            _check_device_grid("scalar", scalar, (nz, ny, nx), self.device, tuple(_SCALAR_TYPES))
+        if scalar_type is None:
+            name = str(getattr(scalar, "dtype", "")).split(".")[-1]
+            if name not in _SCALAR_TYPES:
+                raise ValueError("set_medium_labeled: scalar_type is required with an int address")
+            scalar_type = _SCALAR_TYPES[name]
+        if hasattr(labels, "data_ptr") and hasattr(labels, "shape"):
+            count = 1
+            for v in labels.shape:
+                count *= int(v)
+            if count != nx * ny * nz:
+                raise ValueError(f"labels: {count} elements, the field has {nx * ny * nz}")
+            _check_device_grid("labels", labels, tuple(labels.shape), self.device, ("uint8",))
+        t, _tab = _label_transfer_desc(table, lo, hi, ceil, density_u)
+        d = LabeledMediumDesc()
+        d.res[:] = (nx, ny, nz)
+        d.flags = (DEVMED_SPARSE if sparse else 0) | (DEVMED_MAX_DENSITY if max_density is None else 0)
+        d.d_scalar = _device_ptr(scalar)
+        d.d_labels = _device_ptr(labels)
+        d.scalar_type = scalar_type
+        d.transfer = t
+        d.box_min[:] = box_min
+        d.box_max[:] = box_max
+        d.scale = scale
+        d.max_density = 0.0 if max_density is None else max_density
+        d.g = g
+        d.roughness[:] = roughness
+        d.eta = np.float32(np.float32(1.05) / np.float32(1.01)) if eta is None else eta
+        if any(type(v).__module__.split(".")[0] == "torch" for v in (scalar, labels)):
+            import torch
+            torch.cuda.current_stream(self.device).synchronize()
+        self._c(load().cvr_set_medium_labeled(self._h, C.byref(d)))
+
+    def medium_label_info(self):
+        """(m, counts) of the medium in use, own or shared (cvr_medium_label_info): the rows of the
+        table set_medium_labeled built it with (0: another call built it) and 256 uint64, the
+        voxels per label byte that the build kept (a clip's voxels are not counted, so they sum to
+        medium_clip_info()'s kept), counted on the device during the build."""
+        m = C.c_uint32(0)
+        counts = np.zeros(256, np.uint64)
+        self._c(load().cvr_medium_label_info(self._h, C.byref(m), counts.ctypes.data_as(C.POINTER(C.c_uint64))))
+        return int(m.value), counts
 
     def set_clip(self, lo=None, hi=None, planes=()):
         """The clip region of the next device builds (cvr_set_clip): a crop box lo <= c < hi in

@@ -106,6 +106,10 @@ struct cvr_ctx : cvr::Settings {
   bool medium_clipped = false;
   cvr_clip_desc medium_clip{};
   uint64_t medium_kept = 0;
+  // cvr_medium_label_info's: the rows of the table the medium in use (own or shared) was built
+  // with by cvr_set_medium_labeled (0: by another call) and the kept voxels per label byte
+  uint32_t medium_label_rows = 0;
+  uint64_t medium_label_counts[256] = {};
 
   // Not in Settings on purpose: external_out here, and frame_flush, moments and wf_timing below.  A
   // helper always renders into its parent's buffer, without moments, in-launch output or timing.

@@ -144,6 +144,7 @@ constexpr uint32_t kBuildSparseCellsGrid = 8192, kBuildSparseBoundsGrid = 4096;
 // What the value scans find, in device memory; the host sets ovf_* to ~0 and the rest to 0 first.
 struct VoxelSource;  // below: the caller's arrays, or a scalar field and a transfer table
 constexpr uint32_t kKeptSlots = 32;  // words a clipped build's kept-voxel count is spread over (MedScan::kept)
+constexpr uint32_t kLabelSlots = 8;  // copies of a labelled build's 256 label counters, by the workgroup's index
 struct MedScan {
   unsigned long long ovf_density;  // smallest index whose finite value rounds to +-inf in binary16 (format 1)
   unsigned long long ovf_albedo;   // the same over the albedo's r, g, b (index 4 voxel + channel)
@@ -212,6 +213,13 @@ __host__ __device__ inline float4 transfer_classify(float s, const float4* table
   if (p.flags & 2u) e.w = u;
   return e;
 }
+// The labelled classification (cvr.h: CVR_HAS_LABELS): the statement above on row `label` of a
+// table of m rows of p.n entries, row 0 for a label the table has no row for.
+__host__ __device__ inline float4 label_classify(float s, uint32_t label, const float4* table, uint32_t m,
+                                                 const TransferParams& p) {
+  const uint32_t j = label < m ? label : 0u;
+  return transfer_classify(s, table + (size_t)j * p.n, p);
+}
 // One scalar voxel as the float the classification starts from (exact for the integer types)
 __host__ __device__ inline float scalar_voxel(const void* scalar, uint32_t type, size_t i) {
   switch (type) {
@@ -273,7 +281,9 @@ hipError_t launch_field_histogram(const FieldSrc& f, const FieldBins& b, uint32_
 // Where the build stages take a voxel's values from: the caller's two arrays (scalar null;
 // albedo null: none), or a scalar field of type scalar_type (cvr.h: CVR_SCALAR_*) classified
 // through a table in device memory: the 1-D one by the value (tf), or, with `gradient`, the 2-D
-// one by the value and the gradient magnitude (gtf; res is the field's, the stencil needs it).
+// one by the value and the gradient magnitude (gtf; res is the field's, the stencil needs it), or,
+// with `labels`, a table of label_rows rows of tf.n entries, the row chosen by the voxel's label
+// byte (cvr.h: CVR_HAS_LABELS).
 struct VoxelSource {
   const float* density = nullptr;
   const float* albedo = nullptr;
@@ -284,6 +294,12 @@ struct VoxelSource {
   bool gradient = false;
   uint32_t res[3] = {0u, 0u, 0u};
   GradientParams gtf{};
+  // A labelled source: one label byte per voxel (device memory, any alignment), the table's rows,
+  // and kLabelSlots x 256 zeroed words of device memory that the dense store pass or the leaf-flag
+  // pass adds the kept voxels' label bytes to (label_counts[slot * 256 + byte]; the host adds the slots)
+  const uint8_t* labels = nullptr;
+  uint32_t label_rows = 0;
+  uint32_t* label_counts = nullptr;
   // The clip region the build honours (cvr_clip.h; host memory, hi clamped to the grid), or null.
   // With one, every launch below that takes the source runs its clipped instance: a voxel the
   // region does not keep is (0, the unclipped voxel 0's albedo) and is not read.

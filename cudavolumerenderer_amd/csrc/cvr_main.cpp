@@ -50,6 +50,7 @@ struct Options {
   std::string medium_format = "float";  // --medium-format
   std::string transfer_file, transfer_mode = "linear";  // --transfer, --transfer-mode
   std::string transfer2d_file;         // --transfer2d
+  std::string transfer_labels_file, labels_file;  // --transfer-labels, --labels
   std::vector<float> gradient_range;   // --gradient-range GLO GHI
   bool gradient_auto = false;          // --gradient-range auto
   bool field_stats = false;            // --field-stats
@@ -130,6 +131,13 @@ void usage() {
       "  --histogram-bins N [M] (=256 256)  value bins and gradient bins (N >= 2, N*M <= 65536; M omitted: 1, no gradient)\n"
       "                                     --field-stats, --histogram and --gradient-range auto take --voxel-spacing;\n"
       "                                     with --iterations 0 they run without a render\n"
+      "  --transfer-labels FILE --labels FILE.raw\n"
+      "                                     Raw scenes (and --synthetic bucky): classify the scene's bytes through one\n"
+      "                                     table row per label (cvr_set_medium_scene_labels).  FILE is --transfer2d's\n"
+      "                                     format, an 'n m' line and m*n lines 'r g b density' row by row, m >= 1 (row j\n"
+      "                                     is label j's transfer function); FILE.raw holds one label byte per voxel.\n"
+      "                                     --transfer-mode applies; excludes --transfer and --transfer2d; --field-stats\n"
+      "                                     also prints the voxels per label\n"
       "  --crop X0 Y0 Z0 X1 Y1 Z1           with --transfer or --transfer2d: keep the voxels X0 <= x < X1, Y0 <= y < Y1,\n"
       "                                     Z0 <= z < Z1 (voxel indices; past the grid: to its end) and store the\n"
       "                                     others as empty (cvr_set_clip)\n"
@@ -214,6 +222,8 @@ int parse(int argc, char** argv, Options& o) {
     else if (a == "--transfer") o.transfer_file = need("transfer");
     else if (a == "--transfer-mode") o.transfer_mode = need("transfer-mode");
     else if (a == "--transfer2d") o.transfer2d_file = need("transfer2d");
+    else if (a == "--transfer-labels") o.transfer_labels_file = need("transfer-labels");
+    else if (a == "--labels") o.labels_file = need("labels");
     else if (a == "--gradient-range" || a == "--voxel-spacing") {
       const bool range = a == "--gradient-range";
       std::vector<float>& dst = range ? o.gradient_range : o.voxel_spacing;
@@ -494,10 +504,12 @@ int field_pass(const Options& o, int device, int kernel, const cvr_scene* scene,
 // --transfer2d FILE: a first data line 'n m', then n * m lines of 'r g b density', row by row
 // (blank lines and lines starting with # are skipped) into table; false with a message when the
 // file cannot be read, a line is not what it should be, or the entries are not n * m.
-bool read_transfer2d(const std::string& path, std::vector<float>& table, unsigned& n, unsigned& m) {
+// (--transfer-labels reads the same format with m >= 1: opt names the option, min_m its smallest m)
+bool read_transfer2d(const std::string& path, std::vector<float>& table, unsigned& n, unsigned& m,
+                     const char* opt = "--transfer2d", unsigned min_m = 2) {
   FILE* fp = fopen(path.c_str(), "r");
   if (!fp) {
-    fprintf(stderr, "[ConfigParser] Error: --transfer2d: cannot read '%s'\n", path.c_str());
+    fprintf(stderr, "[ConfigParser] Error: %s: cannot read '%s'\n", opt, path.c_str());
     return false;
   }
   char line[512];
@@ -512,11 +524,11 @@ bool read_transfer2d(const std::string& path, std::vector<float>& table, unsigne
     char extra;
     if (!have_size) {
       if (sscanf(p, "%u %u %c", &n, &m, &extra) != 2) {
-        fprintf(stderr, "[ConfigParser] Error: --transfer2d: line %u of '%s' is not 'n m'\n", lineno, path.c_str());
+        fprintf(stderr, "[ConfigParser] Error: %s: line %u of '%s' is not 'n m'\n", opt, lineno, path.c_str());
         ok = false;
-      } else if (n < 2 || m < 2 || (unsigned long long)n * m > 4096) {
-        fprintf(stderr, "[ConfigParser] Error: --transfer2d: '%s' declares a %u x %u table: n >= 2, m >= 2, n*m <= 4096\n",
-                path.c_str(), n, m);
+      } else if (n < 2 || m < min_m || (unsigned long long)n * m > 4096 || (min_m < 2 && m > 256)) {
+        fprintf(stderr, "[ConfigParser] Error: %s: '%s' declares a %u x %u table: n >= 2, m >= %u%s, n*m <= 4096\n", opt,
+                path.c_str(), n, m, min_m, min_m < 2 ? " and <= 256" : "");
         ok = false;
       }
       have_size = true;
@@ -524,7 +536,7 @@ bool read_transfer2d(const std::string& path, std::vector<float>& table, unsigne
     }
     float v[4];
     if (sscanf(p, "%f %f %f %f %c", &v[0], &v[1], &v[2], &v[3], &extra) != 4) {
-      fprintf(stderr, "[ConfigParser] Error: --transfer2d: line %u of '%s' is not 'r g b density'\n", lineno,
+      fprintf(stderr, "[ConfigParser] Error: %s: line %u of '%s' is not 'r g b density'\n", opt, lineno,
               path.c_str());
       ok = false;
     }
@@ -533,11 +545,11 @@ bool read_transfer2d(const std::string& path, std::vector<float>& table, unsigne
   }
   fclose(fp);
   if (ok && !have_size) {
-    fprintf(stderr, "[ConfigParser] Error: --transfer2d: '%s' holds no 'n m' line\n", path.c_str());
+    fprintf(stderr, "[ConfigParser] Error: %s: '%s' holds no 'n m' line\n", opt, path.c_str());
     ok = false;
   }
   if (ok && table.size() != (size_t)4 * n * m) {
-    fprintf(stderr, "[ConfigParser] Error: --transfer2d: '%s' holds %s %u x %u = %u entries\n", path.c_str(),
+    fprintf(stderr, "[ConfigParser] Error: %s: '%s' holds %s %u x %u = %u entries\n", opt, path.c_str(),
             table.size() < (size_t)4 * n * m ? "fewer than its" : "more than its", n, m, n * m);
     ok = false;
   }
@@ -590,6 +602,14 @@ int main(int argc, char** argv) {
   }
   if (!o.transfer2d_file.empty() && !o.transfer_file.empty()) {
     fprintf(stderr, "[ConfigParser] Error: --transfer2d excludes --transfer\n");
+    return 2;
+  }
+  if (!o.transfer_labels_file.empty() && (!o.transfer_file.empty() || !o.transfer2d_file.empty())) {
+    fprintf(stderr, "[ConfigParser] Error: --transfer-labels excludes --transfer and --transfer2d\n");
+    return 2;
+  }
+  if (o.transfer_labels_file.empty() != o.labels_file.empty()) {
+    fprintf(stderr, "[ConfigParser] Error: --transfer-labels FILE and --labels FILE.raw go together\n");
     return 2;
   }
   // --transfer: the table, and a scene that has one byte per voxel to classify
@@ -683,6 +703,37 @@ int main(int argc, char** argv) {
     transfer2d.ghi = ghi;
     for (int k = 0; k < 3; ++k) transfer2d.spacing[k] = o.voxel_spacing[k];
   }
+  // --transfer-labels, --labels: one table row per label byte, and the label volume
+  std::vector<float> label_table;
+  std::vector<uint8_t> label_bytes;
+  cvr_label_transfer_desc transfer_labels{};
+  if (!o.transfer_labels_file.empty()) {
+    const uint8_t* raw = nullptr;
+    size_t n_raw = 0;
+    if (cvr_scene_raw_bytes(scene, &raw, &n_raw) != CVR_OK || !n_raw) {
+      fprintf(stderr, "[ConfigParser] Error: --transfer-labels applies to Raw scenes only (and --synthetic bucky): this "
+                      "scene has no scalar bytes to classify\n");
+      return 2;
+    }
+    if (!read_transfer2d(o.transfer_labels_file, label_table, transfer_labels.n, transfer_labels.m, "--transfer-labels", 1))
+      return 2;
+    transfer_labels.flags = o.transfer_mode == "ceil" ? CVR_TF_CEIL : 0;
+    transfer_labels.table = label_table.data();
+    FILE* fp = fopen(o.labels_file.c_str(), "rb");
+    if (!fp) {
+      fprintf(stderr, "[ConfigParser] Error: --labels: cannot read '%s'\n", o.labels_file.c_str());
+      return 2;
+    }
+    label_bytes.resize(n_raw + 1);  // (one more: a longer file shows)
+    const size_t got = fread(label_bytes.data(), 1, n_raw + 1, fp);
+    fclose(fp);
+    if (got != n_raw) {
+      fprintf(stderr, "[ConfigParser] Error: --labels: '%s' holds %s %zu bytes, one per voxel of the scene\n",
+              o.labels_file.c_str(), got < n_raw ? "fewer than the" : "more than the", n_raw);
+      return 2;
+    }
+    label_bytes.resize(n_raw);
+  }
   // --crop, --clip-plane: the clip region of the device build (the host uploads do not clip)
   cvr_clip_desc clip{};
   const bool have_clip = !o.crop.empty() || !o.clip_planes.empty();
@@ -694,8 +745,8 @@ int main(int argc, char** argv) {
                       "this scene has no scalar bytes to classify on the device\n");
       return 2;
     }
-    if (!transfer.n && !transfer2d.n) {
-      fprintf(stderr, "[ConfigParser] Error: --crop and --clip-plane need --transfer or --transfer2d (the clip is applied "
+    if (!transfer.n && !transfer2d.n && !transfer_labels.n) {
+      fprintf(stderr, "[ConfigParser] Error: --crop and --clip-plane need --transfer or --transfer2d (or --transfer-labels; the clip is applied "
                       "where the device build classifies the voxel)\n");
       return 2;
     }
@@ -796,6 +847,9 @@ int main(int argc, char** argv) {
       rc = cvr_share_medium(ctx, share);
     } else if (!rc && transfer2d.n) {
       rc = cvr_set_medium_scene_gradient(ctx, scene, &transfer2d, sparse ? CVR_DEVMED_SPARSE : 0);
+    } else if (!rc && transfer_labels.n) {
+      rc = cvr_set_medium_scene_labels(ctx, scene, &transfer_labels, label_bytes.data(), label_bytes.size(),
+                                       sparse ? CVR_DEVMED_SPARSE : 0);
     } else if (!rc && transfer.n) {
       rc = cvr_set_medium_scene_transfer(ctx, scene, &transfer, sparse ? CVR_DEVMED_SPARSE : 0);
     } else if (!rc) {
@@ -827,6 +881,20 @@ int main(int argc, char** argv) {
            (unsigned long long)res.v[0] * res.v[1] * res.v[2]);
     return 0;
   };
+  // --field-stats with --transfer-labels: the kept voxels per label byte, as the build counted them
+  auto print_labels = [&](cvr_ctx* ctx) -> int {
+    uint32_t rows = 0;
+    uint64_t counts[256];
+    if (cvr_medium_label_info(ctx, &rows, counts) != CVR_OK) {
+      fprintf(stderr, "Error: %s\n", cvr_last_error(ctx));
+      return 1;
+    }
+    printf("labels              : %u table rows; kept voxels per label byte:\n", rows);
+    for (unsigned b = 0; b < 256; ++b)
+      if (counts[b]) printf("  label %u: %llu\n", b, (unsigned long long)counts[b]);
+    return 0;
+  };
+  const bool have_labels = transfer_labels.n != 0;
   const std::vector<int> devs = parse_devices(o.devices, o.device);
   if (devs.empty()) {
     fprintf(stderr, "[ConfigParser] Error: --devices needs a count (N >= 1) or a list of two or more device ids "
@@ -842,12 +910,13 @@ int main(int argc, char** argv) {
       printf("[ConfigParser] gradient range set to 0 .. %.9g.\n", (double)gmax);
     }
     if (o.iterations == 0) {  // the field's numbers alone: no render, no image
-      if (o.field_stats && have_clip) {
+      if (o.field_stats && (have_clip || have_labels)) {
         // the kept voxels are counted by the build itself, and nothing renders: a context of this
         // pass's own builds the medium once for the count
         cvr_ctx* c = make_ctx(devs[0], nullptr);
         if (!c) return 1;
-        const int kr = print_kept(c);
+        int kr = have_clip ? print_kept(c) : 0;
+        if (!kr && have_labels) kr = print_labels(c);
         cvr_destroy(c);
         if (kr) return kr;
       }
@@ -916,6 +985,7 @@ int main(int argc, char** argv) {
     }
     // (the first trial's render context: its build counted the kept voxels, no build of its own)
     if (t == 0 && o.field_stats && have_clip && print_kept(ctxs[0])) return 1;
+    if (t == 0 && o.field_stats && have_labels && print_labels(ctxs[0])) return 1;
     cvr_stats st{};
     const auto t0 = std::chrono::steady_clock::now();
     cvr_adaptive_result ares{};

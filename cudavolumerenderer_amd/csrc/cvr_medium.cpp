@@ -1,6 +1,6 @@
 // cvr_medium.cpp - the medium of a context: the host uploads (dense, sparse) and the build from
-// device memory (two arrays, or a scalar field and a 1-D or gradient-magnitude transfer function:
-// build_from_device) through one set of stages, the transfer functions' host statements, and what
+// device memory (two arrays, or a scalar field and a 1-D, gradient-magnitude or per-label transfer
+// function: build_from_device) through one set of stages, the transfer functions' host statements, and what
 // the context tells of the result.
 //
 // Each rule is stated once: the shape guards (dense_shape_check, sparse_shape_check), the dense
@@ -305,7 +305,9 @@ int finish_dense(cvr_ctx* c, const MediumView& v, uint32_t fmt, float max_densit
                       : cvr::V3{uniform_rgb[0], uniform_rgb[1], uniform_rgb[2]};
   }
   set_minfo(c, fmt, max_density, n * B.d, c->d_cells ? n * B.c : 0, n * B.a, bounds_bytes);
-  c->medium_clipped = false;  // (build_from_device notes its clip after this)
+  c->medium_clipped = false;  // (build_from_device notes its clip and its label counts after this)
+  c->medium_label_rows = 0;
+  memset(c->medium_label_counts, 0, sizeof(c->medium_label_counts));
   c->have_medium = true;
   return CVR_OK;
 }
@@ -467,7 +469,9 @@ int finish_sparse(cvr_ctx* c, const SparseBuild& b, DevTemps& tmp, DevmedTimer& 
   set_minfo(c, b.fmt, b.max_density, (np ? np : 1) * B.d, c->d_cells ? ncl * 512 * B.c : 0,
             c->d_leaf_albedo ? np * B.a : 0,
             (g.nb + 1 + g.nleaf + (c->d_emask ? cvr::kEmaskWords : 0)) * sizeof(uint32_t));
-  c->medium_clipped = false;  // (build_from_device notes its clip after this)
+  c->medium_clipped = false;  // (build_from_device notes its clip and its label counts after this)
+  c->medium_label_rows = 0;
+  memset(c->medium_label_counts, 0, sizeof(c->medium_label_counts));
   c->have_medium = true;
   return CVR_OK;
 }
@@ -505,7 +509,12 @@ int source_voxel(cvr_ctx* c, const cvr::VoxelSource& src, const float* host_tabl
   };
   const float s = read(i);
   float4 e;
-  if (src.gradient) {
+  if (src.labels) {
+    uint8_t label = 0;
+    if (failed) return failed;
+    HIP_TRY(c, hipMemcpy(&label, src.labels + i, 1, hipMemcpyDeviceToHost));
+    e = cvr::label_classify(s, label, reinterpret_cast<const float4*>(host_table), src.label_rows, src.tf);
+  } else if (src.gradient) {
     // the voxel and its up to six in-grid neighbours, as the kernels' stencil reads them
     const uint32_t nx = src.res[0], ny = src.res[1];
     const float mag = cvr::gradient_at(read, (uint32_t)(i % nx), (uint32_t)((i / nx) % ny),
@@ -679,6 +688,24 @@ int gradient_check(std::string* err, const cvr_gradient_transfer_desc* t, F afte
   return CVR_OK;
 }
 
+// The labelled descriptor's refusals in cvr.h's order for cvr_set_medium_labeled (which looks at
+// d_scalar and d_labels with the table: after_table)
+template <class F>
+int label_transfer_check(std::string* err, const cvr_label_transfer_desc* t, F after_table) {
+  if (t->n < 2u || t->m < 1u || t->m > 256u || (uint64_t)t->n * t->m > 4096u)
+    return set_err(err, CVR_ERR_INVALID, "label transfer table of %u x %u entries (n >= 2, 1 <= m <= 256, n * m <= 4096)",
+                   t->n, t->m);
+  if ((t->flags & ~(uint32_t)(CVR_TF_CEIL | CVR_TF_DENSITY_U)) || t->reserved)
+    return set_err(err, CVR_ERR_INVALID, "cvr_label_transfer_desc flags 0x%x unknown or reserved 0x%x not 0", t->flags,
+                   t->reserved);
+  if (!t->table) return set_err(err, CVR_ERR_INVALID, "transfer table is NULL");
+  if (int r = after_table()) return r;
+  if (!std::isfinite(t->lo) || !std::isfinite(t->hi) || !(t->hi > t->lo))
+    return set_err(err, CVR_ERR_INVALID, "transfer range lo %g, hi %g: both finite and hi > lo", (double)t->lo,
+                   (double)t->hi);
+  return CVR_OK;
+}
+
 // Both device calls from their checked arguments on: one sequence of stages for either source.
 // b.g is filled for a sparse build; tmp may already hold the call's allocations (the table).
 // The context's clip, when set, is taken here: the source then carries the region, every launch
@@ -709,8 +736,17 @@ int build_from_device(cvr_ctx* c, const DeviceBuild& d, const cvr::VoxelSource& 
   // the value scans: majorant, binary16 overflow, albedo sameness
   cvr::MedScan scan{~0ull, ~0ull, 0u, 0u, {0u, 0u}, {}};
   // the clip the medium was built under and the kept voxels its store or leaf-flag pass counted
+  uint32_t* d_label_counts = nullptr;
   auto note_clip = [&](int result, const cvr::MedScan* d_counted) -> int {
-    if (result || !src.clip) return result;
+    if (result) return result;
+    if (src.labels) {
+      // the kept voxels per label byte, of the store or leaf-flag pass: the slots' sums
+      std::vector<uint32_t> slots((size_t)cvr::kLabelSlots * 256);
+      HIP_TRY(c, hipMemcpy(slots.data(), d_label_counts, slots.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+      for (size_t k = 0; k < slots.size(); ++k) c->medium_label_counts[k & 255u] += slots[k];
+      c->medium_label_rows = src.label_rows;
+    }
+    if (!src.clip) return CVR_OK;
     unsigned long long slots[cvr::kKeptSlots], kept = 0;
     HIP_TRY(c, hipMemcpy(slots, d_counted->kept, sizeof(slots), hipMemcpyDeviceToHost));
     for (unsigned long long v : slots) kept += v;
@@ -722,6 +758,11 @@ int build_from_device(cvr_ctx* c, const DeviceBuild& d, const cvr::VoxelSource& 
   cvr::MedScan* d_scan = nullptr;
   HIP_TRY(c, tmp.alloc((void**)&d_scan, sizeof(scan)));
   HIP_TRY(c, hipMemcpy(d_scan, &scan, sizeof(scan), hipMemcpyHostToDevice));
+  if (src.labels) {
+    HIP_TRY(c, tmp.alloc((void**)&d_label_counts, (size_t)cvr::kLabelSlots * 256 * sizeof(uint32_t)));
+    HIP_TRY(c, hipMemsetAsync(d_label_counts, 0, (size_t)cvr::kLabelSlots * 256 * sizeof(uint32_t), c->stream));
+    src.label_counts = d_label_counts;
+  }
   float first[5] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
   if (konst) memcpy(first, d.const_albedo, 4 * sizeof(float));
   // voxel 0's values (the background, and what a clipped voxel's albedo is), of the unclipped source
@@ -1063,6 +1104,115 @@ int cvr_set_medium_scalar(cvr_ctx* c, const cvr_scalar_medium_desc* d) {
   return build_from_device(c, {view_of(*d), d->flags, nullptr, d->max_density, &table[0].x}, src, b, tmp);
 }
 
+int cvr_classify_labels_host(const void* scalar, uint32_t scalar_type, const uint8_t* labels, size_t n_voxels,
+                             const cvr_label_transfer_desc* t, float* density, float* albedo, uint64_t* counts) {
+  if (!t || (n_voxels && (!scalar || !labels))) return set_err(nullptr, CVR_ERR_INVALID, "NULL argument");
+  if (scalar_type > CVR_SCALAR_I16) return set_err(nullptr, CVR_ERR_INVALID, "unknown scalar_type %u", scalar_type);
+  if (int r = label_transfer_check(nullptr, t, [] { return CVR_OK; })) return r;
+  const cvr::TransferParams p{t->n, t->flags, t->lo, t->hi};
+  // (the table as float4: copied, the caller's need not be 16-byte aligned)
+  std::vector<float4> table((size_t)t->n * t->m);
+  memcpy(table.data(), t->table, table.size() * sizeof(float4));
+  if (counts) memset(counts, 0, 256 * sizeof(uint64_t));
+  for (size_t i = 0; i < n_voxels; ++i) {
+    const float4 e = cvr::label_classify(cvr::scalar_voxel(scalar, scalar_type, i), labels[i], table.data(), t->m, p);
+    if (density) density[i] = e.w;
+    if (albedo) albedo[4 * i] = e.x, albedo[4 * i + 1] = e.y, albedo[4 * i + 2] = e.z, albedo[4 * i + 3] = 1.0f;
+    if (counts) ++counts[labels[i]];
+  }
+  return CVR_OK;
+}
+
+int cvr_set_medium_labeled(cvr_ctx* c, const cvr_labeled_medium_desc* d) {
+  if (!c || !d) return set_err(c ? &c->err : nullptr, CVR_ERR_INVALID, "NULL argument");
+  CVR_NOT_IN_SESSION(c, "cvr_set_medium_labeled");
+  const uint32_t* res = d->res;
+  const bool sparse = (d->flags & CVR_DEVMED_SPARSE) != 0;
+  SparseBuild b{};
+  int r = sparse ? sparse_shape_check(c, res, &b.g) : dense_shape_check(c, res, (uint32_t)c->medium_format);
+  if (r) return r;
+  if (d->flags & ~(uint32_t)(CVR_DEVMED_SPARSE | CVR_DEVMED_MAX_DENSITY))
+    return set_err(&c->err, CVR_ERR_INVALID, "unknown cvr_labeled_medium_desc flags 0x%x", d->flags);
+  if (d->scalar_type > CVR_SCALAR_I16)
+    return set_err(&c->err, CVR_ERR_INVALID, "unknown scalar_type %u", d->scalar_type);
+  const cvr_label_transfer_desc* t = &d->transfer;
+  r = label_transfer_check(&c->err, t, [&]() -> int {
+    return d->d_scalar && d->d_labels ? CVR_OK : set_err(&c->err, CVR_ERR_INVALID, "d_scalar/d_labels is NULL");
+  });
+  if (r) return r;
+  if ((r = ensure_device(c))) return r;
+  if (!device_readable(c, d->d_scalar))
+    return set_err(&c->err, CVR_ERR_INVALID, "d_scalar is not device-accessible memory of device %d", c->device);
+  const size_t size = d->scalar_type == CVR_SCALAR_U8 ? 1 : d->scalar_type == CVR_SCALAR_F32 ? 4 : 2;
+  if ((uintptr_t)d->d_scalar & (size - 1))
+    return set_err(&c->err, CVR_ERR_INVALID, "d_scalar must be %zu-byte aligned", size);
+  if (!device_readable(c, d->d_labels))
+    return set_err(&c->err, CVR_ERR_INVALID, "d_labels is not device-accessible memory of device %d", c->device);
+  // the table goes to the device once; the kernels stage it in LDS per workgroup
+  const size_t entries = (size_t)t->n * t->m;
+  DevTemps tmp;
+  float4* d_table = nullptr;
+  HIP_TRY(c, tmp.alloc((void**)&d_table, entries * sizeof(float4)));
+  HIP_TRY(c, hipMemcpy(d_table, t->table, entries * sizeof(float4), hipMemcpyHostToDevice));
+  std::vector<float4> table(entries);
+  memcpy(table.data(), t->table, entries * sizeof(float4));
+  cvr::VoxelSource src;
+  src.scalar = d->d_scalar;
+  src.scalar_type = d->scalar_type;
+  src.table = d_table;
+  src.tf = {t->n, t->flags, t->lo, t->hi};
+  src.labels = static_cast<const uint8_t*>(d->d_labels);
+  src.label_rows = t->m;
+  memcpy(src.res, res, sizeof(src.res));
+  return build_from_device(c, {view_of(*d), d->flags, nullptr, d->max_density, &table[0].x}, src, b, tmp);
+}
+
+int cvr_medium_label_info(const cvr_ctx* c, uint32_t* m, uint64_t counts[256]) {
+  if (!c) return set_err(nullptr, CVR_ERR_INVALID, "NULL argument");
+  if (!c->have_medium) return set_err(nullptr, CVR_ERR_STATE, "no medium");
+  if (m) *m = c->medium_label_rows;
+  if (counts) memcpy(counts, c->medium_label_counts, sizeof(c->medium_label_counts));
+  return CVR_OK;
+}
+
+int cvr_set_medium_scene_labels(cvr_ctx* c, const cvr_scene* scene, const cvr_label_transfer_desc* t,
+                                const uint8_t* host_labels, size_t n_labels, uint32_t flags) {
+  if (!c || !scene || !t) return set_err(c ? &c->err : nullptr, CVR_ERR_INVALID, "NULL argument");
+  const uint8_t* bytes = nullptr;
+  size_t n = 0;
+  cvr_medium_desc md{};
+  int r = cvr_scene_raw_bytes(scene, &bytes, &n);
+  if (!r) r = cvr_scene_medium(scene, &md);
+  if (r || !n || n != (size_t)md.res[0] * md.res[1] * md.res[2])
+    return set_err(&c->err, CVR_ERR_INVALID, "the scene has no raw bytes (one per voxel): not a Raw scene");
+  if (!host_labels || n_labels != n)
+    return set_err(&c->err, CVR_ERR_INVALID, "%zu labels for a scene of %zu voxels (one byte per voxel)",
+                   host_labels ? n_labels : (size_t)0, n);
+  if ((r = ensure_device(c))) return r;
+  DevTemps tmp;
+  void *d_bytes = nullptr, *d_labels = nullptr;
+  HIP_TRY(c, tmp.alloc(&d_bytes, n));
+  HIP_TRY(c, tmp.alloc(&d_labels, n));
+  HIP_TRY(c, hipMemcpy(d_bytes, bytes, n, hipMemcpyHostToDevice));
+  HIP_TRY(c, hipMemcpy(d_labels, host_labels, n, hipMemcpyHostToDevice));
+  cvr_labeled_medium_desc d{};
+  memcpy(d.res, md.res, sizeof(d.res));
+  d.flags = flags | CVR_DEVMED_MAX_DENSITY;
+  d.d_scalar = d_bytes;
+  d.scalar_type = CVR_SCALAR_U8;
+  d.d_labels = d_labels;
+  d.transfer = *t;
+  d.transfer.lo = 0.0f;
+  d.transfer.hi = (float)*std::max_element(bytes, bytes + n);
+  memcpy(d.box_min, md.box_min, sizeof(d.box_min));
+  memcpy(d.box_max, md.box_max, sizeof(d.box_max));
+  d.scale = md.scale;
+  d.g = md.g;
+  d.roughness[0] = md.roughness[0], d.roughness[1] = md.roughness[1];
+  d.eta = md.eta;
+  return cvr_set_medium_labeled(c, &d);
+}
+
 int cvr_classify_gradient_host(const void* scalar, uint32_t scalar_type, const uint32_t res[3],
                                const cvr_gradient_transfer_desc* t, float* density, float* albedo,
                                float* gradient_magnitude) {
@@ -1313,6 +1463,8 @@ int cvr_share_medium(cvr_ctx* c, const cvr_ctx* src) {
   c->medium_clipped = src->medium_clipped;
   c->medium_clip = src->medium_clip;
   c->medium_kept = src->medium_kept;
+  c->medium_label_rows = src->medium_label_rows;
+  memcpy(c->medium_label_counts, src->medium_label_counts, sizeof(c->medium_label_counts));
   c->have_medium = true;
   c->inited = false;
   return CVR_OK;

@@ -2,7 +2,8 @@
 // cvr_set_medium_scalar and cvr_set_medium_gradient (gfx950): what the host uploads decide with
 // loops over every voxel or leaf, decided here from a voxel source in device memory, the caller's
 // two arrays or a scalar field classified through a transfer table staged in LDS (1-D by the
-// value, or 2-D by the value and the gradient magnitude of a 6-neighbour stencil).  Value scans
+// value, 2-D by the value and the gradient magnitude of a 6-neighbour stencil, or one row per
+// label byte of a label volume).  Value scans
 // (majorant, binary16 overflow, uniform albedo), the dense -> 8^3 leaves
 // rule of cvr.h (leaf flags, exclusive scan, gather), the cell-leaf table and the empty-region
 // mask.  The cells, bounds and brick words are then built by cvr_kernels.hip's kernels, unchanged.
@@ -114,6 +115,36 @@ struct GradientSrc {
     classified((float)S[i], mag, d, a);
   }
 };
+// A scalar field of type T and a label volume of one byte per voxel, classified through a table
+// of m rows of p.n entries: the voxel's label byte chooses the row, row 0 for a byte the table has
+// no row for (cvr.h: CVR_HAS_LABELS; label_classify is the statement).  stage() copies the m x n
+// table into the workgroup's dynamic LDS once.  L may have any alignment.
+template <class T>
+struct LabeledSrc {
+  using Scalar = T;
+  const T* __restrict__ S;
+  const uint8_t* __restrict__ L;
+  const float4* __restrict__ table;
+  TransferParams p;
+  uint32_t m;
+  uint32_t* __restrict__ counts;  // kLabelSlots x 256 words (VoxelSource::label_counts)
+  uint32_t albedo;  // 0: the colours are not looked at (has_albedo() false)
+  const float4* lds;
+  __device__ void stage() {
+    extern __shared__ float4 s_table[];
+    for (uint32_t k = threadIdx.x; k < p.n * m; k += blockDim.x) s_table[k] = table[k];
+    __syncthreads();
+    lds = s_table;
+  }
+  __device__ bool has_albedo() const { return albedo != 0u; }
+  __device__ void classified(float s, uint32_t label, float& d, float4& a) const {
+    const float4 e = label_classify(s, label, lds, m, p);
+    d = e.w;
+    a = make_float4(e.x, e.y, e.z, 1.0f);
+  }
+  __device__ void voxel(size_t i, float& d, float4& a) const { classified((float)S[i], L[i], d, a); }
+  __device__ void voxel(uint32_t, uint32_t, uint32_t, size_t i, float& d, float4& a) const { voxel(i, d, a); }
+};
 // a or, for a clipped voxel, a0, by component (a select of the two float4 objects would be a select
 // of their addresses, and a0's is the kernel's by-value argument: it would be copied to scratch)
 __device__ __forceinline__ float4 keep_or(bool keep, const float4 a, const float4 a0) {
@@ -149,6 +180,17 @@ template <class Src>
 struct is_clipped : std::false_type {};
 template <class Src>
 struct is_clipped<Clipped<Src>> : std::true_type {};
+// the labelled source of a source that has one, clipped or not
+template <class Src>
+struct is_labeled : std::false_type {};
+template <class T>
+struct is_labeled<LabeledSrc<T>> : std::true_type {};
+template <class T>
+struct is_labeled<Clipped<LabeledSrc<T>>> : std::true_type {};
+template <class T>
+__device__ __forceinline__ const LabeledSrc<T>& labeled(const LabeledSrc<T>& s) { return s; }
+template <class T>
+__device__ __forceinline__ const LabeledSrc<T>& labeled(const Clipped<LabeledSrc<T>>& s) { return s.s; }
 // A work-item's count of kept voxels into out->kept: the workgroup's sum through LDS, then one
 // atomic per workgroup that kept any, on one of kKeptSlots words by the workgroup's index (16 384
 // atomics on a single word, one per wave of a 4096-workgroup launch, cost more than the pass they
@@ -164,6 +206,57 @@ __device__ __forceinline__ void commit_kept(uint32_t kept, MedScan* __restrict__
     if (all) atomicAdd(&out->kept[blockIdx.x % kKeptSlots], (unsigned long long)all);
   }
 }
+
+// 0: the label counters compiled out (the A/B partner, profiles/labels/README.md)
+#ifndef CVR_LABEL_COUNTS
+#define CVR_LABEL_COUNTS 1
+#endif
+// The kept voxels per label byte of a labelled build: 256 counters in the workgroup's LDS, beside
+// the table's, and at the workgroup's end one global add per counter that is not zero, into the
+// copy of the 256 words that the workgroup's index names (the host adds the kLabelSlots copies).
+// No voxel and no wave adds to global memory (cvr_field.hip and commit_kept record what that costs).
+// Integer adds: the result does not depend on their order.
+struct LabelCounts {
+  uint32_t* s;
+  // every work-item of the workgroup, before stage(), whose barrier orders the zeroes
+  __device__ __forceinline__ void begin() {
+    __shared__ uint32_t s_counts[256];
+    s = s_counts;
+    for (uint32_t k = threadIdx.x; k < 256u; k += blockDim.x) s_counts[k] = 0u;
+  }
+  // one voxel of label byte `label` in every lane with `active`.  Label volumes are mostly one
+  // label: the lanes that hold the first active lane's label are counted by a ballot and added by
+  // that lane alone, as the field histogram merges its bins; the other lanes add their own.  (The
+  // ballots are of the lanes that get here.)
+  __device__ __forceinline__ void add(uint32_t label, bool active) {
+#if CVR_LABEL_COUNTS
+    const unsigned long long act = __ballot(active);
+    if (act == 0ull) return;  // (wave-uniform)
+    const uint32_t first = (uint32_t)__ffsll((long long)act) - 1u;
+    // (first is the wave's: a lane read, not a shuffle)
+    const uint32_t l0 = (uint32_t)__builtin_amdgcn_readlane((int)label, __builtin_amdgcn_readfirstlane((int)first));
+    const unsigned long long same = __ballot(active && label == l0);
+    if ((threadIdx.x & 63u) == first)
+      atomicAdd(&s[l0], (uint32_t)__popcll(same));
+    else if (active && label != l0)
+      atomicAdd(&s[label], 1u);
+#else
+    (void)label, (void)active;
+#endif
+  }
+  // every work-item of the workgroup, once, after its last add
+  __device__ __forceinline__ void flush(uint32_t* __restrict__ counts) {
+#if CVR_LABEL_COUNTS
+    __syncthreads();
+    for (uint32_t k = threadIdx.x; k < 256u; k += blockDim.x) {
+      const uint32_t v = s[k];
+      if (v) atomicAdd(&counts[(blockIdx.x % kLabelSlots) * 256u + k], v);
+    }
+#else
+    (void)counts;
+#endif
+  }
+};
 
 // ----------------------------------------------------------- value scans ---
 // Streaming reads: consecutive lanes read consecutive 16 bytes (1 KiB per wave and load), a wave
@@ -580,6 +673,177 @@ __global__ __launch_bounds__(256) void k_arrays_clip(Clipped<ArraySrc> src, size
   }
 }
 
+// 1: the labels of the 16-byte groups are loaded wide and brought into place by a byte funnel;
+// 0: one label byte per lane and step (the A/B partner, profiles/labels/README.md)
+#ifndef CVR_LABEL_WIDE
+#define CVR_LABEL_WIDE 1
+#endif
+typedef uint32_t label_words4 __attribute__((ext_vector_type(4), aligned(4)));
+typedef uint32_t label_words2 __attribute__((ext_vector_type(2), aligned(4)));
+
+// The labelled source's two dense passes, with or without a clip (Src: LabeledSrc<T> or
+// Clipped<LabeledSrc<T>>; kStore: emit above).  k_classified's streaming shape: an integer field
+// is cut into a head up to its first 16-byte boundary, whole 16-byte groups and a tail; a wave
+// loads 64 groups and hands the voxels round so that in step k lane l has voxel 64 k + l of its
+// run.  The labels of the same voxels come along as a second stream.  A lane's group of V voxels
+// has V label bytes, at an address whose alignment has nothing to do with the field's: the lane
+// loads the V / 4 aligned words that cover them and, when the bytes do not start on a word, the
+// word after (an aligned word that holds a byte of the volume lies in the volume's page), and a
+// byte funnel (v_alignbyte_b32) shifts them into place, by the one offset r = address & 3 of the
+// whole launch.  The label words are then handed round by the shuffles that hand the scalars round.
+// Of the two ways to an unaligned second stream, this and a hand-round of the labels' own from
+// word-per-lane loads, the funnel was built and measured against a byte per lane and step
+// (CVR_LABEL_WIDE 0; profiles/labels/README.md has the figures); the second hand-round was not built.
+// Head and tail (a float field: every voxel) take one voxel and one label byte per lane, a wave's
+// lanes consecutive voxels.  Behind a clip a wave's run that lies in rows outside the crop box is
+// not read (LinearGrid::rows_outside), as in k_classified_clip.  The store counts the kept voxels
+// per label byte (LabelCounts) and, behind a clip, the kept voxels.
+template <class Src, bool kStore>
+__global__ __launch_bounds__(256) void k_labeled(Src src, size_t n, LinearGrid g, uint32_t format,
+                                                 void* __restrict__ density, void* __restrict__ albedo,
+                                                 MedScan* __restrict__ out) {
+  constexpr bool kClip = is_clipped<Src>::value;
+  using T = typename Src::Scalar;
+  const LabeledSrc<T>& ls = labeled(src);
+  [[maybe_unused]] LabelCounts lc;
+  if constexpr (kStore) lc.begin();
+  src.stage();
+  float4 a0;
+  if constexpr (kClip) {
+    a0 = src.a0;
+  } else {
+    float d0;
+    ls.voxel(0, d0, a0);
+  }
+  DensityScan ds;
+  AlbedoScan as(a0);
+  [[maybe_unused]] uint32_t kept = 0;
+  if constexpr (kClip) {
+    if (!kStore && blockIdx.x == 0 && threadIdx.x == 0) as.take(a0, 0, format);
+  }
+  // voxel i with scalar s and label byte label, in the lanes that have one (every lane of the
+  // wave calls this: the counters' merge is the wave's)
+  auto take = [&](size_t i, bool has, float s, uint32_t label) {
+    bool keep = has;
+    if (has) {
+      float d = 0.0f;
+      float4 a = a0;
+      if constexpr (kClip) {
+        uint32_t x, y, z;
+        g.coords((uint32_t)i, x, y, z);
+        keep = src.keeps(x, y, z);
+      }
+      if (keep) ls.classified(s, label, d, a);
+      emit<kStore>(i, d, a, format, ds, as, density, albedo);
+    }
+    if constexpr (kStore) lc.add(label, keep);
+    if constexpr (kClip) kept += keep;
+  };
+  constexpr uint32_t kSize = (uint32_t)sizeof(T), V = kSize < 4u ? 16u / kSize : 1u;
+  const uint32_t lane = threadIdx.x & 63u;
+  size_t head = 0, body_end = 0;
+  if constexpr (V > 1u) {
+    constexpr uint32_t W = V / 4u;  // label words of a group
+    head = ((16u - (uint32_t)((uintptr_t)ls.S & 15u)) & 15u) / kSize;
+    head = head < n ? head : n;
+    const size_t groups = (n - head) / V;
+    body_end = head + groups * V;
+    const uint4* __restrict__ S16 = reinterpret_cast<const uint4*>(ls.S + head);
+    const uintptr_t la = (uintptr_t)(ls.L + head);
+    [[maybe_unused]] const uint32_t r = (uint32_t)(la & 3u);
+    [[maybe_unused]] const uint32_t* __restrict__ Lw = reinterpret_cast<const uint32_t*>(la - r);
+    const size_t wave = ((size_t)blockIdx.x * 256 + threadIdx.x) >> 6, nwaves = (size_t)gridDim.x * 4;
+    // (the bounds are the wave's: every lane takes part in the shuffles)
+    for (size_t g0 = wave * 64; g0 < groups; g0 += nwaves * 64) {
+      const size_t first = head + g0 * V;
+      if constexpr (kClip) {
+        const size_t last = (first + 64u * V < body_end ? first + 64u * V : body_end) - 1u;
+        if (g.rows_outside(src.r, (uint32_t)first, (uint32_t)last)) {
+          if constexpr (kStore) {
+#pragma unroll
+            for (uint32_t k = 0; k < V; ++k) {
+              const size_t i = first + k * 64u + lane;
+              if (i < body_end) emit<true>(i, 0.0f, a0, format, ds, as, density, albedo);
+            }
+          }
+          continue;
+        }
+      }
+      const bool have = g0 + lane < groups;
+      const uint4 q = have ? S16[g0 + lane] : make_uint4(0u, 0u, 0u, 0u);
+      uint32_t lb[W];
+#if CVR_LABEL_WIDE
+      uint32_t lw[W + 1u];
+#pragma unroll
+      for (uint32_t c = 0; c <= W; ++c) lw[c] = 0u;
+      if (have) {
+        const uint32_t* __restrict__ w = Lw + (g0 + lane) * W;
+        if constexpr (W == 4u) {
+          const label_words4 t = *reinterpret_cast<const label_words4*>(w);
+          lw[0] = t.x, lw[1] = t.y, lw[2] = t.z, lw[3] = t.w;
+        } else {
+          const label_words2 t = *reinterpret_cast<const label_words2*>(w);
+          lw[0] = t.x, lw[1] = t.y;
+        }
+        if (r) lw[W] = w[W];
+      }
+#pragma unroll
+      for (uint32_t c = 0; c < W; ++c) lb[c] = __builtin_amdgcn_alignbyte(lw[c + 1u], lw[c], r);
+#endif
+#pragma unroll
+      for (uint32_t k = 0; k < V; ++k) {
+        const uint32_t j = k * 64u + lane, from = j / V, e = j % V, byte = e * kSize;
+        const uint32_t w0 = __shfl(q.x, from), w1 = __shfl(q.y, from), w2 = __shfl(q.z, from), w3 = __shfl(q.w, from);
+        const uint32_t w = byte < 4u ? w0 : byte < 8u ? w1 : byte < 12u ? w2 : w3;
+        const T v = (T)(w >> ((byte & 3u) * 8u));
+        const size_t i = first + j;
+        const bool has = i < body_end;
+        uint32_t label;
+#if CVR_LABEL_WIDE
+        uint32_t lx = __shfl(lb[0], from);
+#pragma unroll
+        for (uint32_t c = 1; c < W; ++c) {
+          const uint32_t t = __shfl(lb[c], from);
+          lx = (e >> 2) == c ? t : lx;
+        }
+        label = (lx >> ((e & 3u) * 8u)) & 0xFFu;
+#else
+        (void)lb;
+        label = has ? ls.L[i] : 0u;
+#endif
+        take(i, has, (float)v, label);
+      }
+    }
+  }
+  const size_t rest = head + (n - body_end);
+  // (the bounds are the wave's here too)
+  for (size_t e0 = (size_t)blockIdx.x * 256 + (threadIdx.x & ~63u); e0 < rest; e0 += (size_t)gridDim.x * 256) {
+    const size_t e = e0 + lane;
+    const bool has = e < rest;
+    const size_t i = e < head ? e : body_end + (e - head);
+    if constexpr (kClip && V == 1u) {
+      // a float field: the wave's 64 consecutive voxels
+      if (g.rows_outside(src.r, (uint32_t)e0, (uint32_t)(e0 + 63u < n ? e0 + 63u : n - 1u))) {
+        if (kStore && has) emit<true>(i, 0.0f, a0, format, ds, as, density, albedo);
+        continue;
+      }
+    }
+    float s = 0.0f;
+    uint32_t label = 0u;
+    if (has) {
+      s = (float)ls.S[i];
+      label = ls.L[i];
+    }
+    take(i, has, s, label);
+  }
+  if constexpr (!kStore) {
+    commit_in_table_lds(ds, as, out);
+  } else {
+    lc.flush(ls.counts);
+    if constexpr (kClip) commit_kept(kept, out);
+  }
+}
+
 // The context's albedo grid filled with one value (CVR_DEVMED_CONST_ALBEDO, dense).
 __global__ __launch_bounds__(256) void k_fill_albedo(void* __restrict__ dst, size_t n, uint32_t format, float4 v) {
   const uint2 h = half4_bits(v);
@@ -598,12 +862,16 @@ __global__ __launch_bounds__(256) void k_fill_albedo(void* __restrict__ dst, siz
 // (z, y) lines, not one leaf's 8-voxel rows; the 8 lanes of a leaf then OR their findings.
 // A classified source reads one scalar per lane and row here (a wave's run is 64 to 256 bytes),
 // always looks at the colours, and finds the value scans' results on the way (scan), so that a
-// sparse build reads the field once here and once in the gather.
+// sparse build reads the field once here and once in the gather.  A labelled source also counts
+// the kept voxels per label byte here (LabelCounts), the pass that sees every in-grid voxel once.
 template <class Src>
 __global__ __launch_bounds__(256) void k_leaf_flags(Src src, uint32_t nx, uint32_t ny, uint32_t nz, uint32_t lnx,
                                                     uint32_t lny, uint32_t lnz, uint32_t* __restrict__ flags,
                                                     uint32_t format, MedScan* __restrict__ scan) {
   constexpr bool kScan = !std::is_void_v<typename Src::Scalar>, kClip = is_clipped<Src>::value;
+  constexpr bool kLabels = is_labeled<Src>::value;
+  [[maybe_unused]] LabelCounts lc;
+  if constexpr (kLabels) lc.begin();
   src.stage();
   const uint32_t nxc = (lnx + kLeafRunLeaves - 1u) / kLeafRunLeaves;
   const size_t ntasks = (size_t)nxc * lny * lnz;
@@ -645,10 +913,14 @@ __global__ __launch_bounds__(256) void k_leaf_flags(Src src, uint32_t nx, uint32
           const size_t i = ((size_t)z * ny + y) * nx + x;
           float d;
           float4 a;
-          if constexpr (kClip)
-            kept += src.voxel(x, y, z, i, d, a);
-          else
+          if constexpr (kClip) {
+            const bool keep = src.voxel(x, y, z, i, d, a);
+            kept += keep;
+            if constexpr (kLabels) lc.add(labeled(src).L[i], keep);
+          } else {
             src.voxel(x, y, z, i, d, a);
+            if constexpr (kLabels) lc.add(labeled(src).L[i], true);
+          }
           if (kScan) {
             ds.take(d, i, format);
             as.take(a, i, format);
@@ -669,6 +941,7 @@ __global__ __launch_bounds__(256) void k_leaf_flags(Src src, uint32_t nx, uint32
   }
   if constexpr (kScan) commit_in_table_lds(ds, as, scan);
   if constexpr (kClip) commit_kept(kept, scan);
+  if constexpr (kLabels) lc.flush(labeled(src).counts);
 }
 
 // flags[leaf] = 1 iff the leaf or one of its 7 forward neighbours exists (it needs a cell leaf)
@@ -876,8 +1149,13 @@ uint32_t scan_grid(size_t n) { return (uint32_t)std::min<size_t>((n + 255) / 256
 template <class F>
 void with_source(const VoxelSource& v, bool with_albedo, F f) {
   // (the classified scan's reduction reuses the table's LDS: at least 8 entries)
-  const size_t lds = (size_t)std::max(v.gradient ? v.gtf.n * v.gtf.m : v.tf.n, 8u) * sizeof(float4);
+  const size_t lds =
+      (size_t)std::max(v.gradient ? v.gtf.n * v.gtf.m : v.labels ? v.tf.n * v.label_rows : v.tf.n, 8u) * sizeof(float4);
   const uint32_t al = with_albedo ? 1u : 0u;
+  auto labeled_src = [&](auto* S) {
+    using T = std::remove_cv_t<std::remove_pointer_t<decltype(S)>>;
+    f(LabeledSrc<T>{S, v.labels, v.table, v.tf, v.label_rows, v.label_counts, al, nullptr}, lds);
+  };
   auto gradient = [&](auto* S) {
     using T = std::remove_cv_t<std::remove_pointer_t<decltype(S)>>;
     f(GradientSrc<T>{S, v.table, v.gtf, {v.res[0], v.res[1], v.res[2]}, al, nullptr}, lds);
@@ -890,6 +1168,14 @@ void with_source(const VoxelSource& v, bool with_albedo, F f) {
     gradient(static_cast<const int16_t*>(v.scalar));
   else if (v.gradient)
     gradient(static_cast<const float*>(v.scalar));
+  else if (v.labels && v.scalar_type == 1u)
+    labeled_src(static_cast<const uint8_t*>(v.scalar));
+  else if (v.labels && v.scalar_type == 2u)
+    labeled_src(static_cast<const uint16_t*>(v.scalar));
+  else if (v.labels && v.scalar_type == 3u)
+    labeled_src(static_cast<const int16_t*>(v.scalar));
+  else if (v.labels)
+    labeled_src(static_cast<const float*>(v.scalar));
   else if (!v.scalar)
     f(ArraySrc{v.density, with_albedo ? reinterpret_cast<const float4*>(v.albedo) : nullptr}, (size_t)0);
   else if (v.scalar_type == 1u)
@@ -923,7 +1209,10 @@ hipError_t launch_classified(const VoxelSource& v, size_t n, uint32_t format, vo
   with_clipped_source(v, true, [&](auto src, size_t lds) {
     using Src = decltype(src);
     using T = typename Src::Scalar;
-    if constexpr (std::is_same_v<Src, Clipped<ScalarSrc<T>>>) {
+    if constexpr (is_labeled<Src>::value) {
+      hipLaunchKernelGGL((k_labeled<Src, kStore>), dim3(scan_grid(n)), dim3(256), lds, s, src, n, linear_grid(v.res),
+                         format, density, albedo, out);
+    } else if constexpr (std::is_same_v<Src, Clipped<ScalarSrc<T>>>) {
       hipLaunchKernelGGL((k_classified_clip<T, kStore>), dim3(scan_grid(n)), dim3(256), lds, s, src, n,
                          linear_grid(v.res), format, density, albedo, out);
     } else if constexpr (is_clipped<Src>::value && !std::is_void_v<T>) {

@@ -48,6 +48,9 @@ extern "C" {
  *                  cvr_field_histogram_buffers, cvr_debug_field_geometry
  *              6 + CVR_HAS_CLIP (likewise): cvr_clip_desc, cvr_set_clip, cvr_clear_clip, cvr_get_clip,
  *                  cvr_clip_host, cvr_medium_clip_info
+ *              6 + CVR_HAS_LABELS (likewise): cvr_label_transfer_desc, cvr_labeled_medium_desc,
+ *                  cvr_classify_labels_host, cvr_set_medium_labeled, cvr_medium_label_info,
+ *                  cvr_set_medium_scene_labels
  * CVR_ABI_VERSION is the ABI this header declares: 6, the library's (cvr_abi_version()).  ABI 6 only
  * adds to ABI 5, so a host that must also load an ABI 5 library can hold itself to that surface:
  * with CVR_ABI_TARGET defined as 5 before the include, the ABI 6 functions and structs are not
@@ -953,10 +956,98 @@ int cvr_set_medium_gradient(cvr_ctx* ctx, const cvr_gradient_medium_desc* medium
 int cvr_set_medium_scene_gradient(cvr_ctx* ctx, const cvr_scene* scene, const cvr_gradient_transfer_desc* transfer,
                                   uint32_t flags);
 
+/* ---- label volumes: per-segment transfer tables classified on the device (extension within
+ *      ABI 6: CVR_HAS_LABELS) -- */
+/* A scalar field, a label volume of one byte per voxel on the same grid (a segmentation: the byte
+ * names the organ, bone, vessel or tumour the voxel belongs to) and a table of m rows of n entries
+ * (r, g, b, density) give every voxel a density and an albedo: row j is the 1-D transfer function
+ * of label j, entry (j, i) is at j * n + i.  Per voxel, with L its label byte and s its scalar
+ * converted to float (exact for the integer types):
+ *   j = L < m ? L : 0: row 0 is the unlabelled / background row, and a label the table has no row
+ *       for is treated as unlabelled;
+ *   e = exactly the CVR_HAS_TRANSFER statement above applied to entries j * n .. j * n + n - 1, with
+ *       the descriptor's n, lo, hi and flags (CVR_TF_CEIL and CVR_TF_DENSITY_U mean what they mean
+ *       there), the same fp32 operations in the same order, no fused multiply-add;
+ *   albedo = (e_r, e_g, e_b, 1.0f), and the density is as there.
+ * Nothing interpolates across rows.  With m = 1 the statement is cvr_set_medium_scalar's, whatever
+ * the labels hold.  One definition compiles for the build kernels and cvr_classify_labels_host
+ * (cvr_kernels.h), so both return the same bits.  Hiding a segment is a row of density 0: in a
+ * sparse build the leaves that hold only such voxels (and the background's colour) do not exist.
+ * Not supported: labels combined with the 2-D gradient table, per-label lo / hi windows, label
+ * types wider than a byte, smooth (sub-voxel) segment borders (a border voxel's cell interpolates
+ * between the two segments' classified values, as any two neighbours do), labels in cvr_features,
+ * cvr_field_stats or cvr_field_histogram, keeping either field, the host uploads. */
+#define CVR_HAS_LABELS 1
+typedef struct cvr_label_transfer_desc {
+  uint32_t n, m;      /* n >= 2, 1 <= m <= 256, n * m <= 4096 (64 KB of LDS, the 1-D table's budget; the
+                         build's 256 label counters, 1 KB, lie beside it) */
+  uint32_t flags;     /* CVR_TF_* */
+  uint32_t reserved;  /* 0 */
+  const float* table; /* HOST, m * n * 4 floats, row by row */
+  float lo, hi;       /* finite, hi > lo */
+} cvr_label_transfer_desc; /* 32 bytes */
+/* Host only, no GPU: the statement above over n_voxels voxels of `scalar` (host memory of type
+ * scalar_type) and `labels` (n_voxels bytes).  density (n_voxels floats), albedo (4 * n_voxels
+ * floats) and counts may each be NULL; counts is uint64_t[256], the number of voxels with each
+ * label byte.  The descriptor is checked as cvr_set_medium_labeled checks it. */
+int cvr_classify_labels_host(const void* scalar, uint32_t scalar_type, const uint8_t* labels, size_t n_voxels,
+                             const cvr_label_transfer_desc* transfer, float* density, float* albedo,
+                             uint64_t* counts);
+/* cvr_set_medium_scalar with the statement above: its contract, with cvr_classify_labels_host in
+ * the place of cvr_classify_host.  The context ends in the state cvr_set_medium_device leaves on
+ * device copies of that call's density and albedo: equal cvr_medium_info and cvr_medium_layout,
+ * every stored array equal byte for byte, the same paths bit for bit, dense and sparse, in both
+ * medium formats.  Everything derived from values is derived from the classified values: the
+ * majorant, the binary16 overflow refusal with the host call's code, message and index,
+ * uniform-albedo detection, the leaf rule with voxel (0,0,0)'s classified albedo as background,
+ * and dropping the leaf albedo pool.  No dense array of the classified medium exists outside the
+ * context's storage.
+ * flags: CVR_DEVMED_SPARSE and / or CVR_DEVMED_MAX_DENSITY.  d_scalar as cvr_set_medium_scalar's;
+ * d_labels: device memory, res product bytes, x fastest, of any alignment.
+ * Refusals, all CVR_ERR_INVALID with the previous medium kept, in this order:
+ *   1. the host call's shape guards, from res alone and before any pointer is looked at;
+ *   2. unknown flags (CVR_DEVMED_CONST_ALBEDO is one here) or scalar_type;
+ *   3. n < 2, m < 1, m > 256 or n * m > 4096;
+ *   4. unknown transfer flags or reserved not 0;
+ *   5. a NULL table, d_scalar or d_labels;
+ *   6. lo / hi not finite, or hi <= lo;
+ *   7. a d_scalar that is not device-accessible memory of the context's device or is misaligned
+ *      for its type;
+ *   8. a d_labels that is not device-accessible memory of the context's device.
+ * Inside an adaptive session: CVR_ERR_STATE.
+ * Synchronous on the context's stream; both fields are only read (as often as cvr_set_medium_scalar
+ * reads its field) and may be freed afterwards, the context keeps neither.
+ * cvr_debug_device_medium_ms reports this call's groups as it reports cvr_set_medium_scalar's. */
+typedef struct cvr_labeled_medium_desc {
+  uint32_t res[3];
+  uint32_t flags;
+  const void* d_scalar; /* device, res product elements of scalar_type, x fastest, contiguous */
+  uint32_t scalar_type; /* CVR_SCALAR_* */
+  uint32_t reserved;    /* 0 */
+  cvr_label_transfer_desc transfer;
+  float box_min[3], box_max[3];
+  float scale, max_density, g, roughness[2], eta;
+  const void* d_labels; /* device, res product bytes, x fastest, contiguous, any alignment */
+} cvr_labeled_medium_desc; /* 120 bytes */
+int cvr_set_medium_labeled(cvr_ctx* ctx, const cvr_labeled_medium_desc* medium);
+/* Of the current medium, own or shared: *m the rows of the table cvr_set_medium_labeled built it
+ * with, 0 if another call built it, and counts[b] the number of voxels with label byte b that the
+ * build kept, counted on the device in the build's own store or leaf-flag pass.  Voxels a clip
+ * removes are not counted, so the counts sum to cvr_medium_clip_info's kept.  A medium another call
+ * built: all counts 0.  Either pointer may be NULL.  CVR_ERR_STATE: no medium. */
+int cvr_medium_label_info(const cvr_ctx* ctx, uint32_t* m, uint64_t counts[256]);
+/* cvr_set_medium_labeled on a Raw scene's bytes, as cvr_set_medium_scene_transfer: CVR_SCALAR_U8
+ * with lo 0 and hi the largest byte (transfer's lo and hi are ignored).  host_labels: n_labels
+ * bytes in host memory, uploaded to a temporary device buffer and freed; n_labels must equal the
+ * scene's voxel count (CVR_ERR_INVALID).  flags: CVR_DEVMED_SPARSE or 0. */
+int cvr_set_medium_scene_labels(cvr_ctx* ctx, const cvr_scene* scene, const cvr_label_transfer_desc* transfer,
+                                const uint8_t* host_labels, size_t n_labels, uint32_t flags);
+
 /* ---- crop box and clip planes for media built from device memory (extension within ABI 6:
  *      CVR_HAS_CLIP) -- */
-/* A clip region cuts the volume open where the voxel is classified: the three device builds
- * (cvr_set_medium_device, cvr_set_medium_scalar, cvr_set_medium_gradient and their _scene_ forms)
+/* A clip region cuts the volume open where the voxel is classified: the four device builds
+ * (cvr_set_medium_device, cvr_set_medium_scalar, cvr_set_medium_gradient, cvr_set_medium_labeled
+ * and their _scene_ forms)
  * store a voxel outside the region as empty.  Every operation is an integer comparison or fp32 +,
  * x and a comparison in the order written here, no fused multiply-add, so the build kernels and
  * cvr_clip_host decide the same voxels (one definition compiles for both, cvr_clip.h).  For voxel
@@ -978,8 +1069,8 @@ int cvr_set_medium_scene_gradient(cvr_ctx* ctx, const cvr_scene* scene, const cv
  *
  * Contract: with a clip set, a device build leaves the context in the state that
  * cvr_set_medium_device with no clip leaves on device copies of cvr_clip_host's output (for the
- * classified routes: cvr_clip_host applied to cvr_classify_host's / cvr_classify_gradient_host's
- * arrays): equal cvr_medium_info and cvr_medium_layout, every stored array equal byte for byte,
+ * classified routes: cvr_clip_host applied to cvr_classify_host's / cvr_classify_gradient_host's /
+ * cvr_classify_labels_host's arrays): equal cvr_medium_info and cvr_medium_layout, every stored array equal byte for byte,
  * the same paths bit for bit, dense and sparse, in both formats.  Everything derived from values
  * is derived from the clipped values: the CVR_DEVMED_MAX_DENSITY majorant, the binary16 overflow
  * refusal with its code, message and index, uniform-albedo detection, the leaf rule, dropping the
@@ -998,8 +1089,8 @@ int cvr_set_medium_scene_gradient(cvr_ctx* ctx, const cvr_scene* scene, const cv
  * With a clip set the host uploads cvr_set_medium and cvr_set_medium_sparse return
  * CVR_ERR_UNSUPPORTED and keep the previous medium; cvr_share_medium shares whatever the source
  * built, with its clip information.
- * Not supported: cuts at ray level (sub-voxel smooth cut surfaces), per-voxel mask or label
- * volumes, clipping of cvr_features, cvr_field_stats or cvr_field_histogram (they still see the
+ * Not supported: cuts at ray level (sub-voxel smooth cut surfaces), per-voxel mask volumes
+ * (a label volume with a row of density 0 hides a segment: CVR_HAS_LABELS), clipping of cvr_features, cvr_field_stats or cvr_field_histogram (they still see the
  * whole field), the host uploads, inverted or unioned regions. */
 #define CVR_HAS_CLIP 1
 #define CVR_CLIP_MAX_PLANES 8
