@@ -12,6 +12,7 @@ from ._lib import (  # noqa: F401
     OPT_MOMENTS, AdaptiveDesc, AdaptiveResult, AdaptiveSession, block_error,
     DenoiseDesc, denoise_host,
     FeaturesDesc, DenoiseGuidedDesc, features_host, denoise_guided_host,
+    PreviewDesc, PREVIEW_UNSHADED, PREVIEW_HEADLIGHT, preview_host,
     DeviceMediumDesc, MediumLayout, DEVMED_SPARSE, DEVMED_CONST_ALBEDO, DEVMED_MAX_DENSITY,
     MEDIUM_ARRAYS, build_geometry,
     TransferDesc, ScalarMediumDesc, classify_host, raw_transfer_table,
@@ -33,6 +34,7 @@ __all__ = [
     "OPT_MOMENTS", "AdaptiveDesc", "AdaptiveResult", "AdaptiveSession", "block_error",
     "DenoiseDesc", "denoise_host",
     "FeaturesDesc", "DenoiseGuidedDesc", "features_host", "denoise_guided_host",
+    "PreviewDesc", "PREVIEW_UNSHADED", "PREVIEW_HEADLIGHT", "preview_host",
     "DeviceMediumDesc", "MediumLayout", "DEVMED_SPARSE", "DEVMED_CONST_ALBEDO", "DEVMED_MAX_DENSITY",
     "MEDIUM_ARRAYS", "build_geometry",
     "TransferDesc", "ScalarMediumDesc", "classify_host", "raw_transfer_table",

@@ -156,6 +156,30 @@ class DenoiseGuidedDesc(C.Structure):
         super().__init__(DenoiseDesc() if base is None else base, sigma_albedo, sigma_depth, sigma_alpha, flags)
 
 
+PREVIEW_UNSHADED, PREVIEW_HEADLIGHT = 1, 2
+
+
+class PreviewDesc(C.Structure):
+    """cvr_preview_desc: the shaded preview pass.  march: the feature pass's descriptor; light: the
+    direction towards the light (read only without PREVIEW_HEADLIGHT and PREVIEW_UNSHADED);
+    ambient, diffuse, specular: the Blinn-Phong weights, the specular exponent 2^shininess_log2;
+    knee: the gradient magnitude, in units of max_density per finest cell, at which a sample is
+    half lit; background: the colour behind the medium."""
+    _fields_ = [("march", FeaturesDesc), ("light", C.c_float * 3), ("ambient", C.c_float), ("diffuse", C.c_float),
+                ("specular", C.c_float), ("shininess_log2", C.c_uint32), ("knee", C.c_float),
+                ("background", C.c_float * 3), ("flags", C.c_uint32)]
+
+    def __init__(self, march: Optional[FeaturesDesc] = None, light=None, ambient=0.3, diffuse=0.7, specular=0.2,
+                 shininess_log2=4, knee=0.05, background=(0.0, 0.0, 0.0), flags=None):
+        """flags None: PREVIEW_HEADLIGHT unless a light is given."""
+        if flags is None:
+            flags = PREVIEW_HEADLIGHT if light is None else 0
+        light = (0.0, 0.0, 0.0) if light is None else light
+        super().__init__(FeaturesDesc() if march is None else march, (C.c_float * 3)(*[float(v) for v in light]),
+                         ambient, diffuse, specular, shininess_log2, knee,
+                         (C.c_float * 3)(*[float(v) for v in background]), flags)
+
+
 DEVMED_SPARSE, DEVMED_CONST_ALBEDO, DEVMED_MAX_DENSITY = 1, 2, 4
 # cvr_debug_copy_medium's arrays (CVR_MEDIUM_*), by index
 MEDIUM_ARRAYS = ("density", "albedo", "cells", "bounds", "leaf_table", "leaf_density", "leaf_albedo", "cell_slots",
@@ -402,6 +426,9 @@ def load() -> C.CDLL:
                                     P, P]),
         "cvr_features_buffers": (I32, [P, C.POINTER(FeaturesDesc), P, P]),
         "cvr_features": (I32, [P, C.POINTER(FeaturesDesc), P, P, C.c_size_t]),
+        "cvr_preview_host": (I32, [C.POINTER(MediumDesc), FP, FP, FP, U32, U32, U32, U32, I32, C.POINTER(PreviewDesc), P]),
+        "cvr_preview_buffers": (I32, [P, C.POINTER(PreviewDesc), P]),
+        "cvr_preview": (I32, [P, C.POINTER(PreviewDesc), P, C.c_size_t]),
         "cvr_denoise_guided_host": (I32, [P, P, U32, U32, U32, P, C.POINTER(DenoiseGuidedDesc), P, P, P, P]),
         "cvr_denoise_guided_buffers": (I32, [P, P, P, U32, U32, U32, P, C.POINTER(DenoiseGuidedDesc), P, P, P, P]),
         "cvr_denoise_guided": (I32, [P, C.POINTER(DenoiseGuidedDesc), C.POINTER(FeaturesDesc), U32, P, C.c_size_t]),
@@ -560,6 +587,22 @@ def features_host(medium: "MediumDesc", inv_view, raster_to_view, full_res, tile
     _check(load().cvr_features_host(C.byref(medium), _fp(iv), _fp(r2v), _fp(fr), w, h, int(offset[0]), int(offset[1]),
                                     int(world_to_aabb), C.byref(desc), rgba.ctypes.data, depth.ctypes.data))
     return rgba, depth
+
+
+def preview_host(medium: "MediumDesc", inv_view, raster_to_view, full_res, tile=None, offset=(0, 0),
+                 world_to_aabb: int = 0, desc: Optional[PreviewDesc] = None) -> np.ndarray:
+    """The shaded preview's written statement on the CPU (cvr_preview_host; no GPU) on a dense
+    medium's host arrays, features_host's arguments -> rgba (h, w, 4): the composited colour over
+    the background and the opacity.  Context.preview returns the same bits."""
+    iv = np.ascontiguousarray(inv_view, dtype=np.float32).reshape(12)
+    r2v = np.ascontiguousarray(raster_to_view, dtype=np.float32).reshape(2)
+    fr = np.asarray(full_res, dtype=np.float32).reshape(2)
+    w, h = (int(full_res[0]), int(full_res[1])) if tile is None else (int(tile[0]), int(tile[1]))
+    desc = PreviewDesc() if desc is None else desc
+    rgba = np.zeros((max(h, 0), max(w, 0), 4), np.float32)
+    _check(load().cvr_preview_host(C.byref(medium), _fp(iv), _fp(r2v), _fp(fr), w, h, int(offset[0]), int(offset[1]),
+                                   int(world_to_aabb), C.byref(desc), rgba.ctypes.data))
+    return rgba
 
 
 def _transfer_desc(table, lo, hi, ceil, density_u):
@@ -1639,6 +1682,27 @@ class Context:
         floats or None; each an int device address or an object with data_ptr() (a torch tensor)."""
         desc = FeaturesDesc() if desc is None else desc
         self._c(load().cvr_features_buffers(self._h, C.byref(desc), _device_ptr(out_rgba), _device_ptr(out_depth)))
+
+    def preview(self, desc: Optional[PreviewDesc] = None, host_ptr=None) -> np.ndarray:
+        """The shaded preview of the context's medium, camera, resolution and offset (cvr_preview):
+        rgba (h, w, 4), the bits of preview_host.  Synchronous; the context is only read.  Available
+        inside an adaptive session.  host_ptr: a PinnedImage the kernel stores into (returned as its
+        array), or None for a new numpy array."""
+        desc = PreviewDesc() if desc is None else desc
+        w, h = self.resolution
+        if isinstance(host_ptr, PinnedImage):
+            self._c(load().cvr_preview(self._h, C.byref(desc), host_ptr.ptr, host_ptr.floats))
+            return host_ptr.array
+        rgba = np.zeros((h, w, 4), np.float32)
+        self._c(load().cvr_preview(self._h, C.byref(desc), C.c_void_p(rgba.ctypes.data), rgba.size))
+        return rgba
+
+    def preview_buffers(self, out_rgba, desc: Optional[PreviewDesc] = None):
+        """The shaded preview into a device buffer (cvr_preview_buffers), asynchronous on the
+        context's stream: out_rgba tile_w * tile_h * 4 floats (16-byte aligned), an int device
+        address or an object with data_ptr() (a torch tensor)."""
+        desc = PreviewDesc() if desc is None else desc
+        self._c(load().cvr_preview_buffers(self._h, C.byref(desc), _device_ptr(out_rgba)))
 
     def denoise_guided(self, desc: Optional[DenoiseGuidedDesc] = None, n_samples: Optional[int] = None,
                        features: Optional[FeaturesDesc] = None, host_ptr=None) -> np.ndarray:

@@ -223,6 +223,15 @@ void free_environment(cvr_ctx* c);
 // entry points check (state, descriptor, tile), and the launch on the context's stream
 int features_check(cvr_ctx* c, const cvr_features_desc* d);
 int features_launch(cvr_ctx* c, const cvr_features_desc* d, float4* rgba, float* depth);
+// Its parts, for the passes that march as it does (cvr_preview_api.cpp): the descriptor's and the
+// tile's checks (err may be null), the camera and tile of a FeatureParams, and the whole
+// FeatureParams of a context that features_check has passed
+struct FeatureParams;
+int features_desc_check(std::string* err, const cvr_features_desc* d);
+int features_tile_check(std::string* err, uint32_t w, uint32_t h);
+void features_set_view(FeatureParams& P, const float inv_view[12], const float r2v[2], const float full_res[2],
+                       uint32_t tile_w, uint32_t tile_h, uint32_t off_x, uint32_t off_y);
+FeatureParams features_ctx_params(const cvr_ctx* c, const cvr_features_desc* d);
 // f32 -> binary16 -> f32, round to nearest even, subnormals kept (CVR_OPT_MEDIUM_FORMAT 1)
 float half_round1(float f);
 // first finite value of v[0..n) (of every `stride`-th group's first `take` values) that rounds to +-inf

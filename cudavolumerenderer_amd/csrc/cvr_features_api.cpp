@@ -10,9 +10,7 @@
 
 using cvr::set_err;
 
-namespace {
-
-int check_desc(std::string* err, const cvr_features_desc* d) {
+int cvr::features_desc_check(std::string* err, const cvr_features_desc* d) {
   if (!d) return set_err(err, CVR_ERR_INVALID, "NULL features descriptor");
   if (!(d->step >= 0.125f && d->step <= 8.0f))
     return set_err(err, CVR_ERR_INVALID, "features: step %g not in [1/8, 8]", (double)d->step);
@@ -24,14 +22,14 @@ int check_desc(std::string* err, const cvr_features_desc* d) {
   return CVR_OK;
 }
 
-int check_tile(std::string* err, uint32_t w, uint32_t h) {
+int cvr::features_tile_check(std::string* err, uint32_t w, uint32_t h) {
   if (w == 0 || h == 0 || (uint64_t)w * h > (1ull << 24))
     return set_err(err, CVR_ERR_INVALID, "features: a %ux%u tile (1 to 2^24 pixels)", w, h);
   return CVR_OK;
 }
 
-void set_view(cvr::FeatureParams& P, const float inv_view[12], const float r2v[2], const float full_res[2],
-              uint32_t tile_w, uint32_t tile_h, uint32_t off_x, uint32_t off_y) {
+void cvr::features_set_view(cvr::FeatureParams& P, const float inv_view[12], const float r2v[2],
+                            const float full_res[2], uint32_t tile_w, uint32_t tile_h, uint32_t off_x, uint32_t off_y) {
   for (int i = 0; i < 12; ++i) P.M[i] = inv_view[i];
   P.r2v[0] = r2v[0], P.r2v[1] = r2v[1];
   P.full_res[0] = full_res[0], P.full_res[1] = full_res[1];
@@ -40,30 +38,28 @@ void set_view(cvr::FeatureParams& P, const float inv_view[12], const float r2v[2
 }
 
 // The pass for the context's medium, camera, tile and offset (checked: ready, desc valid)
-cvr::FeatureParams ctx_params(const cvr_ctx* c, const cvr_features_desc* d) {
+cvr::FeatureParams cvr::features_ctx_params(const cvr_ctx* c, const cvr_features_desc* d) {
   cvr::FeatureParams P{};
   const uint32_t res[3] = {c->m.rx, c->m.ry, c->m.rz};
   const float bmin[3] = {c->m.bmin.x, c->m.bmin.y, c->m.bmin.z}, bmax[3] = {c->m.bmax.x, c->m.bmax.y, c->m.bmax.z};
   cvr::feature_geometry(P, res, bmin, bmax, c->m.scale, c->world_to_aabb, d->step, d->t_stop, d->max_steps);
-  set_view(P, c->inv_view, c->r2v, c->full_res, c->tile_w, c->tile_h, c->off[0], c->off[1]);
+  features_set_view(P, c->inv_view, c->r2v, c->full_res, c->tile_w, c->tile_h, c->off[0], c->off[1]);
   return P;
 }
-
-}  // namespace
 
 int cvr::features_check(cvr_ctx* c, const cvr_features_desc* d) {
   if (!c->have_medium) return set_err(&c->err, CVR_ERR_STATE, "medium not set (cvr_set_medium)");
   if (!c->have_camera) return set_err(&c->err, CVR_ERR_STATE, "camera not set (cvr_set_camera)");
   if (c->tile_w == 0 || c->tile_h == 0) return set_err(&c->err, CVR_ERR_STATE, "resolution not set");
-  int r = check_desc(&c->err, d);
+  int r = features_desc_check(&c->err, d);
   if (r) return r;
-  return check_tile(&c->err, c->tile_w, c->tile_h);
+  return features_tile_check(&c->err, c->tile_w, c->tile_h);
 }
 
 int cvr::features_launch(cvr_ctx* c, const cvr_features_desc* d, float4* rgba, float* depth) {
   cvr::MediumParams m = c->m;
   if (!c->empty_mask) m.emask = nullptr;  // CVR_OPT_EMPTY_MASK 0: every point loads its brick word
-  HIP_TRY(c, cvr::launch_features(m, ctx_params(c, d), rgba, depth, c->stream));
+  HIP_TRY(c, cvr::launch_features(m, features_ctx_params(c, d), rgba, depth, c->stream));
   return CVR_OK;
 }
 
@@ -79,13 +75,13 @@ int cvr_features_host(const cvr_medium_desc* medium, const float inv_view[12], c
     return set_err(nullptr, CVR_ERR_INVALID, "empty grid");
   if (world_to_aabb != 0 && world_to_aabb != 1)
     return set_err(nullptr, CVR_ERR_INVALID, "features: world_to_aabb must be 0 or 1");
-  int r = check_desc(nullptr, desc);
+  int r = cvr::features_desc_check(nullptr, desc);
   if (r) return r;
-  if ((r = check_tile(nullptr, tile_w, tile_h))) return r;
+  if ((r = cvr::features_tile_check(nullptr, tile_w, tile_h))) return r;
   cvr::FeatureParams P{};
   cvr::feature_geometry(P, medium->res, medium->box_min, medium->box_max, medium->scale, world_to_aabb, desc->step,
                         desc->t_stop, desc->max_steps);
-  set_view(P, inv_view, raster_to_view, full_res, tile_w, tile_h, off_x, off_y);
+  cvr::features_set_view(P, inv_view, raster_to_view, full_res, tile_w, tile_h, off_x, off_y);
   const cvr::FeatureHostTexels tex{medium->density, medium->albedo, medium->res[0], medium->res[1]};
   for (uint32_t y = 0; y < tile_h; ++y)
     for (uint32_t x = 0; x < tile_w; ++x) {

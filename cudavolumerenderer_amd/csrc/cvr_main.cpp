@@ -20,6 +20,9 @@
 //   --features [--feature-step F] (also write the primary-ray feature buffers, cvr_features, as
 //   <output>_albedo.hdr, <output>_alpha.hdr and <output>_depth.hdr), --denoise-guided
 //   [--guide-sigma A Z O] (--denoise through the feature-guided filter, cvr_denoise_guided)
+//   --preview FILE [--preview-light X Y Z] [--preview-shading A D S K] [--preview-knee F]
+//   [--preview-background R G B] [--preview-unshaded] (also write the shaded emission-absorption
+//   preview, cvr_preview, as FILE; with --iterations 0 without a render)
 //   --field-stats, --histogram FILE [--histogram-bins N [M]], --gradient-range auto (the value range,
 //   largest gradient magnitude and value-gradient histogram of a Raw scene's bytes, found on the
 //   device: cvr_field_stats, cvr_field_histogram; with --iterations 0 without a render)
@@ -71,6 +74,13 @@ struct Options {
   unsigned denoise_passes = 5;
   bool features = false;        // --features given
   float feature_step = 1.0f;
+  std::string preview_file;     // --preview FILE
+  std::vector<float> preview_light;  // --preview-light X Y Z (none: the headlight)
+  float preview_shading[3] = {0.3f, 0.7f, 0.2f};  // --preview-shading A D S K: ambient, diffuse, specular ...
+  unsigned preview_shininess_log2 = 4;            // ... and the exponent's log2
+  float preview_knee = 0.05f;
+  float preview_background[3] = {0.0f, 0.0f, 0.0f};
+  bool preview_unshaded = false;
   bool denoise_guided = false;  // --denoise-guided given
   float guide_sigma[3] = {0.4f, 0.1f, 0.4f};
   std::vector<float> default_albedo;
@@ -171,6 +181,15 @@ void usage() {
       "                                     <output>_albedo.hdr, <output>_alpha.hdr and <output>_depth.hdr (and\n"
       "                                     .pfm with --pfm); one tile on one device\n"
       "  --feature-step F (=1)              feature pass: march step in cells of the finest axis, 1/8..8\n"
+      "  --preview FILE                     also write the shaded preview (cvr_preview: one deterministic ray\n"
+      "                                     march per pixel, Blinn-Phong on the density gradient) as the\n"
+      "                                     Radiance file FILE (and FILE.pfm with --pfm); takes --feature-step;\n"
+      "                                     with --iterations 0 it runs without a render; one tile on one device\n"
+      "  --preview-light X Y Z              preview: the direction towards the light (default: a headlight)\n"
+      "  --preview-shading A D S K (=0.3 0.7 0.2 4)  preview: ambient, diffuse, specular, exponent 2^K (K 0..10)\n"
+      "  --preview-knee F (=0.05)           preview: gradient magnitude of a half-lit sample, in majorants per cell\n"
+      "  --preview-background R G B (=0 0 0)  preview: the colour behind the medium\n"
+      "  --preview-unshaded                 preview: plain emission-absorption compositing, no light\n"
       "  --denoise-sigma F (=4)             denoiser: width of the edge-stopping term in standard deviations\n"
       "  --denoise-passes N (=5)            denoiser: a-trous passes, 1..6 (pass k has step 2^k)\n"
       "  --rng-binding path|thread (=path)  regenerationSK: thread = the reference's Rng(seed + tid)\n"
@@ -302,6 +321,17 @@ int parse(int argc, char** argv, Options& o) {
     else if (a == "--guide-sigma") {
       for (int k = 0; k < 3; ++k) o.guide_sigma[k] = strtof(need("guide-sigma").c_str(), nullptr);
     } else if (a == "--features") o.features = true;
+    else if (a == "--preview") o.preview_file = need("preview");
+    else if (a == "--preview-light") {
+      o.preview_light.clear();
+      for (int k = 0; k < 3; ++k) o.preview_light.push_back(strtof(need("preview-light").c_str(), nullptr));
+    } else if (a == "--preview-shading") {
+      for (int k = 0; k < 3; ++k) o.preview_shading[k] = strtof(need("preview-shading").c_str(), nullptr);
+      o.preview_shininess_log2 = (unsigned)strtoul(need("preview-shading").c_str(), nullptr, 10);
+    } else if (a == "--preview-knee") o.preview_knee = strtof(need("preview-knee").c_str(), nullptr);
+    else if (a == "--preview-background") {
+      for (int k = 0; k < 3; ++k) o.preview_background[k] = strtof(need("preview-background").c_str(), nullptr);
+    } else if (a == "--preview-unshaded") o.preview_unshaded = true;
     else if (a == "--feature-step") o.feature_step = strtof(need("feature-step").c_str(), nullptr);
     else if (a == "--denoise-sigma") o.denoise_sigma = strtof(need("denoise-sigma").c_str(), nullptr);
     else if (a == "--denoise-passes") o.denoise_passes = (unsigned)strtoul(need("denoise-passes").c_str(), nullptr, 10);
@@ -920,8 +950,10 @@ int main(int argc, char** argv) {
         cvr_destroy(c);
         if (kr) return kr;
       }
-      cvr_free_image(env_rgb);
-      return 0;
+      if (o.preview_file.empty()) {
+        cvr_free_image(env_rgb);
+        return 0;
+      }
     }
   }
   const unsigned ntiles = o.tiles[0] * o.tiles[1];
@@ -931,11 +963,49 @@ int main(int argc, char** argv) {
     return 2;
   }
   const bool filtered = o.denoise || o.denoise_guided;
-  if ((o.adaptive || filtered || o.features) && (n_dev > 1 || ntiles > 1)) {
+  const bool preview = !o.preview_file.empty();
+  if ((o.adaptive || filtered || o.features || preview) && (n_dev > 1 || ntiles > 1)) {
     fprintf(stderr, "[ConfigParser] Error: %s renders one tile on one device (no --devices > 1, no "
                     "--number-of-tiles above 1 1)\n",
-            o.adaptive ? "--noise-target" : o.denoise ? "--denoise" : o.denoise_guided ? "--denoise-guided" : "--features");
+            o.adaptive ? "--noise-target" : o.denoise ? "--denoise" : o.denoise_guided ? "--denoise-guided"
+                                                                : o.features     ? "--features"
+                                                                                 : "--preview");
     return 2;
+  }
+  // --preview: the pass on ctx's medium and camera, written as FILE (and FILE.pfm with --pfm)
+  auto write_preview = [&](cvr_ctx* ctx) -> int {
+    cvr_preview_desc pd{};
+    pd.march = {o.feature_step, 1.0f / 256.0f, 4096u, 0u};
+    pd.ambient = o.preview_shading[0], pd.diffuse = o.preview_shading[1], pd.specular = o.preview_shading[2];
+    pd.shininess_log2 = o.preview_shininess_log2;
+    pd.knee = o.preview_knee;
+    for (int k = 0; k < 3; ++k) pd.background[k] = o.preview_background[k];
+    for (size_t k = 0; k < o.preview_light.size(); ++k) pd.light[k] = o.preview_light[k];
+    pd.flags = (o.preview_unshaded ? CVR_PREVIEW_UNSHADED : 0u) | (o.preview_light.empty() ? CVR_PREVIEW_HEADLIGHT : 0u);
+    std::vector<float> img((size_t)W * H * 4, 0.0f);
+    int rc = cvr_set_resolution(ctx, W, H);
+    if (!rc) rc = cvr_set_offset(ctx, 0, 0);
+    if (!rc) rc = cvr_preview(ctx, &pd, img.data(), img.size());
+    if (rc != CVR_OK) {
+      fprintf(stderr, "Error: %s\n", cvr_last_error(ctx));
+      return 1;
+    }
+    if (cvr_write_hdr(o.preview_file.c_str(), img.data(), W, H) != CVR_OK ||
+        (o.pfm && write_pfm(o.preview_file + ".pfm", img.data(), W, H))) {
+      fprintf(stderr, "Error: could not write %s%s\n", o.preview_file.c_str(), o.pfm ? " / .pfm" : "");
+      return 1;
+    }
+    printf("preview             : %s\n", o.preview_file.c_str());
+    return 0;
+  };
+  if (preview && o.iterations == 0) {  // the preview alone: no render, no image
+    cvr_ctx* c = make_ctx(devs[0], nullptr);
+    if (!c) return 1;
+    const int pr = write_preview(c);
+    cvr_destroy(c);
+    cvr_free_image(env_rgb);
+    cvr_scene_destroy(scene);
+    return pr;
   }
   if (filtered && !o.adaptive && o.iterations < 2) {
     fprintf(stderr, "[ConfigParser] Error: %s needs --iterations of at least 2 (a variance per pixel)\n",
@@ -1128,6 +1198,7 @@ int main(int argc, char** argv) {
         return 1;
       }
     }
+    if (preview && t == 0 && write_preview(ctxs[0])) return 1;
     struct cvr_medium_info mi;
     if (cvr_medium_info(ctxs[0], &mi) == CVR_OK)
       printf("medium on device    : %s, %llu bytes (density %llu, cells %llu, albedo %llu, bounds %llu)\n",

@@ -51,6 +51,8 @@ extern "C" {
  *              6 + CVR_HAS_LABELS (likewise): cvr_label_transfer_desc, cvr_labeled_medium_desc,
  *                  cvr_classify_labels_host, cvr_set_medium_labeled, cvr_medium_label_info,
  *                  cvr_set_medium_scene_labels
+ *              6 + CVR_HAS_PREVIEW (likewise): cvr_preview_desc, cvr_preview_host, cvr_preview_buffers,
+ *                  cvr_preview
  * CVR_ABI_VERSION is the ABI this header declares: 6, the library's (cvr_abi_version()).  ABI 6 only
  * adds to ABI 5, so a host that must also load an ABI 5 library can hold itself to that surface:
  * with CVR_ABI_TARGET defined as 5 before the include, the ABI 6 functions and structs are not
@@ -1355,7 +1357,7 @@ void cvr_free_image(float* rgb);
  * step in [1/8, 8], t_stop in [0, 1) (0: the march never stops early), max_steps 1..65536,
  * flags 0: else CVR_ERR_INVALID.  The defaults of the bindings and the CLI are 1, 1/256, 4096.
  * Not supported: a ray refracted at the GGX boundary (the ray is the straight camera ray; the
- * buffers are guides, not radiance), shading or lighting, temporal accumulation. */
+ * buffers are guides, not radiance), shading or lighting (CVR_HAS_PREVIEW below is the lit pass), temporal accumulation. */
 #define CVR_HAS_FEATURES 1
 typedef struct cvr_features_desc {
   float step;
@@ -1414,6 +1416,87 @@ int cvr_denoise_guided_buffers(cvr_ctx* ctx, const float* d_sum_rgba, const floa
  * n_samples and the adaptive session as cvr_denoise. */
 int cvr_denoise_guided(cvr_ctx* ctx, const cvr_denoise_guided_desc* desc, const cvr_features_desc* features,
                        uint32_t n_samples, float* host_rgba, size_t host_floats);
+
+/* ---- shaded preview (extension within ABI 6: CVR_HAS_PREVIEW) ----------- */
+/* The picture a volume viewer shows while tables, crops and clip planes are edited: a
+ * gradient-shaded emission-absorption rendering of the medium the context holds.  Per pixel, one
+ * deterministic ray march along the straight camera ray through the pixel's centre composites
+ * colour front to back, lights each contributing sample with Blinn-Phong shading on the gradient
+ * of the stored density and lays the result over a background colour.  No RNG, no walk, nothing
+ * of the context is written.  All arithmetic is fp32 +, -, x, /, sqrt in the order written here
+ * (correctly rounded, no fused multiply-add but the ones the density and albedo lookups of
+ * CVR_HAS_FEATURES name), so the device kernel and cvr_preview_host return the same bits (one
+ * definition compiles for both, cvr_preview.h).
+ * The ray, the chord, the steps and the per-step values p, rho, s, a, w and c (the albedo at p) are
+ * exactly those of CVR_HAS_FEATURES, with `march` as its descriptor.  From T = 1 and C = W = 0; a
+ * step with not s > 0 contributes nothing and computes no gradient.  For each contributing step:
+ *   With CVR_PREVIEW_UNSHADED: e = c.
+ *   Otherwise, the gradient: h_a = e_a / res_a (the three cell sizes delta is made from; e =
+ *     box_max - box_min), G_a = (rho(p + h_a u_a) - rho(p - h_a u_a)) / h_a, where u_a is the unit
+ *     vector of axis a and rho(.) the interpolated density of CVR_HAS_FEATURES at a point that
+ *     differs from p in component a only (one add or one subtract): six more lookups, with the
+ *     clamped taps and all.  m = sqrt((G_x G_x + G_y G_y) + G_z G_z).
+ *   If not m > 0 (zero or NaN): e = c.
+ *   Otherwise, shading: n_a = G_a / m (the outward normal is -n).
+ *     L = -d with CVR_PREVIEW_HEADLIGHT; without it the descriptor's light direction, normalised
+ *     once per call: light_a / sqrt((l_x l_x + l_y l_y) + l_z l_z).  V = -d.
+ *     nl = -((n_x L_x + n_y L_y) + n_z L_z), replaced by 0 unless nl > 0.
+ *     sp = 0.  If specular > 0: H = L + V, hh = sqrt((H_x H_x + H_y H_y) + H_z H_z); if hh > 0:
+ *       nh = -((n_x H_x + n_y H_y) + n_z H_z) / hh, replaced by 0 unless nh > 0, then squared
+ *       shininess_log2 times (nh = nh nh: the exponent 2^shininess_log2 without a pow, which
+ *       cvr_detmath.h does not have); sp = the result.
+ *     f = ambient + diffuse nl,  lit_c = f c_c + specular sp,
+ *     q = m / (m + knee_abs) with knee_abs = knee (max_density / min(min(h_x, h_y), h_z)) computed
+ *       once per call; max_density is the majorant in use: cvr_medium_info.max_density_eff on the
+ *       device, medium->max_density in cvr_preview_host.  The blend keeps homogeneous regions,
+ *       where the normal is noise, unlit.
+ *     e_c = (1 - q) c_c + q lit_c.
+ *   C_c += w e_c, W += w, T = T - w; the march ends after a step that leaves T < t_stop.
+ * Output: (C_r + T bg_r, C_g + T bg_g, C_b + T bg_b, W); a pixel without a chord gives
+ *   (bg_r, bg_g, bg_b, 0).
+ * The bit-equality contract is that of CVR_HAS_FEATURES: media with finite, non-negative density
+ * and finite albedo; independent of the storage (dense or sparse, CVR_OPT_CELLS, CVR_OPT_BOUNDS,
+ * CVR_OPT_UNIFORM_ALBEDO, CVR_OPT_EMPTY_MASK); a CVR_FORMAT_F16 medium gives the bits of the
+ * cvr_half_round-ed arrays with max_density_eff as max_density.  The six gradient lookups are
+ * skipped, exactly, where the feature pass's are (an empty super-brick, the zero cell leaf).
+ * Refused with CVR_ERR_INVALID, in this order: a NULL descriptor; `march` as cvr_features refuses
+ * it; flags other than the two below; ambient, diffuse or specular negative or not finite;
+ * shininess_log2 > 10; knee negative or not finite; a background component negative or not
+ * finite; without either flag, a light that is not finite or has zero length (the fp32 length as
+ * computed above: components so small or large that it is 0 or inf are refused as well).
+ * The defaults of the bindings and the CLI: CVR_PREVIEW_HEADLIGHT, ambient 0.3, diffuse 0.7,
+ * specular 0.2, shininess_log2 4, knee 0.05, a black background, march 1, 1/256, 4096.
+ * Not supported: shadows or ambient occlusion, the environment map as a light, more than one
+ * light, the refraction at the GGX boundary (the ray is the straight camera ray), gradients of
+ * the original scalar field (the pass sees the stored density only), tone mapping, the preview
+ * as a denoiser guide, more than one tile or device in the CLI, temporal accumulation. */
+#define CVR_HAS_PREVIEW 1
+#define CVR_PREVIEW_UNSHADED 1u  /* e = c: plain emission-absorption compositing, no gradient */
+#define CVR_PREVIEW_HEADLIGHT 2u /* the light shines along the ray: L = -d */
+typedef struct cvr_preview_desc {
+  cvr_features_desc march;
+  float light[3]; /* the direction towards the light, any length; not read with a flag set */
+  float ambient, diffuse, specular;
+  uint32_t shininess_log2; /* the specular exponent is 2^shininess_log2, 0..10 */
+  float knee;
+  float background[3];
+  uint32_t flags;
+} cvr_preview_desc; /* 64 bytes */
+/* Host only, no GPU: the written statement on a dense medium's host arrays; the arguments of
+ * cvr_features_host with this descriptor and no depth plane.  out_rgba: tile_w * tile_h * 4
+ * floats.  Refuses what cvr_features_host refuses. */
+int cvr_preview_host(const cvr_medium_desc* medium, const float inv_view[12], const float raster_to_view[2],
+                     const float full_res[2], uint32_t tile_w, uint32_t tile_h, uint32_t off_x, uint32_t off_y,
+                     int world_to_aabb, const cvr_preview_desc* desc, float* out_rgba);
+/* The pass on the context's medium (own or shared, any storage), camera, resolution and offset,
+ * into device memory or the device address of pinned host memory (16-byte aligned), asynchronous
+ * on the context's stream.  State as cvr_features_buffers: the context is only read; available
+ * between cvr_adaptive_begin and cvr_adaptive_end; no medium, camera or resolution: CVR_ERR_STATE. */
+int cvr_preview_buffers(cvr_ctx* ctx, const cvr_preview_desc* desc, float* d_out_rgba);
+/* The same into host memory (tile_w * tile_h * 4 floats; host_floats smaller: CVR_ERR_INVALID).
+ * Synchronous.  Pinned or registered memory is stored into by the kernel, other memory through a
+ * staging copy. */
+int cvr_preview(cvr_ctx* ctx, const cvr_preview_desc* desc, float* host_rgba, size_t host_floats);
 #endif /* CVR_ABI_VERSION >= 6 */
 
 /* Pinned, device-mapped host memory for cvr_render_share_to_host /
