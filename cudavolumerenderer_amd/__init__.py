@@ -13,6 +13,7 @@ from ._lib import (  # noqa: F401
     DenoiseDesc, denoise_host,
     FeaturesDesc, DenoiseGuidedDesc, features_host, denoise_guided_host,
     PreviewDesc, PREVIEW_UNSHADED, PREVIEW_HEADLIGHT, preview_host,
+    LightVolumeDesc, LightVolumeInfo, light_volume_host, preview_shadowed_host,
     DeviceMediumDesc, MediumLayout, DEVMED_SPARSE, DEVMED_CONST_ALBEDO, DEVMED_MAX_DENSITY,
     MEDIUM_ARRAYS, build_geometry,
     TransferDesc, ScalarMediumDesc, classify_host, raw_transfer_table,
@@ -35,6 +36,7 @@ __all__ = [
     "DenoiseDesc", "denoise_host",
     "FeaturesDesc", "DenoiseGuidedDesc", "features_host", "denoise_guided_host",
     "PreviewDesc", "PREVIEW_UNSHADED", "PREVIEW_HEADLIGHT", "preview_host",
+    "LightVolumeDesc", "LightVolumeInfo", "light_volume_host", "preview_shadowed_host",
     "DeviceMediumDesc", "MediumLayout", "DEVMED_SPARSE", "DEVMED_CONST_ALBEDO", "DEVMED_MAX_DENSITY",
     "MEDIUM_ARRAYS", "build_geometry",
     "TransferDesc", "ScalarMediumDesc", "classify_host", "raw_transfer_table",

@@ -180,6 +180,27 @@ class PreviewDesc(C.Structure):
                          (C.c_float * 3)(*[float(v) for v in background]), flags)
 
 
+class LightVolumeDesc(C.Structure):
+    """cvr_light_volume_desc: the light volume of the shadowed preview.  res: its nodes per axis
+    (x, y, z), each 1..1024; light: the direction towards the light, any length; march: the feature
+    pass's descriptor for the march from each node towards the light."""
+    _fields_ = [("res", C.c_uint32 * 3), ("flags", C.c_uint32), ("light", C.c_float * 3), ("reserved", C.c_float),
+                ("march", FeaturesDesc)]
+
+    def __init__(self, res=(1, 1, 1), light=(0.0, 0.0, 1.0), march: Optional[FeaturesDesc] = None, flags=0):
+        super().__init__((C.c_uint32 * 3)(*[int(v) for v in res]), flags, (C.c_float * 3)(*[float(v) for v in light]),
+                         0.0, FeaturesDesc() if march is None else march)
+
+
+class LightVolumeInfo(C.Structure):
+    """cvr_light_volume_info: the context's light volume (valid 0: none, everything 0)."""
+    _fields_ = [("res", C.c_uint32 * 3), ("valid", C.c_uint32), ("light", C.c_float * 3), ("reserved", C.c_float),
+                ("bytes", C.c_uint64)]
+
+    def as_dict(self):
+        return {"res": tuple(self.res), "valid": bool(self.valid), "light": tuple(self.light), "bytes": self.bytes}
+
+
 DEVMED_SPARSE, DEVMED_CONST_ALBEDO, DEVMED_MAX_DENSITY = 1, 2, 4
 # cvr_debug_copy_medium's arrays (CVR_MEDIUM_*), by index
 MEDIUM_ARRAYS = ("density", "albedo", "cells", "bounds", "leaf_table", "leaf_density", "leaf_albedo", "cell_slots",
@@ -429,6 +450,16 @@ def load() -> C.CDLL:
         "cvr_preview_host": (I32, [C.POINTER(MediumDesc), FP, FP, FP, U32, U32, U32, U32, I32, C.POINTER(PreviewDesc), P]),
         "cvr_preview_buffers": (I32, [P, C.POINTER(PreviewDesc), P]),
         "cvr_preview": (I32, [P, C.POINTER(PreviewDesc), P, C.c_size_t]),
+        "cvr_light_volume_host": (I32, [C.POINTER(MediumDesc), I32, C.POINTER(LightVolumeDesc), P]),
+        "cvr_build_light_volume": (I32, [P, C.POINTER(LightVolumeDesc)]),
+        "cvr_light_volume_default_res": (I32, [P, C.POINTER(U32)]),
+        "cvr_light_volume_info": (I32, [P, C.POINTER(LightVolumeInfo)]),
+        "cvr_copy_light_volume": (I32, [P, P, C.c_size_t]),
+        "cvr_clear_light_volume": (I32, [P]),
+        "cvr_preview_shadowed_host": (I32, [C.POINTER(MediumDesc), FP, FP, FP, U32, U32, U32, U32, I32,
+                                            C.POINTER(PreviewDesc), C.POINTER(LightVolumeDesc), P, C.c_float, P]),
+        "cvr_preview_shadowed_buffers": (I32, [P, C.POINTER(PreviewDesc), C.c_float, P]),
+        "cvr_preview_shadowed": (I32, [P, C.POINTER(PreviewDesc), C.c_float, P, C.c_size_t]),
         "cvr_denoise_guided_host": (I32, [P, P, U32, U32, U32, P, C.POINTER(DenoiseGuidedDesc), P, P, P, P]),
         "cvr_denoise_guided_buffers": (I32, [P, P, P, U32, U32, U32, P, C.POINTER(DenoiseGuidedDesc), P, P, P, P]),
         "cvr_denoise_guided": (I32, [P, C.POINTER(DenoiseGuidedDesc), C.POINTER(FeaturesDesc), U32, P, C.c_size_t]),
@@ -602,6 +633,37 @@ def preview_host(medium: "MediumDesc", inv_view, raster_to_view, full_res, tile=
     rgba = np.zeros((max(h, 0), max(w, 0), 4), np.float32)
     _check(load().cvr_preview_host(C.byref(medium), _fp(iv), _fp(r2v), _fp(fr), w, h, int(offset[0]), int(offset[1]),
                                    int(world_to_aabb), C.byref(desc), rgba.ctypes.data))
+    return rgba
+
+
+def light_volume_host(medium: "MediumDesc", desc: LightVolumeDesc, world_to_aabb: int = 0) -> np.ndarray:
+    """The light volume's written statement on the CPU (cvr_light_volume_host; no GPU) on a dense
+    medium's host arrays -> the transmittances (z, y, x) of desc.res.  Context.light_volume returns
+    the same bits."""
+    out = np.zeros(tuple(int(v) for v in desc.res)[::-1], np.float32)
+    _check(load().cvr_light_volume_host(C.byref(medium), int(world_to_aabb), C.byref(desc), out.ctypes.data))
+    return out
+
+
+def preview_shadowed_host(medium: "MediumDesc", inv_view, raster_to_view, full_res, volume_desc: LightVolumeDesc,
+                          volume, tile=None, offset=(0, 0), world_to_aabb: int = 0,
+                          desc: Optional[PreviewDesc] = None, shadow: float = 0.7) -> np.ndarray:
+    """The shadowed preview's written statement on the CPU (cvr_preview_shadowed_host; no GPU):
+    preview_host's arguments plus the light volume (light_volume_host's array and its descriptor)
+    and the shadow strength -> rgba (h, w, 4).  desc None: the default shading without the
+    headlight; its light is not read (the volume's is).  Context.preview_shadowed returns the same bits."""
+    iv = np.ascontiguousarray(inv_view, dtype=np.float32).reshape(12)
+    r2v = np.ascontiguousarray(raster_to_view, dtype=np.float32).reshape(2)
+    fr = np.asarray(full_res, dtype=np.float32).reshape(2)
+    w, h = (int(full_res[0]), int(full_res[1])) if tile is None else (int(tile[0]), int(tile[1]))
+    desc = PreviewDesc(flags=0) if desc is None else desc
+    vol = np.ascontiguousarray(volume, dtype=np.float32)
+    if vol.shape != tuple(int(v) for v in volume_desc.res)[::-1]:
+        raise CvrError(-1, f"preview_shadowed_host: volume {vol.shape}, expected (z, y, x) of res {tuple(volume_desc.res)}")
+    rgba = np.zeros((max(h, 0), max(w, 0), 4), np.float32)
+    _check(load().cvr_preview_shadowed_host(C.byref(medium), _fp(iv), _fp(r2v), _fp(fr), w, h, int(offset[0]),
+                                            int(offset[1]), int(world_to_aabb), C.byref(desc), C.byref(volume_desc),
+                                            vol.ctypes.data, float(shadow), rgba.ctypes.data))
     return rgba
 
 
@@ -1703,6 +1765,56 @@ class Context:
         address or an object with data_ptr() (a torch tensor)."""
         desc = PreviewDesc() if desc is None else desc
         self._c(load().cvr_preview_buffers(self._h, C.byref(desc), _device_ptr(out_rgba)))
+
+    def build_light_volume(self, light, res=None, march: Optional[FeaturesDesc] = None) -> LightVolumeDesc:
+        """The light volume of the context's medium for the direction `light` towards the light
+        (cvr_build_light_volume), asynchronous on the context's stream, into memory the context
+        owns; it replaces the previous one.  res (x, y, z): None for min(256, ceil(medium res / 2))
+        per axis.  Returns the descriptor used.  Available inside an adaptive session."""
+        if res is None:
+            r = (C.c_uint32 * 3)()
+            self._c(load().cvr_light_volume_default_res(self._h, r))
+            res = tuple(r)
+        desc = LightVolumeDesc(res, light, march)
+        self._c(load().cvr_build_light_volume(self._h, C.byref(desc)))
+        return desc
+
+    def light_volume_info(self) -> LightVolumeInfo:
+        """res, the normalised light, bytes and `valid` of the context's light volume."""
+        info = LightVolumeInfo()
+        self._c(load().cvr_light_volume_info(self._h, C.byref(info)))
+        return info
+
+    def light_volume(self) -> np.ndarray:
+        """The context's light volume (cvr_copy_light_volume): transmittances (z, y, x), the bits of
+        light_volume_host.  Synchronous."""
+        info = self.light_volume_info()
+        out = np.zeros(tuple(info.res)[::-1] if info.valid else (0, 0, 0), np.float32)
+        self._c(load().cvr_copy_light_volume(self._h, C.c_void_p(out.ctypes.data), out.size))
+        return out
+
+    def clear_light_volume(self):
+        self._c(load().cvr_clear_light_volume(self._h))
+
+    def preview_shadowed(self, desc: Optional[PreviewDesc] = None, shadow: float = 0.7, host_ptr=None) -> np.ndarray:
+        """Context.preview with the context's light volume (cvr_preview_shadowed): every
+        contributing sample's light scaled by 1 - shadow (1 - S), S the volume's value there; the
+        bits of preview_shadowed_host.  desc None: the default shading without the headlight; its
+        light is not read (the volume's is)."""
+        desc = PreviewDesc(flags=0) if desc is None else desc
+        w, h = self.resolution
+        if isinstance(host_ptr, PinnedImage):
+            self._c(load().cvr_preview_shadowed(self._h, C.byref(desc), float(shadow), host_ptr.ptr, host_ptr.floats))
+            return host_ptr.array
+        rgba = np.zeros((h, w, 4), np.float32)
+        self._c(load().cvr_preview_shadowed(self._h, C.byref(desc), float(shadow), C.c_void_p(rgba.ctypes.data), rgba.size))
+        return rgba
+
+    def preview_shadowed_buffers(self, out_rgba, desc: Optional[PreviewDesc] = None, shadow: float = 0.7):
+        """The shadowed preview into a device buffer (cvr_preview_shadowed_buffers), asynchronous on
+        the context's stream; out_rgba as preview_buffers'."""
+        desc = PreviewDesc(flags=0) if desc is None else desc
+        self._c(load().cvr_preview_shadowed_buffers(self._h, C.byref(desc), float(shadow), _device_ptr(out_rgba)))
 
     def denoise_guided(self, desc: Optional[DenoiseGuidedDesc] = None, n_samples: Optional[int] = None,
                        features: Optional[FeaturesDesc] = None, host_ptr=None) -> np.ndarray:

@@ -194,6 +194,7 @@ int cvr_destroy(cvr_ctx* c) {
   if (c->ad.d_counts) (void)hipFree(c->ad.d_counts);
   if (c->d_dn) (void)hipFree(c->d_dn);
   if (c->d_feat) (void)hipFree(c->d_feat);
+  if (c->d_lightvol) (void)hipFree(c->d_lightvol);
   if (c->ev_start) (void)hipEventDestroy(c->ev_start);
   if (c->ev_stop) (void)hipEventDestroy(c->ev_stop);
   if (c->own_stream) (void)hipStreamDestroy(c->own_stream);

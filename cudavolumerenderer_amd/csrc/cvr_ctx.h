@@ -206,6 +206,17 @@ struct cvr_ctx : cvr::Settings {
   cvr::EnvParams env{};
   cvr::EnvParams* d_env_hdr = nullptr;
   float env_max = 0.0f;  // the largest stored component
+  // cvr_build_light_volume: the context's own light volume (its own also when the medium is
+  // shared) and its record: the grid, the light as given and normalised, and the
+  // CVR_OPT_WORLD_TO_AABB it was built under.  The allocation is kept when the volume is dropped.
+  float* d_lightvol = nullptr;
+  size_t lightvol_floats = 0;  // floats the allocation holds
+  struct LightVol {
+    bool valid = false;
+    uint32_t res[3] = {0, 0, 0};
+    float light[3] = {0, 0, 0}, L[3] = {0, 0, 0};
+    int world_to_aabb = 0;
+  } lightvol;
 };
 
 namespace cvr {
@@ -232,6 +243,15 @@ int features_tile_check(std::string* err, uint32_t w, uint32_t h);
 void features_set_view(FeatureParams& P, const float inv_view[12], const float r2v[2], const float full_res[2],
                        uint32_t tile_w, uint32_t tile_h, uint32_t off_x, uint32_t off_y);
 FeatureParams features_ctx_params(const cvr_ctx* c, const cvr_features_desc* d);
+// The preview pass's (cvr_preview_api.cpp), for the pass that shadows it (cvr_shadow_api.cpp): the
+// descriptor's own fields in cvr.h's order (err may be null; check_light 0: the light is not
+// read, so not judged), and a PreviewParams' shading constants for a light (Q.F is filled)
+struct PreviewParams;
+int preview_shading_check(std::string* err, const cvr_preview_desc* d, bool check_light);
+void preview_set_shading(PreviewParams& Q, const cvr_preview_desc* d, const float light[3], float max_density);
+// The light volume is no longer the medium's: every call that replaces or drops the context's
+// medium calls this (the allocation stays for the next build; cvr_clear_light_volume frees it)
+inline void drop_light_volume(cvr_ctx* c) { c->lightvol.valid = false; }
 // f32 -> binary16 -> f32, round to nearest even, subnormals kept (CVR_OPT_MEDIUM_FORMAT 1)
 float half_round1(float f);
 // first finite value of v[0..n) (of every `stride`-th group's first `take` values) that rounds to +-inf

@@ -23,6 +23,9 @@
 //   --preview FILE [--preview-light X Y Z] [--preview-shading A D S K] [--preview-knee F]
 //   [--preview-background R G B] [--preview-unshaded] (also write the shaded emission-absorption
 //   preview, cvr_preview, as FILE; with --iterations 0 without a render)
+//   --preview-shadows F [--preview-shadow-res X Y Z] [--preview-shadow-step F] (the preview with
+//   directional shadows of strength F from a light volume, cvr_build_light_volume and
+//   cvr_preview_shadowed; needs --preview and --preview-light)
 //   --field-stats, --histogram FILE [--histogram-bins N [M]], --gradient-range auto (the value range,
 //   largest gradient magnitude and value-gradient histogram of a Raw scene's bytes, found on the
 //   device: cvr_field_stats, cvr_field_histogram; with --iterations 0 without a render)
@@ -81,6 +84,10 @@ struct Options {
   float preview_knee = 0.05f;
   float preview_background[3] = {0.0f, 0.0f, 0.0f};
   bool preview_unshaded = false;
+  float preview_shadows = 0.0f;              // --preview-shadows F: the strength ...
+  bool preview_shadows_set = false;          // ... and whether it was given
+  std::vector<unsigned> preview_shadow_res;  // --preview-shadow-res X Y Z (none: the default grid)
+  float preview_shadow_step = 1.0f;          // --preview-shadow-step F: the light volume's march step
   bool denoise_guided = false;  // --denoise-guided given
   float guide_sigma[3] = {0.4f, 0.1f, 0.4f};
   std::vector<float> default_albedo;
@@ -190,6 +197,10 @@ void usage() {
       "  --preview-knee F (=0.05)           preview: gradient magnitude of a half-lit sample, in majorants per cell\n"
       "  --preview-background R G B (=0 0 0)  preview: the colour behind the medium\n"
       "  --preview-unshaded                 preview: plain emission-absorption compositing, no light\n"
+      "  --preview-shadows F                preview: directional shadows of strength F in [0, 1] from a light volume\n"
+      "                                     (needs --preview and --preview-light)\n"
+      "  --preview-shadow-res X Y Z         preview: the light volume's nodes (default: half the medium's, at most 256)\n"
+      "  --preview-shadow-step F (=1)       preview: the step of the march towards the light, in cells\n"
       "  --denoise-sigma F (=4)             denoiser: width of the edge-stopping term in standard deviations\n"
       "  --denoise-passes N (=5)            denoiser: a-trous passes, 1..6 (pass k has step 2^k)\n"
       "  --rng-binding path|thread (=path)  regenerationSK: thread = the reference's Rng(seed + tid)\n"
@@ -332,6 +343,13 @@ int parse(int argc, char** argv, Options& o) {
     else if (a == "--preview-background") {
       for (int k = 0; k < 3; ++k) o.preview_background[k] = strtof(need("preview-background").c_str(), nullptr);
     } else if (a == "--preview-unshaded") o.preview_unshaded = true;
+    else if (a == "--preview-shadows") {
+      o.preview_shadows = strtof(need("preview-shadows").c_str(), nullptr);
+      o.preview_shadows_set = true;
+    } else if (a == "--preview-shadow-res") {
+      o.preview_shadow_res.clear();
+      for (int k = 0; k < 3; ++k) o.preview_shadow_res.push_back((unsigned)strtoul(need("preview-shadow-res").c_str(), nullptr, 10));
+    } else if (a == "--preview-shadow-step") o.preview_shadow_step = strtof(need("preview-shadow-step").c_str(), nullptr);
     else if (a == "--feature-step") o.feature_step = strtof(need("feature-step").c_str(), nullptr);
     else if (a == "--denoise-sigma") o.denoise_sigma = strtof(need("denoise-sigma").c_str(), nullptr);
     else if (a == "--denoise-passes") o.denoise_passes = (unsigned)strtoul(need("denoise-passes").c_str(), nullptr, 10);
@@ -603,6 +621,14 @@ int main(int argc, char** argv) {
   const int kernel = cvr_kernel_from_name(o.kernel.c_str());
   if (kernel == CVR_KERNEL_UNKNOWN) {  // RendererFactory.h:75-76 throws
     fprintf(stderr, "[RendererFactory] Error: kernel %s unknown\n", o.kernel.c_str());
+    return 2;
+  }
+  if ((o.preview_shadows_set || !o.preview_shadow_res.empty()) &&
+      (!o.preview_shadows_set || o.preview_file.empty() || o.preview_light.empty())) {
+    fprintf(stderr, "[ConfigParser] Error: %s\n",
+            !o.preview_shadows_set ? "--preview-shadow-res needs --preview-shadows F"
+                                   : "--preview-shadows needs --preview FILE and --preview-light X Y Z (the shadows' "
+                                     "directional light)");
     return 2;
   }
   cvr_scene* scene = nullptr;
@@ -985,7 +1011,17 @@ int main(int argc, char** argv) {
     std::vector<float> img((size_t)W * H * 4, 0.0f);
     int rc = cvr_set_resolution(ctx, W, H);
     if (!rc) rc = cvr_set_offset(ctx, 0, 0);
-    if (!rc) rc = cvr_preview(ctx, &pd, img.data(), img.size());
+    if (!rc && o.preview_shadows_set) {
+      cvr_light_volume_desc vd{};
+      for (int k = 0; k < 3; ++k) vd.light[k] = o.preview_light[k];
+      vd.march = {o.preview_shadow_step, 1.0f / 256.0f, 4096u, 0u};
+      if (o.preview_shadow_res.empty()) rc = cvr_light_volume_default_res(ctx, vd.res);
+      for (size_t k = 0; k < o.preview_shadow_res.size(); ++k) vd.res[k] = o.preview_shadow_res[k];
+      if (!rc) rc = cvr_build_light_volume(ctx, &vd);
+      if (!rc) rc = cvr_preview_shadowed(ctx, &pd, o.preview_shadows, img.data(), img.size());
+    } else if (!rc) {
+      rc = cvr_preview(ctx, &pd, img.data(), img.size());
+    }
     if (rc != CVR_OK) {
       fprintf(stderr, "Error: %s\n", cvr_last_error(ctx));
       return 1;

@@ -245,6 +245,7 @@ int dense_grids(cvr_ctx* c, size_t n, uint32_t fmt) {
   const FormatBytes B = format_bytes(fmt);
   free_sparse(c);
   c->have_medium = false;
+  drop_light_volume(c);
   if (n != c->n_voxels || !c->d_density || c->grids_format != fmt) {
     drop_dense(c);
     HIP_TRY(c, hipMalloc(&c->d_density, n * B.d));
@@ -407,11 +408,13 @@ int finish_sparse(cvr_ctx* c, const SparseBuild& b, DevTemps& tmp, DevmedTimer& 
   int r = b.fmt ? refuse_overflow() : CVR_OK;
   if (r) {
     c->have_medium = false;
+    drop_light_volume(c);
     return r;
   }
   // drop the previous medium (dense or sparse)
   drop_dense(c);
   c->have_medium = false;
+  drop_light_volume(c);
   free_sparse(c);
   tmp.keep(b.d_table);
   c->d_leaves = b.d_table;
@@ -829,6 +832,7 @@ int build_from_device(cvr_ctx* c, const DeviceBuild& d, const cvr::VoxelSource& 
     }
     if (bad_d || bad_a) {
       c->have_medium = false;
+      drop_light_volume(c);
       return set_err(&c->err, CVR_ERR_INVALID, "medium format half: %s value %g at index %zu rounds to infinity",
                      bad_d ? "density" : "albedo", (double)value, at);
     }
@@ -900,6 +904,7 @@ int cvr_set_medium(cvr_ctx* c, const cvr_medium_desc* md) {
     const bool bad_a = !bad_d && half_overflows(md->albedo, n, 4, 3, &at);
     if (bad_d || bad_a) {
       c->have_medium = false;
+      drop_light_volume(c);
       return set_err(&c->err, CVR_ERR_INVALID, "medium format half: %s value %g at index %zu rounds to infinity",
                      bad_d ? "density" : "albedo", (double)(bad_d ? md->density : md->albedo)[at], at);
     }
@@ -1457,6 +1462,7 @@ int cvr_share_medium(cvr_ctx* c, const cvr_ctx* src) {
   // drop this context's own medium; the kernels read the source's buffers
   drop_dense(c);
   free_sparse(c);
+  drop_light_volume(c);
   c->m = src->m;
   c->minfo = src->minfo;
   c->n_cell_leaves = src->n_cell_leaves;

@@ -46,16 +46,22 @@ inline void preview_constants(PreviewParams& Q, const float light[3], int headli
   Q.knee_abs = knee * (max_density / det_fminf(det_fminf(Q.h[0], Q.h[1]), Q.h[2]));
 }
 
-// The emitted colour of a contributing sample at p with albedo c, ray direction d.
+// The shading terms of a contributing sample at p, ray direction d: the gradient's magnitude m,
+// the diffuse cosine nl and the specular factor sp.  False when not m > 0 (a flat neighbourhood,
+// or a NaN): the sample is unlit and nl, sp are not set.
+struct PreviewTerms {
+  float m, nl, sp;
+};
 template <class Tex>
-CVR_HD F3 preview_shade(const Tex& tex, const PreviewParams& Q, F3 p, F3 d, F3 c) {
+CVR_HD bool preview_terms(const Tex& tex, const PreviewParams& Q, F3 p, F3 d, PreviewTerms& k) {
   const FeatureParams& P = Q.F;
   const float hx = Q.h[0], hy = Q.h[1], hz = Q.h[2];
   const float gx = (feat_density(tex, P, F3{p.x + hx, p.y, p.z}) - feat_density(tex, P, F3{p.x - hx, p.y, p.z})) / hx;
   const float gy = (feat_density(tex, P, F3{p.x, p.y + hy, p.z}) - feat_density(tex, P, F3{p.x, p.y - hy, p.z})) / hy;
   const float gz = (feat_density(tex, P, F3{p.x, p.y, p.z + hz}) - feat_density(tex, P, F3{p.x, p.y, p.z - hz})) / hz;
   const float m = det_sqrtf((gx * gx + gy * gy) + gz * gz);
-  if (!(m > 0.0f)) return c;  // a flat neighbourhood, or a NaN: unlit
+  k.m = m;
+  if (!(m > 0.0f)) return false;
   const float nx = gx / m, ny = gy / m, nz = gz / m;  // the outward normal is -n
   const float vx = -d.x, vy = -d.y, vz = -d.z;
   const float lx = Q.headlight ? vx : Q.L[0], ly = Q.headlight ? vy : Q.L[1], lz = Q.headlight ? vz : Q.L[2];
@@ -72,9 +78,19 @@ CVR_HD F3 preview_shade(const Tex& tex, const PreviewParams& Q, F3 p, F3 d, F3 c
       sp = nh;
     }
   }
-  const float f = Q.ambient + Q.diffuse * nl;
-  const float s = Q.specular * sp;
-  const float q = m / (m + Q.knee_abs), q1 = 1.0f - q;
+  k.nl = nl;
+  k.sp = sp;
+  return true;
+}
+
+// The emitted colour of a contributing sample at p with albedo c, ray direction d.
+template <class Tex>
+CVR_HD F3 preview_shade(const Tex& tex, const PreviewParams& Q, F3 p, F3 d, F3 c) {
+  PreviewTerms k;
+  if (!preview_terms(tex, Q, p, d, k)) return c;
+  const float f = Q.ambient + Q.diffuse * k.nl;
+  const float s = Q.specular * k.sp;
+  const float q = k.m / (k.m + Q.knee_abs), q1 = 1.0f - q;
   return F3{q1 * c.x + q * (f * c.x + s), q1 * c.y + q * (f * c.y + s), q1 * c.z + q * (f * c.z + s)};
 }
 

@@ -12,11 +12,11 @@
 using cvr::set_err;
 
 namespace {
-
 bool weight_ok(float v) { return std::isfinite(v) && !(v < 0.0f); }
+}  // namespace
 
 // The descriptor's own fields, in cvr.h's order (the NULL test and `march` come before)
-int check_shading(std::string* err, const cvr_preview_desc* d) {
+int cvr::preview_shading_check(std::string* err, const cvr_preview_desc* d, bool check_light) {
   if (d->flags & ~(CVR_PREVIEW_UNSHADED | CVR_PREVIEW_HEADLIGHT))
     return set_err(err, CVR_ERR_INVALID, "preview: unknown flags 0x%x", d->flags);
   if (!weight_ok(d->ambient) || !weight_ok(d->diffuse) || !weight_ok(d->specular))
@@ -28,7 +28,7 @@ int check_shading(std::string* err, const cvr_preview_desc* d) {
   for (int a = 0; a < 3; ++a)
     if (!weight_ok(d->background[a]))
       return set_err(err, CVR_ERR_INVALID, "preview: background %g must be finite and >= 0", (double)d->background[a]);
-  if (!(d->flags & (CVR_PREVIEW_UNSHADED | CVR_PREVIEW_HEADLIGHT))) {
+  if (check_light && !(d->flags & (CVR_PREVIEW_UNSHADED | CVR_PREVIEW_HEADLIGHT))) {
     // the length as preview_constants computes it: components that underflow or overflow it are refused too
     const float* l = d->light;
     const float len = det_sqrtf((l[0] * l[0] + l[1] * l[1]) + l[2] * l[2]);
@@ -38,18 +38,20 @@ int check_shading(std::string* err, const cvr_preview_desc* d) {
   return CVR_OK;
 }
 
-// Q.F is filled; max_density: the majorant in use
-void set_shading(cvr::PreviewParams& Q, const cvr_preview_desc* d, float max_density) {
+// Q.F is filled; light: the direction in use (the descriptor's for cvr_preview); max_density: the majorant in use
+void cvr::preview_set_shading(cvr::PreviewParams& Q, const cvr_preview_desc* d, const float light[3], float max_density) {
   const int headlight = (d->flags & (CVR_PREVIEW_UNSHADED | CVR_PREVIEW_HEADLIGHT)) != 0;  // (unshaded: no light is read)
-  cvr::preview_constants(Q, d->light, headlight, d->ambient, d->diffuse, d->specular, d->shininess_log2, d->knee,
+  cvr::preview_constants(Q, light, headlight, d->ambient, d->diffuse, d->specular, d->shininess_log2, d->knee,
                          d->background, max_density);
 }
+
+namespace {
 
 // State, descriptor and tile of a context call
 int preview_check(cvr_ctx* c, const cvr_preview_desc* d) {
   int r = cvr::features_check(c, d ? &d->march : nullptr);
   if (r) return r;
-  return check_shading(&c->err, d);
+  return cvr::preview_shading_check(&c->err, d, true);
 }
 
 int preview_launch(cvr_ctx* c, const cvr_preview_desc* d, float4* rgba) {
@@ -57,7 +59,7 @@ int preview_launch(cvr_ctx* c, const cvr_preview_desc* d, float4* rgba) {
   if (!c->empty_mask) m.emask = nullptr;  // CVR_OPT_EMPTY_MASK 0, as features_launch honours it
   cvr::PreviewParams Q{};
   Q.F = cvr::features_ctx_params(c, &d->march);
-  set_shading(Q, d, c->minfo.max_density_eff);
+  cvr::preview_set_shading(Q, d, d->light, c->minfo.max_density_eff);
   HIP_TRY(c, cvr::launch_preview(m, Q, !(d->flags & CVR_PREVIEW_UNSHADED), rgba, c->stream));
   return CVR_OK;
 }
@@ -79,13 +81,13 @@ int cvr_preview_host(const cvr_medium_desc* medium, const float inv_view[12], co
     return set_err(nullptr, CVR_ERR_INVALID, "preview: world_to_aabb must be 0 or 1");
   int r = cvr::features_desc_check(nullptr, &desc->march);
   if (r) return r;
-  if ((r = check_shading(nullptr, desc))) return r;
+  if ((r = cvr::preview_shading_check(nullptr, desc, true))) return r;
   if ((r = cvr::features_tile_check(nullptr, tile_w, tile_h))) return r;
   cvr::PreviewParams Q{};
   cvr::feature_geometry(Q.F, medium->res, medium->box_min, medium->box_max, medium->scale, world_to_aabb,
                         desc->march.step, desc->march.t_stop, desc->march.max_steps);
   cvr::features_set_view(Q.F, inv_view, raster_to_view, full_res, tile_w, tile_h, off_x, off_y);
-  set_shading(Q, desc, medium->max_density);
+  cvr::preview_set_shading(Q, desc, desc->light, medium->max_density);
   const cvr::FeatureHostTexels tex{medium->density, medium->albedo, medium->res[0], medium->res[1]};
   const bool shaded = !(desc->flags & CVR_PREVIEW_UNSHADED);
   for (uint32_t y = 0; y < tile_h; ++y)

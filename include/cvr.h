@@ -53,6 +53,10 @@ extern "C" {
  *                  cvr_set_medium_scene_labels
  *              6 + CVR_HAS_PREVIEW (likewise): cvr_preview_desc, cvr_preview_host, cvr_preview_buffers,
  *                  cvr_preview
+ *              6 + CVR_HAS_SHADOWS (likewise): cvr_light_volume_desc, cvr_light_volume_info,
+ *                  cvr_light_volume_host, cvr_build_light_volume, cvr_light_volume_default_res,
+ *                  cvr_copy_light_volume, cvr_clear_light_volume, cvr_preview_shadowed_host, cvr_preview_shadowed_buffers,
+ *                  cvr_preview_shadowed
  * CVR_ABI_VERSION is the ABI this header declares: 6, the library's (cvr_abi_version()).  ABI 6 only
  * adds to ABI 5, so a host that must also load an ABI 5 library can hold itself to that surface:
  * with CVR_ABI_TARGET defined as 5 before the include, the ABI 6 functions and structs are not
@@ -1466,8 +1470,8 @@ int cvr_denoise_guided(cvr_ctx* ctx, const cvr_denoise_guided_desc* desc, const 
  * computed above: components so small or large that it is 0 or inf are refused as well).
  * The defaults of the bindings and the CLI: CVR_PREVIEW_HEADLIGHT, ambient 0.3, diffuse 0.7,
  * specular 0.2, shininess_log2 4, knee 0.05, a black background, march 1, 1/256, 4096.
- * Not supported: shadows or ambient occlusion, the environment map as a light, more than one
- * light, the refraction at the GGX boundary (the ray is the straight camera ray), gradients of
+ * Not supported: ambient occlusion (directional shadows: CVR_HAS_SHADOWS below), the environment
+ * map as a light, more than one light, the refraction at the GGX boundary (the ray is the straight camera ray), gradients of
  * the original scalar field (the pass sees the stored density only), tone mapping, the preview
  * as a denoiser guide, more than one tile or device in the CLI, temporal accumulation. */
 #define CVR_HAS_PREVIEW 1
@@ -1497,6 +1501,107 @@ int cvr_preview_buffers(cvr_ctx* ctx, const cvr_preview_desc* desc, float* d_out
  * Synchronous.  Pinned or registered memory is stored into by the kernel, other memory through a
  * staging copy. */
 int cvr_preview(cvr_ctx* ctx, const cvr_preview_desc* desc, float* host_rgba, size_t host_floats);
+
+/* ---- shadowed preview (extension within ABI 6: CVR_HAS_SHADOWS) --------- */
+/* Directional shadows for the preview: a light volume holds, per node of a grid over the medium's
+ * box, the transmittance from the node to the box's surface towards the light; the shadowed
+ * preview scales the light of every contributing sample by the volume's trilinear value there.
+ * The volume is computed once per (medium, light): an edit of the camera, the shading weights or
+ * the shadow strength costs nothing extra, an edit of the table, the crop or the clip one rebuild.
+ * All arithmetic is fp32 +, -, x, /, sqrt in the order written here (correctly rounded, no fused
+ * multiply-add but the ones the density and albedo lookups and the trilinear of CVR_HAS_FEATURES
+ * name), so the kernels and the two host statements return the same bits (one definition compiles
+ * for both, cvr_shadow.h).
+ * Light volume.  res_a nodes per axis, each 1..1024, their product at most 2^27; fp32, x fastest.
+ *   L_a = light_a / sqrt((l_x l_x + l_y l_y) + l_z l_z): the direction towards the light,
+ *     normalised as CVR_HAS_PREVIEW normalises its light.
+ *   Node (i, j, k) sits at its cell's centre: p0_a = box_min_a + ((float)i_a + 0.5f) (e_a /
+ *     (float)res_a), e = box_max - box_min.
+ *   The march is that of CVR_HAS_FEATURES with `march` as its descriptor (delta from march.step
+ *   and the medium's cell sizes), along the ray p0 + t L: the chord is its slab test with o = p0,
+ *   d = L (t0 is 0 for a node inside); no chord: S = 1.  n = min(max_steps, ceil(t1 / delta)) (a
+ *   quotient that is NaN or inf marches max_steps).  From T = 1, for i < n: t = ((float)i + 0.5f)
+ *   delta, the march ends unless t < t1; p = p0 + t L (a multiply, then an add, per component);
+ *   rho = the interpolated density at p; s = (scale rho) delta; a step with not s > 0 is skipped;
+ *   otherwise T = T - T (s / (1 + s)), and the march ends after a step that leaves T < t_stop.
+ *   S = T.  The step opacity is the preview's own, so light and eye see the same medium.
+ * Lookup at a world point p: u_a = ((p_a - box_min_a) / e_a) (float)res_a - 0.5f, i_a =
+ *   floor(u_a) (as an int, saturating), f_a = u_a - (float)i_a, taps i_a and i_a + 1, each clamped
+ *   into [0, res_a - 1] as signed integers; the eight taps interpolate by the trilinear of
+ *   CVR_HAS_FEATURES (x, then y, then z).
+ * Shadowed preview: the pass of CVR_HAS_PREVIEW with, per contributing sample, S = lookup(p) and
+ *   V = 1 - shadow (1 - S), and e replaced:
+ *   With CVR_PREVIEW_UNSHADED, or if not m > 0: e_c = V c_c.
+ *   Otherwise: L is the light volume's; the descriptor's `light` is neither read nor judged.
+ *     f = ambient + (diffuse nl) V,  lit_c = f c_c + (specular sp) V,
+ *     e_c = (1 - q) (V c_c) + q lit_c.
+ *   w, W, T and the early stop are untouched.  Hence, exactly: shadow = 0 gives cvr_preview's bits
+ *   for the same descriptor with `light` set to the light volume descriptor's; the alpha plane is
+ *   cvr_preview's for every shadow; every rgb value is at most the one shadow = 0 gives (fp32
+ *   multiply and add are monotone and 0 <= V <= 1).
+ * The contract on the medium and the independence of the storage are those of CVR_HAS_FEATURES;
+ * the build skips, exactly, what the feature pass skips on a sparse medium.
+ * cvr_build_light_volume refuses with CVR_ERR_INVALID, in this order: a NULL descriptor; flags
+ * other than 0; a res axis of 0 or above 1024, or a product above 2^27; a light that is not
+ * finite or whose fp32 length as computed above is 0 or inf; `march` as cvr_features refuses it.
+ * No medium: CVR_ERR_STATE.
+ * The shadowed preview refuses, in this order: what cvr_preview refuses but for the light;
+ * CVR_PREVIEW_HEADLIGHT (shadows need the directional light); a shadow that is not finite or
+ * outside [0, 1] (CVR_ERR_INVALID); no light volume, then a stale one (CVR_ERR_STATE).  Every call
+ * that replaces or drops the context's medium drops the light volume: cvr_set_medium* (the
+ * cvr_set_medium_scene_* calls included), cvr_share_medium, and their failures that leave the
+ * context without a medium.  A volume built under another CVR_OPT_WORLD_TO_AABB than the one in
+ * force at preview time is stale.
+ * The defaults of the bindings and the CLI: res_a = min(256, ceil(medium res_a / 2)), shadow 0.7,
+ * march 1, 1/256, 4096.
+ * Not supported: ambient occlusion, shadows under the headlight, more than one light, a binary16
+ * light volume, partial rebuilds, the environment map as a light, shadows in cvr_features or the
+ * path tracer. */
+#define CVR_HAS_SHADOWS 1
+typedef struct cvr_light_volume_desc {
+  uint32_t res[3];
+  uint32_t flags; /* 0 */
+  float light[3]; /* the direction towards the light, any length */
+  float reserved;
+  cvr_features_desc march;
+} cvr_light_volume_desc; /* 48 bytes */
+struct cvr_light_volume_info {
+  uint32_t res[3];
+  uint32_t valid; /* 1: the context holds a volume of its medium (res, light, bytes are its); else all 0 */
+  float light[3]; /* normalised */
+  float reserved;
+  uint64_t bytes;
+}; /* 40 bytes */
+/* Host only, no GPU: the written statement on a dense medium's host arrays (as cvr_features_host
+ * reads them).  out: res_x * res_y * res_z floats.  A NULL pointer, an empty grid, world_to_aabb
+ * other than 0 / 1, and what cvr_build_light_volume refuses: CVR_ERR_INVALID. */
+int cvr_light_volume_host(const cvr_medium_desc* medium, int world_to_aabb, const cvr_light_volume_desc* desc,
+                          float* out);
+/* The light volume of the context's medium (own or shared, any storage), asynchronous on the
+ * context's stream, into memory the context owns (also when the medium is shared); it replaces
+ * the context's previous volume.  Honours CVR_OPT_EMPTY_MASK as cvr_features does.  Touches
+ * neither the medium nor the framebuffer: available between cvr_adaptive_begin and
+ * cvr_adaptive_end. */
+int cvr_build_light_volume(cvr_ctx* ctx, const cvr_light_volume_desc* desc);
+/* The default grid for the context's medium: res_a = min(256, ceil(medium res_a / 2)).  No medium: CVR_ERR_STATE. */
+int cvr_light_volume_default_res(const cvr_ctx* ctx, uint32_t res[3]);
+int cvr_light_volume_info(const cvr_ctx* ctx, struct cvr_light_volume_info* out);
+/* Synchronous.  No valid volume: CVR_ERR_STATE; fewer floats than nodes: CVR_ERR_INVALID. */
+int cvr_copy_light_volume(cvr_ctx* ctx, float* host, size_t host_floats);
+/* Drops the volume and frees its memory (waits for the context's stream). */
+int cvr_clear_light_volume(cvr_ctx* ctx);
+/* cvr_preview_host's arguments, the descriptor the volume was made with (cvr_light_volume_host),
+ * its array, and the shadow strength. */
+int cvr_preview_shadowed_host(const cvr_medium_desc* medium, const float inv_view[12], const float raster_to_view[2],
+                              const float full_res[2], uint32_t tile_w, uint32_t tile_h, uint32_t off_x,
+                              uint32_t off_y, int world_to_aabb, const cvr_preview_desc* desc,
+                              const cvr_light_volume_desc* volume_desc, const float* volume, float shadow,
+                              float* out_rgba);
+/* cvr_preview_buffers and cvr_preview with the context's light volume: the same destinations and
+ * state rules. */
+int cvr_preview_shadowed_buffers(cvr_ctx* ctx, const cvr_preview_desc* desc, float shadow, float* d_out_rgba);
+int cvr_preview_shadowed(cvr_ctx* ctx, const cvr_preview_desc* desc, float shadow, float* host_rgba,
+                         size_t host_floats);
 #endif /* CVR_ABI_VERSION >= 6 */
 
 /* Pinned, device-mapped host memory for cvr_render_share_to_host /
