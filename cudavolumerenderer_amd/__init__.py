@@ -15,7 +15,7 @@ from ._lib import (  # noqa: F401
     PreviewDesc, PREVIEW_UNSHADED, PREVIEW_HEADLIGHT, preview_host,
     LightVolumeDesc, LightVolumeInfo, light_volume_host, preview_shadowed_host,
     DeviceMediumDesc, MediumLayout, DEVMED_SPARSE, DEVMED_CONST_ALBEDO, DEVMED_MAX_DENSITY,
-    MEDIUM_ARRAYS, build_geometry,
+    MEDIUM_ARRAYS, build_geometry, wpool_rows,
     TransferDesc, ScalarMediumDesc, classify_host, raw_transfer_table,
     GradientTransferDesc, GradientMediumDesc, classify_gradient_host,
     LabelTransferDesc, LabeledMediumDesc, classify_labels_host,
@@ -38,7 +38,7 @@ __all__ = [
     "PreviewDesc", "PREVIEW_UNSHADED", "PREVIEW_HEADLIGHT", "preview_host",
     "LightVolumeDesc", "LightVolumeInfo", "light_volume_host", "preview_shadowed_host",
     "DeviceMediumDesc", "MediumLayout", "DEVMED_SPARSE", "DEVMED_CONST_ALBEDO", "DEVMED_MAX_DENSITY",
-    "MEDIUM_ARRAYS", "build_geometry",
+    "MEDIUM_ARRAYS", "build_geometry", "wpool_rows",
     "TransferDesc", "ScalarMediumDesc", "classify_host", "raw_transfer_table",
     "GradientTransferDesc", "GradientMediumDesc", "classify_gradient_host",
     "LabelTransferDesc", "LabeledMediumDesc", "classify_labels_host",

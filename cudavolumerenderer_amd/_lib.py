@@ -499,6 +499,8 @@ def load() -> C.CDLL:
         "cvr_trace_env": (I32, [P, U32, U32, C.POINTER(EnvRecord)]),
         "cvr_read_image": (I32, [C.c_char_p, C.POINTER(U32), C.POINTER(U32), C.POINTER(FP)]),
         "cvr_free_image": (None, [FP]),
+        "cvr_debug_wpool_rows": (I32, [C.POINTER(C.c_int32), U32, C.POINTER(U32)]),
+        "cvr_debug_last_wpool": (I32, [P, C.POINTER(C.c_int32), C.POINTER(U32)]),
     }
     # an older experiment build (tools' --lib, A/B against a previous commit) may lack newer entry
     # points; the in-tree library must export every one (tests/test_host_abi.py)
@@ -831,6 +833,16 @@ def build_geometry() -> dict:
     if out[15] != len(names):
         raise RuntimeError(f"cvr_debug_build_geometry fills {out[15]} entries, this binding knows {len(names)}")
     return dict(zip(names, (int(v) for v in out)))
+
+
+def wpool_rows() -> list:
+    """The wave-pool kernel instances the library ships, in table order, as (eps, waves, med, record,
+    flush) tuples of ints (cvr_debug_wpool_rows; no GPU needed)."""
+    n = C.c_uint32(0)
+    _check(load().cvr_debug_wpool_rows(None, 0, C.byref(n)))
+    rows = (C.c_int32 * (5 * n.value))()
+    _check(load().cvr_debug_wpool_rows(rows, n.value, C.byref(n)))
+    return [tuple(int(v) for v in rows[5 * i:5 * i + 5]) for i in range(n.value)]
 
 
 def field_geometry() -> dict:
@@ -1925,6 +1937,13 @@ class Context:
         b, f = C.c_uint32(0), C.c_uint32(0)
         self._c(load().cvr_frame_flush_info(self._h, C.byref(b), C.byref(f)))
         return b.value, f.value
+
+    def last_wpool(self):
+        """((eps, waves, med, record, flush), grid in waves) of the context's last wave-pool launch
+        (cvr_debug_last_wpool); CvrError -3 before any."""
+        inst, grid = (C.c_int32 * 5)(), C.c_uint32(0)
+        self._c(load().cvr_debug_last_wpool(self._h, inst, C.byref(grid)))
+        return tuple(int(v) for v in inst), grid.value
 
     def render_share_to_host(self, host_ptr: int, host_floats: int, width, height, n_tiles=(1, 1), iterations=20,
                              first_tile: int = 0, tile_stride: int = 1):

@@ -727,6 +727,30 @@ int cvr_trace_launch(cvr_ctx* c, cvr_path_record* out, uint64_t n_out) {
   return CVR_OK;
 }
 
+static void wpool_instance_ints(const cvr::WpoolInstance& k, int32_t out[5]) {
+  out[0] = k.eps;
+  out[1] = k.waves;
+  out[2] = k.med;
+  out[3] = k.record;
+  out[4] = k.flush;
+}
+
+int cvr_debug_wpool_rows(int32_t* rows, uint32_t capacity, uint32_t* count) {
+  if (!count || (capacity && !rows)) return set_err(nullptr, CVR_ERR_INVALID, "NULL argument");
+  std::vector<cvr::WpoolInstance> ids(capacity);
+  *count = cvr::wpool_rows(ids.data(), capacity);
+  for (uint32_t i = 0; i < capacity && i < *count; ++i) wpool_instance_ints(ids[i], rows + 5 * (size_t)i);
+  return CVR_OK;
+}
+
+int cvr_debug_last_wpool(const cvr_ctx* c, int32_t instance[5], uint32_t* grid_waves) {
+  if (!c || !instance || !grid_waves) return set_err(nullptr, CVR_ERR_INVALID, "NULL argument");
+  if (!c->last_wpool_valid) return set_err(nullptr, CVR_ERR_STATE, "no wave-pool launch yet");
+  wpool_instance_ints(c->last_wpool, instance);
+  *grid_waves = c->last_wpool_grid;
+  return CVR_OK;
+}
+
 int cvr_trace_paths(cvr_ctx* c, uint32_t first, uint32_t count, cvr_path_record* out) {
   if (!c || !out) return set_err(c ? &c->err : nullptr, CVR_ERR_INVALID, "NULL argument");
   CVR_NOT_IN_SESSION(c, "cvr_trace_paths");

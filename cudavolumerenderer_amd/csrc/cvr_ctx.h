@@ -169,6 +169,10 @@ struct cvr_ctx : cvr::Settings {
   cvr::FrameFlush flush_hdr{};
   bool flush_hdr_valid = false;  // d_flush holds flush_hdr
   uint32_t flush_last_blocks = 0, flush_fallbacks = 0;
+  // cvr_debug_last_wpool: the instance and the grid (in waves) of the last wave-pool launch that was enqueued
+  bool last_wpool_valid = false;
+  cvr::WpoolInstance last_wpool{};
+  uint32_t last_wpool_grid = 0;
 
   // CVR_OPT_MOMENTS: the owned framebuffer holds a second float4 per pixel behind the tile
   int moments = 0;

@@ -79,6 +79,9 @@ uint32_t wpool_slots(const WpoolInstance& k);
 // several wave-private pools per workgroup that share one LDS copy of the launch
 // parameters and the empty-region mask.  A wave-pool grid (in waves) is a multiple.
 uint32_t wpool_wpg(const WpoolInstance& k);
+// The instances the library ships, in table order (cvr_debug_wpool_rows; host only, no device): at most
+// `capacity` of them are written to out (which may be null when capacity is 0); returns their number.
+uint32_t wpool_rows(WpoolInstance* out, uint32_t capacity);
 // regenerationSK with the RNG bound to the persistent thread (CVR_OPT_RNG_BINDING 1):
 // `grid` one-wave workgroups, path ids from the launch's single queue head.
 hipError_t launch_regen_thread(const MediumParams& m, const LaunchParams& L, bool scatter_eps, uint32_t grid,

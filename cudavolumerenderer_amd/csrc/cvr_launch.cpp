@@ -738,6 +738,13 @@ int launch(cvr_ctx* c, const LaunchArgs& a) {
       L.frame_done = a.frame_done;
     }
     HIP_TRY(c, cvr::launch_wpool(launch_medium(c), L, q, grid, c->stream));
+    // cvr_debug_last_wpool: every wave-pool launch passes here (cvr_launch_render, cvr_trace_launch's with
+    // a.rec, cvr_render_frame's bands and its flushing launch with a.frame_done); an empty launch ran nothing
+    if (L.path_count > 0) {
+      c->last_wpool_valid = true;
+      c->last_wpool = k;
+      c->last_wpool_grid = grid;
+    }
   } else if (L.path_count > 0) {
     if ((r = wf_render(c, L, eps))) return r;
   }

@@ -1587,5 +1587,9 @@ hipError_t wpool_occupancy(const WpoolInstance& k, int* waves_per_cu) {
   *waves_per_cu *= (int)row.wpg;
   return e;
 }
+uint32_t wpool_rows(WpoolInstance* out, uint32_t capacity) {
+  for (uint32_t i = 0; i < capacity && i < (uint32_t)kWpoolRows; ++i) out[i] = kWpoolTable[i].id;
+  return (uint32_t)kWpoolRows;
+}
 
 }  // namespace cvr

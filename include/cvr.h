@@ -57,6 +57,7 @@ extern "C" {
  *                  cvr_light_volume_host, cvr_build_light_volume, cvr_light_volume_default_res,
  *                  cvr_copy_light_volume, cvr_clear_light_volume, cvr_preview_shadowed_host, cvr_preview_shadowed_buffers,
  *                  cvr_preview_shadowed
+ *              6 + CVR_HAS_WPOOL_DEBUG (likewise): cvr_debug_wpool_rows, cvr_debug_last_wpool
  * CVR_ABI_VERSION is the ABI this header declares: 6, the library's (cvr_abi_version()).  ABI 6 only
  * adds to ABI 5, so a host that must also load an ABI 5 library can hold itself to that surface:
  * with CVR_ABI_TARGET defined as 5 before the include, the ABI 6 functions and structs are not
@@ -1602,6 +1603,26 @@ int cvr_preview_shadowed_host(const cvr_medium_desc* medium, const float inv_vie
 int cvr_preview_shadowed_buffers(cvr_ctx* ctx, const cvr_preview_desc* desc, float shadow, float* d_out_rgba);
 int cvr_preview_shadowed(cvr_ctx* ctx, const cvr_preview_desc* desc, float shadow, float* host_rgba,
                          size_t host_floats);
+
+/* ---- which wave-pool kernel instance ran (tests; extension within ABI 6: CVR_HAS_WPOOL_DEBUG) -- */
+/* The wave pool (CVR_OPT_SCHEDULER 3) is one kernel compiled once per combination of scatter
+ * offset, register budget, medium layout and feature.  An instance is five ints:
+ *   [0] 1: a scatter's origin is moved back by eps (every kernel id but regenerationSK);
+ *   [1] waves per SIMD (CVR_OPT_WAVES: 3, 4, 5 or 6);
+ *   [2] the medium: layout 0 any dense medium, 1 sparse, 2 dense with cells and bounds, 3 the same
+ *       with a uniform albedo; or-ed with 4 naiveMK's walk, 8 CVR_OPT_COUNT_WORDS, 16 the half
+ *       format, 32 CVR_OPT_MOMENTS, 64 an environment map;
+ *   [3] 1: cvr_trace_launch's records;  [4] 1: cvr_render_frame's in-launch output. */
+#define CVR_HAS_WPOOL_DEBUG 1
+/* Debug, host only (no device is needed): the instances the library ships.  *count receives their
+ * number; the first min(capacity, *count) are written to rows, five ints each (rows may be NULL
+ * when capacity is 0, so a first call asks for the count). */
+int cvr_debug_wpool_rows(int32_t* rows, uint32_t capacity, uint32_t* count);
+/* Debug: the instance the context's last wave-pool launch ran (cvr_launch_render, cvr_trace_launch,
+ * cvr_render_frame and every other call that renders on this context) and that launch's grid in
+ * waves.  Written once the launch is enqueued; a launch that fails, an empty launch and a launch
+ * of another scheduler leave it as it was.  No wave-pool launch yet: CVR_ERR_STATE. */
+int cvr_debug_last_wpool(const cvr_ctx* ctx, int32_t instance[5], uint32_t* grid_waves);
 #endif /* CVR_ABI_VERSION >= 6 */
 
 /* Pinned, device-mapped host memory for cvr_render_share_to_host /

@@ -1,4 +1,5 @@
-"""Directions, map sizes and a rotation shared by the environment-map tests (plain numpy)."""
+"""Directions, map sizes, a rotation, a test map and the records' per-pixel sums shared by the
+environment-map tests (plain numpy)."""
 import itertools
 
 import numpy as np
@@ -18,3 +19,25 @@ def random_dirs(n, seed=5):
     rng = np.random.default_rng(seed)
     d = rng.standard_normal((n, 3))
     return (d / np.linalg.norm(d, axis=1, keepdims=True)).astype(np.float32)
+
+
+def env_image(W, H, seed=0, channels=3):
+    """A positive map with structure in both directions and a bright patch (a 'sun')."""
+    rng = np.random.default_rng(100 + seed + W)
+    yy, xx = np.mgrid[0:H, 0:W]
+    img = np.zeros((H, W, channels), np.float32)
+    for c in range(3):
+        img[..., c] = (0.2 + 0.8 * rng.random((H, W)) + np.sin(2 * np.pi * xx / W + c) ** 2 + yy / H).astype(np.float32)
+    img[H // 3, W // 2, :3] = (40.0, 30.0, 20.0)
+    if channels == 4:
+        img[..., 3] = -7.0  # ignored: never read into the stored texels
+    return img
+
+
+def record_sums(rec, tile, iters, field="C", square=False):
+    """fp64 per-pixel sums of the records' contributions (square: of their fp32 squares)."""
+    px = tile[0] * tile[1]
+    v = rec[field].astype(np.float32)
+    if square:
+        v = (v * v).astype(np.float32)
+    return v.astype(np.float64).reshape(iters, px, 3).sum(axis=0).reshape(tile[1], tile[0], 3)

@@ -130,8 +130,15 @@ def medium_params(case, **override):
     return p
 
 
-def n_paths(case):
-    return case.tile[0] * case.tile[1] * SAMPLES
+def at_tile(case, tile):
+    """The case's view rendered as an image of tile[0] x tile[1] pixels of its own (full = tile, no
+    offset): the same camera and parameters at another pixel count.  (A camera's raster_to_view depends
+    on the aspect alone, so a square case keeps its view at any square size.)"""
+    return case._replace(full=tuple(tile), tile=tuple(tile), offset=(0, 0))
+
+
+def n_paths(case, samples=SAMPLES):
+    return case.tile[0] * case.tile[1] * samples
 
 
 def make_oracle(oracle_mod, case, density=None, albedo=None, max_density=MAX_DENSITY, **override):

@@ -40,6 +40,18 @@ def assert_pixels_close(gpu, cpu, n_contrib, what=""):
                            f"at {np.unravel_index(np.argmax(diff - bound), diff.shape)}")
 
 
+def assert_sums_close(gpu, cpu, n, what):
+    """The summation bound with every pixel's own n (arrays (P, 3), n (P,))."""
+    ng, nc = np.isnan(gpu), np.isnan(cpu)
+    assert (ng == nc).all(), f"{what}: NaN pattern differs: gpu {ng.sum()} cpu {nc.sum()}"
+    g = np.where(ng, 0, gpu).astype(np.float64)
+    c = np.where(nc, 0, cpu).astype(np.float64)
+    bound = 2.0 * np.maximum(n - 1, 0)[:, None] * 2.0 ** -24 * np.maximum(np.abs(g), np.abs(c)) + 1e-30
+    diff = np.abs(g - c)
+    bad = diff > bound
+    assert not bad.any(), f"{what}: {bad.sum()} values out of tolerance; worst diff {diff.max()}"
+
+
 def oracle_for_scene(oracle_mod, scene):
     """The oracle over a loaded or synthetic scene (dense or leaf storage)."""
     if scene.is_sparse:

@@ -25,7 +25,7 @@ from concurrent.futures import ThreadPoolExecutor
 import numpy as np
 import pytest
 
-from parity_util import COUNTERS, NTHREADS, assert_counters_equal, oracle_for_scene
+from parity_util import COUNTERS, NTHREADS, assert_counters_equal, assert_sums_close, oracle_for_scene  # noqa: F401
 from test_sparse import CLOUD_SMALL
 
 pytestmark = pytest.mark.gpu
@@ -110,18 +110,6 @@ class Sums:
             self.s1.append(s1.copy())
             self.s2.append(s2.copy())
             self.cnt.append(cnt.copy())
-
-
-def assert_sums_close(gpu, cpu, n, what):
-    """The summation bound with every pixel's own n (arrays (P, 3), n (P,))."""
-    ng, nc = np.isnan(gpu), np.isnan(cpu)
-    assert (ng == nc).all(), f"{what}: NaN pattern differs: gpu {ng.sum()} cpu {nc.sum()}"
-    g = np.where(ng, 0, gpu).astype(np.float64)
-    c = np.where(nc, 0, cpu).astype(np.float64)
-    bound = 2.0 * np.maximum(n - 1, 0)[:, None] * 2.0 ** -24 * np.maximum(np.abs(g), np.abs(c)) + 1e-30
-    diff = np.abs(g - c)
-    bad = diff > bound
-    assert not bad.any(), f"{what}: {bad.sum()} values out of tolerance; worst diff {diff.max()}"
 
 
 def block_pixels(b):

@@ -18,7 +18,7 @@ import numpy as np
 import pytest
 import torch  # (imported before libcvr is loaded, as tests/test_gpu_denoise.py does)
 
-from envmap_util import ROT, SIZES, random_dirs, special_dirs
+from envmap_util import ROT, SIZES, env_image, random_dirs, record_sums, special_dirs
 from media import SCALE, dense_arrays, sparse_desc, sparse_small, staircase
 from parity_util import COUNTERS, assert_pixels_close
 
@@ -33,19 +33,6 @@ SEED = 3
 
 def bits(a):
     return np.ascontiguousarray(a, np.float32).view(np.uint32)
-
-
-def env_image(W, H, seed=0, channels=3):
-    """A positive map with structure in both directions and a bright patch (a 'sun')."""
-    rng = np.random.default_rng(100 + seed + W)
-    yy, xx = np.mgrid[0:H, 0:W]
-    img = np.zeros((H, W, channels), np.float32)
-    for c in range(3):
-        img[..., c] = (0.2 + 0.8 * rng.random((H, W)) + np.sin(2 * np.pi * xx / W + c) ** 2 + yy / H).astype(np.float32)
-    img[H // 3, W // 2, :3] = (40.0, 30.0, 20.0)
-    if channels == 4:
-        img[..., 3] = -7.0  # ignored: never read into the stored texels
-    return img
 
 
 def two_tone(W=16, H=8):
@@ -111,15 +98,6 @@ def records(ctx, iters, tile=TILE):
     ctx.set_iterations(iters)
     ctx.set_seed(SEED)
     return ctx.trace_env(0, tile[0] * tile[1] * iters)
-
-
-def record_sums(rec, tile, iters, field="C", square=False):
-    """fp64 per-pixel sums of the records' contributions (square: of their fp32 squares)."""
-    px = tile[0] * tile[1]
-    v = rec[field].astype(np.float32)
-    if square:
-        v = (v * v).astype(np.float32)
-    return v.astype(np.float64).reshape(iters, px, 3).sum(axis=0).reshape(tile[1], tile[0], 3)
 
 
 # ------------------------------------------------------ 1. the lookup alone --
