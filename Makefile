@@ -12,9 +12,9 @@ HIPFLAGS := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -ffp-contract=off \
             -fhip-fp32-correctly-rounded-divide-sqrt -Iinclude -I$(CSRC) -Wall
 OBJDIR ?= build/obj
 SRCS_HIP := $(CSRC)/cvr_kernels.hip $(CSRC)/cvr_persistent.hip $(CSRC)/cvr_pool.hip $(CSRC)/cvr_wpool.hip $(CSRC)/cvr_wavefront.hip \
-            $(CSRC)/cvr_denoise.hip $(CSRC)/cvr_medium_build.hip $(CSRC)/cvr_env.hip $(CSRC)/cvr_features.hip $(CSRC)/cvr_field.hip $(CSRC)/cvr_preview.hip $(CSRC)/cvr_shadow.hip
+            $(CSRC)/cvr_denoise.hip $(CSRC)/cvr_medium_build.hip $(CSRC)/cvr_env.hip $(CSRC)/cvr_features.hip $(CSRC)/cvr_field.hip $(CSRC)/cvr_preview.hip $(CSRC)/cvr_shadow.hip $(CSRC)/cvr_project.hip
 SRCS_CPP := $(CSRC)/cvr_api.cpp $(CSRC)/cvr_launch.cpp $(CSRC)/cvr_frame.cpp $(CSRC)/cvr_adaptive.cpp \
-            $(CSRC)/cvr_denoise_api.cpp $(CSRC)/cvr_medium.cpp $(CSRC)/cvr_environment.cpp $(CSRC)/cvr_features_api.cpp $(CSRC)/cvr_preview_api.cpp $(CSRC)/cvr_shadow_api.cpp $(CSRC)/cvr_field_api.cpp $(CSRC)/cvr_image_io.cpp $(CSRC)/cvr_scene.cpp $(CSRC)/cvr_vdb.cpp $(CSRC)/cvr_mhd.cpp $(CSRC)/cvr_xml.cpp
+            $(CSRC)/cvr_denoise_api.cpp $(CSRC)/cvr_medium.cpp $(CSRC)/cvr_environment.cpp $(CSRC)/cvr_features_api.cpp $(CSRC)/cvr_preview_api.cpp $(CSRC)/cvr_shadow_api.cpp $(CSRC)/cvr_field_api.cpp $(CSRC)/cvr_project_api.cpp $(CSRC)/cvr_image_io.cpp $(CSRC)/cvr_scene.cpp $(CSRC)/cvr_vdb.cpp $(CSRC)/cvr_mhd.cpp $(CSRC)/cvr_xml.cpp
 OBJS := $(patsubst $(CSRC)/%.hip,$(OBJDIR)/%.o,$(SRCS_HIP)) $(patsubst $(CSRC)/%.cpp,$(OBJDIR)/%.o,$(SRCS_CPP))
 HDRS := include/cvr.h include/cvr_detmath.h $(wildcard $(CSRC)/*.h)
 # Per-file flags, HIPFLAGS_<file name without .hip>; every rule that compiles a .hip file goes through
@@ -146,3 +146,5 @@ $(eval $(call host_asan,preview,cvr_preview_api cvr_features_api))
 # cvr_light_volume_host, cvr_preview_shadowed_host and their descriptors' checks (the march's and the shading's
 # checks are cvr_features_api.cpp's and cvr_preview_api.cpp's)
 $(eval $(call host_asan,shadow,cvr_shadow_api cvr_preview_api cvr_features_api))
+# cvr_field_project_host and the projection descriptor's checks
+$(eval $(call host_asan,project,cvr_project_api))

@@ -21,6 +21,7 @@ from ._lib import (  # noqa: F401
     LabelTransferDesc, LabeledMediumDesc, classify_labels_host,
     ClipDesc, CLIP_MAX_PLANES, clip_host, plane_from_box,
     FieldDesc, HistogramDesc, FieldStats, field_stats_host, field_histogram_host, field_geometry,
+    ProjectDesc, PROJECT_MAX, PROJECT_MIN, PROJECT_MEAN, PROJECT_ISO, PROJECT_HEADLIGHT, field_project_host,
     SCALAR_F32, SCALAR_U8, SCALAR_U16, SCALAR_I16, TF_CEIL, TF_DENSITY_U,
     EnvironmentDesc, EnvironmentInfo, ENV_HOST, ENV_DEVICE, ENV_RECORD_DTYPE, environment_eval_host,
     environment_eval_host_fn, read_image, rotation_y,
@@ -44,6 +45,7 @@ __all__ = [
     "LabelTransferDesc", "LabeledMediumDesc", "classify_labels_host",
     "ClipDesc", "CLIP_MAX_PLANES", "clip_host", "plane_from_box",
     "FieldDesc", "HistogramDesc", "FieldStats", "field_stats_host", "field_histogram_host", "field_geometry",
+    "ProjectDesc", "PROJECT_MAX", "PROJECT_MIN", "PROJECT_MEAN", "PROJECT_ISO", "PROJECT_HEADLIGHT", "field_project_host",
     "SCALAR_F32", "SCALAR_U8", "SCALAR_U16", "SCALAR_I16", "TF_CEIL", "TF_DENSITY_U",
     "EnvironmentDesc", "EnvironmentInfo", "ENV_HOST", "ENV_DEVICE", "ENV_RECORD_DTYPE", "environment_eval_host",
     "environment_eval_host_fn", "read_image", "rotation_y",

@@ -312,6 +312,40 @@ class HistogramDesc(C.Structure):
                 ("lo", C.c_float), ("hi", C.c_float), ("glo", C.c_float), ("ghi", C.c_float)]
 
 
+PROJECT_MAX, PROJECT_MIN, PROJECT_MEAN, PROJECT_ISO = 0, 1, 2, 3
+PROJECT_HEADLIGHT = 1
+_PROJECT_MODES = {"max": PROJECT_MAX, "min": PROJECT_MIN, "mean": PROJECT_MEAN, "iso": PROJECT_ISO}
+
+
+class ProjectDesc(C.Structure):
+    """cvr_project_desc: a projection of a raw scalar field.  mode: PROJECT_MAX, _MIN, _MEAN (shown
+    through the window lo..hi) or PROJECT_ISO (the first sample >= iso, its bracket bisected
+    `refine` times, lit by the field's gradient); box_min, box_max: the world box the field fills;
+    step in cells of the finest axis; light: the direction towards the light (read only for ISO
+    without PROJECT_HEADLIGHT); ambient, diffuse, specular, the exponent 2^shininess_log2;
+    colour: the projection's full-scale colour, the surface's colour; background."""
+    _fields_ = [("mode", C.c_uint32), ("flags", C.c_uint32), ("box_min", C.c_float * 3), ("box_max", C.c_float * 3),
+                ("step", C.c_float), ("max_steps", C.c_uint32), ("lo", C.c_float), ("hi", C.c_float),
+                ("iso", C.c_float), ("refine", C.c_uint32), ("light", C.c_float * 3), ("ambient", C.c_float),
+                ("diffuse", C.c_float), ("specular", C.c_float), ("shininess_log2", C.c_uint32),
+                ("colour", C.c_float * 3), ("background", C.c_float * 3), ("reserved", C.c_uint32)]
+
+    def __init__(self, mode=PROJECT_MAX, box_min=(-0.5, -0.5, -0.5), box_max=(0.5, 0.5, 0.5), lo=0.0, hi=1.0, iso=0.5,
+                 step=1.0, max_steps=4096, refine=4, light=None, ambient=0.3, diffuse=0.7, specular=0.2,
+                 shininess_log2=4, colour=(1.0, 1.0, 1.0), background=(0.0, 0.0, 0.0), flags=None):
+        """mode: a PROJECT_* value or "max", "min", "mean", "iso"; flags None: PROJECT_HEADLIGHT unless
+        a light is given."""
+        if flags is None:
+            flags = PROJECT_HEADLIGHT if light is None else 0
+        light = (0.0, 0.0, 0.0) if light is None else light
+        f3 = lambda v: (C.c_float * 3)(*[float(x) for x in v])  # noqa: E731
+        super().__init__(_PROJECT_MODES.get(mode, mode), flags, f3(box_min), f3(box_max), step, max_steps, lo, hi, iso,
+                         refine, f3(light), ambient, diffuse, specular, shininess_log2, f3(colour), f3(background), 0)
+
+
+assert C.sizeof(ProjectDesc) == 112
+
+
 # What field_stats_host and Context.field_stats return: numpy float32 vmin, vmax, gmax (their bits
 # are the library's) and the two NaN counts
 FieldStats = namedtuple("FieldStats", "vmin vmax gmax nan_values nan_gradients")
@@ -489,6 +523,9 @@ def load() -> C.CDLL:
         "cvr_field_stats": (I32, [P, C.POINTER(FieldDesc), C.POINTER(FieldStatsStruct)]),
         "cvr_field_histogram": (I32, [P, C.POINTER(FieldDesc), C.POINTER(HistogramDesc), P]),
         "cvr_field_histogram_buffers": (I32, [P, C.POINTER(FieldDesc), C.POINTER(HistogramDesc), P]),
+        "cvr_field_project_host": (I32, [C.POINTER(FieldDesc), C.POINTER(ProjectDesc), FP, FP, FP, U32, U32, U32, U32, P, P, P]),
+        "cvr_field_project_buffers": (I32, [P, C.POINTER(FieldDesc), C.POINTER(ProjectDesc), P, P, P]),
+        "cvr_field_project": (I32, [P, C.POINTER(FieldDesc), C.POINTER(ProjectDesc), P, P, P, C.c_size_t]),
         "cvr_debug_field_geometry": (I32, [C.POINTER(U32)]),
         "cvr_set_environment": (I32, [P, C.POINTER(EnvironmentDesc)]),
         "cvr_clear_environment": (I32, [P]),
@@ -908,6 +945,27 @@ def field_histogram_host(scalar, n, m=1, *, lo, hi, glo=None, ghi=None, spacing=
     counts = np.empty((max(int(m), 0), max(int(n), 0)), np.uint32)
     _check(load().cvr_field_histogram_host(C.byref(f), C.byref(h), counts.ctypes.data))
     return counts
+
+
+def field_project_host(scalar, inv_view, raster_to_view, full_res, desc: Optional[ProjectDesc] = None, tile=None,
+                       offset=(0, 0)):
+    """The field projections' written statement on the CPU (cvr_field_project_host; no GPU): of a
+    (z, y, x) numpy array of dtype uint8, uint16, int16 or float32 filling desc's box, for tile
+    (w, h) (default: full_res) at `offset` of the full image -> (rgba (h, w, 4), value (h, w): the
+    projected or the surface's field value, depth (h, w): its distance over the box diagonal).
+    Context.field_project returns the same bits from the device."""
+    _src, f = _host_field(scalar, (1.0, 1.0, 1.0))
+    iv = np.ascontiguousarray(inv_view, dtype=np.float32).reshape(12)
+    r2v = np.ascontiguousarray(raster_to_view, dtype=np.float32).reshape(2)
+    fr = np.asarray(full_res, dtype=np.float32).reshape(2)
+    w, h = (int(full_res[0]), int(full_res[1])) if tile is None else (int(tile[0]), int(tile[1]))
+    desc = ProjectDesc() if desc is None else desc
+    rgba = np.zeros((max(h, 0), max(w, 0), 4), np.float32)
+    value = np.zeros((max(h, 0), max(w, 0)), np.float32)
+    depth = np.zeros((max(h, 0), max(w, 0)), np.float32)
+    _check(load().cvr_field_project_host(C.byref(f), C.byref(desc), _fp(iv), _fp(r2v), _fp(fr), w, h, int(offset[0]),
+                                         int(offset[1]), rgba.ctypes.data, value.ctypes.data, depth.ctypes.data))
+    return rgba, value, depth
 
 
 def raw_transfer_table() -> np.ndarray:
@@ -1506,6 +1564,42 @@ class Context:
         counts = np.empty((max(int(m), 0), max(int(n), 0)), np.uint32)
         self._c(load().cvr_field_histogram(self._h, C.byref(f), C.byref(h), counts.ctypes.data))
         return counts
+
+    def field_project(self, scalar, desc: Optional[ProjectDesc] = None, value=True, depth=True, scalar_type=None,
+                      res=None):
+        """field_project_host of a scalar field in device memory (cvr_field_project) for the
+        context's camera, resolution and offset, the same bits: (rgba (h, w, 4), value (h, w),
+        depth (h, w)) as numpy arrays; value / depth False: that plane is not computed and None is
+        returned for it.  scalar is what set_medium_gradient accepts.  Synchronous; torch's current
+        stream is synchronised first; the context needs no medium and is only read."""
+        f, torch_tensor = self._device_field("field_project", scalar, (1.0, 1.0, 1.0), scalar_type, res)
+        desc = ProjectDesc() if desc is None else desc
+        if torch_tensor:
+            import torch
+            torch.cuda.current_stream(self.device).synchronize()
+        w, h = self.resolution
+        rgba = np.zeros((h, w, 4), np.float32)
+        v = np.zeros((h, w), np.float32) if value else None
+        z = np.zeros((h, w), np.float32) if depth else None
+        self._c(load().cvr_field_project(self._h, C.byref(f), C.byref(desc), rgba.ctypes.data,
+                                         None if v is None else v.ctypes.data, None if z is None else z.ctypes.data,
+                                         rgba.size))
+        return rgba, v, z
+
+    def field_project_buffers(self, scalar, out_rgba, out_value=None, out_depth=None, desc: Optional[ProjectDesc] = None,
+                              scalar_type=None, res=None):
+        """The projection into device buffers (cvr_field_project_buffers), ordered on the context's
+        stream and not synchronised (the field must stay until it has run): out_rgba tile_w * tile_h
+        * 4 floats (16-byte aligned), out_value and out_depth tile_w * tile_h floats or None; each an
+        int device address or an object with data_ptr() (a torch tensor).  torch's current stream is
+        synchronised first."""
+        f, torch_tensor = self._device_field("field_project_buffers", scalar, (1.0, 1.0, 1.0), scalar_type, res)
+        desc = ProjectDesc() if desc is None else desc
+        if torch_tensor:
+            import torch
+            torch.cuda.current_stream(self.device).synchronize()
+        self._c(load().cvr_field_project_buffers(self._h, C.byref(f), C.byref(desc), _device_ptr(out_rgba),
+                                                 _device_ptr(out_value), _device_ptr(out_depth)))
 
     def set_environment(self, image, scale: float = 1.0, rotation=None):
         """Light the scene with a latitude-longitude map (cvr_set_environment): an escaping path adds

@@ -29,6 +29,12 @@
 //   --field-stats, --histogram FILE [--histogram-bins N [M]], --gradient-range auto (the value range,
 //   largest gradient magnitude and value-gradient histogram of a Raw scene's bytes, found on the
 //   device: cvr_field_stats, cvr_field_histogram; with --iterations 0 without a render)
+//   --project max|min|mean|iso FILE [--project-window LO HI] [--iso V] [--project-step F]
+//   [--project-refine N] [--project-colour R G B] (also write a projection of a Raw scene's bytes,
+//   cvr_field_project, as FILE: the maximum, minimum or mean along each camera ray shown through
+//   the window LO..HI, or the first-hit isosurface at V lit by the field's gradient; the light,
+//   the weights and the background are --preview-light, --preview-shading and
+//   --preview-background; with --iterations 0 without a render)
 //
 // Differences from the reference, on purpose: the timer is wall clock (the
 // reference uses clock(), i.e. CPU time, Main.cpp:51-77); main does not wait
@@ -88,6 +94,13 @@ struct Options {
   bool preview_shadows_set = false;          // ... and whether it was given
   std::vector<unsigned> preview_shadow_res;  // --preview-shadow-res X Y Z (none: the default grid)
   float preview_shadow_step = 1.0f;          // --preview-shadow-step F: the light volume's march step
+  std::string project_mode, project_file;  // --project max|min|mean|iso FILE
+  std::vector<float> project_window;       // --project-window LO HI (none: 0 .. the largest byte)
+  float project_iso = 0.0f;                // --iso V ...
+  bool project_iso_set = false;            // ... (not given: half the largest byte)
+  float project_step = 1.0f;
+  unsigned project_refine = 4;
+  float project_colour[3] = {1.0f, 1.0f, 1.0f};
   bool denoise_guided = false;  // --denoise-guided given
   float guide_sigma[3] = {0.4f, 0.1f, 0.4f};
   std::vector<float> default_albedo;
@@ -201,6 +214,17 @@ void usage() {
       "                                     (needs --preview and --preview-light)\n"
       "  --preview-shadow-res X Y Z         preview: the light volume's nodes (default: half the medium's, at most 256)\n"
       "  --preview-shadow-step F (=1)       preview: the step of the march towards the light, in cells\n"
+      "  --project max|min|mean|iso FILE    Raw scenes (and --synthetic bucky): also write a projection of the bytes\n"
+      "                                     (cvr_field_project): the maximum, minimum or mean along each camera ray, or\n"
+      "                                     the first-hit isosurface lit by the field's gradient (--preview-light,\n"
+      "                                     --preview-shading and --preview-background apply); with --iterations 0 it\n"
+      "                                     runs without a render; one tile on one device\n"
+      "  --project-window LO HI             projection: the values shown black and full colour (default: 0 and the\n"
+      "                                     largest byte)\n"
+      "  --iso V                            projection: the isosurface's level (default: half the largest byte)\n"
+      "  --project-step F (=1)              projection: the march's step, in cells\n"
+      "  --project-refine N (=4)            projection: bisections of the isosurface's bracket, 0..8\n"
+      "  --project-colour R G B (=1 1 1)    projection: the full-scale colour, the surface's colour\n"
       "  --denoise-sigma F (=4)             denoiser: width of the edge-stopping term in standard deviations\n"
       "  --denoise-passes N (=5)            denoiser: a-trous passes, 1..6 (pass k has step 2^k)\n"
       "  --rng-binding path|thread (=path)  regenerationSK: thread = the reference's Rng(seed + tid)\n"
@@ -350,6 +374,20 @@ int parse(int argc, char** argv, Options& o) {
       o.preview_shadow_res.clear();
       for (int k = 0; k < 3; ++k) o.preview_shadow_res.push_back((unsigned)strtoul(need("preview-shadow-res").c_str(), nullptr, 10));
     } else if (a == "--preview-shadow-step") o.preview_shadow_step = strtof(need("preview-shadow-step").c_str(), nullptr);
+    else if (a == "--project") {
+      o.project_mode = need("project");
+      o.project_file = need("project");
+    } else if (a == "--project-window") {
+      o.project_window.clear();
+      for (int k = 0; k < 2; ++k) o.project_window.push_back(strtof(need("project-window").c_str(), nullptr));
+    } else if (a == "--iso") {
+      o.project_iso = strtof(need("iso").c_str(), nullptr);
+      o.project_iso_set = true;
+    } else if (a == "--project-step") o.project_step = strtof(need("project-step").c_str(), nullptr);
+    else if (a == "--project-refine") o.project_refine = (unsigned)strtoul(need("project-refine").c_str(), nullptr, 10);
+    else if (a == "--project-colour") {
+      for (int k = 0; k < 3; ++k) o.project_colour[k] = strtof(need("project-colour").c_str(), nullptr);
+    }
     else if (a == "--feature-step") o.feature_step = strtof(need("feature-step").c_str(), nullptr);
     else if (a == "--denoise-sigma") o.denoise_sigma = strtof(need("denoise-sigma").c_str(), nullptr);
     else if (a == "--denoise-passes") o.denoise_passes = (unsigned)strtoul(need("denoise-passes").c_str(), nullptr, 10);
@@ -549,6 +587,69 @@ int field_pass(const Options& o, int device, int kernel, const cvr_scene* scene,
   return done(0);
 }
 
+// --project: the scene's bytes as a u8 field in the scene's box, handed to the device as field_pass
+// hands them, projected for the camera into one W x H tile and written as o.project_file (and
+// .pfm with --pfm).  The context holds no medium.
+int project_pass(const Options& o, int device, int kernel, const cvr_scene* scene, const float inv_view[12],
+                 const float r2v[2], const float full_res[2], unsigned W, unsigned H) {
+  const uint8_t* raw = nullptr;
+  size_t n_raw = 0;
+  cvr_medium_desc md{};
+  if (cvr_scene_raw_bytes(scene, &raw, &n_raw) != CVR_OK || !n_raw || cvr_scene_medium(scene, &md) != CVR_OK ||
+      n_raw != (size_t)md.res[0] * md.res[1] * md.res[2])
+    return 1;
+  void* pinned = nullptr;
+  cvr_ctx* ctx = nullptr;
+  auto done = [&](int code) {
+    if (ctx) cvr_destroy(ctx);
+    if (pinned) cvr_host_free(pinned);
+    return code;
+  };
+  auto failed = [&]() {
+    fprintf(stderr, "Error: %s\n", cvr_last_error(ctx));
+    return done(1);
+  };
+  if (cvr_host_alloc(n_raw, &pinned) != CVR_OK || cvr_create(device, kernel, &ctx) != CVR_OK) return failed();
+  memcpy(pinned, raw, n_raw);
+  cvr_field_desc f{};
+  memcpy(f.res, md.res, sizeof(f.res));
+  f.scalar_type = CVR_SCALAR_U8;
+  f.scalar = pinned;
+  const float top = (float)*std::max_element(raw, raw + n_raw);
+  cvr_project_desc d{};
+  d.mode = o.project_mode == "max" ? CVR_PROJECT_MAX : o.project_mode == "min" ? CVR_PROJECT_MIN
+           : o.project_mode == "mean" ? CVR_PROJECT_MEAN : CVR_PROJECT_ISO;
+  d.flags = o.preview_light.empty() ? CVR_PROJECT_HEADLIGHT : 0u;
+  for (int k = 0; k < 3; ++k) {
+    d.box_min[k] = md.box_min[k], d.box_max[k] = md.box_max[k];
+    d.colour[k] = o.project_colour[k], d.background[k] = o.preview_background[k];
+  }
+  d.step = o.project_step, d.max_steps = 4096u;
+  d.lo = o.project_window.empty() ? 0.0f : o.project_window[0];
+  d.hi = o.project_window.empty() ? (top > 0.0f ? top : 1.0f) : o.project_window[1];
+  d.iso = o.project_iso_set ? o.project_iso : 0.5f * top;
+  d.refine = o.project_refine;
+  for (size_t k = 0; k < o.preview_light.size(); ++k) d.light[k] = o.preview_light[k];
+  d.ambient = o.preview_shading[0], d.diffuse = o.preview_shading[1], d.specular = o.preview_shading[2];
+  d.shininess_log2 = o.preview_shininess_log2;
+  std::vector<float> img((size_t)W * H * 4, 0.0f);
+  if (cvr_set_camera(ctx, inv_view, r2v, full_res) != CVR_OK || cvr_set_resolution(ctx, W, H) != CVR_OK ||
+      cvr_set_offset(ctx, 0, 0) != CVR_OK ||
+      cvr_field_project(ctx, &f, &d, img.data(), nullptr, nullptr, img.size()) != CVR_OK)
+    return failed();
+  if (cvr_write_hdr(o.project_file.c_str(), img.data(), W, H) != CVR_OK ||
+      (o.pfm && write_pfm(o.project_file + ".pfm", img.data(), W, H))) {
+    fprintf(stderr, "Error: could not write %s%s\n", o.project_file.c_str(), o.pfm ? " / .pfm" : "");
+    return done(1);
+  }
+  if (d.mode == CVR_PROJECT_ISO)
+    printf("projection          : iso at %g, written to %s\n", (double)d.iso, o.project_file.c_str());
+  else
+    printf("projection          : %s over values %g .. %g, written to %s\n", o.project_mode.c_str(), (double)d.lo,
+           (double)d.hi, o.project_file.c_str());
+  return done(0);
+}
+
 // --transfer2d FILE: a first data line 'n m', then n * m lines of 'r g b density', row by row
 // (blank lines and lines starting with # are skipped) into table; false with a message when the
 // file cannot be read, a line is not what it should be, or the entries are not n * m.
@@ -697,14 +798,22 @@ int main(int argc, char** argv) {
     fprintf(stderr, "[ConfigParser] Error: --gradient-range applies to --transfer2d only (and to --histogram)\n");
     return 2;
   }
-  if (field_work) {
+  const bool project = !o.project_file.empty();
+  if (project && o.project_mode != "max" && o.project_mode != "min" && o.project_mode != "mean" && o.project_mode != "iso") {
+    fprintf(stderr, "[ConfigParser] Error: --project takes max, min, mean or iso and a file name\n");
+    return 2;
+  }
+  if (field_work || project) {
     const uint8_t* raw = nullptr;
     size_t n_raw = 0;
     if (cvr_scene_raw_bytes(scene, &raw, &n_raw) != CVR_OK || !n_raw) {
       fprintf(stderr, "[ConfigParser] Error: %s applies to Raw scenes only (and --synthetic bucky): this scene has no "
-                      "scalar bytes\n", o.field_stats ? "--field-stats" : want_histogram ? "--histogram" : "--gradient-range auto");
+                      "scalar bytes\n", o.field_stats ? "--field-stats" : want_histogram ? "--histogram"
+                                        : o.gradient_auto ? "--gradient-range auto" : "--project");
       return 2;
     }
+  }
+  if (field_work) {
     const unsigned hn = o.histogram_bins[0], hm = o.histogram_bins[1];
     if (want_histogram && (hn < 2u || hm < 1u || (unsigned long long)hn * hm > 65536ull)) {
       fprintf(stderr, "[ConfigParser] Error: --histogram-bins %u %u: N >= 2, M >= 1, N*M <= 65536\n", hn, hm);
@@ -976,7 +1085,7 @@ int main(int argc, char** argv) {
         cvr_destroy(c);
         if (kr) return kr;
       }
-      if (o.preview_file.empty()) {
+      if (o.preview_file.empty() && !project) {
         cvr_free_image(env_rgb);
         return 0;
       }
@@ -990,12 +1099,13 @@ int main(int argc, char** argv) {
   }
   const bool filtered = o.denoise || o.denoise_guided;
   const bool preview = !o.preview_file.empty();
-  if ((o.adaptive || filtered || o.features || preview) && (n_dev > 1 || ntiles > 1)) {
+  if ((o.adaptive || filtered || o.features || preview || project) && (n_dev > 1 || ntiles > 1)) {
     fprintf(stderr, "[ConfigParser] Error: %s renders one tile on one device (no --devices > 1, no "
                     "--number-of-tiles above 1 1)\n",
             o.adaptive ? "--noise-target" : o.denoise ? "--denoise" : o.denoise_guided ? "--denoise-guided"
                                                                 : o.features     ? "--features"
-                                                                                 : "--preview");
+                                                                : preview        ? "--preview"
+                                                                                 : "--project");
     return 2;
   }
   // --preview: the pass on ctx's medium and camera, written as FILE (and FILE.pfm with --pfm)
@@ -1034,6 +1144,14 @@ int main(int argc, char** argv) {
     printf("preview             : %s\n", o.preview_file.c_str());
     return 0;
   };
+  if (project) {  // the projection needs no medium: a context of its own, before any render
+    if (int pr = project_pass(o, devs[0], kernel, scene, inv_view, r2v, full_res, W, H)) return pr;
+    if (o.iterations == 0 && !preview) {
+      cvr_free_image(env_rgb);
+      cvr_scene_destroy(scene);
+      return 0;
+    }
+  }
   if (preview && o.iterations == 0) {  // the preview alone: no render, no image
     cvr_ctx* c = make_ctx(devs[0], nullptr);
     if (!c) return 1;

@@ -52,13 +52,9 @@ inline void preview_constants(PreviewParams& Q, const float light[3], int headli
 struct PreviewTerms {
   float m, nl, sp;
 };
-template <class Tex>
-CVR_HD bool preview_terms(const Tex& tex, const PreviewParams& Q, F3 p, F3 d, PreviewTerms& k) {
-  const FeatureParams& P = Q.F;
-  const float hx = Q.h[0], hy = Q.h[1], hz = Q.h[2];
-  const float gx = (feat_density(tex, P, F3{p.x + hx, p.y, p.z}) - feat_density(tex, P, F3{p.x - hx, p.y, p.z})) / hx;
-  const float gy = (feat_density(tex, P, F3{p.x, p.y + hy, p.z}) - feat_density(tex, P, F3{p.x, p.y - hy, p.z})) / hy;
-  const float gz = (feat_density(tex, P, F3{p.x, p.y, p.z + hz}) - feat_density(tex, P, F3{p.x, p.y, p.z - hz})) / hz;
+// The terms of a gradient (gx, gy, gz), whatever it was taken of: the stored density below, the
+// raw field in cvr_project.h
+CVR_HD bool preview_light_terms(const PreviewParams& Q, float gx, float gy, float gz, F3 d, PreviewTerms& k) {
   const float m = det_sqrtf((gx * gx + gy * gy) + gz * gz);
   k.m = m;
   if (!(m > 0.0f)) return false;
@@ -81,6 +77,15 @@ CVR_HD bool preview_terms(const Tex& tex, const PreviewParams& Q, F3 p, F3 d, Pr
   k.nl = nl;
   k.sp = sp;
   return true;
+}
+template <class Tex>
+CVR_HD bool preview_terms(const Tex& tex, const PreviewParams& Q, F3 p, F3 d, PreviewTerms& k) {
+  const FeatureParams& P = Q.F;
+  const float hx = Q.h[0], hy = Q.h[1], hz = Q.h[2];
+  const float gx = (feat_density(tex, P, F3{p.x + hx, p.y, p.z}) - feat_density(tex, P, F3{p.x - hx, p.y, p.z})) / hx;
+  const float gy = (feat_density(tex, P, F3{p.x, p.y + hy, p.z}) - feat_density(tex, P, F3{p.x, p.y - hy, p.z})) / hy;
+  const float gz = (feat_density(tex, P, F3{p.x, p.y, p.z + hz}) - feat_density(tex, P, F3{p.x, p.y, p.z - hz})) / hz;
+  return preview_light_terms(Q, gx, gy, gz, d, k);
 }
 
 // The emitted colour of a contributing sample at p with albedo c, ray direction d.

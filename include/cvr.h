@@ -57,6 +57,8 @@ extern "C" {
  *                  cvr_light_volume_host, cvr_build_light_volume, cvr_light_volume_default_res,
  *                  cvr_copy_light_volume, cvr_clear_light_volume, cvr_preview_shadowed_host, cvr_preview_shadowed_buffers,
  *                  cvr_preview_shadowed
+ *              6 + CVR_HAS_FIELD_PROJECT (likewise): cvr_project_desc, cvr_field_project_host,
+ *                  cvr_field_project_buffers, cvr_field_project
  *              6 + CVR_HAS_WPOOL_DEBUG (likewise): cvr_debug_wpool_rows, cvr_debug_last_wpool
  * CVR_ABI_VERSION is the ABI this header declares: 6, the library's (cvr_abi_version()).  ABI 6 only
  * adds to ABI 5, so a host that must also load an ABI 5 library can hold itself to that surface:
@@ -1473,7 +1475,8 @@ int cvr_denoise_guided(cvr_ctx* ctx, const cvr_denoise_guided_desc* desc, const 
  * specular 0.2, shininess_log2 4, knee 0.05, a black background, march 1, 1/256, 4096.
  * Not supported: ambient occlusion (directional shadows: CVR_HAS_SHADOWS below), the environment
  * map as a light, more than one light, the refraction at the GGX boundary (the ray is the straight camera ray), gradients of
- * the original scalar field (the pass sees the stored density only), tone mapping, the preview
+ * the original scalar field (the pass sees the stored density only; CVR_HAS_FIELD_PROJECT below lights an
+ * isosurface of the field itself), tone mapping, the preview
  * as a denoiser guide, more than one tile or device in the CLI, temporal accumulation. */
 #define CVR_HAS_PREVIEW 1
 #define CVR_PREVIEW_UNSHADED 1u  /* e = c: plain emission-absorption compositing, no gradient */
@@ -1603,6 +1606,111 @@ int cvr_preview_shadowed_host(const cvr_medium_desc* medium, const float inv_vie
 int cvr_preview_shadowed_buffers(cvr_ctx* ctx, const cvr_preview_desc* desc, float shadow, float* d_out_rgba);
 int cvr_preview_shadowed(cvr_ctx* ctx, const cvr_preview_desc* desc, float shadow, float* host_rgba,
                          size_t host_floats);
+
+/* ---- field projections (extension within ABI 6: CVR_HAS_FIELD_PROJECT) --- */
+/* The two views a volume viewer shows before any transfer table exists, and what a user reads a
+ * threshold from (the iso, lo or hi of the classifications): intensity projections of the raw
+ * scalar field (maximum: MIP, minimum: MinIP, mean: the X-ray view) and its first-hit isosurface
+ * lit by the field's own gradient.  The field is a typed scalar field in device memory
+ * (cvr_field_desc); no medium is needed or touched.  Per pixel, one deterministic march along the
+ * straight camera ray through the pixel's centre.  Every operation is fp32 +, -, x, /, sqrt in the
+ * order written here (correctly rounded, no fused multiply-add but the fma of the trilinear's
+ * lerps), so the device kernels and cvr_field_project_host return the same bits (one definition
+ * compiles for both, cvr_project.h).
+ * Ray, chord and steps are exactly those of CVR_HAS_FEATURES with the descriptor's box as the box
+ * and the field's res as res: the ray through the pixel centre, the slab test with its minNum /
+ * maxNum rules, delta = step min(min(e_x / res_x, e_y / res_y), e_z / res_z), e = box_max -
+ * box_min, n = min(max_steps, ceil((t1 - t0) / delta)), t_i = t0 + ((float)i + 0.5f) delta, a
+ * t_i >= t1 is dropped; there is no t_stop.  p_i = o + t_i d (a multiply, then an add).
+ * Field value S(p) at a world point p: c_a = ((p_a - box_min_a) / e_a) (float)(res_a - 1): voxel i
+ *   sits at node i / (res - 1) of the box, the albedo coordinate of CVR_HAS_FEATURES, geometrically
+ *   right for every box (no quirk Q4).  Lower corner floor(c) (saturating, a NaN to INT_MIN),
+ *   weights c - corner, the 8 taps clamped as the feature pass clamps its (quirk Q5: an index below
+ *   0 wraps and clamps to res - 1), each tap converted to float (exact for the integer types), and
+ *   the feature pass's trilinear, lerp(a, b, f) = fma(b, f, a (1 - f)), x then y then z.
+ *   The view aligns with cvr_preview of a medium built from the same field in the same box
+ *   whenever CVR_OPT_WORLD_TO_AABB is 1 or the box is the unit box at the origin.
+ * CVR_PROJECT_MAX: from cnt = 0; for each sample v = S(p_i), a NaN v is skipped; if cnt == 0 or
+ *   v > V: V = v, tz = t_i (the first maximum wins); cnt++.  value = V.
+ * CVR_PROJECT_MIN: the same with v < V.
+ * CVR_PROJECT_MEAN: from Sum = 0: Sum += v, cnt++, a NaN skipped.  value = Sum / (float)cnt, tz = 0.
+ * These three: t = (value - lo) / (hi - lo), u = t > 0 ? t : 0, then u = u < 1 ? u : 1 (the
+ *   classifications' u); rgba = (u colour_r, u colour_g, u colour_b, 1); depth = tz / diag, diag =
+ *   sqrt((e_x e_x + e_y e_y) + e_z e_z).  With cnt == 0 (no chord, or only NaN samples):
+ *   rgba = (bg_r, bg_g, bg_b, 0), value 0, depth 0.
+ * CVR_PROJECT_ISO: inside(v) is v >= iso (a NaN is not inside).  The hit is the first sample i
+ *   with inside(S(p_i)); with none the output is the background, alpha 0, value 0, depth 0.
+ *   i = 0: t_hit = t_0 (the cut face, where the box slices the solid).  Otherwise ta = t_(i-1),
+ *   tb = t_i, and `refine` times: tm = ta + 0.5f (tb - ta); if inside(S(o + tm d)) tb = tm, else
+ *   ta = tm; t_hit = tb.  p = o + t_hit d, value = S(p) (recomputed at p), depth = t_hit / diag.
+ *   The gradient is the construction of CVR_HAS_PREVIEW on S: h_a = e_a / res_a,
+ *   G_a = (S(p + h_a u_a) - S(p - h_a u_a)) / h_a (six more lookups, clamped taps and all),
+ *   m = sqrt((G_x G_x + G_y G_y) + G_z G_z).  If not m > 0: rgb = colour.  Otherwise n = G / m and
+ *   L, V, nl, H, hh, nh, the shininess_log2 squarings and sp exactly as CVR_HAS_PREVIEW writes
+ *   them (CVR_PROJECT_HEADLIGHT: L = -d; else the light normalised once per call);
+ *   f = ambient + diffuse nl, rgb_c = f colour_c + specular sp: no knee.  rgba = (rgb, 1).
+ * Refusals, all CVR_ERR_INVALID, in this order:
+ *   1. NULL arguments (the context, a descriptor, a camera array of the host call);
+ *   2. a zero extent, or more than 2^32 - 1 voxels: from res alone;
+ *   3. an unknown scalar_type or mode, unknown flags, or a non-zero reserved (either descriptor's);
+ *   4. a box that is not finite or has box_max_a <= box_min_a;
+ *   5. step outside [1/8, 8] or max_steps outside 1..65536;
+ *   6. the three projections: lo / hi not finite, or hi <= lo;
+ *   7. CVR_PROJECT_ISO: iso not finite, refine > 8, or ambient, diffuse, specular, shininess_log2
+ *      and (without the headlight) the light as cvr_preview refuses them;
+ *   8. a colour or background component that is negative or not finite;
+ *   9. a NULL scalar or rgba pointer;
+ *  10. a scalar misaligned for its type, an rgba plane not 16-byte aligned (a value or depth plane:
+ *      4-byte), or, the device calls, memory that is not device-accessible on the context's device.
+ * The tile is judged between 8 and 9 (a zero side or more than 2^24 pixels: CVR_ERR_INVALID; the
+ * device calls: host_floats too small likewise).  The device calls return CVR_ERR_STATE without a
+ * camera or a resolution, after rule 1.  The field's spacing is not read: the box gives the
+ * geometry.  Fields of modes the rule does not name (lo, hi for ISO; iso, refine, the light and
+ * the weights for the projections) are neither read nor judged.
+ * Like the field calls above, the device calls only borrow the context's device, stream, camera,
+ * resolution and offset: they work without a medium and inside an adaptive session and write
+ * nothing of the context.  The defaults of the bindings and the CLI: step 1, max_steps 4096,
+ * refine 4, the headlight, 0.3 / 0.7 / 0.2, exponent 2^4, a white colour, a black background.
+ * Not supported: the context's crop and clip planes, transfer-function colouring of the
+ * projection, depth-cued or local MIP, more than one isosurface or translucent surfaces,
+ * empty-space skipping (a brick's maximum does not bound a trilinear sample: DESIGN.md), sparse
+ * fields, keeping the field, more than one tile or device in the CLI. */
+#define CVR_HAS_FIELD_PROJECT 1
+enum { CVR_PROJECT_MAX = 0, CVR_PROJECT_MIN = 1, CVR_PROJECT_MEAN = 2, CVR_PROJECT_ISO = 3 };
+#define CVR_PROJECT_HEADLIGHT 1u /* ISO: the light shines along the ray, L = -d */
+typedef struct cvr_project_desc {
+  uint32_t mode;  /* CVR_PROJECT_* */
+  uint32_t flags; /* CVR_PROJECT_HEADLIGHT */
+  float box_min[3], box_max[3];
+  float step;         /* in cells of the finest axis, 1/8..8 */
+  uint32_t max_steps; /* 1..65536 */
+  float lo, hi;       /* the projections' display window */
+  float iso;
+  uint32_t refine; /* bisections of the hit's bracket, 0..8 */
+  float light[3];  /* the direction towards the light, any length; not read with the headlight */
+  float ambient, diffuse, specular;
+  uint32_t shininess_log2; /* the specular exponent is 2^shininess_log2, 0..10 */
+  float colour[3], background[3];
+  uint32_t reserved; /* 0 */
+} cvr_project_desc; /* 112 bytes */
+/* Host only, no GPU: the written statement on a field in host memory, the camera and tile as
+ * cvr_features_host takes them.  out_rgba: tile_w * tile_h * 4 floats; out_value, out_depth:
+ * tile_w * tile_h floats each, may be NULL. */
+int cvr_field_project_host(const cvr_field_desc* field, const cvr_project_desc* desc, const float inv_view[12],
+                           const float raster_to_view[2], const float full_res[2], uint32_t tile_w, uint32_t tile_h,
+                           uint32_t off_x, uint32_t off_y, float* out_rgba, float* out_value, float* out_depth);
+/* The pass on a field in device memory (or pinned host memory) for the context's camera,
+ * resolution and offset, into device memory or the device address of pinned host memory
+ * (d_out_value, d_out_depth may be NULL), asynchronous on the context's stream: the field must
+ * stay until the stream has run it. */
+int cvr_field_project_buffers(cvr_ctx* ctx, const cvr_field_desc* field, const cvr_project_desc* desc,
+                              float* d_out_rgba, float* d_out_value, float* d_out_depth);
+/* The same into host memory (host_rgba: tile_w * tile_h * 4 floats, host_floats smaller:
+ * CVR_ERR_INVALID; host_value, host_depth: tile_w * tile_h floats or NULL).  Synchronous: the
+ * field may be freed when it returns.  Pinned or registered memory is stored into by the kernel,
+ * other memory (host_rgba not 16-byte aligned included) through a staging copy. */
+int cvr_field_project(cvr_ctx* ctx, const cvr_field_desc* field, const cvr_project_desc* desc, float* host_rgba,
+                      float* host_value, float* host_depth, size_t host_floats);
 
 /* ---- which wave-pool kernel instance ran (tests; extension within ABI 6: CVR_HAS_WPOOL_DEBUG) -- */
 /* The wave pool (CVR_OPT_SCHEDULER 3) is one kernel compiled once per combination of scatter
