@@ -1763,7 +1763,9 @@ class Context:
         return load().cvr_output_ptr(self._h) or 0
 
     def set_stream(self, stream_ptr: Optional[int]):
-        """Launch on `stream_ptr` (a hipStream_t; 0/None = the null stream)."""
+        """Launch on `stream_ptr` (a hipStream_t; 0/None = the null stream).  A different stream
+        than the one in use: waits first for the work pending on the stream being left; the stream
+        must stay valid until the context has left it or is closed (cvr_set_stream)."""
         self._c(load().cvr_set_stream(self._h, C.c_void_p(stream_ptr) if stream_ptr else None))
 
     def use_own_stream(self):

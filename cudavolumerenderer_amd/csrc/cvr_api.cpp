@@ -339,7 +339,16 @@ void* cvr_output_ptr(cvr_ctx* c) { return c ? c->d_out : nullptr; }
 int cvr_set_stream(cvr_ctx* c, void* s) {
   if (!c) return set_err(nullptr, CVR_ERR_INVALID, "NULL ctx");
   CVR_NOT_IN_SESSION(c, "cvr_set_stream");
-  c->stream = static_cast<hipStream_t>(s);  // NULL = the device's null stream
+  const hipStream_t next = static_cast<hipStream_t>(s);  // NULL = the device's null stream
+  if (next != c->stream) {
+    // the work queues, the wave-pool scratch, the filter's images and the light volume are
+    // single-stream state: what is pending on the stream being left ends before the next call
+    // starts on the new one
+    int r = ensure_device(c);
+    if (r) return r;
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+  }
+  c->stream = next;
   return CVR_OK;
 }
 

@@ -454,7 +454,17 @@ int cvr_set_output(cvr_ctx* ctx, void* device_tile_buffer);
 void* cvr_output_ptr(cvr_ctx* ctx);
 /* Run on a caller stream (hipStream_t), e.g. a framework's current stream;
  * NULL is the device's null stream.  cvr_own_stream() returns the
- * non-blocking stream the context creates for itself (the default). */
+ * non-blocking stream the context creates for itself (the default).
+ * Every call ordered "on the context's stream" is ordered on this stream, after
+ * what the caller queued there before the call and before what it queues there
+ * afterwards; the library touches no other stream for it.
+ * Leaving a stream: the context's work queues, wave-pool scratch, filter images
+ * and light volume are single-stream state, so a call that names a different
+ * stream first waits (on the host) for the work pending on the stream it
+ * leaves; naming the stream already in use waits for nothing.  The caller's
+ * stream must stay valid until the context has left it (this call with another
+ * stream has returned) or has been destroyed: cvr_destroy waits for it too.
+ * CVR_ERR_STATE inside an adaptive session. */
 int cvr_set_stream(cvr_ctx* ctx, void* hip_stream);
 void* cvr_own_stream(cvr_ctx* ctx);
 int cvr_set_option(cvr_ctx* ctx, int option, int64_t value);
