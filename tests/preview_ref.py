@@ -4,10 +4,12 @@ call in the written order, so every intermediate is rounded as the text says.  T
 the trilinear and the exact fused multiply-add are features_ref's (the restatement of
 CVR_HAS_FEATURES, which the text refers to for them).
 
-preview(...) -> rgba (h, w, 4)."""
+preview(...) -> rgba (h, w, 4).  preview_fetch(res, density, albedo, ...) is the same march over two
+fetch functions and an optional tap log (features_ref.features_fetch's); preview() is preview_fetch
+over features_ref.array_fetch."""
 import numpy as np
 
-from features_ref import chord, fma, maxnum, minnum, rays, trilinear  # noqa: F401
+from features_ref import array_fetch, chord, fma, march, maxnum, minnum, rays, support_skip, trilinear  # noqa: F401
 
 F = np.float32
 _ERR = dict(invalid="ignore", divide="ignore", over="ignore", under="ignore")
@@ -21,10 +23,17 @@ def dot3(a, b):
 
 def preview(density, albedo, box_min, box_max, scale, max_density, inv_view, r2v, full, tile, offset=(0, 0), w2a=0,
             step=1.0, t_stop=1.0 / 256.0, max_steps=4096, light=(0, 0, 0), ambient=0.3, diffuse=0.7, specular=0.2,
-            shininess_log2=4, knee=0.05, background=(0, 0, 0), flags=HEADLIGHT):
-    density = np.asarray(density, F)
-    albedo = np.asarray(albedo, F)
-    res = density.shape[::-1]
+            shininess_log2=4, knee=0.05, background=(0, 0, 0), flags=HEADLIGHT, taps=None):
+    """The march over a dense medium's arrays: preview_fetch over array_fetch."""
+    res, dens, alb = array_fetch(density, albedo)
+    return preview_fetch(res, dens, alb, box_min, box_max, scale, max_density, inv_view, r2v, full, tile, offset, w2a, step,
+                         t_stop, max_steps, light, ambient, diffuse, specular, shininess_log2, knee, background, flags, taps)
+
+
+def preview_fetch(res, density, albedo, box_min, box_max, scale, max_density, inv_view, r2v, full, tile, offset=(0, 0),
+                  w2a=0, step=1.0, t_stop=1.0 / 256.0, max_steps=4096, light=(0, 0, 0), ambient=0.3, diffuse=0.7,
+                  specular=0.2, shininess_log2=4, knee=0.05, background=(0, 0, 0), flags=HEADLIGHT, taps=None, support=None):
+    res = tuple(int(r) for r in res)
     fres = np.array(res, F)
     bmin, bmax = np.asarray(box_min, F), np.asarray(box_max, F)
     e = bmax - bmin
@@ -43,9 +52,9 @@ def preview(density, albedo, box_min, box_max, scale, max_density, inv_view, r2v
         l = np.asarray(light, F)
         L_fixed = (l / np.sqrt((l[0] * l[0] + l[1] * l[1]) + l[2] * l[2])).astype(F)
 
-    def rho_at(p):
+    def rho_at(p, log):
         cg = fma((p - shift).astype(F), g, F(0))
-        return trilinear(lambda x, y, z: density[z, y, x], cg[:, 0], cg[:, 1], cg[:, 2], res)
+        return trilinear(density, cg[:, 0], cg[:, 1], cg[:, 2], res, log)
 
     o, d = rays(inv_view, r2v, full, tile, offset)
     n_px = d.shape[0]
@@ -55,30 +64,9 @@ def preview(density, albedo, box_min, box_max, scale, max_density, inv_view, r2v
         n = np.where(q < F(max_steps), np.where(q > 0, q, 0), max_steps)
     n = np.where(has, n, 0).astype(np.int64)
 
-    T = np.ones(n_px, F)
-    Cc = np.zeros((n_px, 3), F)
-    W = np.zeros(n_px, F)
-    live = n > 0
-    for i in range(int(n.max(initial=0))):
-        live &= i < n
-        t = t0 + (F(i) + F(0.5)) * delta
-        with np.errstate(**_ERR):
-            live &= t < t1
-        if not live.any():
-            break
-        k = np.nonzero(live)[0]
-        p = (o + t[k][:, None] * d[k]).astype(F)
-        rho = rho_at(p)
-        with np.errstate(**_ERR):
-            s = (scale * rho) * delta
-            hit = s > 0
-        kh, sh, ph = k[hit], s[hit], p[hit]
-        if not kh.size:
-            continue
-        a = sh / (F(1) + sh)
-        w = T[kh] * a
+    def emission(kh, th, ph, log):
         ca = ((ph - bmin) / e) * ag
-        c = trilinear(lambda x, y, z: albedo[z, y, x, :3], ca[:, 0], ca[:, 1], ca[:, 2], res).astype(F)
+        c = trilinear(albedo, ca[:, 0], ca[:, 1], ca[:, 2], res).astype(F)
         em = c.copy()
         if shaded:
             G = np.zeros_like(ph)
@@ -86,7 +74,7 @@ def preview(density, albedo, box_min, box_max, scale, max_density, inv_view, r2v
                 hi, lo = ph.copy(), ph.copy()
                 hi[:, ax] = ph[:, ax] + h[ax]
                 lo[:, ax] = ph[:, ax] - h[ax]
-                G[:, ax] = (rho_at(hi) - rho_at(lo)) / h[ax]
+                G[:, ax] = (rho_at(hi, log) - rho_at(lo, log)) / h[ax]
             with np.errstate(**_ERR):
                 m = np.sqrt(dot3(G, G)).astype(F)
                 lit = m > 0
@@ -111,13 +99,28 @@ def preview(density, albedo, box_min, box_max, scale, max_density, inv_view, r2v
                 litc = f[:, None] * cl + (specular * sp)[:, None]
                 qq = ml / (ml + knee_abs)
                 em[lit] = (F(1) - qq)[:, None] * cl + qq[:, None] * litc
-        Cc[kh] += w[:, None] * em
-        W[kh] += w
-        T[kh] = T[kh] - w
-        live[kh[T[kh] < t_stop]] = False
+        return em
+
+    skip = None if support is None else support_skip(support, res, shift, g)
+    Cc, W, T = march(o, d, n, t0, t1, delta, scale, t_stop, rho_at, emission, 3, skip, taps)
     rgba = np.zeros((n_px, 4), F)
     rgba[:, :3] = Cc + T[:, None] * bg
     rgba[:, 3] = W
     rgba[~has, :3] = bg
     rgba[~has, 3] = 0
     return rgba.reshape(tile[1], tile[0], 4)
+
+
+def unshaded_from(sums, background=(0, 0, 0)):
+    """The unshaded preview of the march whose sums features_ref.features_fetch left in `sums`: an
+    unshaded sample's emission is its albedo c, so the preview's C is the feature pass's A, sample
+    for sample in the same order, and rgba = (A + T background, W), the background alone without a
+    chord."""
+    bg = np.asarray(background, F)
+    rgba = np.zeros(sums["W"].shape + (4,), F)
+    rgba[:, :3] = sums["A"] + sums["T"][:, None] * bg
+    rgba[:, 3] = sums["W"]
+    rgba[~sums["has"], :3] = bg
+    rgba[~sums["has"], 3] = 0
+    w, h = sums["tile"]
+    return rgba.reshape(h, w, 4)

@@ -105,6 +105,58 @@ def test_small_and_nan_fields(cvr, ctx, name, mode):
             assert (got[0] == np.array([0.25, 0.5, 0.125, 0.0], F)).all() and not got[1].any() and not got[2].any()
 
 
+# ------------------------------------------------ a voxel index past 2^31 ----
+BIG = (2049, 1024, 1024)      # (z, y, x): 2^31 + 2^20 voxels, the last z layer past index 2^31
+BIG_BLOCK = 32
+# just outside the far corner, looking down -z through the block's 32 x 32 cells of the + z face:
+# at the block's far side, 0.036 from the eye, the 30 degree view is 0.019 wide, inside the block's 0.031
+BIG_EYE, BIG_AT, BIG_FOV = (0.488, 0.482, 0.52), (0.4853, 0.4853, 0.4922), 30.0
+
+
+def big_block():
+    return np.random.default_rng(17).integers(1, 256, (BIG_BLOCK,) * 3).astype(np.uint8)
+
+
+def test_field_index_past_2_31(cvr, ctx):
+    """A uint8 field of 1024 x 1024 x 2049 voxels, zero but for a 32^3 block of random values at the
+    far corner, whose last z layer lies past voxel index 2^31: the host statement reads the same
+    array through size_t.  The camera's rays enter through that layer."""
+    block = big_block()
+    t = torch.zeros(BIG, dtype=torch.uint8, device="cuda")
+    t[-BIG_BLOCK:, -BIG_BLOCK:, -BIG_BLOCK:] = torch.from_numpy(block).cuda()
+    a = np.zeros(BIG, np.uint8)   # (untouched pages are never read: the host statement reads only the taps)
+    a[-BIG_BLOCK:, -BIG_BLOCK:, -BIG_BLOCK:] = block
+    assert a.size == (1 << 31) + (1 << 20) and a.reshape(-1)[1 << 31:].any()
+    full = (32, 32)
+    c = params.look_at(BIG_EYE, BIG_AT, fov=BIG_FOV, full=full)
+    ctx.set_camera(c.inv_view, c.r2v, full)
+    ctx.set_resolution(*full)
+    ctx.set_offset(0, 0)
+    for mode in ("max", "mean", "iso"):
+        d = cvr.ProjectDesc(mode, UNIT[0], UNIT[1], lo=0.0, hi=255.0, iso=128.0, refine=4, **LOOK)
+        want = cvr.field_project_host(a, c.inv_view, c.r2v, full, d)
+        share = float((want[1] != 0).mean())
+        print(f"{mode}: {100 * share:.1f} % of the pixels have a value")
+        assert share >= 0.95, mode
+        assert_planes(ctx.field_project(t, d), want, f"2^31 + 2^20 voxels, {mode}")
+
+
+def test_field_past_2_32_is_refused(cvr, ctx):
+    """More than 2^32 - 1 voxels: refused before the field is read (a one-element dummy)."""
+    one = torch.zeros(1, dtype=torch.uint8, device="cuda")
+    ctx.set_resolution(8, 8)
+    c = camera("oblique", (8, 8))
+    ctx.set_camera(c.inv_view, c.r2v, (8, 8))
+    rgba = torch.zeros((8, 8, 4), device="cuda")
+    for res in ((65536, 65536, 1), (1024, 1024, 4096)):
+        with pytest.raises(cvr.CvrError) as e:
+            ctx.field_project_buffers(one.data_ptr(), rgba, None, None, cvr.ProjectDesc("max"), scalar_type=cvr.SCALAR_U8, res=res)
+        assert e.value.code == INVALID and "more than 2^32 - 1" in str(e.value)
+        with pytest.raises(cvr.CvrError) as e:
+            ctx.field_project(one.data_ptr(), cvr.ProjectDesc("max"), scalar_type=cvr.SCALAR_U8, res=res)
+        assert e.value.code == INVALID and "more than 2^32 - 1" in str(e.value)
+
+
 # ----------------------------------------------------------- entry points ----
 def test_destinations(cvr, ctx):
     lib = cvr.load()
